@@ -99,8 +99,8 @@ __global__ void signal_hist_kernel(const short* __restrict__ raw, const long lon
 }
 
 // many reads per launch: blockIdx.y = read, raw = the reads' samples back to back, [lo, hi) absolute sample indices
-// vrange [2][reads]: the smallest | largest sample value of every read's slice (initialised to large / small by the caller's two memsets): the order statistics and
-// the value table then touch the few thousand bins a read really has, not all 65,536 (round 6)
+// vrange [2][reads]: the smallest | largest sample value of every read's slice (initialised to large / small by the caller's two memsets): the order statistics
+// touch the few thousand bins a read really has, not all 65,536 (round 6), and so does the value table of a read whose events all lie inside its slice
 __global__ void signal_hist_batch_kernel(const short* __restrict__ raw, const long long* __restrict__ lo, const long long* __restrict__ hi,
                                          unsigned* __restrict__ hist /*[reads][65536]*/, int* __restrict__ vrange) {
     extern __shared__ __attribute__((aligned(16))) unsigned lh[];
@@ -120,14 +120,43 @@ __global__ void signal_lut_kernel(double* __restrict__ lut, const Norm p) {
     lut[i] = rint(v * 1000.0) / 1000.0;
 }
 
-__global__ void signal_lut_batch_kernel(double* __restrict__ lut /*[reads][65536]*/, const Norm* __restrict__ norms, const int* __restrict__ vrange) {
+// full[r] = 0: the entries of the values in vrange only - every sample an event of read r touches lies in its covered slice.  full[r] = 1: all 65,536 -
+// an event reaches outside the slice (before start_0, e.g. into the open-pore current ahead of the strand, or past start_last + length_last) and may
+// touch any value; the reference normalises the whole signal (myDetect.py:275, :282).  The table buffer is reused across calls: an entry left out here
+// holds an earlier read's normalisation.
+__global__ void signal_lut_batch_kernel(double* __restrict__ lut /*[reads][65536]*/, const Norm* __restrict__ norms, const int* __restrict__ vrange,
+                                        const int* __restrict__ full) {
 #pragma clang fp contract(off)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i - 32768 < vrange[blockIdx.y] || i - 32768 > vrange[gridDim.y + blockIdx.y]) return;      // no sample of this read has the value: the entry is never read
+    if (!full[blockIdx.y] && (i - 32768 < vrange[blockIdx.y] || i - 32768 > vrange[gridDim.y + blockIdx.y])) return;      // no event of this read reads the entry
     const Norm p = norms[blockIdx.y];
     double v = ((double)(i - 32768) - p.mshift) / p.mscale;
     v = v > p.upper ? p.upper : (v < p.lower ? p.lower : v);
     lut[size_t(blockIdx.y) * 65536 + i] = rint(v * 1000.0) / 1000.0;
+}
+
+// full[r] = 1 for a read with an event whose samples - clamped at the read's end as event_stats_one clamps them - reach outside its covered slice
+// [lo, hi) (absolute sample indices).  Only the events a statistics kernel reads count: e - ev_off[r] < n_stat[r] (all of them in the batched call,
+// those before first_empty in the resident form).  The caller zeroes full.
+__global__ void event_reach_batch_kernel(const unsigned long long* __restrict__ ev_start, const unsigned long long* __restrict__ ev_length,
+                                         const long long* __restrict__ ev_off, const long long* __restrict__ n_stat, const long long* __restrict__ lo,
+                                         const long long* __restrict__ hi, const long long* __restrict__ raw_off, const int n_reads, const long long n_events,
+                                         int* __restrict__ full) {
+    const long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (e >= n_events) return;
+    int a = 0, b = n_reads - 1;                      // the last read whose first event is <= e
+    while (a < b) {
+        const int mid = (a + b + 1) >> 1;
+        if (ev_off[mid] <= e) a = mid;
+        else b = mid - 1;
+    }
+    const int r = a;
+    if (e - ev_off[r] >= n_stat[r]) return;
+    const unsigned long long base = (unsigned long long)raw_off[r], n = (unsigned long long)(raw_off[r + 1] - raw_off[r]);
+    const unsigned long long st = ev_start[e];
+    unsigned long long t = st + ev_length[e];
+    if (t > n) t = n;
+    if (st < t && (base + st < (unsigned long long)lo[r] || base + t > (unsigned long long)hi[r])) full[r] = 1;
 }
 
 __global__ void signal_gather_kernel(const short* __restrict__ raw, const long long n, const double* __restrict__ lut,
@@ -257,8 +286,10 @@ __global__ void event_stats_batch_kernel(const short* __restrict__ raw, const lo
 // The RESIDENT form (round 6, dm_signal_event_stats_device): the statistics do not go back to the host.  ev3[e] = (mean, stdv, length) of merged event e
 // of the batch - exactly the three values get_Feature (myDetect.py:892-900) puts into a feature row - written where rows_assemble_kernel reads them.
 // An event at or behind its read's first empty event keeps the basecaller's values (fb_mean / fb_stdv: the reference's loop stops there, :334-340);
-// the read of an event is found by binary search over the event offsets (a wave's 64 events nearly always share it).  flag bit 0: a value the
-// split-f16 classifier kernels refuse (|v| > 65504 or NaN) - the batch then runs the fp32 kernel.
+// the read of an event is found by binary search over the event offsets (a wave's 64 events nearly always share it).  flag bit 0: a mean or stdv
+// this kernel computed (an event before its read's first empty one) that the split-f16 classifier kernels refuse (|v| > 65504 or NaN) - the batch then
+// runs the fp32 kernel.  Lengths and fall-back values are host data: dm_rows_emit_resident range-checks those of the events rows show, and an event no
+// row shows does not decide the kernel (as in the host-statistics form, which checks the rows only).
 __global__ void event_ev3_batch_kernel(const short* __restrict__ raw, const long long* __restrict__ raw_off, const double* __restrict__ lut,
                                        const unsigned long long* __restrict__ ev_start, const unsigned long long* __restrict__ ev_length,
                                        const long long* __restrict__ ev_off, const long long* __restrict__ n_stat, const int n_reads, const long long n_events,
@@ -277,15 +308,14 @@ __global__ void event_ev3_batch_kernel(const short* __restrict__ raw, const long
     if (e - ev_off[r] < n_stat[r]) {
         const long long base = raw_off[r];
         event_stats_one(raw + base, raw_off[r + 1] - base, lut + size_t(r) * 65536, ev_start[e], len, &mean, &stdv);
+        if (!(fabsf(mean) <= 65504.0f) || !(fabsf(stdv) <= 65504.0f)) atomicOr(flag, 1);
     } else {
         mean = fb_mean ? fb_mean[e] : __builtin_nanf("");
         stdv = fb_stdv ? fb_stdv[e] : __builtin_nanf("");
     }
-    const float flen = (float)(double)len;
     ev3[3 * e] = mean;
     ev3[3 * e + 1] = stdv;
-    ev3[3 * e + 2] = flen;
-    if (!(fabsf(mean) <= 65504.0f) || !(fabsf(stdv) <= 65504.0f) || !(flen <= 65504.0f)) atomicOr(flag, 1);
+    ev3[3 * e + 2] = (float)(double)len;
 }
 
 // ---- device: the same order statistics, one workgroup per read (dm_signal_event_stats_batch) ----
@@ -541,12 +571,13 @@ struct dm_signal {
     sig::Norm* d_bnorm = nullptr;         // [cap_reads]
     int* d_bflag = nullptr;               // [cap_reads]: 1 = this read needs the host order statistics
     int* d_vrange = nullptr;              // [2][n_reads] of the call (capacity 2 * cap_reads): smallest | largest sample value of a read's slice
+    int* d_bfull = nullptr;               // [cap_reads]: 1 = an event of the read reaches outside its slice, its value table is written whole
     bool host_order_statistics = false;   // DEEPMOD_SIGNAL_HOST_NORM=1: always take the host path (the cross-check of the tests)
     int* d_evread = nullptr;              // [cap_ev]
     int64_t cap_reads = 0, cap_evread = 0;
     float* d_fb = nullptr;                // resident form: fall-back mean | stdv of the batch's events, [2][cap_fb]
     int64_t cap_fb = 0;
-    long long* d_evoff = nullptr;         // resident form: ev_off [cap_reads + 1] | n_stat [cap_reads + 1]
+    long long* d_evoff = nullptr;         // ev_off [cap_reads + 1] | n_stat [cap_reads + 1]: the events a statistics kernel computes
     int* d_rflag = nullptr;               // resident form: range flag of the call
     unsigned* h_bhist = nullptr;          // page-locked, [cap_hbhist][65536]: the histograms come back by DMA
     int64_t cap_hbhist = 0;
@@ -595,6 +626,7 @@ void dm_signal_destroy(dm_signal* s) {
     (void)hipFree(s->d_bnorm);
     (void)hipFree(s->d_bflag);
     (void)hipFree(s->d_vrange);
+    (void)hipFree(s->d_bfull);
     (void)hipFree(s->d_evread);
     (void)hipFree(s->d_fb);
     (void)hipFree(s->d_evoff);
@@ -783,7 +815,7 @@ static int signal_batch_impl(dm_signal* s, int64_t n_reads, const int16_t* raw, 
     long long* hi = lo + (n_reads + 1);
     long long* off = hi + (n_reads + 1);
     std::vector<int> ev_read(resident ? 0 : n_ev);
-    std::vector<long long> evmeta(resident ? size_t(2) * (n_reads + 1) : 0);     // ev_off | n_stat
+    std::vector<long long> evmeta(size_t(2) * (n_reads + 1));     // ev_off | n_stat (the events a statistics kernel computes: all of them outside the resident form)
     for (int64_t r = 0; r < n_reads; ++r) {
         const int64_t e0 = ev_off[r], e1 = ev_off[r + 1], nr = raw_off[r + 1] - raw_off[r];
         if (e1 <= e0 || nr <= 0) return fail(DM_EINVAL, "read %lld of the batch has no events or no samples", (long long)r);
@@ -792,18 +824,19 @@ static int signal_batch_impl(dm_signal* s, int64_t n_reads, const int16_t* raw, 
         lo[r] = raw_off[r] + l;
         hi[r] = raw_off[r] + h;
         off[r] = raw_off[r];
+        evmeta[size_t(r)] = e0;
+        evmeta[size_t(n_reads + 1 + r)] = e1 - e0;
         if (resident) {
             const int64_t fe = first_empty[r] < 0 ? 0 : std::min<int64_t>(first_empty[r], e1 - e0);
             if (fe < e1 - e0 && (!fb_mean || !fb_stdv))
                 return fail(DM_EINVAL, "read %lld has an empty event (%lld of %lld) and the call has no fall-back values", (long long)r, (long long)fe, (long long)(e1 - e0));
-            evmeta[size_t(r)] = e0;
             evmeta[size_t(n_reads + 1 + r)] = fe;
         } else {
             for (int64_t e = e0; e < e1; ++e) ev_read[e] = int(r);
         }
     }
     off[n_reads] = n_raw;
-    if (resident) evmeta[size_t(n_reads)] = n_ev;
+    evmeta[size_t(n_reads)] = n_ev;
     // buffers
     if (s->cap_raw < n_raw) {
         (void)hipFree(s->d_raw);
@@ -837,7 +870,9 @@ static int signal_batch_impl(dm_signal* s, int64_t n_reads, const int16_t* raw, 
         (void)hipFree(s->d_bflag);
         (void)hipFree(s->d_evoff);
         (void)hipFree(s->d_vrange);
+        (void)hipFree(s->d_bfull);
         s->d_vrange = nullptr;
+        s->d_bfull = nullptr;
         s->d_bflag = nullptr;
         s->d_bhist = nullptr;
         s->d_blut = nullptr;
@@ -853,6 +888,7 @@ static int signal_batch_impl(dm_signal* s, int64_t n_reads, const int16_t* raw, 
         HIP_TRY(hipMalloc(&s->d_bflag, size_t(cap) * sizeof(int)));
         HIP_TRY(hipMalloc(&s->d_evoff, size_t(2) * (cap + 1) * sizeof(long long)));
         HIP_TRY(hipMalloc(&s->d_vrange, size_t(2) * cap * sizeof(int)));
+        HIP_TRY(hipMalloc(&s->d_bfull, size_t(cap) * sizeof(int)));
         s->cap_reads = cap;
     }
     const bool with_fb = resident && fb_mean && fb_stdv;
@@ -870,8 +906,8 @@ static int signal_batch_impl(dm_signal* s, int64_t n_reads, const int16_t* raw, 
     HIP_TRY(hipMemcpyAsync(s->d_ev + s->cap_ev, ev_length, size_t(n_ev) * 8, hipMemcpyHostToDevice, s->stream));
     if (!resident) HIP_TRY(hipMemcpyAsync(s->d_evread, ev_read.data(), size_t(n_ev) * sizeof(int), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipMemcpyAsync(s->d_bmeta, meta.data(), meta.size() * sizeof(long long), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->d_evoff, evmeta.data(), evmeta.size() * sizeof(long long), hipMemcpyHostToDevice, s->stream));
     if (resident) {
-        HIP_TRY(hipMemcpyAsync(s->d_evoff, evmeta.data(), evmeta.size() * sizeof(long long), hipMemcpyHostToDevice, s->stream));
         HIP_TRY(hipMemsetAsync(s->d_rflag, 0, sizeof(int), s->stream));
         if (with_fb) {
             HIP_TRY(hipMemcpyAsync(s->d_fb, fb_mean, size_t(n_ev) * 4, hipMemcpyHostToDevice, s->stream));
@@ -896,12 +932,17 @@ static int signal_batch_impl(dm_signal* s, int64_t n_reads, const int16_t* raw, 
                            s->d_raw, d_lo, d_hi, s->d_bhist, s->d_vrange);
         HIP_TRY(hipGetLastError());
     }
+    // reads whose value table the events need whole (an event outside the covered slice): a pass over the event tables on the device, 16 B per event
+    HIP_TRY(hipMemsetAsync(s->d_bfull, 0, size_t(n_reads) * sizeof(int), s->stream));
+    hipLaunchKernelGGL(sig::event_reach_batch_kernel, dim3(unsigned((n_ev + 255) / 256)), dim3(256), 0, s->stream, s->d_ev, s->d_ev + s->cap_ev, s->d_evoff,
+                       s->d_evoff + (n_reads + 1), d_lo, d_hi, d_off, int(n_reads), (long long)n_ev, s->d_bfull);
+    HIP_TRY(hipGetLastError());
     // 2. order statistics of all reads on the device, 3. value tables, 4. statistics of all events: one stream, no host round trip
     std::vector<sig::Norm> norms(n_reads);
     std::vector<int> flags(n_reads, 0);
     int range_flag = 0;
     auto tables_and_stats = [&]() -> int {
-        hipLaunchKernelGGL(sig::signal_lut_batch_kernel, dim3(256, unsigned(n_reads)), dim3(256), 0, s->stream, s->d_blut, s->d_bnorm, s->d_vrange);
+        hipLaunchKernelGGL(sig::signal_lut_batch_kernel, dim3(256, unsigned(n_reads)), dim3(256), 0, s->stream, s->d_blut, s->d_bnorm, s->d_vrange, s->d_bfull);
         HIP_TRY(hipGetLastError());
         if (resident) {
             hipLaunchKernelGGL(sig::event_ev3_batch_kernel, dim3(unsigned((n_ev + 255) / 256)), dim3(256), 0, s->stream, s->d_raw, d_off, s->d_blut,
@@ -996,7 +1037,7 @@ int dm_signal_event_stats_batch(dm_signal* s, int64_t n_reads, const int16_t* ra
 // caller, written on the handle's stream and complete when the call returns) takes (mean, stdv, length) of every merged event of the batch, the table's
 // fall-back values (fb_mean / fb_stdv [n_events], host, needed only when some read has an empty event) already merged; dm_rows_assemble reads them in place
 // (dm_rows_emit_resident's descriptors index this block).  Host arrays should be page-locked (dm_host_alloc): the uploads then overlap whatever else
-// the device does.  first_empty [n_reads]: INPUT, from dm_signal_plan_batch.  flags (optional): bit 0 = a value outside the split-f16 kernels' range.
+// the device does.  first_empty [n_reads]: INPUT, from dm_signal_plan_batch.  flags (optional): bit 0 = a mean or stdv the call computed is outside the split-f16 kernels' range (lengths and fall-back values: dm_rows_emit_resident's in_range, for the events rows show).
 int dm_signal_event_stats_device(dm_signal* s, int64_t n_reads, const int16_t* raw, const int64_t* raw_off, const uint64_t* ev_start,
                                  const uint64_t* ev_length, const int64_t* ev_off, const int64_t* first_empty, const float* fb_mean, const float* fb_stdv,
                                  float* d_ev3, double* norm6, int32_t* flags) {

@@ -725,6 +725,9 @@ def _print_stream_stats(stats, wall, since_start=None, planning=None):
         print('\twindows run through the classifier: %d of those %d base-positions (only a window centred on base %s can reach the BED, '
               'myDetect.py:1091; --storePred 1 classifies every base as the reference does) = %.3g windows/s'
               % (tot['submit_classified'], rows, _BASE_OF_RUN[0], tot['submit_classified'] / max(wall, 1e-9)))
+    if tot['batches']:
+        print('\tclassifier: %d of %d batches switched to the fp32 kernel (a feature row outside the split-f16 kernels\' range, or NaN)'
+              % (tot['submit_f32_batches'], tot['batches']))
     host = {k[5:]: v for k, v in tot.items() if k.startswith('prep_')}
     busy = sum(host.values()) + tot['submit']
     parts = ['%s %.0f%%' % (k, 100 * v / max(busy, 1e-9)) for k, v in sorted(host.items(), key=lambda kv: -kv[1])]

@@ -79,7 +79,10 @@ class SignalNormalizer:
     def event_stats_device(self, raw, raw_off, ev_start, ev_length, ev_off, block_ptr: int, fb_mean=None, fb_stdv=None):
         """The RESIDENT form (dm_signal_plan_batch + dm_signal_event_stats_device): the statistics of every merged event of the batch - (mean, stdv,
         length), the fall-back values fb_mean / fb_stdv merged in for events at or behind a read's first empty event - are written into the device
-        block at block_ptr ([n_events][3] float32) and stay there.  -> (first_empty int64[n], range flag)"""
+        block at block_ptr ([n_events][3] float32) and stay there.  -> (first_empty int64[n], range flag)
+
+        The range flag is 1 when a mean or stdv the call computed (an event before its read's first empty one) is outside the split-f16 kernels' range
+        or NaN.  Lengths and fall-back values do not raise it: dm_rows_emit_resident range-checks those of the events that feature rows show."""
         n = len(raw_off) - 1
         raw = np.ascontiguousarray(raw, dtype=np.int16)
         st = np.ascontiguousarray(ev_start, dtype=np.uint64)

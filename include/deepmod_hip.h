@@ -329,7 +329,9 @@ int dm_signal_event_stats_batch(dm_signal* s, int64_t n_reads, const int16_t* ra
  * values get_Feature (:892-900) copies into a feature row - with the basecaller's values (fb_mean / fb_stdv, host, may be NULL when no read has an empty
  * event) merged in for events at or behind first_empty.  dm_rows_emit_resident's descriptors index that block and dm_rows_assemble reads it in place: no
  * D2H -> feeder -> H2D of the statistics.  The block is complete when the call returns; host arrays should be page-locked (dm_host_alloc).
- * flags (optional): bit 0 = a value outside the split-f16 kernels' range (the batch then takes DM_PREC_F32). */
+ * flags (optional): bit 0 = a mean or stdv the call computed (an event before its read's first_empty) is outside the split-f16 kernels' range (the batch
+ * then takes DM_PREC_F32).  Lengths and fall-back values are host data: dm_rows_emit_resident's in_range covers them for the events rows show, so an
+ * event no row shows decides the kernel in neither form. */
 int dm_signal_plan_batch(int64_t n_reads, const int64_t* raw_off, const int64_t* ev_off, const uint64_t* ev_start, const uint64_t* ev_length,
                          int64_t* first_empty);
 int dm_signal_event_stats_device(dm_signal* s, int64_t n_reads, const int16_t* raw, const int64_t* raw_off, const uint64_t* ev_start,

@@ -59,6 +59,8 @@ def oracle_raw_container(path, genome, weights, tie=1e-4, nthreads=0):
         sig, _ = signal_oracle.mnormalized(rd['raw'], ev)
         mean, stdv, first_empty = signal_oracle.event_stats(sig, ev)
         assert first_empty == len(ev)
+        if rd['read_id'] not in sam:            # no alignment record: handle_record never sees the read, it makes no feature rows
+            continue
         s = sam[rd['read_id']]
         o = readmap_oracle.map_read(int(s[1]), int(s[3]), s[5], s[9], genome, len(ev))
         assert o['status'] == 'ok' and o['n_ev'] >= 50

@@ -196,6 +196,92 @@ def test_raw_reads_with_an_empty_event_and_a_stalled_event_through_the_resident_
         assert a == open('%s/stored/mod_pos.chrS%s.C.bed' % (out, strand), 'rb').read()
 
 
+def _edit_open_pore_and_hidden_stall(files):
+    """Edits of three raw containers for the test below.  Container 0, read 1: the samples ahead of its first event become an open-pore level above
+    the strand, and a merged event in the middle of its table starts there (an event before start_0 of the covered slice).  Container 0, read 2: a stalled
+    event of 70,000 samples that rows show.  Container 2, read 1: a stalled event of 70,000 samples, and its alignment record is removed - no row shows it.
+    -> the read ids of the open-pore read and the hidden read"""
+    from deepmod_amd import npzmap, rawreads
+    z = {k: np.array(v) for k, v in npzmap.load(files[0]).items()}
+    ro, eo = z['raw_off'], z['ev_off']
+    st, ln, mv, raw = np.array(z['ev_start']), np.array(z['ev_length']), np.array(z['ev_move']), np.array(z['raw'])
+    head = int(st[eo[1]])                                    # read 1's samples [0, head) lie before its first event
+    assert head >= 60
+    rng = np.random.default_rng(4)
+    raw[ro[1]:ro[1] + head] = np.round(rng.normal(raw[ro[1]:ro[2]].max() + 250, 8, head)).astype(np.int16)
+    # a container event in the middle that starts a merged event (move > 0) whose merged length fits in the head: it now starts at sample 10
+    for j in range(eo[1] + (eo[2] - eo[1]) // 2, eo[2] - 1):
+        k = j + 1
+        while k < eo[2] and mv[k] == 0:
+            k += 1
+        if mv[j] > 0 and 10 + int(ln[j:k].sum()) <= head:
+            break
+    st[j] = 10
+    ln[eo[2] + 200] = 70000                                  # read 2: a stalled event inside its rows
+    z['raw'], z['ev_start'], z['ev_length'] = raw, st, ln
+    npzmap.savez_aligned(files[0], **z)
+    z = {k: np.array(v) for k, v in npzmap.load(files[2]).items()}
+    ln = np.array(z['ev_length'])
+    ln[z['ev_off'][1] + 100] = 70000                          # read 1 of the third container: a stalled event ...
+    z['ev_length'] = ln
+    npzmap.savez_aligned(files[2], **z)
+    ids = [rd['read_id'] for rd in rawreads.load_raw_container(files[2])]
+    sam = files[2][:-len(rawreads.RAW_SUFFIX)] + '.sam'
+    lines = open(sam).read().splitlines(True)
+    open(sam, 'w').writelines(ln_ for ln_ in lines if ln_.split('\t')[0] != ids[1])       # ... in a read without an alignment record
+    assert len(lines) == len(open(sam).readlines()) + 1
+    return [rd['read_id'] for rd in rawreads.load_raw_container(files[0])][1], ids[1]
+
+
+def test_raw_reads_with_an_open_pore_event_and_a_hidden_stall_match_the_oracle_in_every_form(tmp_path, gpu_device):
+    """An event that starts in the open-pore current ahead of the strand (before the slice mnormalized's medians are taken from, myDetect.py:272) reads
+    table entries of sample values the slice does not have: the reference normalises the whole signal (:275, :282), so must every form of the signal
+    stage.  A stalled event of 70,000 samples in a read no row shows must not change the classifier kernel of its batch in one form and not in the other,
+    while a stalled event that rows show switches its batch in both.  The streaming command with the statistics resident on the device, with
+    DEEPMOD_STATS_ON_DEVICE=0 and the stored path (--storePred 1) write the BED bytes of the oracle chain."""
+    import re
+    from deepmod_amd import readmap
+    from oracle_pipeline import oracle_raw_container
+    wrk = tmp_path / 'raw'
+    files, fasta = synth_reads.write_synthetic_raw_run(str(wrk), n_reads=16, reads_per_file=4, genome_len=20000, seed=5, chrom='chrS')       # min|p1-0.5| = 2.6e-4 after the edits
+    _edit_open_pore_and_hidden_stall(files)
+    prefix = str(tmp_path / 'model' / 'mod_train_synth')
+    os.makedirs(os.path.dirname(prefix))
+    w = synth.write_synthetic_checkpoint(prefix, seed=26, scale=4.0)
+    out = str(tmp_path / 'out')
+    base = [sys.executable, os.path.join(ROOT, 'bin', 'DeepMod.py'), 'detect', '--wrkBase', str(wrk), '--modfile', prefix, '--Ref', fasta, '--outFolder', out,
+            '--threads', '2', '--files_per_thread', '2', '--Base', 'C', '--gpus', '1', '--alignStr', 'minimap2']
+    runs = {}
+    for name, extra, env in (('resident', [], {}), ('hoststats', [], {'DEEPMOD_STATS_ON_DEVICE': '0'}), ('stored', ['--storePred', '1'], {})):
+        res = subprocess.run(base + ['--FileID', name] + extra, capture_output=True, text=True, timeout=600, env=dict(os.environ, **env))
+        assert res.returncode == 0, res.stdout[-1500:] + res.stderr[-3000:]
+        runs[name] = res.stdout
+    m = re.search(r'event statistics resident on the device for (\d+) of (\d+) rows', runs['resident'])
+    assert m and int(m.group(1)) == int(m.group(2)) > 0, runs['resident'][-1500:]
+    assert 'Streaming detect: 15 reads' in runs['resident'] and 'Streaming detect: 15 reads' in runs['hoststats']
+    f32 = {}
+    for name in ('resident', 'hoststats'):
+        m = re.search(r'classifier: (\d+) of (\d+) batches switched to the fp32 kernel', runs[name])
+        assert m, runs[name][-1500:]
+        f32[name] = int(m.group(1))
+    assert f32['resident'] == f32['hoststats'] >= 1, f32        # the shown stall switches its batch, the hidden one none
+    genome = readmap.read_fasta(fasta)['chrS']
+    by_strand, n_reads, min_margin = {'+': [], '-': []}, 0, 1.0
+    for f in files:
+        got_reads, n, margin, _ties = oracle_raw_container(f, genome, w)
+        for strand in '+-':
+            by_strand[strand].extend(got_reads[strand])
+        n_reads += n
+        min_margin = min(min_margin, margin)
+    assert n_reads == 15
+    assert min_margin > 1e-4, 'edited set has a near-tie window (%.2e); pick another seed' % min_margin
+    for strand, reads in by_strand.items():
+        want = detect_oracle.sum_handler_oracle('chrS', strand, 'C', reads)
+        assert len(want) > 300
+        for name in runs:
+            assert open('%s/%s/mod_pos.chrS%s.C.bed' % (out, name, strand), 'rb').read() == want, (name, strand)
+
+
 def test_two_rank_run_that_cannot_build_its_communicator_fails_fast_and_clean(tmp_path, gpu_device):
     """`--gpus 2` with both GPU processes on device 0 (DEEPMOD_ONE_DEVICE=1, a test hook for one-GPU boxes): two real ranks and their
     feeders start, meet at the file rendezvous, and RCCL refuses the communicator (two ranks on one device).  The product has no merge

@@ -12,6 +12,9 @@ from conftest import GOLDEN
 from oracle import signal_oracle
 
 CASES = ['typical', 'even_slice', 'long_events', 'mid_events', 'outliers', 'clamped_tail', 'empty_late', 'empty_early']
+# host_signal_edges.npz (make_golden_signal.py --edges): events outside the covered slice, value / length / alignment edges of the device kernels
+EDGE_CASES = ['open_pore_a', 'open_pore_b', 'open_pore_c', 'overlap_tail', 'extreme_values', 'sum_boundaries'] + \
+    ['slice_mod8_%d' % i for i in range(8)] + ['slice_in_one_group', 'distinct_4096', 'distinct_4097']
 EVENT_DTYPE = [("mean", "<f4"), ("stdv", "<f4"), ("start", np.uint64), ("length", np.uint64), ("model_state", "U5")]
 
 
@@ -53,6 +56,53 @@ def test_oracle_matches_reference_golden(golden, name):
     assert _same_f32(out['stdv'], golden[name + '.stdv'])
     if name + '.signal' in golden:
         assert np.array_equal(sig, golden[name + '.signal'])
+
+
+@pytest.fixture(scope="module")
+def edge_golden():
+    return np.load(os.path.join(GOLDEN, "host_signal_edges.npz"))
+
+
+def test_edge_golden_covers_its_cases(edge_golden):
+    """the fixture holds what its names promise: events that reach outside the covered slice, every residue of the slice's ends mod 8,
+    4,096 and 4,097 distinct values in a slice, the ends of the int16 range and of the LDS bins, numpy's summation boundaries"""
+    assert sorted({k.split('.')[0] for k in edge_golden.files}) == sorted(EDGE_CASES)
+    def case(name):
+        raw, st, ln = edge_golden[name + '.raw'], edge_golden[name + '.start'].astype(np.int64), edge_golden[name + '.length'].astype(np.int64)
+        return raw, st, ln, int(st[0]), int(st[-1] + ln[-1])
+    for name in ('open_pore_a', 'open_pore_b', 'overlap_tail'):
+        raw, st, ln, lo, hi = case(name)
+        outside = [(s, s + n) for s, n in zip(st, ln) if s < lo or s + n > hi]
+        vals = raw[lo:hi]
+        assert outside and any(raw[a:b].max() > vals.max() or raw[a:b].min() < vals.min() for a, b in outside), name
+    raw, st, ln, lo, hi = case('open_pore_c')
+    assert np.any(np.diff(st) < 0) and st.min() == lo and (st + ln).max() <= hi
+    assert {(case('slice_mod8_%d' % i)[3] % 8, case('slice_mod8_%d' % i)[4] % 8) for i in range(8)} == {(i, (10 - i) % 8) for i in range(8)}
+    raw, st, ln, lo, hi = case('slice_in_one_group')
+    assert lo // 8 == (hi - 1) // 8 and hi - lo > 1
+    for nv in (4096, 4097):
+        raw, st, ln, lo, hi = case('distinct_%d' % nv)
+        assert len(np.unique(raw[lo:hi])) == nv
+    raw, st, ln, lo, hi = case('extreme_values')
+    assert {-32768, 32767, -2049, -2048, 6143, 6144} <= set(raw[lo:hi].tolist())
+    raw, st, ln, lo, hi = case('sum_boundaries')
+    assert {1, 7, 8, 9, 127, 128, 129, 8191, 8192, 8193, 16385} <= set(ln.tolist())
+
+
+@pytest.mark.parametrize("name", EDGE_CASES)
+def test_oracle_matches_reference_edge_golden(edge_golden, name):
+    """the oracle normalises the whole signal as the reference does (myDetect.py:275, :282), so an event outside the covered slice reads the
+    same values in both"""
+    raw = edge_golden[name + '.raw']
+    ev = _events(edge_golden, name)
+    sig, norm = signal_oracle.mnormalized(raw, ev)
+    mean, stdv, first_empty = signal_oracle.event_stats(sig, ev)
+    out = _apply_reference_rule(ev, mean, stdv, first_empty)
+    assert len(out) == int(edge_golden[name + '.n_kept'])
+    assert _same_f32(out['mean'], edge_golden[name + '.mean'])
+    assert _same_f32(out['stdv'], edge_golden[name + '.stdv'])
+    if name + '.signal' in edge_golden:
+        assert np.array_equal(sig, edge_golden[name + '.signal'])
 
 
 def _random_case(seed, n_raw, mean_len, loc=480.0, scale=70.0):
@@ -196,13 +246,14 @@ def test_batched_call_is_bit_identical_to_per_read_calls():
 
 
 @pytest.mark.gpu
-def test_resident_statistics_block_equals_the_batched_call():
+def test_resident_statistics_block_equals_the_batched_call_and_flags_computed_statistics_only():
     """Round 6 (dm_signal_plan_batch + dm_signal_event_stats_device): the statistics that stay on the device are, bit for bit, what the batched call
     returns to the host with the reference's rule applied (events before a read's first empty event take the signal's statistics, the ones behind keep
     the basecaller's, myDetect.py:334-340), next to float(length) - the three values get_Feature copies into a feature row (:892-900).  first_empty
-    from the host-only planner equals the batched call's; a read with an empty event and no fall-back values is refused; a length beyond the
-    split-f16 kernels' range raises the range flag; a read that makes the device order statistics step aside (constant signal) takes the same path
-    as in the batched call."""
+    from the host-only planner equals the batched call's; a read with an empty event and no fall-back values is refused.  The range flag covers the
+    statistics the call computed: NaN statistics raise it, a length beyond the split-f16 kernels' range does not (a length is host data, which
+    dm_rows_emit_resident range-checks for the events rows show: test_stream_feeders.py::test_a_stalled_event_picks_the_fp32_kernel_only_where_rows_show_it).
+    A read that makes the device order statistics step aside (constant signal) takes the same path as in the batched call."""
     from deepmod_amd import _lib, signal
     from deepmod_amd.model import DeviceArray
     cases = [_random_case(60 + i, n, ml) for i, (n, ml) in enumerate([(120_000, 9.0), (65_536, 2.0), (90_001, 11.0), (300_000, 300.0), (7_000, 5.0)])]
@@ -239,11 +290,13 @@ def test_resident_statistics_block_equals_the_batched_call():
         want_mean[:f], want_stdv[:f] = mean[:f], stdv[:f]
         assert _same_f32(got[e0:e1, 0], want_mean) and _same_f32(got[e0:e1, 1], want_stdv)
         assert _same_f32(got[e0:e1, 2], ln[e0:e1].astype(np.float64).astype(np.float32))
-    # a stalled event of 70,000 samples: representable by the fp32 kernel only
+    # a stalled event of 70,000 samples (representable by the fp32 kernel only): a length is host data, the flag covers the statistics the call computed;
+    # dm_rows_emit_resident range-checks the lengths of the events rows show (test_stream_feeders.py::test_a_stalled_event_picks_the_fp32_kernel_only_where_rows_show_it)
     ln2 = ln.copy()
     ln2[10] = 70_000
     _, flag = nz.event_stats_device(raw_all, raw_off, st, ln2, ev_off, blk.ptr, fb_mean, fb_stdv)
-    assert flag == 1
+    assert flag == 0
+    assert _same_f32(blk.to_host()[10, 2], np.float32(70_000))
     # the host order statistics (constant signal: division by zero like numpy) behind the same call
     const = np.full(30_000, 612, np.int16)
     cl = np.full(3000, 10, np.uint64)

@@ -313,6 +313,34 @@ class _PostingOracleNormalizer(_OracleNormalizer):
         return key
 
 
+def test_a_stalled_event_picks_the_fp32_kernel_only_where_rows_show_it(tmp_path):
+    """A merged event of 70,000 samples (beyond the split-f16 kernels' range): inside a read's rows, dm_rows_emit_resident reports in_range == 0 and the
+    batch takes the fp32 kernel, as the host-statistics (device) form does; in a read that no row shows (its alignment record is gone) neither form
+    switches - the resident signal stage does not flag lengths, its flag covers only the statistics it computed (test_signal.py)."""
+    from deepmod_amd import npzmap, rawreads
+    mo = {'Base': 'C', 'outFolder': str(tmp_path), 'fnum': 7, 'hidden': 100, 'windowsize': 21, 'alignStr': 'minimap2',
+          'region': [[None, None, None]], 'ConUnk': True, 'SignalGroup': 'simple', 'outLevel': 3, 'select_base': True}
+    for hidden in (False, True):
+        files, fasta = synth_reads.write_synthetic_raw_run(str(tmp_path / ('in%d' % hidden)), n_reads=8, reads_per_file=4, genome_len=20000, seed=6,
+                                                           chrom='chrS', min_len=300, max_len=1200)
+        z = {k: np.array(v) for k, v in npzmap.load(files[0]).items()}
+        ln = np.array(z['ev_length'])
+        ln[z['ev_off'][1] + 100] = 70000
+        z['ev_length'] = ln
+        npzmap.savez_aligned(files[0], **z)
+        if hidden:
+            sam = files[0][:-len(rawreads.RAW_SUFFIX)] + '.sam'
+            rid = [rd['read_id'] for rd in rawreads.load_raw_container(files[0])][1]
+            lines = open(sam).readlines()
+            open(sam, 'w').writelines(x for x in lines if x.split('\t')[0] != rid)
+            assert len(open(sam).readlines()) == len(lines) - 1
+        plain, posting = _OracleNormalizer(), _PostingOracleNormalizer()
+        dev = stream._prepare_batch_c(dict(mo, Ref=fasta), files, lambda: plain)
+        res = stream._prepare_batch_c(dict(mo, Ref=fasta), files, lambda: posting)
+        assert res.sig is not None and dev.sig is None and res.n_reads == dev.n_reads == 8 - hidden
+        assert res.f32 == dev.f32 == (not hidden), hidden
+
+
 def test_resident_form_of_a_raw_batch_equals_the_device_form(tmp_path):
     """Round 6: with a signal stage that keeps its statistics on the device (post_arrays), a batch of raw containers hands over NO per-event values -
     only a class byte per row, a descriptor per read whose event indices point into the signal stage's block, the window list, positions and flags.
