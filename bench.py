@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — BASELINE.json metric on BASELINE.json config 2.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 A "step" is one pass of the hot path over one batch of 65,536 synthetic 7-feature x wd21 windows
 that are already resident in HBM: dm_predict_windows (BiLSTM classify) + dm_summary_add (per-position
@@ -11,6 +11,11 @@ batches); the only collective is ONE integer RCCL reduce-scatter of the per-posi
 left with the all-rank sums of its slice of the contig - the merge the streaming detect uses), inside the timed region,
 through the product's C ABI (dm_comm_create once, dm_summary_reduce_scatter) - barriers and the max-over-ranks of the
 elapsed time go through the same communicator.  Rank 0 prints ONE JSON line.
+
+A plain run does only what `value` needs: set-up, warm-up, the K timed steps, --dump-outputs, the line (with the roofline of the
+timed launches and the socket power sampled while they ran).  Every side measurement that takes a run of its own is behind --full:
+the 1.5 s steady-state leg, the other MFMA modes, the trained-like model, host-buffer rates, both end-to-end legs (`extras`), the
+CPU baselines with the parity against the oracle, and at N > 1 the host-fed rate of all ranks.
 """
 from __future__ import annotations
 
@@ -576,14 +581,17 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=4)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the line's own measurement, every side measurement as well (several minutes): the steady-state power leg, extras, "
+                         "cpu_baseline and parity; at N > 1 the host-fed rate of all ranks")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline and parity")
     ap.add_argument("--precision", choices=sorted(PRECISIONS) + ["auto"], default="f16x3",
                     help="MFMA mode of the classifier kernel (f16x3 and f32 meet the 1e-4 probability tolerance; f16i8 is the reduced-precision mode; "
                          "auto = what the command line does: f16x3 unless the model's own calibration run lets f16i8 in)")
     ap.add_argument("--weights", choices=["synthetic", "trained-like"], default="synthetic",
                     help="synthetic: U(-a, a) kernels at scale 4 (seed 26; the workload of every round); trained-like: tests/golden/trained_like_weights.npz")
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed side measurements (other precision, host-buffer rate, e2e)")
-    ap.add_argument("--no-e2e", action="store_true", help="skip extras.e2e (configs[2] through bin/DeepMod.py detect: ~6 GB of synthetic input in /dev/shm or /tmp)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the untimed side measurements (other precision, host-buffer rate, e2e)")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip extras.e2e (configs[2] through bin/DeepMod.py detect: ~6 GB of synthetic input in /dev/shm or /tmp)")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32, ~13 MB): "
                                                           "prob, cls and a fixed sample of the touch / cov / mod counters")
     args = ap.parse_args()
@@ -756,9 +764,9 @@ def main():
     value = total_windows / elapsed
     # N > 1, after the timed region: what `value` cannot show - the ranks feeding their GPUs from HOST memory at the same time (pageable
     # x[65536,21,7] in, prob + cls out, synchronous: 588 B in + 9 B out per window over PCIe, all ranks at once; never `value`).  A curve
-    # that bends here and not in `value` is the host side of the node (PCIe / memory bandwidth), not the GPUs
+    # that bends here and not in `value` is the host side of the node (PCIe / memory bandwidth), not the GPUs.  --full only
     host_fed = None
-    if control is not None:
+    if control is not None and args.full:
         err = None                                    # (every rank reaches every barrier / max below whatever its own calls do)
         try:
             m.set_option(_lib.DM_OPT_ASYNC, 0)
@@ -793,7 +801,8 @@ def main():
                                    "synthetic weights (real .data shards absent), %d windows/step resident in HBM, "
                                    "%d distinct batches (1,048,576 windows)" % (BATCH, n_batches),
                        "batch": BATCH, "windows_total": total_windows, "parallelism": "window-sharded x%d" % world, "forced_dist_dry_run": bool(dist_mode and world == 1), "all_ranks_on_device_0_test_hook": os.environ.get("DM_BENCH_ONE_DEVICE") == "1", "setup_launches": SETUP_LAUNCHES,
-                       "precision": P["label"], "weights": args.weights, "calibration_gate": calibration},
+                       "precision": P["label"], "weights": args.weights, "calibration_gate": calibration,
+                       "full": args.full},
             "roofline": {"bound": "mfma", "achieved": achieved, "peak": P["peak"], "unit": "TFLOP/s",
                          "frac": achieved / P["peak"], "traffic": (traffic or {}).get("bytes"),
                          "traffic_detail": traffic, "algorithmic_bytes": 596 * BATCH,
@@ -822,7 +831,7 @@ def main():
             out["multi_gpu"] = {"collective": "NOT RUN: RCCL could not be set up, the final merge of the counters was skipped (barriers and the "
                                               "max over ranks went through the rendezvous files); the data path has no collective, so `value` stands",
                                 "rccl_error": comm_error, "per_rank": per_rank, "host_fed_all_ranks": host_fed, "measured_on_hardware_with_more_than_one_rank": bool(world > 1 and os.environ.get("DM_BENCH_ONE_DEVICE") != "1")}
-        if world == 1 and plog is not None and plog.available:
+        if args.full and world == 1 and plog is not None and plog.available:
             try:
                 st = out["roofline"]["power"]["steady"] = steady_power_leg(m, model, _lib, plog, x_dev[0], prob_dev, cls_dev)
                 # the K timed steps are ~30 ms, shorter than the firmware's power averaging: the same launches in the steady state of the box, beside it
@@ -835,7 +844,7 @@ def main():
                 out["roofline"]["power"]["steady"] = {"error": repr(exc)}
         if plog is not None:
             plog.stop()
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             out["extras"] = extras(m, _lib, model, args.precision, x_dev[0], x0, prob_dev, cls_dev)
             if not args.no_e2e and args.precision == "f16x3":
                 try:
@@ -848,7 +857,7 @@ def main():
                     out["extras"]["e2e_raw"] = {"error": repr(exc)}
         tl = (out.get("extras") or {}).get("trained_like_model") or {}
         wt, mt = tl.pop("weights_obj", None), tl.pop("model_obj", None)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             ref, out["cpu_baseline"] = cpu_baseline(weights, x0)
             m.set_option(_lib.DM_OPT_ASYNC, 0)
             out["parity"] = parity_field(m, x0[:16384], ref)

@@ -370,6 +370,40 @@ def test_wave_pair_experiment_kernel_is_refused_or_bit_identical(gpu_device):
     m.close()
 
 
+def _bench_line(args, timeout=900):
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
+    assert res.returncode == 0, res.stdout[-1000:] + res.stderr[-3000:]
+    lines = [l for l in res.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{"), res.stdout[:600]
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_is_the_headline_only(gpu_device):
+    """A run without --full: the headline fields of the line, the roofline of the timed launches, none of the side measurements."""
+    out = _bench_line(["--gpus", "1", "--steps", "2", "--warmup", "1"])
+    assert out["metric"].startswith("base-positions/sec") and out["unit"] == "base-positions/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f16x3" and out["steps"] == 2 and out["warmup"] == 1 and out["config"]["full"] is False
+    assert out["value"] > 1e6 and out["ms_per_step"] > 0 and out["summary_check"]["touch"] > 0
+    assert out["roofline"]["launches"] == 2 and out["roofline"]["frac"] > 0
+    assert not {"extras", "cpu_baseline", "parity"} & set(out) and "steady" not in out["roofline"] and "steady" not in out["roofline"]["power"]
+
+
+def test_bench_full_runs_the_side_measurements(gpu_device):
+    """--full keeps every side leg of the line (here without the end-to-end legs and the CPU baseline, which are minutes, not seconds)."""
+    out = _bench_line(["--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-e2e", "--no-cpu-baseline"])
+    assert out["config"]["full"] is True and out["value"] > 1e6
+    x = out["extras"]
+    assert x["other_precision"]["precision"] == "f32" and x["opt_in_precision"]["precision"] == "f16i8"
+    assert x["other_precision"]["launches"] == 32 and x["opt_in_precision"]["launches"] == 64
+    assert x["trained_like_model"]["launches"] == 64 and x["host_buffers"]["value"] > 0
+    if out["roofline"]["power"]["timed_region"] and out["roofline"]["power"]["timed_region"].get("available"):
+        assert out["roofline"]["steady"]["launches"] > 0
+
+
 def test_bench_distributed_path_single_rank(gpu_device):
     """The N > 1 code path of bench.py exercised with one rank (DM_BENCH_FORCE_DIST=1 under torch.distributed.run, which is
     only the launcher): file rendezvous, ONE persistent RCCL communicator created through the C ABI (dm_comm_create), the

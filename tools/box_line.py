@@ -1,9 +1,9 @@
-"""Dev tool (GPU box): one line per box for profiles/<round>/box_spread.txt - `python bench.py --no-cpu-baseline` reduced to the launch time of the main leg,
+"""Dev tool (GPU box): one line per box for profiles/<round>/box_spread.txt - `python bench.py --full --no-cpu-baseline` reduced to the launch time of the main leg,
 the steady leg with its on-box power / clock, the opt-in int8 kernel, the fp32 kernel and the two end-to-end legs (feature containers: whole command; raw
 containers: whole command and steady state).  Run it on several fresh boxes back to back."""
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline"], capture_output=True, text=True).stdout
+out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline"], capture_output=True, text=True).stdout
 d = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
 r = d["roofline"]; s = r["power"].get("steady") or {}; x = d["extras"]; st = r.get("steady") or {}
 e, er = x.get("e2e") or {}, x.get("e2e_raw") or {}

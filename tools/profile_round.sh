@@ -7,8 +7,8 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --steps 8 --warmup 1 --no-cpu-baseline --no-extras --precision $PREC"
-BKT="python $R/bench.py --steps 32 --warmup 1 --no-cpu-baseline --no-extras --precision $PREC"      # 32 + 1 untimed, 32 timed launches
+B="python $R/bench.py --full --steps 8 --warmup 1 --no-cpu-baseline --no-extras --precision $PREC"
+BKT="python $R/bench.py --full --steps 32 --warmup 1 --no-cpu-baseline --no-extras --precision $PREC"      # 32 + 1 untimed, 32 timed launches
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- $BKT > $OUT/kt.log 2>&1; echo "kt rc=$?"
 for C in "FETCH_SIZE" "WRITE_SIZE" \
          "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE" \
