@@ -34,7 +34,8 @@ def build_parser():
     com.add_argument('--windowsize', type=int, default=21, help='window size (odd)')
     com.add_argument('--alignStr', choices=['bwa', 'minimap2'], default='minimap2', help='aligner run on raw containers when on PATH; otherwise side-car <container>.sam files are read')
     com.add_argument('--SignalGroup', choices=['simple', 'rundif'], default='simple', help='accepted for compatibility')
-    com.add_argument('--move', action='store_true', default=False, help='accepted for compatibility')
+    com.add_argument('--move', action='store_true', default=False,
+                     help='raw containers: take the events from the basecaller move tables (Guppy and later: Move, first_sample_template and the Fastq sequence) instead of an event table')
     det = sub.add_parser('detect', parents=[com], help='detect modifications')
     det.add_argument('--Ref', help='reference genome FASTA (raw containers: reference bases of the aligned reads)')
     det.add_argument('--predDet', type=int, choices=[0, 1], default=1, help='1: predict + summarise; 0: summarise only')
@@ -90,7 +91,7 @@ def mDetect(args):
     from deepmod_amd import _lib, detect
     mo = {k: getattr(args, k) for k in ('outLevel', 'wrkBase', 'FileID', 'outFolder', 'recursive', 'threads', 'files_per_thread',
                                          'windowsize', 'predDet', 'predpath', 'modfile', 'fnum', 'hidden', 'outputlayer', 'Base',
-                                         'mod_cluster', 'Ref', 'alignStr', 'SignalGroup', 'basecall_1d', 'basecall_2strand', 'storePred')}
+                                         'mod_cluster', 'Ref', 'alignStr', 'SignalGroup', 'basecall_1d', 'basecall_2strand', 'storePred', 'move')}
     for k in ('threads', 'files_per_thread', 'windowsize', 'fnum', 'hidden'):
         non_negative(mo[k], k)
     if mo['threads'] < 1:

@@ -32,6 +32,7 @@ DM_OK, DM_EINVAL, DM_EDEVICE, DM_ENOMEM, DM_ESTATE, DM_ERCCL, DM_ERANGE = 0, -1,
  DM_MAP_EVENTS_AFTER_CLIP) = range(14)
 DM_MAP_INFO_LEN = 16
 DM_MAP_OK, DM_MAP_NO_MATCH, DM_MAP_NEED_ROWS = 0, 1, 2
+DM_MOVE_OK, DM_MOVE_COUNT, DM_MOVE_OUTSIDE = 0, 1, 2
 DM_WEIGHT_FLOATS = 408402
 
 _c = ctypes
@@ -100,6 +101,9 @@ SIGNATURES = [
     ("dm_signal_event_stats_batch", _c.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("dm_signal_plan_batch", _c.c_int, [_i64, _vp, _vp, _vp, _vp, _vp]),
     ("dm_signal_event_stats_device", _c.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("dm_signal_move_stats_device", _c.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("dm_signal_move_chunk", _i64, []),
+    ("dm_move_events", _i64, [_i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("dm_events_merge", _i64, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("dm_rows_create", _vp, [_c.c_char]),
     ("dm_rows_destroy", None, [_vp]),

@@ -206,6 +206,19 @@ inline bool offsets_ok(const int64_t* off, int64_t n, int64_t total) {
     return off[n] <= total;
 }
 
+// dm_move_events: 0x80 in every byte of the eight at p that equals 1 (exact - no carry crosses a byte), byte j of memory in bits 8 j .. 8 j + 7
+#if defined(__BYTE_ORDER__) && __BYTE_ORDER__ == __ORDER_LITTLE_ENDIAN__
+constexpr bool kMoveWords = true;
+#else
+constexpr bool kMoveWords = false;
+#endif
+inline uint64_t move_ones8(const uint8_t* p) {
+    uint64_t v;
+    std::memcpy(&v, p, 8);
+    const uint64_t x = v ^ 0x0101010101010101ull, m = 0x7f7f7f7f7f7f7f7full;
+    return ~(((x & m) + m) | x | m);
+}
+
 }  // namespace rowsbatch
 
 extern "C" {
@@ -262,6 +275,77 @@ int64_t dm_events_merge(int64_t n_reads, int64_t n_events, const int64_t* ev_off
                 o_len[w - 1] += length[i];
             }
         }
+    }
+    mev_off[n_reads] = w;
+    return w;
+}
+
+// getEvent with --move (myDetect.py:136-153 -> MoveTable.getMove_Info, MoveTable.py:7-54), for all reads of a container: the event table of a read
+// from its basecaller MOVE TABLE.  A boundary is every table index i in 1 .. L-1 with move[i] == 1 (move[0] is never looked at, any other value is no
+// boundary); the stride is the reference's constant 2 (:30-33).  Event 0 starts at first_sample_template, boundary i ends the current event and starts
+// the next at first + 2 i, the last event ends at the read's last sample.  The bases are the Fastq sequence itself.  Where the reference is undefined
+// the read FAILS (status, no events written, mev_off[r + 1] == mev_off[r]):
+//   DM_MOVE_COUNT     boundaries != bases - 1 (the reference raises IndexError for too many and leaves np.empty rows uninitialised for too few)
+//   DM_MOVE_OUTSIDE   first < 0, first >= samples, or the last boundary starts its event at or behind the read's end (np.mean of an empty slice;
+//                     a negative length wrapped into uint64)
+// so every event of a read that passes is non-empty and inside the signal.  DM_MOVE_COUNT is decided first.  All tables come from disk: offsets are
+// checked against n_move / n_fq / the sample offsets' own order before a byte is read; outputs are sized for n_fq events.
+// Returns the number of events written (mev_off[n_reads]) or a negative code.
+int64_t dm_move_events(int64_t n_reads, int64_t n_move, const uint8_t* move, const int64_t* mv_off, const int64_t* first, const int64_t* raw_off,
+                       int64_t n_fq, const char* fq, const int64_t* fq_off, int64_t* mev_off, int32_t* status, uint64_t* m_start, uint64_t* m_length,
+                       char* m_base) {
+    if (n_reads < 0 || n_move < 0 || n_fq < 0 || !mv_off || !first || !raw_off || !fq_off || !mev_off || !status || (n_move > 0 && !move) ||
+        (n_fq > 0 && (!fq || !m_start || !m_length || !m_base)))
+        return fail(DM_EINVAL, "dm_move_events: bad argument");
+    if (!rowsbatch::offsets_ok(mv_off, n_reads, n_move))
+        return fail(DM_EINVAL, "dm_move_events: the move offsets decrease or run past the %lld entries of the table", (long long)n_move);
+    if (!rowsbatch::offsets_ok(fq_off, n_reads, n_fq))
+        return fail(DM_EINVAL, "dm_move_events: the sequence offsets decrease or run past the %lld bases", (long long)n_fq);
+    if (!rowsbatch::offsets_ok(raw_off, n_reads, INT64_MAX))
+        return fail(DM_EINVAL, "dm_move_events: the signal offsets decrease");
+    int64_t w = 0;
+    for (int64_t r = 0; r < n_reads; ++r) {
+        mev_off[r] = w;
+        const uint8_t* mv = move + mv_off[r];
+        const int64_t len = mv_off[r + 1] - mv_off[r], nrow = fq_off[r + 1] - fq_off[r], nsig = raw_off[r + 1] - raw_off[r], f = first[r];
+        // (eight table entries per step where the byte order allows it: the byte loop was a third of a feeder's time on a run of move containers)
+        int64_t nb = 0, last = 0, i = 1;
+        for (; rowsbatch::kMoveWords && i + 8 <= len; i += 8)
+            if (const uint64_t hit = rowsbatch::move_ones8(mv + i)) {
+                nb += __builtin_popcountll(hit);
+                last = i + (63 - __builtin_clzll(hit)) / 8;
+            }
+        for (; i < len; ++i)
+            if (mv[i] == 1) {
+                ++nb;
+                last = i;
+            }
+        if (nb != nrow - 1) {
+            status[r] = DM_MOVE_COUNT;
+            continue;
+        }
+        if (f < 0 || f >= nsig || (nb > 0 && 2 * last >= nsig - f)) {      // (nsig - f > 0 here: no overflow; last < 2^62 for any table in memory)
+            status[r] = DM_MOVE_OUTSIDE;
+            continue;
+        }
+        status[r] = DM_MOVE_OK;
+        uint64_t pivot = uint64_t(f);
+        int64_t k = w;
+        auto boundary = [&](const int64_t at) {
+            const uint64_t next = uint64_t(f) + 2 * uint64_t(at);
+            m_start[k] = pivot;
+            m_length[k] = next - pivot;
+            pivot = next;
+            ++k;
+        };
+        for (i = 1; rowsbatch::kMoveWords && i + 8 <= len; i += 8)
+            for (uint64_t hit = rowsbatch::move_ones8(mv + i); hit; hit &= hit - 1) boundary(i + __builtin_ctzll(hit) / 8);
+        for (; i < len; ++i)
+            if (mv[i] == 1) boundary(i);
+        m_start[k] = pivot;
+        m_length[k] = uint64_t(nsig) - pivot;
+        std::memcpy(m_base + w, fq + fq_off[r], size_t(nrow));
+        w += nrow;
     }
     mev_off[n_reads] = w;
     return w;

@@ -318,6 +318,185 @@ __global__ void event_ev3_batch_kernel(const short* __restrict__ raw, const long
     ev3[3 * e + 2] = (float)(double)len;
 }
 
+// ---- event tables from basecaller move tables (detect --move; dm_signal_move_stats_device) ----
+// Reference: MoveTable.py:7-54.  A boundary is a table index i in 1 .. L-1 with move[i] == 1; boundary number k (0-based, in table order) starts event
+// k + 1 at first + 2 i, event 0 starts at first, the last event ends at the read's last sample.  That is a segmented count-and-compact over one byte per
+// two samples.  The tables of the batch lie back to back; read r's table is cut into chunks of MOVE_CHUNK bytes counted from its 16-byte-aligned base
+// (mv_off[r] & ~15), so that every lane loads one aligned 16-byte word; chunk_off[r] = first chunk of read r (host arithmetic over <= 4,096 reads).
+//   1. move_count_kernel   one workgroup per chunk: the number of boundaries in it and the table index of its last one;
+//   2. move_scan_kernel    one workgroup per read: exclusive scan of its chunks' counts, then the read's status (dm_move_events' rules: the count
+//                          against the expected event count, the last boundary and `first` against the read's samples), n_stat and start[0];
+//                          an invalid read's slots are zeroed here and nothing else ever writes them;
+//   3. move_write_kernel   one workgroup per chunk again: rank of a boundary = chunk base + lanes before it (five __ballot / __popcll rounds over the
+//                          bits of the lanes' counts) + earlier bits of its own lane's word -> start[rank + 1];
+//   4. move_length_kernel  one thread per event: length[k] = start[k + 1] - start[k], the last one from the read's sample count.
+// No atomics: every output has exactly one writer, so the tables are the same bits whatever the scheduling.  Every store is guarded by the read's
+// status and its expected event count.
+constexpr int MOVE_THREADS = 256;
+constexpr int MOVE_CHUNK = MOVE_THREADS * 16;       // table bytes per workgroup
+
+// the last read whose first chunk / event is <= c (reads without chunks / events share an offset with their successor and are never chosen)
+__device__ __forceinline__ int move_find_read(const long long* __restrict__ off, const int n_reads, const long long c) {
+    int a = 0, b = n_reads - 1;
+    while (a < b) {
+        const int mid = (a + b + 1) >> 1;
+        if (off[mid] <= c) a = mid;
+        else b = mid - 1;
+    }
+    return a;
+}
+
+// bit j set: byte j of the lane's 16-byte word (absolute table byte a + j) is a boundary of the read whose table is [t0, t1): equal to 1, behind the
+// read's index 0 and before its end.  Bytes of a neighbouring read (or behind the last table) that the aligned word holds are masked off.
+__device__ __forceinline__ unsigned move_mask16(const unsigned char* __restrict__ move, const long long a, const long long t0, const long long t1) {
+    if (a >= t1 || a + 16 <= t0 + 1) return 0u;
+    const uint4 q = *reinterpret_cast<const uint4*>(move + a);
+    const unsigned w[4] = {q.x, q.y, q.z, q.w};
+    unsigned m = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) m |= (((w[k] >> (8 * b)) & 0xffu) == 1u ? 1u : 0u) << (4 * k + b);
+    const long long jlo = t0 + 1 - a, jhi = t1 - a;                 // valid bytes: jlo <= j < jhi
+    const unsigned lo = jlo <= 0 ? 0u : (1u << (unsigned)jlo) - 1u;  // (jlo <= 15 here)
+    const unsigned hi = jhi >= 16 ? 0xffffu : (1u << (unsigned)jhi) - 1u;
+    return m & hi & ~lo;
+}
+
+// number of boundaries in the lanes before this one (wave64): the lanes' counts are <= 16, so five ballots - one per bit of the count - and the
+// population count of each ballot below the lane.  *total = the wave's count.
+__device__ __forceinline__ int move_wave_prefix(const int cnt, int* total) {
+    const unsigned long long below = (1ull << (threadIdx.x & 63)) - 1ull;
+    int pre = 0, tot = 0;
+#pragma unroll
+    for (int b = 0; b < 5; ++b) {
+        const unsigned long long v = __ballot((cnt >> b) & 1);
+        pre += __popcll(v & below) << b;
+        tot += __popcll(v) << b;
+    }
+    *total = tot;
+    return pre;
+}
+
+__global__ __launch_bounds__(MOVE_THREADS) void move_count_kernel(const unsigned char* __restrict__ move, const long long* __restrict__ mv_off,
+                                                                  const long long* __restrict__ chunk_off, const int n_reads,
+                                                                  int* __restrict__ ccnt, int* __restrict__ clast) {
+    __shared__ int w_cnt[MOVE_THREADS / 64], w_last[MOVE_THREADS / 64];
+    const long long c = blockIdx.x;
+    const int r = move_find_read(chunk_off, n_reads, c);
+    const long long t0 = mv_off[r], t1 = mv_off[r + 1];
+    const long long a = (t0 & ~15ll) + (c - chunk_off[r]) * MOVE_CHUNK + threadIdx.x * 16;
+    const unsigned m = move_mask16(move, a, t0, t1);
+    int tot;
+    (void)move_wave_prefix(__popc(m), &tot);
+    // the wave's last boundary: the highest bit of the highest lane that has one (table index relative to the read; -1: none)
+    const unsigned long long has = __ballot(m != 0u);
+    const int mine = m ? int(a - t0) + 31 - __clz(m) : -1;
+    const int last = has ? __shfl(mine, 63 - __clzll(has), 64) : -1;
+    if ((threadIdx.x & 63) == 0) {
+        w_cnt[threadIdx.x >> 6] = tot;
+        w_last[threadIdx.x >> 6] = last;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int n = 0, l = -1;
+#pragma unroll
+        for (int k = 0; k < MOVE_THREADS / 64; ++k) {
+            n += w_cnt[k];
+            l = w_last[k] > l ? w_last[k] : l;
+        }
+        ccnt[c] = n;
+        clast[c] = l;
+    }
+}
+
+__global__ __launch_bounds__(MOVE_THREADS) void move_scan_kernel(const int* __restrict__ ccnt, const int* __restrict__ clast, const long long* __restrict__ chunk_off,
+                                                                 const long long* __restrict__ first, const long long* __restrict__ raw_off,
+                                                                 const long long* __restrict__ ev_off, int* __restrict__ cbase, int* __restrict__ status,
+                                                                 long long* __restrict__ n_stat, unsigned long long* __restrict__ ev_start,
+                                                                 unsigned long long* __restrict__ ev_length) {
+    __shared__ int sh[MOVE_THREADS];
+    __shared__ int sh_status;
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const long long c0 = chunk_off[r], nch = chunk_off[r + 1] - c0;
+    long long carry = 0;            // boundaries of the chunks before this tile (the same value in every thread)
+    int last = -1;
+    for (long long t = 0; t < nch; t += MOVE_THREADS) {
+        const long long i = t + tid;
+        const int v = i < nch ? ccnt[c0 + i] : 0;
+        if (i < nch) last = clast[c0 + i] > last ? clast[c0 + i] : last;
+        sh[tid] = v;
+        __syncthreads();
+        for (int o = 1; o < MOVE_THREADS; o <<= 1) {
+            const int x = tid >= o ? sh[tid - o] : 0;
+            __syncthreads();
+            sh[tid] += x;
+            __syncthreads();
+        }
+        if (i < nch) cbase[c0 + i] = int(carry) + sh[tid] - v;
+        carry += sh[MOVE_THREADS - 1];
+        __syncthreads();
+    }
+    sh[tid] = last;
+    __syncthreads();
+    for (int o = MOVE_THREADS / 2; o > 0; o >>= 1) {
+        if (tid < o) sh[tid] = sh[tid + o] > sh[tid] ? sh[tid + o] : sh[tid];
+        __syncthreads();
+    }
+    const long long e0 = ev_off[r], nrow = ev_off[r + 1] - e0, nsig = raw_off[r + 1] - raw_off[r], f = first[r];
+    if (tid == 0) {
+        int st = 0;
+        if (carry != nrow - 1) st = 1;                                                       // DM_MOVE_COUNT
+        else if (f < 0 || f >= nsig || (carry > 0 && 2ll * sh[0] >= nsig - f)) st = 2;      // DM_MOVE_OUTSIDE
+        status[r] = st;
+        n_stat[r] = st ? 0 : nrow;
+        if (!st && nrow > 0) ev_start[e0] = (unsigned long long)f;
+        sh_status = st;
+    }
+    __syncthreads();
+    if (sh_status)
+        for (long long k = tid; k < nrow; k += MOVE_THREADS) {
+            ev_start[e0 + k] = 0ull;
+            ev_length[e0 + k] = 0ull;
+        }
+}
+
+__global__ __launch_bounds__(MOVE_THREADS) void move_write_kernel(const unsigned char* __restrict__ move, const long long* __restrict__ mv_off,
+                                                                  const long long* __restrict__ chunk_off, const int n_reads, const int* __restrict__ cbase,
+                                                                  const int* __restrict__ status, const long long* __restrict__ first,
+                                                                  const long long* __restrict__ ev_off, unsigned long long* __restrict__ ev_start) {
+    __shared__ int w_cnt[MOVE_THREADS / 64];
+    const long long c = blockIdx.x;
+    const int r = move_find_read(chunk_off, n_reads, c);
+    if (status[r]) return;                          // (uniform: the whole workgroup belongs to one read)
+    const long long t0 = mv_off[r], t1 = mv_off[r + 1];
+    const long long a = (t0 & ~15ll) + (c - chunk_off[r]) * MOVE_CHUNK + threadIdx.x * 16;
+    unsigned m = move_mask16(move, a, t0, t1);
+    int tot;
+    const int pre = move_wave_prefix(__popc(m), &tot);
+    if ((threadIdx.x & 63) == 0) w_cnt[threadIdx.x >> 6] = tot;
+    __syncthreads();
+    long long k = (long long)cbase[c] + pre;        // number of the lane's first boundary within the read
+    for (int w = 0; w < int(threadIdx.x >> 6); ++w) k += w_cnt[w];
+    const long long e0 = ev_off[r], nrow = ev_off[r + 1] - e0, f = first[r];
+    while (m) {
+        const int j = __ffs(m) - 1;
+        m &= m - 1u;
+        if (k + 1 < nrow) ev_start[e0 + k + 1] = (unsigned long long)(f + 2 * (a + j - t0));
+        ++k;
+    }
+}
+
+__global__ void move_length_kernel(const unsigned long long* __restrict__ ev_start, const long long* __restrict__ ev_off, const long long* __restrict__ raw_off,
+                                   const int* __restrict__ status, const int n_reads, const long long n_events, unsigned long long* __restrict__ ev_length) {
+    const long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (e >= n_events) return;
+    const int r = move_find_read(ev_off, n_reads, e);
+    if (status[r]) return;                          // zeroed by move_scan_kernel
+    const unsigned long long end = e + 1 < ev_off[r + 1] ? ev_start[e + 1] : (unsigned long long)(raw_off[r + 1] - raw_off[r]);
+    ev_length[e] = end - ev_start[e];
+}
+
 // ---- device: the same order statistics, one workgroup per read (dm_signal_event_stats_batch) ----
 // The distinct sample values of a read (a few hundred to a few thousand of the 65,536 bins) are compacted into LDS; the four
 // medians are k-th elements of (key, count) lists: two of them in the natural order of the values ((x - mshift) / mscale is
@@ -581,6 +760,22 @@ struct dm_signal {
     int* d_rflag = nullptr;               // resident form: range flag of the call
     unsigned* h_bhist = nullptr;          // page-locked, [cap_hbhist][65536]: the histograms come back by DMA
     int64_t cap_hbhist = 0;
+    // dm_signal_move_stats_device: grow-only device buffers of the segmentation kernels
+    unsigned char* d_move = nullptr;      // the batch's move tables, [cap_move + 16] (the last aligned 16-byte word may reach behind the tables)
+    int64_t cap_move = 0;
+    long long* d_mvmeta = nullptr;        // mv_off [n + 1] | chunk_off [n + 1] | first [n + 1] of the call (capacity 3 * (cap_mvreads + 1))
+    int* d_mvstatus = nullptr;            // [cap_mvreads]
+    int64_t cap_mvreads = 0;
+    int* d_mvchunk = nullptr;             // count | last | base of every chunk, [3][cap_chunks]
+    int64_t cap_chunks = 0;
+};
+
+// the move-table front of signal_batch_impl (dm_signal_move_stats_device): the event tables are built on the device
+struct MoveInput {
+    const uint8_t* move;
+    const int64_t* mv_off;
+    const int64_t* first;
+    int32_t* status;        // out, [n_reads]
 };
 
 extern "C" {
@@ -631,6 +826,10 @@ void dm_signal_destroy(dm_signal* s) {
     (void)hipFree(s->d_fb);
     (void)hipFree(s->d_evoff);
     (void)hipFree(s->d_rflag);
+    (void)hipFree(s->d_move);
+    (void)hipFree(s->d_mvmeta);
+    (void)hipFree(s->d_mvstatus);
+    (void)hipFree(s->d_mvchunk);
     if (s->h_bhist) (void)hipHostFree(s->h_bhist);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
@@ -796,18 +995,20 @@ int dm_signal_plan_batch(int64_t n_reads, const int64_t* raw_off, const int64_t*
 // d_ev3 != NULL: the resident form (dm_signal_event_stats_device) - no per-event download; first_empty is then an INPUT (dm_signal_plan_batch).
 static int signal_batch_impl(dm_signal* s, int64_t n_reads, const int16_t* raw, const int64_t* raw_off, const uint64_t* ev_start,
                              const uint64_t* ev_length, const int64_t* ev_off, float* ev_mean, float* ev_stdv, double* norm6,
-                             int64_t* first_empty, const float* fb_mean, const float* fb_stdv, float* d_ev3, int32_t* flags_out) {
+                             int64_t* first_empty, const float* fb_mean, const float* fb_stdv, float* d_ev3, int32_t* flags_out,
+                             const MoveInput* mv = nullptr) {
     const bool resident = d_ev3 != nullptr;
     if (!s) return fail(DM_EINVAL, "null signal handle");
     if (n_reads < 0) return fail(DM_EINVAL, "negative read count");
     if (n_reads == 0) return DM_OK;
-    if (!raw || !raw_off || !ev_start || !ev_length || !ev_off) return fail(DM_EINVAL, "null input");
+    if (!raw || !raw_off || !ev_off || (mv ? (!mv->move || !mv->mv_off || !mv->first || !mv->status || !resident) : (!ev_start || !ev_length)))
+        return fail(DM_EINVAL, "null input");
     if (is_device_ptr(raw) || is_device_ptr(ev_start) || is_device_ptr(ev_mean)) return fail(DM_EINVAL, "the batched call takes host arrays");
     const int64_t n_raw = raw_off[n_reads], n_ev = ev_off[n_reads];
     if (raw_off[0] != 0 || ev_off[0] != 0) return fail(DM_EINVAL, "the offset tables of a batch start at 0");
     if (n_raw <= 0 || n_ev <= 0) return fail(DM_EINVAL, "empty batch");
     if (n_reads > 4096) return fail(DM_EINVAL, "at most 4096 reads per call (%lld given)", (long long)n_reads);
-    if (resident && (!first_empty || !is_device_ptr(d_ev3))) return fail(DM_EINVAL, "the resident form takes first_empty (dm_signal_plan_batch) and a device block");
+    if (resident && ((!first_empty && !mv) || !is_device_ptr(d_ev3))) return fail(DM_EINVAL, "the resident form takes first_empty (dm_signal_plan_batch) and a device block");
     HIP_TRY(hipSetDevice(s->device));
     // per-read slice covered by the events (myDetect.py:272), absolute sample indices
     std::vector<long long> meta(size_t(3) * (n_reads + 1));
@@ -816,7 +1017,35 @@ static int signal_batch_impl(dm_signal* s, int64_t n_reads, const int16_t* raw, 
     long long* off = hi + (n_reads + 1);
     std::vector<int> ev_read(resident ? 0 : n_ev);
     std::vector<long long> evmeta(size_t(2) * (n_reads + 1));     // ev_off | n_stat (the events a statistics kernel computes: all of them outside the resident form)
-    for (int64_t r = 0; r < n_reads; ++r) {
+    std::vector<long long> mvmeta(mv ? size_t(3) * (n_reads + 1) : 0);       // mv_off | chunk_off | first
+    int64_t n_mv = 0, n_chunks = 0;
+    if (mv) {
+        if (mv->mv_off[0] != 0) return fail(DM_EINVAL, "the offset tables of a batch start at 0");
+        if (is_device_ptr(mv->move)) return fail(DM_EINVAL, "the batched call takes host arrays");
+        for (int64_t r = 0; r < n_reads; ++r) {
+            const int64_t t0 = mv->mv_off[r], t1 = mv->mv_off[r + 1], nr = raw_off[r + 1] - raw_off[r];
+            if (t1 < t0 || t1 - t0 >= (int64_t(1) << 30)) return fail(DM_EINVAL, "read %lld: the move offsets decrease (or a table of 2^30 entries and more)", (long long)r);
+            if (ev_off[r + 1] < ev_off[r] || nr <= 0) return fail(DM_EINVAL, "read %lld of the batch has no samples (or its event offsets decrease)", (long long)r);
+            // the normalisation slice is [first, samples) - known without the events; a read whose `first` lies outside its samples fails on the
+            // device (DM_MOVE_OUTSIDE) and shows no statistics: its whole signal stands in, so that the order statistics see an ordinary read
+            const int64_t f = mv->first[r];
+            lo[r] = raw_off[r] + (f >= 0 && f < nr ? f : 0);
+            hi[r] = raw_off[r + 1];
+            off[r] = raw_off[r];
+            evmeta[size_t(r)] = ev_off[r];
+            evmeta[size_t(n_reads + 1 + r)] = 0;            // n_stat: written by move_scan_kernel
+            mvmeta[size_t(r)] = t0;
+            mvmeta[size_t(n_reads + 1 + r)] = n_chunks;
+            mvmeta[size_t(2 * (n_reads + 1) + r)] = f;
+            n_chunks += (t1 - (t0 & ~int64_t(15)) + sig::MOVE_CHUNK - 1) / sig::MOVE_CHUNK * (t1 > t0 ? 1 : 0);
+        }
+        n_mv = mv->mv_off[n_reads];
+        mvmeta[size_t(n_reads)] = n_mv;
+        mvmeta[size_t(2 * n_reads + 1)] = n_chunks;
+        mvmeta[size_t(3 * n_reads + 2)] = 0;
+        if (n_chunks >= (int64_t(1) << 31)) return fail(DM_EINVAL, "move tables of %lld chunks", (long long)n_chunks);
+    }
+    for (int64_t r = 0; r < n_reads && !mv; ++r) {
         const int64_t e0 = ev_off[r], e1 = ev_off[r + 1], nr = raw_off[r + 1] - raw_off[r];
         if (e1 <= e0 || nr <= 0) return fail(DM_EINVAL, "read %lld of the batch has no events or no samples", (long long)r);
         long long l, h;
@@ -901,9 +1130,40 @@ static int signal_batch_impl(dm_signal* s, int64_t n_reads, const int16_t* raw, 
         s->cap_fb = cap;
     }
     if (resident && !s->d_rflag) HIP_TRY(hipMalloc(&s->d_rflag, sizeof(int)));
+    if (mv) {
+        if (s->cap_move < n_mv || !s->d_move) {
+            (void)hipFree(s->d_move);
+            s->d_move = nullptr;
+            s->cap_move = 0;
+            const int64_t cap = n_mv + (n_mv >> 2);
+            HIP_TRY(hipMalloc(&s->d_move, size_t(cap) + 16));
+            s->cap_move = cap;
+        }
+        if (s->cap_mvreads < n_reads) {
+            (void)hipFree(s->d_mvmeta);
+            (void)hipFree(s->d_mvstatus);
+            s->d_mvmeta = nullptr;
+            s->d_mvstatus = nullptr;
+            s->cap_mvreads = 0;
+            const int64_t cap = n_reads + (n_reads >> 1);
+            HIP_TRY(hipMalloc(&s->d_mvmeta, size_t(3) * (cap + 1) * sizeof(long long)));
+            HIP_TRY(hipMalloc(&s->d_mvstatus, size_t(cap) * sizeof(int)));
+            s->cap_mvreads = cap;
+        }
+        if (s->cap_chunks < n_chunks || !s->d_mvchunk) {
+            (void)hipFree(s->d_mvchunk);
+            s->d_mvchunk = nullptr;
+            s->cap_chunks = 0;
+            const int64_t cap = n_chunks + (n_chunks >> 2) + 1;
+            HIP_TRY(hipMalloc(&s->d_mvchunk, size_t(3) * cap * sizeof(int)));
+            s->cap_chunks = cap;
+        }
+    }
     HIP_TRY(hipMemcpyAsync(s->d_raw, raw, size_t(n_raw) * sizeof(short), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(s->d_ev, ev_start, size_t(n_ev) * 8, hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(s->d_ev + s->cap_ev, ev_length, size_t(n_ev) * 8, hipMemcpyHostToDevice, s->stream));
+    if (!mv) {
+        HIP_TRY(hipMemcpyAsync(s->d_ev, ev_start, size_t(n_ev) * 8, hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(s->d_ev + s->cap_ev, ev_length, size_t(n_ev) * 8, hipMemcpyHostToDevice, s->stream));
+    }
     if (!resident) HIP_TRY(hipMemcpyAsync(s->d_evread, ev_read.data(), size_t(n_ev) * sizeof(int), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipMemcpyAsync(s->d_bmeta, meta.data(), meta.size() * sizeof(long long), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipMemcpyAsync(s->d_evoff, evmeta.data(), evmeta.size() * sizeof(long long), hipMemcpyHostToDevice, s->stream));
@@ -917,6 +1177,36 @@ static int signal_batch_impl(dm_signal* s, int64_t n_reads, const int16_t* raw, 
     long long* d_lo = s->d_bmeta;
     long long* d_hi = s->d_bmeta + (n_reads + 1);
     long long* d_off = s->d_bmeta + 2 * (n_reads + 1);
+    std::vector<int> mv_status(mv ? n_reads : 0, 0);
+    if (mv) {
+        // 0. the event tables from the move tables (behind the uploads of d_bmeta / d_evoff on the same stream; no host wait before the statistics)
+        if (n_mv > 0) HIP_TRY(hipMemcpyAsync(s->d_move, mv->move, size_t(n_mv), hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(s->d_mvmeta, mvmeta.data(), mvmeta.size() * sizeof(long long), hipMemcpyHostToDevice, s->stream));
+        const long long* d_mvoff = s->d_mvmeta;
+        const long long* d_choff = s->d_mvmeta + (n_reads + 1);
+        const long long* d_first = s->d_mvmeta + 2 * (n_reads + 1);
+        int* d_ccnt = s->d_mvchunk;
+        int* d_clast = s->d_mvchunk + s->cap_chunks;
+        int* d_cbase = s->d_mvchunk + 2 * s->cap_chunks;
+        if (n_chunks > 0) {
+            hipLaunchKernelGGL(sig::move_count_kernel, dim3(unsigned(n_chunks)), dim3(sig::MOVE_THREADS), 0, s->stream, s->d_move, d_mvoff, d_choff, int(n_reads),
+                               d_ccnt, d_clast);
+            HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(sig::move_scan_kernel, dim3(unsigned(n_reads)), dim3(sig::MOVE_THREADS), 0, s->stream, d_ccnt, d_clast, d_choff, d_first, d_off,
+                           s->d_evoff, d_cbase, s->d_mvstatus, s->d_evoff + (n_reads + 1), s->d_ev, s->d_ev + s->cap_ev);
+        HIP_TRY(hipGetLastError());
+        if (n_chunks > 0) {
+            hipLaunchKernelGGL(sig::move_write_kernel, dim3(unsigned(n_chunks)), dim3(sig::MOVE_THREADS), 0, s->stream, s->d_move, d_mvoff, d_choff, int(n_reads),
+                               d_cbase, s->d_mvstatus, d_first, s->d_evoff, s->d_ev);
+            HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(sig::move_length_kernel, dim3(unsigned((n_ev + 255) / 256)), dim3(256), 0, s->stream, s->d_ev, s->d_evoff, d_off, s->d_mvstatus,
+                           int(n_reads), (long long)n_ev, s->d_ev + s->cap_ev);
+        HIP_TRY(hipGetLastError());
+        // (the statuses come back behind the statistics kernels, next to the range flag: a download enqueued here would make the host wait for the
+        // segmentation before it launches them)
+    }
     // 1. histograms of all reads
     HIP_TRY(hipMemsetAsync(s->d_bhist, 0, size_t(n_reads) * 65536 * sizeof(unsigned), s->stream));
     {
@@ -950,6 +1240,7 @@ static int signal_batch_impl(dm_signal* s, int64_t n_reads, const int16_t* raw, 
                                with_fb ? s->d_fb : nullptr, with_fb ? s->d_fb + s->cap_fb : nullptr, d_ev3, s->d_rflag);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(&range_flag, s->d_rflag, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+            if (mv) HIP_TRY(hipMemcpyAsync(mv_status.data(), s->d_mvstatus, size_t(n_reads) * sizeof(int), hipMemcpyDeviceToHost, s->stream));
             return DM_OK;
         }
         hipLaunchKernelGGL(sig::event_stats_batch_kernel, dim3(unsigned((n_ev + 255) / 256)), dim3(256), 0, s->stream, s->d_raw, d_off, s->d_blut,
@@ -1000,6 +1291,8 @@ static int signal_batch_impl(dm_signal* s, int64_t n_reads, const int16_t* raw, 
         HIP_TRY(hipStreamSynchronize(s->stream));
     }
     if (flags_out) *flags_out = range_flag ? 1 : 0;
+    if (mv)
+        for (int64_t r = 0; r < n_reads; ++r) mv->status[r] = mv_status[r];
     if (norm6)
         for (int64_t r = 0; r < n_reads; ++r) {
             double* o = norm6 + 6 * r;
@@ -1045,5 +1338,17 @@ int dm_signal_event_stats_device(dm_signal* s, int64_t n_reads, const int16_t* r
     return signal_batch_impl(s, n_reads, raw, raw_off, ev_start, ev_length, ev_off, nullptr, nullptr, norm6, const_cast<int64_t*>(first_empty), fb_mean, fb_stdv,
                              d_ev3, flags);
 }
+
+// The resident form for reads with move tables (detect --move): see include/deepmod_hip.h.  The segmentation kernels (sig::move_*_kernel) write the
+// handle's event tables, the statistics kernels above run unchanged.  No fall-back values: every event of a read that passes is non-empty
+// (first_empty == its event count), and a read that fails shows no statistics.
+int dm_signal_move_stats_device(dm_signal* s, int64_t n_reads, const int16_t* raw, const int64_t* raw_off, const uint8_t* move, const int64_t* mv_off,
+                                const int64_t* first, const int64_t* ev_off, float* d_ev3, int32_t* status, double* norm6, int32_t* flags) {
+    if (!d_ev3) return fail(DM_EINVAL, "dm_signal_move_stats_device: null device block");
+    const MoveInput mv{move, mv_off, first, status};
+    return signal_batch_impl(s, n_reads, raw, raw_off, nullptr, nullptr, ev_off, nullptr, nullptr, norm6, nullptr, nullptr, nullptr, d_ev3, flags, &mv);
+}
+
+int64_t dm_signal_move_chunk(void) { return sig::MOVE_CHUNK; }
 
 }  // extern "C"

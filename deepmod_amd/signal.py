@@ -99,6 +99,24 @@ class SignalNormalizer:
                                                           None if fs is None else fs.ctypes.data, block_ptr, None, ctypes.byref(flags)))
         return first_empty, int(flags.value)
 
+    def move_stats_device(self, raw, raw_off, move, mv_off, first, ev_off, block_ptr: int):
+        """The resident form for reads with move tables (dm_signal_move_stats_device): the event tables are built on the device from the tables
+        (uint8, back to back; mv_off / first per read; ev_off = the cumulative Fastq lengths), then the statistics as event_stats_device computes
+        them.  -> (status int32[n] - dm_move_events' codes, computed on the device -, range flag)"""
+        n = len(raw_off) - 1
+        raw = np.ascontiguousarray(raw, dtype=np.int16)
+        move = np.ascontiguousarray(move, dtype=np.uint8)
+        if len(move) == 0:
+            move = np.zeros(1, np.uint8)
+        raw_off, mv_off, first, ev_off = (np.ascontiguousarray(a, np.int64) for a in (raw_off, mv_off, first, ev_off))
+        if len(mv_off) != n + 1 or len(ev_off) != n + 1 or len(first) != n or int(mv_off[-1]) > len(move) or int(raw_off[-1]) > len(raw):
+            raise ValueError("offset tables that do not fit their arrays")
+        status = np.empty(n, np.int32)
+        flags = ctypes.c_int32(0)
+        _lib.check(self._lib.dm_signal_move_stats_device(self._h, n, raw.ctypes.data, raw_off.ctypes.data, move.ctypes.data, mv_off.ctypes.data, first.ctypes.data,
+                                                         ev_off.ctypes.data, block_ptr, status.ctypes.data, None, ctypes.byref(flags)))
+        return status, int(flags.value)
+
     def event_stats_batch(self, reads):
         """reads: [(raw int16[n], ev_start uint64[E], ev_length uint64[E])] -> [(mean, stdv, norm dict, first_empty)] with one
         device round trip for the whole list (dm_signal_event_stats_batch; bit-identical to per-read event_stats)."""
@@ -122,6 +140,27 @@ class SignalNormalizer:
         keys = ("mshift", "mscale", "read_med", "read_mad", "lower_lim", "upper_lim")
         return [(mean[ev_off[i]:ev_off[i + 1]], stdv[ev_off[i]:ev_off[i + 1]], dict(zip(keys, norm6[i].tolist())), int(first_empty[i]))
                 for i in range(n)]
+
+
+def move_events(move, mv_off, first, raw_off, fq, fq_off):
+    """dm_move_events (host, no device): the event tables of reads with move tables.  move uint8 / fq bytes back to back with their offsets, first
+    (first_sample_template) per read, raw_off the sample offsets.  -> (mev_off int64[n + 1], status int32[n], start uint64[E], length uint64[E], bases 'S1'[E])
+    A read with a non-zero status (DM_MOVE_COUNT, DM_MOVE_OUTSIDE) has no events.  Raises for offset tables that do not fit their arrays."""
+    lib = _lib.load()
+    move = np.ascontiguousarray(move, np.uint8)
+    fq = np.ascontiguousarray(np.frombuffer(fq, np.uint8) if isinstance(fq, (bytes, bytearray)) else fq, np.uint8)
+    mv_off, first, raw_off, fq_off = (np.ascontiguousarray(a, np.int64) for a in (mv_off, first, raw_off, fq_off))
+    n = len(first)
+    if len(mv_off) != n + 1 or len(raw_off) != n + 1 or len(fq_off) != n + 1:
+        raise ValueError("offset tables of the wrong length")
+    cap = max(len(fq), 1)
+    mev_off, status = np.empty(n + 1, np.int64), np.empty(max(n, 1), np.int32)
+    start, length, bases = np.empty(cap, np.uint64), np.empty(cap, np.uint64), np.empty(cap, 'S1')
+    got = lib.dm_move_events(n, len(move), move.ctypes.data, mv_off.ctypes.data, first.ctypes.data, raw_off.ctypes.data, len(fq), fq.ctypes.data,
+                             fq_off.ctypes.data, mev_off.ctypes.data, status.ctypes.data, start.ctypes.data, length.ctypes.data, bases.ctypes.data)
+    if got < 0:
+        _lib.check(int(got))
+    return mev_off, status[:n], start[:got], length[:got], bases[:got]
 
 
 _default: Optional[SignalNormalizer] = None

@@ -287,31 +287,50 @@ def _prepare_batch_c(moptions, files: List[str], make_normalizer=None, alloc=Non
                 from . import signal as dmsignal
                 normalizer = dmsignal.SignalNormalizer(int(moptions.get('device', 0)))
             ids, id_src, raw_parts, raw_offs, ev_offs = [], [], [], [0], [0]
+            use_move = bool(moptions.get('move'))       # detect --move: the events come from the basecaller move tables (rawreads.py)
+            move_parts, mv_offs, firsts = [], [0], []   # ... which travel to the signal stage themselves in the resident form
             merges = []                     # per container that was merged: the arguments of its dm_events_merge call (kept alive), for _fallback_values
             opened = []
+            opened_mv = []
+
+            def _open_container(f5f):
+                """-> (mapped members, read metas, n, sample offsets) of a format-2 container, the offsets checked against the samples they index"""
+                z = npzmap.load(f5f, lazy=('ev_mean', 'ev_stdv'))
+                if 'format' not in z:
+                    raise ValueError('format-1 raw container')
+                meta = json.loads(str(z['meta']))
+                n = len(meta)
+                ro = _c_arr(z['raw_off'], np.int64)
+                if len(ro) != n + 1 or ro[0] != 0 or (np.diff(ro) < 0).any() or ro[-1] > len(z['raw']):
+                    raise ValueError('signal offsets of a damaged container')
+                return z, meta, n, ro
             for f5f in raw_files:
                 try:
-                    z = npzmap.load(f5f, lazy=('ev_mean', 'ev_stdv'))
-                    if 'format' not in z:
-                        raise ValueError('format-1 raw container')
-                    meta = json.loads(str(z['meta']))
-                    n = len(meta)
-                    eo = _c_arr(z['ev_off'], np.int64)
-                    if len(eo) != n + 1:
-                        raise ValueError('event offsets of a damaged container')
-                    ms = _c_arr(z['ev_model_state'], z['ev_model_state'].dtype)
-                    args = [_c_arr(z['ev_mean'], np.float64), _c_arr(z['ev_stdv'], np.float64), _c_arr(z['ev_start'], np.uint64),
-                            _c_arr(z['ev_length'], np.uint64)]
-                    mv = _c_arr(z['ev_move'], np.int64)
-                    ro = _c_arr(z['raw_off'], np.int64)
-                    if len(ro) != n + 1 or ro[0] != 0 or (np.diff(ro) < 0).any() or ro[-1] > len(z['raw']):
-                        raise ValueError('signal offsets of a damaged container')
-                    opened.append((f5f, z, meta, n, eo, max(int(eo[-1]), 0), ms, args, mv, ro))
+                    z, meta, n, ro = _open_container(f5f)
+                    if not use_move:
+                        eo = _c_arr(z['ev_off'], np.int64)
+                        if len(eo) != n + 1:
+                            raise ValueError('event offsets of a damaged container')
+                        ms = _c_arr(z['ev_model_state'], z['ev_model_state'].dtype)
+                        args = [_c_arr(z['ev_mean'], np.float64), _c_arr(z['ev_stdv'], np.float64), _c_arr(z['ev_start'], np.uint64),
+                                _c_arr(z['ev_length'], np.uint64)]
+                        mv = _c_arr(z['ev_move'], np.int64)
+                        opened.append((f5f, z, meta, n, eo, max(int(eo[-1]), 0), ms, args, mv, ro))
+                    elif not all(k in z for k in rawreads.MOVE_MEMBERS):
+                        opened_mv.append((f5f, z, meta, n, ro, None))
+                    else:
+                        if z['mv'].dtype != np.uint8 or z['fq'].dtype != np.uint8:
+                            raise ValueError('move tables of a damaged container')
+                        mvt, mvo, fst, fq, fqo = (_c_arr(z[k], dt) for k, dt in zip(rawreads.MOVE_MEMBERS, (np.uint8, np.int64, np.int64, np.uint8, np.int64)))
+                        # (dm_move_events checks the order of the offsets and their ends against the arrays)
+                        if len(mvo) != n + 1 or len(fqo) != n + 1 or len(fst) != n or (n and (mvo[0] != 0 or fqo[0] != 0)):
+                            raise ValueError('move offsets of a damaged container')
+                        opened_mv.append((f5f, z, meta, n, ro, (mvt, mvo, fst, fq, fqo)))
                 except Exception:
                     out.errors["Cannot open fast5 or other errors"].append(f5f)
                     print("Cannot open fast5 or other errors: {}".format(f5f))
             # the merged event tables of the whole batch, written in place container after container (no per-container pieces to concatenate)
-            cap_ev = sum(o[5] for o in opened)
+            cap_ev = sum(o[5] for o in opened) + sum(len(o[5][3]) for o in opened_mv if o[5] is not None)
             m_start, m_len, m_base = np.empty(max(cap_ev, 1), np.uint64), np.empty(max(cap_ev, 1), np.uint64), np.empty(max(cap_ev, 1), 'S1')
             w = 0
             for f5f, z, meta, n, eo, ne, ms, args, mv, ro in opened:
@@ -337,6 +356,41 @@ def _prepare_batch_c(moptions, files: List[str], make_normalizer=None, alloc=Non
                 raw_offs.extend((raw_offs[-1] + ro[1:]).tolist())
                 ev_offs.extend((ev_offs[-1] + mev_off[1:]).tolist())
                 w += got
+            for f5f, z, meta, n, ro, mvd in opened_mv:
+                if mvd is None:                 # a container without move data: the reference's reason, per read
+                    out.errors['No move data'].extend([f5f] * n)
+                    continue
+                mvt, mvo, fst, fq, fqo = mvd
+                mev_off, status = np.empty(n + 1, np.int64), np.empty(max(n, 1), np.int32)
+                got = lib.dm_move_events(n, len(mvt), mvt.ctypes.data, mvo.ctypes.data, fst.ctypes.data, ro.ctypes.data, len(fq), fq.ctypes.data, fqo.ctypes.data,
+                                         mev_off.ctypes.data, status.ctypes.data, m_start.ctypes.data + 8 * w, m_len.ctypes.data + 8 * w, m_base.ctypes.data + w)
+                if got < 0:
+                    out.errors["Cannot open fast5 or other errors"].append(f5f)
+                    print("Cannot open fast5 or other errors: {}".format(f5f))
+                    continue
+                keep.append(mvd)
+                good = np.flatnonzero(status[:n] == 0)
+                for i in np.flatnonzero(status[:n] != 0):       # where the reference is undefined the read fails (rawreads.py)
+                    out.errors["Cannot open fast5 or other errors"].append(f5f)
+                    print("Cannot open fast5 or other errors: {} (read {}: move table, status {})".format(f5f, meta[i]['read_id'], status[i]))
+                for i in good:
+                    ids.append(meta[i]['read_id'].replace(" ", ":::").replace("\t", "|||"))
+                    id_src.append(f5f)
+                if len(good) == n:              # the usual case: the container's arrays as they lie
+                    raw_parts.append(z['raw'][:int(ro[-1])])
+                    move_parts.append(mvt[:int(mvo[-1])])
+                    raw_offs.extend((raw_offs[-1] + ro[1:]).tolist())
+                    mv_offs.extend((mv_offs[-1] + mvo[1:]).tolist())
+                else:
+                    for i in good:
+                        raw_parts.append(z['raw'][int(ro[i]):int(ro[i + 1])])
+                        move_parts.append(mvt[int(mvo[i]):int(mvo[i + 1])])
+                        raw_offs.append(raw_offs[-1] + int(ro[i + 1] - ro[i]))
+                        mv_offs.append(mv_offs[-1] + int(mvo[i + 1] - mvo[i]))
+                firsts.extend(fst[good].tolist())
+                per_read = (mev_off[1:] - mev_off[:-1])[good]               # (a failed read has no events: mev_off is already the compacted table's)
+                ev_offs.extend((ev_offs[-1] + np.cumsum(per_read)).tolist())
+                w += got
             t1 = time.perf_counter()
             out.timing['load'] += t1 - t0
             if ids:
@@ -347,6 +401,8 @@ def _prepare_batch_c(moptions, files: List[str], make_normalizer=None, alloc=Non
                 def _fallback_values():
                     """The basecaller's mean / stdv of every merged event of the batch (getEvent's rounding): needed only for events at or behind a read's
                     first empty event - the containers are merged once more, this time with the value columns."""
+                    if use_move:
+                        raise RuntimeError('a move read with an empty event: dm_move_events admits none')
                     mm_, ms_ = np.empty(max(w, 1), np.float32), np.empty(max(w, 1), np.float32)
                     for margs, ne, got, at, _keep in merges:
                         a_, b_ = np.empty(ne, np.float32), np.empty(ne, np.float32)
@@ -364,7 +420,17 @@ def _prepare_batch_c(moptions, files: List[str], make_normalizer=None, alloc=Non
                                  and bool(moptions.get('rows_on_device', os.environ.get('DEEPMOD_ROWS_ON_DEVICE', '1') != '0'))
                                  and bool(moptions.get('stats_on_device', os.environ.get('DEEPMOD_STATS_ON_DEVICE', '1') != '0')))
                 try:
-                    if want_resident:
+                    if want_resident and use_move:
+                        # every event of a read that passed dm_move_events is non-empty: first_empty is the event count.  The move tables themselves are
+                        # posted (one byte per two samples instead of 16 per event) and segmented on the device; moptions['move_on_device'] = False /
+                        # DEEPMOD_MOVE_ON_DEVICE=0 posts the host-built tables through the event-table request instead
+                        first_empty = (mev_off[1:] - mev_off[:-1]).astype(np.int64)
+                        if hasattr(normalizer, 'post_move') and bool(moptions.get('move_on_device', os.environ.get('DEEPMOD_MOVE_ON_DEVICE', '1') != '0')):
+                            out.sig = normalizer.post_move(raw_parts, raw_off, move_parts, np.array(mv_offs, np.int64), np.array(firsts, np.int64), mev_off)
+                        else:
+                            out.sig = normalizer.post_arrays(raw_parts, raw_off, m_start, m_len, mev_off, first_empty, None, None)
+                        s_mean = s_stdv = None
+                    elif want_resident:
                         first_empty = np.empty(len(raw_off) - 1, np.int64)
                         _lib.check(lib.dm_signal_plan_batch(len(raw_off) - 1, raw_off.ctypes.data, mev_off.ctypes.data, m_start.ctypes.data, m_len.ctypes.data,
                                                             first_empty.ctypes.data))
@@ -736,6 +802,18 @@ def _sig_layout_res(n: int, n_raw: int, n_ev: int, with_fb: bool):
     return o
 
 
+def _sig_layout_move(n: int, n_raw: int, n_mv: int):
+    """request of the resident form for move reads: [raw i16 | raw_off i64 | ev_off i64 | mv_off i64 | first i64 | move u8] - inputs only"""
+    up = lambda v: -(-v // 64) * 64
+    o = {}
+    pos = 0
+    for name, nbytes in (('raw', 2 * n_raw), ('raw_off', 8 * (n + 1)), ('ev_off', 8 * (n + 1)), ('mv_off', 8 * (n + 1)), ('first', 8 * n), ('move', n_mv)):
+        o[name] = pos
+        pos = up(pos + nbytes)
+    o['end'] = pos
+    return o
+
+
 class SignalResults:
     """GPU process: what the signal server threads hand to the batch loop - per resident request (feeder, number) the device block of its
     statistics, the range flag of dm_signal_event_stats_device and an error text.  The server registers a result when its call has returned (the block
@@ -815,28 +893,19 @@ class RemoteSignalNormalizer:
         self._res_files = [None, None]     # (mapping, size, path) of the two request files of the resident form
 
     # ---- resident form: post and go on ----
-    def post_arrays(self, raw_parts, raw_off, ev_start, ev_length, ev_off, first_empty, fb_mean=None, fb_stdv=None):
-        """Write a request of the resident form (dm_signal_event_stats_device) into one of this feeder's two request files and queue it: no wait for the
-        statistics - they stay on the device, the GPU process finds them under the returned (feeder, number) when the batch arrives.  The only wait is
-        for the file itself: request k reuses the file of request k - 2, which the server must have copied into its page-locked memory (its
-        acknowledgement; usually long there)."""
+    def _request_file(self, seq: int, nbytes: int):
+        """the request file of resident request `seq` (the file of request seq - 2, which the server must have copied), at least nbytes large"""
         import mmap
-        from . import _lib
-        seq = self._posted = self._posted + 1
         while seq - 2 > 0 and (seq - 2) not in self._acked:
             self._take_answer(block=True)
         self._acked.discard(seq - 2)
-        n = len(raw_off) - 1
-        n_raw, n_ev = int(raw_off[-1]), int(ev_off[-1])
-        with_fb = fb_mean is not None and fb_stdv is not None
-        o = _sig_layout_res(n, n_raw, n_ev, with_fb)
         files = self._res_files
         slot = seq % 2
         cur = files[slot]
-        if cur is None or cur[1] < o['end']:
+        if cur is None or cur[1] < nbytes:
             if cur is not None:
                 cur[0].close()
-            size = max(1 << 22, int(o['end'] * 1.5))
+            size = max(1 << 22, int(nbytes * 1.5))
             path = self.path + '_r%d' % slot
             fd = os.open(path, os.O_CREAT | os.O_RDWR, 0o600)
             try:
@@ -844,7 +913,37 @@ class RemoteSignalNormalizer:
                 cur = files[slot] = (mmap.mmap(fd, size), size, path)
             finally:
                 os.close(fd)
-        mm, size, path = cur
+        return cur
+
+    def post_move(self, raw_parts, raw_off, move_parts, mv_off, first, ev_off):
+        """post_arrays for move reads (dm_signal_move_stats_device): the move tables travel instead of (start, length) tables - the server's kernels
+        segment them.  ev_off: the cumulative Fastq lengths, the event count every read must have (the feeder has checked it: dm_move_events)."""
+        seq = self._posted = self._posted + 1
+        n = len(raw_off) - 1
+        n_raw, n_ev, n_mv = int(raw_off[-1]), int(ev_off[-1]), int(mv_off[-1])
+        o = _sig_layout_move(n, n_raw, n_mv)
+        mm, size, path = self._request_file(seq, o['end'])
+        np.concatenate([np.asarray(p) for p in raw_parts], out=np.frombuffer(mm, np.int16, n_raw, o['raw']), casting='same_kind')
+        np.frombuffer(mm, np.int64, n + 1, o['raw_off'])[:] = raw_off
+        np.frombuffer(mm, np.int64, n + 1, o['ev_off'])[:] = ev_off
+        np.frombuffer(mm, np.int64, n + 1, o['mv_off'])[:] = mv_off
+        np.frombuffer(mm, np.int64, n, o['first'])[:] = first
+        if n_mv:
+            np.concatenate([np.asarray(p) for p in move_parts], out=np.frombuffer(mm, np.uint8, n_mv, o['move']), casting='same_kind')
+        self.requests.put(('mov', self.wid, path, size, n, n_raw, n_ev, seq, n_mv))
+        return (self.wid, seq)
+
+    def post_arrays(self, raw_parts, raw_off, ev_start, ev_length, ev_off, first_empty, fb_mean=None, fb_stdv=None):
+        """Write a request of the resident form (dm_signal_event_stats_device) into one of this feeder's two request files and queue it: no wait for the
+        statistics - they stay on the device, the GPU process finds them under the returned (feeder, number) when the batch arrives.  The only wait is
+        for the file itself: request k reuses the file of request k - 2, which the server must have copied into its page-locked memory (its
+        acknowledgement; usually long there)."""
+        seq = self._posted = self._posted + 1
+        n = len(raw_off) - 1
+        n_raw, n_ev = int(raw_off[-1]), int(ev_off[-1])
+        with_fb = fb_mean is not None and fb_stdv is not None
+        o = _sig_layout_res(n, n_raw, n_ev, with_fb)
+        mm, size, path = self._request_file(seq, o['end'])
         np.concatenate([np.asarray(p) for p in raw_parts], out=np.frombuffer(mm, np.int16, n_raw, o['raw']), casting='same_kind')
         np.frombuffer(mm, np.int64, n + 1, o['raw_off'])[:] = raw_off
         np.frombuffer(mm, np.int64, n + 1, o['ev_off'])[:] = ev_off
@@ -958,7 +1057,9 @@ def signal_server(requests, answers, device: int, stats=None, results: Optional[
                                                                        go back into the request file;
       ('res', wid, path, file size, n, n_raw, n_ev, number, with_fb)  resident form (round 6): answers[wid] gets ('ack', number, error) as soon
                                                                        as the request file has been copied (the feeder may write it again), the
-                                                                       statistics go into a device block registered in `results` under (wid, number).
+                                                                       statistics go into a device block registered in `results` under (wid, number);
+      ('mov', wid, path, file size, n, n_raw, n_ev, number, n_mv)     resident form for move reads (detect --move): move tables instead of event
+                                                                       tables (dm_signal_move_stats_device), answered like 'res'.
     Inputs are copied to page-locked memory (uploads from the shared-memory mapping itself are slow)."""
     import mmap
     from . import _lib, model as dm, signal as dmsignal
@@ -971,8 +1072,11 @@ def signal_server(requests, answers, device: int, stats=None, results: Optional[
             req = requests.get()
             if req is None:
                 return
-            resident = req[0] == 'res'
-            if resident:
+            resident = req[0] in ('res', 'mov')
+            moved = req[0] == 'mov'
+            if moved:
+                _, wid, path, size, n, n_raw, n_ev, seq, n_mv = req
+            elif resident:
                 _, wid, path, size, n, n_raw, n_ev, seq, with_fb = req
             else:
                 wid, path, size, n, n_raw, n_ev = req
@@ -991,7 +1095,7 @@ def signal_server(requests, answers, device: int, stats=None, results: Optional[
                     finally:
                         os.close(fd)
                 mm = maps[path][0]
-                o = _sig_layout_res(n, n_raw, n_ev, with_fb) if resident else _sig_layout(n, n_raw, n_ev)
+                o = _sig_layout_move(n, n_raw, n_mv) if moved else _sig_layout_res(n, n_raw, n_ev, with_fb) if resident else _sig_layout(n, n_raw, n_ev)
                 n_in = o['end'] if resident else o['in_end']
                 if pinned is None or pinned.nbytes < o['end']:
                     if pinned is not None:
@@ -1006,14 +1110,23 @@ def signal_server(requests, answers, device: int, stats=None, results: Optional[
                     acked = True
                     blk = blocks.take(12 * max(n_ev, 1))
                     flags = ctypes.c_int32(0)
-                    rc = lib.dm_signal_event_stats_device(norm._h, n, base + o['raw'], base + o['raw_off'], base + o['ev_start'], base + o['ev_length'],
-                                                          base + o['ev_off'], base + o['first_empty'], (base + o['fb_mean']) if with_fb else None,
-                                                          (base + o['fb_stdv']) if with_fb else None, blk.ptr, None, ctypes.byref(flags))
+                    bad = 0
+                    if moved:
+                        status = np.empty(n, np.int32)
+                        rc = lib.dm_signal_move_stats_device(norm._h, n, base + o['raw'], base + o['raw_off'], base + o['move'], base + o['mv_off'],
+                                                             base + o['first'], base + o['ev_off'], blk.ptr, status.ctypes.data, None, ctypes.byref(flags))
+                        bad = int(np.count_nonzero(status)) if rc == 0 else 0
+                    else:
+                        rc = lib.dm_signal_event_stats_device(norm._h, n, base + o['raw'], base + o['raw_off'], base + o['ev_start'], base + o['ev_length'],
+                                                              base + o['ev_off'], base + o['first_empty'], (base + o['fb_mean']) if with_fb else None,
+                                                              (base + o['fb_stdv']) if with_fb else None, blk.ptr, None, ctypes.byref(flags))
                     if stats is not None:
                         stats['signal_server_call'] += time.perf_counter() - t1
                         stats['signal_server_copy'] += t1 - t0
                     if rc != 0:
                         results.put((wid, seq), None, 0, 'signal stage: ' + _lib.last_error())
+                    elif bad:           # the feeder posts only reads that passed dm_move_events: the device disagrees with the host definition
+                        results.put((wid, seq), None, 0, 'signal stage: the device fails %d move tables that dm_move_events passed' % bad)
                     else:
                         results.put((wid, seq), blk, int(flags.value), None)
                         blk = None              # the batch loop owns it now
@@ -1042,6 +1155,9 @@ def signal_server(requests, answers, device: int, stats=None, results: Optional[
                 stats['signal_requests'] += 1
                 stats['signal_samples'] += n_raw
                 stats['signal_events'] += n_ev
+                if moved:
+                    stats['signal_move_requests'] += 1
+                    stats['signal_move_bytes'] += n_mv
     finally:
         for mm, _ in maps.values():
             mm.close()

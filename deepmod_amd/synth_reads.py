@@ -105,10 +105,15 @@ def _revcomp(s: str) -> str:
 
 
 def synthetic_raw_read(rng, genome: str, chrom: str, read_id: str, min_len=400, max_len=1500, p_sub=0.06, p_ins=0.02,
-                       p_del=0.02, max_clip=12, p_stay=0.25) -> Dict:
+                       p_del=0.02, max_clip=12, p_stay=0.25, move: bool = False, twin: bool = False) -> Dict:
     """-> {'read_id', 'raw' int16, 'events_data', 'sam' line}: a truth alignment with substitutions / indels / soft
     clips on either strand; one basecaller event (plus `stay` continuation events, move == 0) per read base; the raw
-    signal is 520 + 75 * (level of the base + noise) DAC counts with ~8 samples per event."""
+    signal is 520 + 75 * (level of the base + noise) DAC counts with ~8 samples per event.
+
+    move=True: the same kind of read as a basecaller with MOVE TABLES writes it (Guppy and later) - one segment per base whose
+    boundaries fall on first_sample_template + 2 i, the last one running to the end of the signal; the read carries 'move' (uint8, one
+    entry per two samples from first_sample_template on), 'first_sample_template' and 'fq_seq' instead of 'events_data'.  twin=True adds
+    'twin': the same read with an event table - one move == 1 event per segment, the same start / length, model_state 'NN' + base + 'NN'."""
     strand = '+' if rng.random() < 0.5 else '-'
     span = int(rng.integers(min_len, max_len + 1))
     start = int(rng.integers(0, len(genome) - span - 1))
@@ -146,6 +151,22 @@ def synthetic_raw_read(rng, genome: str, chrom: str, read_id: str, min_len=400, 
     ev_rows, chunks = [], []
     cursor = int(rng.integers(20, 200))
     chunks.append(np.round(520 + 75 * rng.normal(0, 1.0, cursor)))
+    if move:
+        first = cursor
+        for b in basecall:
+            ln = 2 * (1 + int(rng.geometric(0.3)))          # even: the next boundary is on first + 2 i again (~ 8.7 samples per base)
+            lvl = rng.normal(_MU[b], 0.3, ln)
+            chunks.append(np.round(520 + 75 * lvl))
+            ev_rows.append((float(lvl.mean()), float(lvl.std()), cursor, ln, 'NN' + b + 'NN', 1))
+            cursor += ln
+        raw = np.clip(np.concatenate(chunks), -32768, 32767).astype(np.int16)
+        table = np.zeros((len(raw) - first) // 2, np.uint8)
+        table[[(r[2] - first) // 2 for r in ev_rows]] = 1
+        sam = '\t'.join([read_id, '0' if strand == '+' else '16', chrom, str(start + 1), '60', cigar, '*', '0', '0', samseq, '*'])
+        rd = {'read_id': read_id, 'raw': raw, 'move': table, 'first_sample_template': first, 'fq_seq': basecall, 'sam': sam}
+        if twin:
+            rd['twin'] = {'read_id': read_id, 'raw': raw, 'events_data': np.array(ev_rows, dtype=rawreads.EVENTS_DATA_DTYPE), 'sam': sam}
+        return rd
     for b in basecall:
         n_sub = 1 + int(rng.random() < p_stay) + int(rng.random() < p_stay * 0.3)
         for k in range(n_sub):
@@ -162,32 +183,40 @@ def synthetic_raw_read(rng, genome: str, chrom: str, read_id: str, min_len=400, 
 
 
 def write_synthetic_raw_run(out_dir: str, n_reads: int = 40, reads_per_file: int = 5, genome_len: int = 30000, seed: int = 1,
-                            chrom: str = 'NC_000913.3', part: int = 0, **read_kw):
+                            chrom: str = 'NC_000913.3', part: int = 0, move: bool = False, twin_dir: str = None, **read_kw):
     """Raw containers + side-car SAM files + genome FASTA.  -> (container paths, fasta path).
     `part` > 0 writes another slice of the same run (same genome, its own reads and file names; the FASTA is part 0's),
-    so that a large run can be generated by several processes."""
+    so that a large run can be generated by several processes.
+    move=True: reads with move tables (synthetic_raw_read(move=True)) for `detect --move`; twin_dir: the same run once more with event
+    tables (the reads' twins, same file names under twin_dir) - both runs must give the same BED files."""
     from . import rawreads
-    os.makedirs(out_dir, exist_ok=True)
     genome = synthetic_genome(genome_len, seed)
+    dirs = [out_dir] + ([twin_dir] if move and twin_dir else [])
+    for d in dirs:
+        os.makedirs(d, exist_ok=True)
+        if part == 0:
+            with open(os.path.join(d, 'genome.fa'), 'w') as fh:
+                fh.write('>%s synthetic\n' % chrom)
+                for i in range(0, len(genome), 60):
+                    fh.write(genome[i:i + 60].lower() if (i // 60) % 7 == 3 else genome[i:i + 60])   # soft-masked stretches: upper-cased on load
+                    fh.write('\n')
     fasta = os.path.join(out_dir, 'genome.fa')
-    if part == 0:
-        with open(fasta, 'w') as fh:
-            fh.write('>%s synthetic\n' % chrom)
-            for i in range(0, len(genome), 60):
-                fh.write(genome[i:i + 60].lower() if (i // 60) % 7 == 3 else genome[i:i + 60])   # soft-masked stretches: upper-cased on load
-                fh.write('\n')
+    if move:
+        read_kw = dict(read_kw, move=True, twin=len(dirs) > 1)
     rng = np.random.default_rng(seed + 11 + 1000003 * part)
     files, batch = [], []
     for i in range(n_reads):
         batch.append(synthetic_raw_read(rng, genome, chrom, 'rawread_%05d' % i if part == 0 else 'rawread_p%d_%05d' % (part, i), **read_kw))
         if len(batch) == reads_per_file or i == n_reads - 1:
-            stem = os.path.join(out_dir, 'raw_%04d' % len(files) if part == 0 else 'raw_p%d_%04d' % (part, len(files)))
-            rawreads.save_raw_container(stem + rawreads.RAW_SUFFIX, batch)
-            with open(stem + '.sam', 'w') as fh:
-                fh.write('@SQ\tSN:%s\tLN:%d\n' % (chrom, len(genome)))
-                for rd in batch:
-                    fh.write(rd['sam'] + '\n')
-            files.append(stem + rawreads.RAW_SUFFIX)
+            name = 'raw_%04d' % len(files) if part == 0 else 'raw_p%d_%04d' % (part, len(files))
+            for d in dirs:
+                stem = os.path.join(d, name)
+                rawreads.save_raw_container(stem + rawreads.RAW_SUFFIX, batch if d == out_dir else [rd['twin'] for rd in batch])
+                with open(stem + '.sam', 'w') as fh:
+                    fh.write('@SQ\tSN:%s\tLN:%d\n' % (chrom, len(genome)))
+                    for rd in batch:
+                        fh.write(rd['sam'] + '\n')
+            files.append(os.path.join(out_dir, name) + rawreads.RAW_SUFFIX)
             batch = []
     return files, fasta
 

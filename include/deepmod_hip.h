@@ -338,6 +338,17 @@ int dm_signal_event_stats_device(dm_signal* s, int64_t n_reads, const int16_t* r
                                  const uint64_t* ev_length, const int64_t* ev_off, const int64_t* first_empty, const float* fb_mean, const float* fb_stdv,
                                  float* d_ev3, double* norm6, int32_t* flags);
 
+/* The resident form for reads with MOVE TABLES (detect --move): the event tables are built on the device.  move / mv_off / first as dm_move_events takes
+ * them (batch-wide), ev_off [n_reads + 1] = the cumulative Fastq lengths (the event count every read must have).  A segmentation pass (per-chunk boundary
+ * counts, a scan per read, one store per boundary) writes the handle's (start, length) tables, then the kernels of dm_signal_event_stats_device run
+ * unchanged on the same stream; a read's normalisation slice is [first, samples).  status [n_reads] (host, out) = dm_move_events' status of every read,
+ * computed on the device: a read with a non-zero status writes nothing outside its own slots and contributes no statistics (its rows of d_ev3 are
+ * NaN, NaN, 0).  Every read needs at least one sample and the batch at least one expected event.  flags: as dm_signal_event_stats_device.
+ * dm_signal_move_chunk: table bytes one workgroup of the segmentation kernels takes (a read's chunks start at its table's 16-byte-aligned base). */
+int dm_signal_move_stats_device(dm_signal* s, int64_t n_reads, const int16_t* raw, const int64_t* raw_off, const uint8_t* move, const int64_t* mv_off,
+                                const int64_t* first, const int64_t* ev_off, float* d_ev3, int32_t* status, double* norm6, int32_t* flags);
+int64_t dm_signal_move_chunk(void);
+
 /* ---- SAM record -> per-base alignment table (host code, no GPU needed) ---------------------
  * Replaces the alignment walk of handle_record, myDetect.py:515-714: clip stripping, one row per M/I/D/N/=/X
  * position, first/last-match trimming of table and event slice, '-' strand flip + complement, the CpG gap swap.
@@ -396,6 +407,18 @@ typedef struct dm_rowsbatch dm_rowsbatch;
 int64_t dm_events_merge(int64_t n_reads, int64_t n_events, const int64_t* ev_off, const double* mean, const double* stdv, const uint64_t* start,
                         const uint64_t* length, const uint32_t* model_state, int32_t ms_width, const int64_t* move, int64_t* mev_off,
                         float* m_mean, float* m_stdv, uint64_t* m_start, uint64_t* m_length, char* m_base);
+/* getEvent with --move (myDetect.py:136-153, MoveTable.py:7-54): the event tables of a container's reads from their basecaller move tables (uint8, back
+ * to back in `move`, read r = move[mv_off[r] .. mv_off[r+1])).  A boundary is every index i in 1 .. L-1 with move[i] == 1; event 0 starts at first[r]
+ * (first_sample_template), boundary i starts the next event at first[r] + 2 i (the reference's stride, :30-33), the last event ends at the read's last
+ * sample (raw_off[r+1] - raw_off[r] samples).  m_base is a copy of the Fastq bytes (fq, fq_off); a read has fq_off[r+1] - fq_off[r] events.  status[r]: */
+#define DM_MOVE_OK 0
+#define DM_MOVE_COUNT 1           /* boundaries != bases - 1: the reference is undefined (IndexError / uninitialised rows); decided first */
+#define DM_MOVE_OUTSIDE 2         /* first < 0, first >= samples, or the last boundary at or behind the read's end: an event outside the signal */
+/* A read with a non-zero status gets no events (mev_off[r+1] == mev_off[r]).  Outputs are sized for n_fq events.  Offsets are checked against
+ * n_move / n_fq before anything is read.  -> events written, or a negative code.  dm_signal_move_stats_device computes the same tables on the device. */
+int64_t dm_move_events(int64_t n_reads, int64_t n_move, const uint8_t* move, const int64_t* mv_off, const int64_t* first, const int64_t* raw_off,
+                       int64_t n_fq, const char* fq, const int64_t* fq_off, int64_t* mev_off, int32_t* status, uint64_t* m_start, uint64_t* m_length,
+                       char* m_base);
 dm_rowsbatch* dm_rows_create(char base);
 void dm_rows_destroy(dm_rowsbatch* h);
 int dm_rows_add_packed(dm_rowsbatch* h, int64_t n_reads, int64_t n_tx_rows, int64_t n_table_rows, int64_t n_events, int32_t n_contigs,
