@@ -21,13 +21,14 @@ gloo transport) - only the transport and the device calls are replaced, the shar
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import json
 import os
 import queue
 import threading
 import time
-from collections import defaultdict
+from collections import defaultdict, namedtuple
 from typing import Dict, Iterable, List, Optional, Tuple
 
 import numpy as np
@@ -259,380 +260,493 @@ def _c_arr(a, dtype):
     return np.ascontiguousarray(a, dtype=dtype)
 
 
-def _prepare_batch_c(moptions, files: List[str], make_normalizer=None, alloc=None) -> Prepared:
-    """prepare_batch with the per-read work behind the C ABI: one dm_events_merge per raw container, one signal request, one
-    dm_rows_add_raw / dm_rows_add_packed per input kind, dm_rows_info + dm_rows_emit straight into the hand-over arrays.
-    Same Prepared (rows, pos, flags, groups, errors) as the Python path below, which stays as the restatement the tests compare
-    with (tests/test_stream_feeders.py)."""
-    import ctypes
+def _option_on(moptions, key: str) -> bool:
+    """An on/off switch of the batch builder: moptions[key] wins, else DEEPMOD_<KEY> of the environment ('0' is off); on by default."""
+    return bool(moptions.get(key, os.environ.get('DEEPMOD_' + key.upper(), '1') != '0'))
+
+
+def _container_failed(out: Prepared, f5f: str, detail: str = '') -> None:
+    """A raw container (with `detail`: one read of it) that cannot be used: one line of the ledger, one of the log; the batch goes on without it."""
+    out.errors["Cannot open fast5 or other errors"].append(f5f)
+    print("Cannot open fast5 or other errors: {}{}".format(f5f, detail))
+
+
+class _BatchRefused(Exception):
+    """The batched signal call cannot take a read of this batch (events covering no signal): the per-read Python path builds the batch and reports it."""
+
+
+# the rows handle of a batch and what goes with it - keep: see _rows_handle; contigs: name -> index, srcs: source file of every read, both in the order of adding
+_Rows = namedtuple('_Rows', 'lib h keep contigs srcs')
+
+
+@contextlib.contextmanager
+def _rows_handle(lib, base: str):
+    """dm_rows_create ... dm_rows_destroy around a block, and the ONE owner of what the handle borrows: dm_rows_add_raw / dm_rows_add_packed keep the
+    pointers they get until emit, so a stage appends the Python objects behind every pointer to `keep` before its add call - no array is valid between
+    add and emit merely because some local is still alive.  Handle and list go when the block is left, on every path."""
+    from . import _lib
+    rows = _Rows(lib, lib.dm_rows_create(base.encode('ascii')), [], {}, [])
+    if not rows.h:
+        raise _lib.DeepModHipError("dm_rows_create: " + _lib.last_error())
+    try:
+        yield rows
+    finally:
+        lib.dm_rows_destroy(rows.h)
+        del rows.keep[:]
+
+
+# an open raw container with event tables: z the mapped members, meta one record per read, raw_off / ev_off i64[n + 1] (raw_off checked against the samples),
+# values = the ev_mean, ev_stdv (f64), ev_start, ev_length (u64) columns, move the ev_move column (i64)
+_EventContainer = namedtuple('_EventContainer', 'path z meta n raw_off ev_off n_ev model_state values move')
+# ... under --move: mv, mv_off, first, fq, fq_off are rawreads.MOVE_MEMBERS, all None for a container without move data
+_MoveContainer = namedtuple('_MoveContainer', 'path z meta n raw_off mv mv_off first fq fq_off', defaults=(None,) * 5)
+# what the signal stage gave for a batch: s_mean / s_stdv the statistics of every merged event (None: they stay on the device under `sig`), first_empty per read,
+# m_mean / m_stdv the basecaller's values for the events at or behind a first empty event (None: no read has one)
+_SignalStats = namedtuple('_SignalStats', 's_mean s_stdv first_empty m_mean m_stdv sig')
+
+
+def _open_raw_container(f5f: str):
+    """-> (mapped members, read metas, n, sample offsets) of a format-2 container, the offsets checked against the samples they index"""
+    from . import npzmap
+    z = npzmap.load(f5f, lazy=('ev_mean', 'ev_stdv'))
+    if 'format' not in z:
+        raise ValueError('format-1 raw container')
+    meta = json.loads(str(z['meta']))
+    n = len(meta)
+    ro = _c_arr(z['raw_off'], np.int64)
+    if len(ro) != n + 1 or ro[0] != 0 or (np.diff(ro) < 0).any() or ro[-1] > len(z['raw']):
+        raise ValueError('signal offsets of a damaged container')
+    return z, meta, n, ro
+
+
+def _open_event_container(f5f: str) -> _EventContainer:
+    """Open stage, event tables: path -> the columns dm_events_merge reads.  ValueError (or whatever the reader raises) for a damaged container."""
+    z, meta, n, ro = _open_raw_container(f5f)
+    eo = _c_arr(z['ev_off'], np.int64)
+    if len(eo) != n + 1:
+        raise ValueError('event offsets of a damaged container')
+    ms = _c_arr(z['ev_model_state'], z['ev_model_state'].dtype)
+    values = [_c_arr(z['ev_mean'], np.float64), _c_arr(z['ev_stdv'], np.float64), _c_arr(z['ev_start'], np.uint64), _c_arr(z['ev_length'], np.uint64)]
+    return _EventContainer(f5f, z, meta, n, ro, eo, max(int(eo[-1]), 0), ms, values, _c_arr(z['ev_move'], np.int64))
+
+
+def _open_move_container(f5f: str) -> _MoveContainer:
+    """Open stage, detect --move: path -> the members dm_move_events reads (rawreads.py).  A container without them is no error here: its reads get the
+    reference's reason one by one (_move_event_tables)."""
+    z, meta, n, ro = _open_raw_container(f5f)
+    if not all(k in z for k in rawreads.MOVE_MEMBERS):
+        return _MoveContainer(f5f, z, meta, n, ro)
+    if z['mv'].dtype != np.uint8 or z['fq'].dtype != np.uint8:
+        raise ValueError('move tables of a damaged container')
+    mvt, mvo, fst, fq, fqo = (_c_arr(z[k], dt) for k, dt in zip(rawreads.MOVE_MEMBERS, (np.uint8, np.int64, np.int64, np.uint8, np.int64)))
+    # (dm_move_events checks the order of the offsets and their ends against the arrays)
+    if len(mvo) != n + 1 or len(fqo) != n + 1 or len(fst) != n or (n and (mvo[0] != 0 or fqo[0] != 0)):
+        raise ValueError('move offsets of a damaged container')
+    return _MoveContainer(f5f, z, meta, n, ro, mvt, mvo, fst, fq, fqo)
+
+
+class _RawBatch:
+    """What the raw containers of a batch contribute, read after read in the order the signal request and dm_rows_add_raw see them: ids (None: a read without
+    events) and id_src per read; raw_parts, whose concatenation is the samples; the merged event tables m_start / m_len / m_base, written in place at `w`
+    container after container; under --move the move tables (move_parts, mv_offs, firsts), which travel to the signal stage themselves in the resident form.
+    The *_offs lists grow while containers are added, raw_off / ev_off are their int64 arrays (_raw_events).  merges: (container, its merged offsets, events,
+    position) of every dm_events_merge call - the record owns the arrays that call read, so _fallback_values can repeat it."""
+    __slots__ = ('use_move', 'ids', 'id_src', 'raw_parts', 'raw_offs', 'ev_offs', 'raw_off', 'ev_off', 'm_start', 'm_len', 'm_base', 'w', 'move_parts', 'mv_offs', 'firsts', 'merges')
+
+    def __init__(self, use_move: bool, cap_ev: int):
+        self.use_move, self.w, self.merges, self.raw_off, self.ev_off = use_move, 0, [], None, None
+        self.ids, self.id_src, self.raw_parts, self.raw_offs, self.ev_offs = [], [], [], [0], [0]
+        self.move_parts, self.mv_offs, self.firsts = [], [0], []
+        self.m_start, self.m_len, self.m_base = np.empty(max(cap_ev, 1), np.uint64), np.empty(max(cap_ev, 1), np.uint64), np.empty(max(cap_ev, 1), 'S1')
+
+    def tables_at_w(self):
+        """where the next container's merged (start, length, base) go"""
+        return self.m_start.ctypes.data + 8 * self.w, self.m_len.ctypes.data + 8 * self.w, self.m_base.ctypes.data + self.w
+
+
+def _merge_args(c: _EventContainer, mev_off: np.ndarray):
+    """the input arguments of dm_events_merge for container c (the value and table outputs follow them)"""
+    return (c.n, min(len(a) for a in c.values + [c.move, c.model_state]), c.ev_off.ctypes.data, *[a.ctypes.data for a in c.values],
+            c.model_state.ctypes.data, c.model_state.dtype.itemsize // 4, c.move.ctypes.data, mev_off.ctypes.data)
+
+
+def _merge_event_tables(lib, out: Prepared, opened: List[_EventContainer], b: _RawBatch) -> None:
+    """Event tables of the batch, event-table containers: one dm_events_merge per container (getEvent's merge, rawreads.py) appends its reads to `b`.
+    A read without events is a 'No events data' line of the ledger and keeps its place with id None."""
+    for c in opened:
+        mev_off = np.empty(c.n + 1, np.int64)
+        # (the basecaller's mean / stdv are merged later and only if a read of the batch has an empty event: _fallback_values)
+        got = lib.dm_events_merge(*_merge_args(c, mev_off), None, None, *b.tables_at_w())
+        if got < 0:             # offsets that decrease or run past the table: a damaged container, the batch goes on without it
+            _container_failed(out, c.path)
+            continue
+        b.merges.append((c, mev_off, got, b.w))
+        per_read = mev_off[1:] - mev_off[:-1]
+        for i, m in enumerate(c.meta):
+            rid = m['read_id'].replace(" ", ":::").replace("\t", "|||")
+            if per_read[i] == 0:
+                out.errors['No events data'].append(c.path)
+                rid = None
+            b.ids.append(rid)
+            b.id_src.append(c.path)
+        b.raw_parts.append(c.z['raw'][:int(c.raw_off[-1])])          # samples behind the last read's end would shift every later container's offsets
+        b.raw_offs.extend((b.raw_offs[-1] + c.raw_off[1:]).tolist())
+        b.ev_offs.extend((b.ev_offs[-1] + mev_off[1:]).tolist())
+        b.w += got
+
+
+def _move_event_tables(lib, out: Prepared, opened: List[_MoveContainer], b: _RawBatch) -> None:
+    """Event tables of the batch, detect --move: one dm_move_events per container segments its move tables (rawreads.py) and appends the reads that
+    passed to `b`, with their move tables for the resident form of the signal request."""
+    for c in opened:
+        if c.mv is None:                 # a container without move data: the reference's reason, per read
+            out.errors['No move data'].extend([c.path] * c.n)
+            continue
+        n, ro, mvt, mvo = c.n, c.raw_off, c.mv, c.mv_off
+        mev_off, status = np.empty(n + 1, np.int64), np.empty(max(n, 1), np.int32)
+        got = lib.dm_move_events(n, len(mvt), mvt.ctypes.data, mvo.ctypes.data, c.first.ctypes.data, ro.ctypes.data, len(c.fq), c.fq.ctypes.data,
+                                 c.fq_off.ctypes.data, mev_off.ctypes.data, status.ctypes.data, *b.tables_at_w())
+        if got < 0:
+            _container_failed(out, c.path)
+            continue
+        good = np.flatnonzero(status[:n] == 0)
+        for i in np.flatnonzero(status[:n] != 0):       # where the reference is undefined the read fails (rawreads.py)
+            _container_failed(out, c.path, " (read {}: move table, status {})".format(c.meta[i]['read_id'], status[i]))
+        for i in good:
+            b.ids.append(c.meta[i]['read_id'].replace(" ", ":::").replace("\t", "|||"))
+            b.id_src.append(c.path)
+        for lo, hi in ([(0, n)] if len(good) == n else [(i, i + 1) for i in good]):      # the usual case: the container's arrays as they lie, else read by read
+            b.raw_parts.append(c.z['raw'][int(ro[lo]):int(ro[hi])])
+            b.move_parts.append(mvt[int(mvo[lo]):int(mvo[hi])])
+            b.raw_offs.extend((b.raw_offs[-1] + (ro[lo + 1:hi + 1] - ro[lo])).tolist())
+            b.mv_offs.extend((b.mv_offs[-1] + (mvo[lo + 1:hi + 1] - mvo[lo])).tolist())
+        b.firsts.extend(c.first[good].tolist())
+        per_read = (mev_off[1:] - mev_off[:-1])[good]               # (a failed read has no events: mev_off is already the compacted table's)
+        b.ev_offs.extend((b.ev_offs[-1] + np.cumsum(per_read)).tolist())
+        b.w += got
+
+
+def _raw_events(lib, out: Prepared, raw_files: List[str], use_move: bool) -> _RawBatch:
+    """Raw containers stage: paths -> the reads, samples and merged event tables of the batch (the reference's get_Event_Signals up to the signal
+    normalisation, myDetect.py:392-465).  A container that cannot be opened or merged is reported and left out."""
+    opener = _open_move_container if use_move else _open_event_container       # detect --move: the events come from the basecaller move tables (rawreads.py)
+    opened = []
+    for f5f in raw_files:
+        try:
+            opened.append(opener(f5f))
+        except Exception:
+            _container_failed(out, f5f)
+    # the merged event tables of the whole batch, written in place container after container (no per-container pieces to concatenate)
+    b = _RawBatch(use_move, sum(len(c.fq) for c in opened if c.mv is not None) if use_move else sum(c.n_ev for c in opened))
+    (_move_event_tables if use_move else _merge_event_tables)(lib, out, opened, b)
+    b.m_start, b.m_len, b.m_base = b.m_start[:b.w], b.m_len[:b.w], b.m_base[:b.w]
+    b.raw_off, b.ev_off = np.array(b.raw_offs, np.int64), np.array(b.ev_offs, np.int64)
+    return b
+
+
+def _fallback_values(lib, b: _RawBatch):
+    """The basecaller's mean / stdv of every merged event of the batch (getEvent's rounding): needed only for events at or behind a read's
+    first empty event - the containers are merged once more, this time with the value columns."""
+    from . import _lib
+    if b.use_move:
+        raise RuntimeError('a move read with an empty event: dm_move_events admits none')
+    mm_, ms_ = np.empty(max(b.w, 1), np.float32), np.empty(max(b.w, 1), np.float32)
+    for c, mev_off, got, at in b.merges:
+        a_, b_ = np.empty(c.n_ev, np.float32), np.empty(c.n_ev, np.float32)
+        scratch = (np.empty(c.n_ev, np.uint64), np.empty(c.n_ev, np.uint64), np.empty(c.n_ev, 'S1'))
+        if lib.dm_events_merge(*_merge_args(c, mev_off), a_.ctypes.data, b_.ctypes.data, scratch[0].ctypes.data, scratch[1].ctypes.data, scratch[2].ctypes.data) != got:
+            raise _lib.DeepModHipError('dm_events_merge: ' + _lib.last_error())
+        mm_[at:at + got], ms_[at:at + got] = a_[:got], b_[:got]
+    return mm_[:b.w], ms_[:b.w]
+
+
+def _signal_request(lib, moptions, normalizer, b: _RawBatch, only_raw: bool, select_base: bool, rows_on_device: bool) -> _SignalStats:
+    """Signal stage: the one request of the batch (normalisation + event statistics), in one of four ways: resident with the move tables segmented on the
+    device, resident with host-built tables, resident, synchronous.  _BatchRefused when the batched call cannot take a read."""
+    from . import _lib
+    # resident form (round 6): a batch of raw containers only, whose rows are built on the device anyway - the signal request is POSTED
+    # (samples + event tables into the server's request file, no wait) and its statistics never come back: the feeder needs only
+    # first_empty (host arithmetic, dm_signal_plan_batch) to walk its alignments while the signal kernels run
+    want_resident = (hasattr(normalizer, 'post_arrays') and only_raw and select_base and rows_on_device and _option_on(moptions, 'stats_on_device'))
+    raw_off, mev_off, m_start, m_len = b.raw_off, b.ev_off, b.m_start, b.m_len
+    per_read = mev_off[1:] - mev_off[:-1]
+    s_mean = s_stdv = m_mean = m_stdv = sig = None
+    try:
+        if want_resident and b.use_move:
+            # every event of a read that passed dm_move_events is non-empty: first_empty is the event count.  The move tables themselves are
+            # posted (one byte per two samples instead of 16 per event) and segmented on the device; moptions['move_on_device'] = False /
+            # DEEPMOD_MOVE_ON_DEVICE=0 posts the host-built tables through the event-table request instead
+            first_empty = per_read.astype(np.int64)
+            if hasattr(normalizer, 'post_move') and _option_on(moptions, 'move_on_device'):
+                sig = normalizer.post_move(b.raw_parts, raw_off, b.move_parts, np.array(b.mv_offs, np.int64), np.array(b.firsts, np.int64), mev_off)
+            else:
+                sig = normalizer.post_arrays(b.raw_parts, raw_off, m_start, m_len, mev_off, first_empty, None, None)
+        elif want_resident:
+            first_empty = np.empty(len(raw_off) - 1, np.int64)
+            _lib.check(lib.dm_signal_plan_batch(len(raw_off) - 1, raw_off.ctypes.data, mev_off.ctypes.data, m_start.ctypes.data, m_len.ctypes.data,
+                                                first_empty.ctypes.data))
+            if bool((first_empty < per_read).any()):
+                m_mean, m_stdv = _fallback_values(lib, b)
+            sig = normalizer.post_arrays(b.raw_parts, raw_off, m_start, m_len, mev_off, first_empty, m_mean, m_stdv)
+        else:
+            s_mean, s_stdv, first_empty = normalizer.event_stats_arrays(b.raw_parts, raw_off, m_start, m_len, mev_off)
+            if bool((np.asarray(first_empty) < per_read).any()):
+                m_mean, m_stdv = _fallback_values(lib, b)
+    except _lib.DeepModHipError as exc:
+        # a read the batched signal call cannot take (events covering no signal): the per-read Python path reports it
+        raise _BatchRefused() from exc
+    return _SignalStats(s_mean, s_stdv, first_empty, m_mean, m_stdv, sig)
+
+
+def _add_alignments(rows: _Rows, out: Prepared, moptions, raw_files: List[str], b: _RawBatch, st: _SignalStats) -> None:
+    """Alignment stage (myDetect.py:488-715): the reads of `b` and their statistics -> alignment records (the reference's own aligner call when the binary is
+    on PATH, else the side-car .sam files) -> one dm_rows_add_raw, which walks them and plans the feature rows (get_Feature, :839-903)."""
     from . import _lib, detect, readmap
+    mev_off, contigs = b.ev_off, rows.contigs
+    f5data = {}
+    for gi, rid in enumerate(b.ids):
+        if rid is None:
+            continue
+        if rid in f5data:
+            print('Duplicate id', rid, b.id_src[gi])
+        call = b.m_base[mev_off[gi]:mev_off[gi + 1]].tobytes().decode('ascii', 'replace') if moptions.get('Ref') else ''
+        f5data[rid] = (call, gi, None, b.id_src[gi], (0, 0))
+    align_info = detect._alignment_lines(moptions, {'Error': out.errors}, raw_files, f5data)
+    if align_info is None:
+        for f5k in sorted(f5data.keys()):
+            out.errors["Cannot running aligment"].append(f5data[f5k][3])
+        return
+    sp_param = {'f5data': f5data, 'ref_info': {}, 'f5status': "", 'line': ""}
+    f5align = readmap.parse_sam(moptions, {'Error': out.errors}, sp_param, align_info, f5data)
+    recs = list(f5align.items())
+    nrec = len(recs)
+    seqs = readmap.read_fasta(moptions['Ref']) if moptions.get('Ref') else {}
+    ref_bytes = _REF_BYTES.setdefault(moptions.get('Ref'), {})
+    flag = np.zeros(nrec, np.int32); pos1 = np.zeros(nrec, np.int64); rlen = np.zeros(nrec, np.int64)
+    cidx = np.full(nrec, -1, np.int32); ev_read = np.zeros(nrec, np.int32); skip = np.zeros(nrec, np.uint8)
+    cig_b, seq_b = [], []
+    for i, (qname, (mapq, fl, rname, ps, cigar, seq)) in enumerate(recs):
+        flag[i], pos1[i], ev_read[i] = fl, ps, f5data[qname][1]
+        cig_b.append(cigar.encode('ascii')); seq_b.append(seq.encode('ascii'))
+        rlen[i] = len(seq_b[-1])
+        if (not moptions.get('ConUnk', True)) and any(ch in rname for ch in '_-/:'):
+            skip[i] = 1
+        if rname not in contigs:
+            contigs[rname] = len(contigs)
+        cidx[i] = contigs[rname]
+        if rname in seqs and rname not in ref_bytes:
+            ref_bytes[rname] = seqs[rname].encode('ascii')
+        if rname not in seqs:
+            print('Fatal Error!!! cannot find the chrosome sequence %s' % rname)
+    names = sorted(contigs, key=contigs.get)
+    nct = len(names)
+    ref_used = [ref_bytes.get(nm) for nm in names]
+    ref_ptr = (ctypes.c_char_p * max(nct, 1))(*ref_used)
+    ref_len = np.array([len(ref_bytes[nm]) if nm in ref_bytes else 0 for nm in names] or [0], np.int64)
+    cig_ptr = (ctypes.c_char_p * max(nrec, 1))(*cig_b)
+    seq_ptr = (ctypes.c_char_p * max(nrec, 1))(*seq_b)
+    region = [mr for mr in moptions.get('region', [[None, None, None]])]
+    any_all = any(mr[0] in ['', None] and mr[1] in ['', None] and mr[2] in ['', None] for mr in region)
+    if any_all:
+        region = []
+    elif not region:
+        skip[:] = 1          # an EMPTY region list matches nothing (myDetect.py:548-556 leaves isinreg False): n_region = 0 below means "no filter"
+    rg_c = np.array([(-1 if mr[0] in ['', None] else contigs.get(mr[0], 0x7fffffff)) for mr in region] or [0], np.int32)   # a contig no record of the batch names: matches nothing
+    rg_lo = np.array([(-1 if mr[1] in ['', None] else int(mr[1])) for mr in region] or [0], np.int64)
+    rg_hi = np.array([(-1 if mr[2] in ['', None] else int(mr[2])) for mr in region] or [0], np.int64)
+    rows.keep.extend([flag, pos1, rlen, cidx, ev_read, skip, cig_b, seq_b, ref_used, ref_ptr, ref_len, cig_ptr, seq_ptr, mev_off, st.m_mean, st.m_stdv,
+                      b.m_len, b.m_base, st.s_mean, st.s_stdv, st.first_empty, rg_c, rg_lo, rg_hi])
+    ptr = lambda a: None if a is None else a.ctypes.data
+    _lib.check(rows.lib.dm_rows_add_raw(rows.h, nrec, flag.ctypes.data, pos1.ctypes.data, cig_ptr, seq_ptr, rlen.ctypes.data, cidx.ctypes.data,
+                                        ev_read.ctypes.data, skip.ctypes.data, nct, ref_ptr, ref_len.ctypes.data, len(mev_off) - 1, len(b.m_len), mev_off.ctypes.data,
+                                        ptr(st.m_mean), ptr(st.m_stdv), b.m_len.ctypes.data, b.m_base.ctypes.data, ptr(st.s_mean), ptr(st.s_stdv),
+                                        st.first_empty.ctypes.data, len(region), rg_c.ctypes.data, rg_lo.ctypes.data, rg_hi.ctypes.data))
+    rows.srcs.extend(f5data[q][3] for q, _ in recs)
+    for nm in names:
+        if nm in ref_bytes:
+            out.contig_len[nm] = len(ref_bytes[nm])
+
+
+def _add_feature_containers(rows: _Rows, out: Prepared, files: List[str]) -> None:
+    """Feature containers stage: every other file of the batch enters at the prediction step (the arguments of mPredict1, myDetect.py:787-834) -
+    predstore.load_packed, then one dm_rows_add_packed per container.  out.timing['load'] covers the reading, ['rows'] the rest."""
+    from . import _lib
+    contigs, strands_c = rows.contigs, {'+': 0, '-': 1}
+    t0 = time.perf_counter()
+    for cf in files:
+        if cf.endswith(rawreads.RAW_SUFFIX):
+            continue
+        try:
+            pk = predstore.load_packed(cf)
+        except Exception:
+            out.errors["Cannot open container"].append(cf)
+            continue
+        t1 = time.perf_counter()
+        out.timing['load'] += t1 - t0
+        meta = pk['reads']
+        n = len(meta)
+        if n:
+            for m in meta:
+                if m['chr'] not in contigs:
+                    contigs[m['chr']] = len(contigs)
+            row_off, bmi_off, ev_off = (_c_arr(pk[k], np.int64) for k in ('row_off', 'bmi_off', 'ev_off'))
+            tx, refbasei = _c_arr(pk['tx'], np.float32), _c_arr(pk['refbasei'], np.int64)
+            refbase, readbase, evbase = (_c_arr(pk[k], 'S1') for k in ('refbase', 'readbase', 'evbase'))
+            arrs = [row_off, bmi_off, ev_off, tx, refbase, readbase, refbasei, evbase,
+                    np.array([m['start_clip'] for m in meta], np.int64), np.array([m['end_clip'] for m in meta], np.int64),
+                    np.array([contigs[m['chr']] for m in meta], np.int32), np.array([strands_c[m['strand']] for m in meta], np.int32)]
+            rows.keep.append(arrs)
+            n_tab = min(len(refbase), len(readbase), len(refbasei))
+            if (min(len(row_off), len(bmi_off), len(ev_off)) != n + 1 or tx.ndim != 2 or tx.shape[1] != 7 or
+                    rows.lib.dm_rows_add_packed(rows.h, n, len(tx), n_tab, len(evbase), len(contigs), *[a.ctypes.data for a in arrs]) != 0):
+                # offset tables that do not fit their arrays (a truncated / damaged container): the file is reported, the batch goes on
+                out.errors["Cannot open container"].append(cf)
+                print("Cannot open container: %s (%s)" % (cf, _lib.last_error() or 'offset tables of the wrong length'))
+                continue
+            rows.srcs.extend([cf] * n)
+        for c, ln in pk.get('contig_len', {}).items():
+            out.contig_len[c] = max(out.contig_len.get(c, 0), int(ln))
+        t0 = time.perf_counter()
+        out.timing['rows'] += t0 - t1
+
+
+def _rows_info(rows: _Rows, out: Prepared, compact: bool):
+    """Info and ledger stage: dm_rows_info -> the sizes (R feature rows, T position entries, S windows on a base of interest), the ledger line or the
+    log lines of every read that failed (myDetect.py:702-705, :826-828) and the read / window counts of the batch."""
+    from . import _lib
+    srcs = rows.srcs
+    nreads = len(srcs)
+    info = np.zeros((max(nreads, 1), 8), np.int64)
+    mism = np.zeros((20, 4), np.int64)
+    R, T, S, nm = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    if rows.lib.dm_rows_info(rows.h, ctypes.byref(R), ctypes.byref(T), ctypes.byref(S), info.ctypes.data, mism.ctypes.data, 20, ctypes.byref(nm)) < 0:
+        raise _lib.DeepModHipError("dm_rows_info: " + _lib.last_error())
+    for i in range(nreads):
+        st = int(info[i, 0])
+        if st in _ROWS_ERRORS:
+            out.errors[_ROWS_ERRORS[st]].append(srcs[i])
+        elif st == 3:
+            print("Errorfast5 " + srcs[i])
+            print('match-Error!!! no first and/or last match', srcs[i])
+    for j in range(min(int(nm.value), 20)):
+        print('Error Does not match: read %d of the batch (%s), table row %d, event %d, %d bases differ'
+              % (mism[j, 0], srcs[int(mism[j, 0])], mism[j, 1], mism[j, 2], mism[j, 3]))
+    R, T, S = int(R.value), int(T.value), int(S.value)
+    if compact:
+        T = S + (T - R)                 # [S windows on a base of interest | extras]
+    ok = info[:nreads, 0] == 0
+    out.n_reads = int(ok.sum())
+    out.n_windows = int(info[:nreads, 3][ok].sum())
+    out.n_rows = R
+    return R, T, S
+
+
+def _heap_alloc(R: int, T: int, S: int = 0, dev=None):
+    """`alloc` of a batch that stays in this process: the tuples a feeder's alloc returns (feeder_process_main), from the heap"""
+    if dev is not None:
+        return (np.empty((max(dev[0], 1), 3), np.float32), np.empty(R, np.uint8), np.empty((dev[1], 4), np.int64), np.empty(T, np.int64), np.empty(T, np.uint8),
+                np.empty(S, np.int32))
+    return (np.empty((R, 7), np.float32), np.empty(T, np.int64), np.empty(T, np.uint8)) + ((np.empty(S, np.int32),) if S else ())
+
+
+def _allocate(rows: _Rows, out: Prepared, alloc, R: int, T: int, S: int, compact: bool, rows_on_device: bool) -> None:
+    """Allocate stage: the hand-over arrays of a batch of R > 0 rows, as fields of `out`, straight in the hand-over slot when `alloc` is given.  Four
+    shapes: rows | pos | flags (classic); the same with sel (compact); ev3 | code | rdesc | pos | flags | sel (device form); the same without ev3
+    (resident form).  alloc(R, T), alloc(R, T, S) and alloc(R, T, S, dev=(events, reads)) return them in that order."""
+    from . import _lib
+    # device form (round 5): a batch of raw reads only hands over (mean, stdv, length) per event, a class byte per row and a descriptor per
+    # read; the [R][7] matrix is built on the device.  moptions['rows_on_device'] = False / DEEPMOD_ROWS_ON_DEVICE=0: rows on the host as before
+    dev_form = None
+    resident = out.sig is not None
+    if compact and (resident or rows_on_device):
+        ne, nr = ctypes.c_int64(), ctypes.c_int64()
+        if rows.lib.dm_rows_device_info(rows.h, ctypes.byref(ne), ctypes.byref(nr)) == 1:
+            dev_form = (0 if resident else int(ne.value), int(nr.value))
+    if resident and dev_form is None:
+        raise _lib.DeepModHipError('a batch whose statistics stay on the device must be a batch of raw reads')
+    alloc = alloc or _heap_alloc
+    if dev_form is not None:
+        out.ev3, out.code, out.rdesc, out.pos, out.flags, sel = alloc(R, T, S, dev=dev_form)
+        out.sel = sel if S else np.zeros(0, np.int32)
+        if resident:
+            out.ev3 = None
+        out.rows = None
+    else:
+        got = alloc(R, T, S) if compact else alloc(R, T)
+        out.rows, out.pos, out.flags = got[:3]
+        out.sel = (got[3] if S else np.zeros(0, np.int32)) if compact else None
+
+
+def _emit(rows: _Rows, out: Prepared, compact: bool) -> None:
+    """Emit stage: dm_rows_emit* writes the allocated arrays in the form _allocate chose, reads grouped by (contig in name order, strand); then the groups,
+    the lower bounds of the contig lengths and the range flag (which classifier kernel takes the batch) are read back."""
+    from . import _lib
+    lib, h, contigs = rows.lib, rows.h, rows.contigs
+    names = sorted(contigs, key=contigs.get)
+    rank = np.empty(max(len(names), 1), np.int32)
+    rank[np.argsort(np.array(names, dtype=object), kind='stable') if names else []] = np.arange(len(names), dtype=np.int32)
+    clen = np.zeros(max(len(names), 1), np.int64)
+    groups = np.zeros((2 * max(len(names), 1), 8), np.int64)
+    in_range = ctypes.c_int32(1)
+    sel_dummy = np.zeros(1, np.int32)
+    sel_ptr = (out.sel.ctypes.data if len(out.sel) else sel_dummy.ctypes.data) if compact else None
+    tail = (out.pos.ctypes.data, out.flags.ctypes.data, groups.ctypes.data, len(groups), clen.ctypes.data, len(clen), ctypes.byref(in_range))
+    if out.sig is not None:
+        ng = lib.dm_rows_emit_resident(h, rank.ctypes.data, out.code.ctypes.data, out.rdesc.ctypes.data, sel_ptr, *tail)
+    elif out.ev3 is not None:
+        ng = lib.dm_rows_emit_device(h, rank.ctypes.data, out.ev3.ctypes.data, out.code.ctypes.data, out.rdesc.ctypes.data, sel_ptr, *tail)
+    else:
+        ng = lib.dm_rows_emit(h, rank.ctypes.data, out.rows.ctypes.data, sel_ptr, *tail)
+    if ng < 0:
+        raise _lib.DeepModHipError("dm_rows_emit: " + _lib.last_error())
+    out.groups = [(names[int(g[0])], '+-'[int(g[1])]) + tuple(int(v) for v in (g[2:8] if compact else g[2:6])) for g in groups[:ng]]
+    for i, nmn in enumerate(names):
+        if clen[i] > out.contig_len.get(nmn, 0):
+            out.contig_len[nmn] = int(clen[i])        # lower bound when no reference length is known
+    out.f32 = not bool(in_range.value)
+
+
+def _prepare_batch_c(moptions, files: List[str], make_normalizer=None, alloc=None) -> Prepared:
+    """prepare_batch with the per-read work behind the C ABI, as the stages above: one dm_events_merge / dm_move_events per raw
+    container, one signal request, one dm_rows_add_raw / dm_rows_add_packed per input kind, dm_rows_info + dm_rows_emit straight into the hand-over
+    arrays.  Same Prepared (rows, pos, flags, groups, errors) as the Python path below, which stays as the restatement the tests compare with
+    (tests/test_stream_feeders.py)."""
+    from . import _lib
     lib = _lib.load()
     out = Prepared()
     out.files = list(files)
-    base = moptions['Base']
-    h = lib.dm_rows_create(base.encode('ascii'))
-    if not h:
-        raise _lib.DeepModHipError("dm_rows_create: " + _lib.last_error())
-    keep = []                       # arrays the handle borrows until emit
-    contigs: Dict[str, int] = {}
-    srcs: List[str] = []            # source file of every read, in the order the reads were added
-    strands_c = {'+': 0, '-': 1}
+    # compact form unless the caller wants every window classified (moptions['select_base'] = False / DEEPMOD_SELECT_BASE=0)
+    compact, rows_on_device = _option_on(moptions, 'select_base'), _option_on(moptions, 'rows_on_device')
+    raw_files = [f for f in files if f.endswith(rawreads.RAW_SUFFIX)]
     try:
-        t0 = time.perf_counter()
-        raw_files = [f for f in files if f.endswith(rawreads.RAW_SUFFIX)]
-        if raw_files:
-            from . import npzmap
-            normalizer = make_normalizer() if make_normalizer else None
-            if normalizer is None:
-                from . import signal as dmsignal
-                normalizer = dmsignal.SignalNormalizer(int(moptions.get('device', 0)))
-            ids, id_src, raw_parts, raw_offs, ev_offs = [], [], [], [0], [0]
-            use_move = bool(moptions.get('move'))       # detect --move: the events come from the basecaller move tables (rawreads.py)
-            move_parts, mv_offs, firsts = [], [0], []   # ... which travel to the signal stage themselves in the resident form
-            merges = []                     # per container that was merged: the arguments of its dm_events_merge call (kept alive), for _fallback_values
-            opened = []
-            opened_mv = []
-
-            def _open_container(f5f):
-                """-> (mapped members, read metas, n, sample offsets) of a format-2 container, the offsets checked against the samples they index"""
-                z = npzmap.load(f5f, lazy=('ev_mean', 'ev_stdv'))
-                if 'format' not in z:
-                    raise ValueError('format-1 raw container')
-                meta = json.loads(str(z['meta']))
-                n = len(meta)
-                ro = _c_arr(z['raw_off'], np.int64)
-                if len(ro) != n + 1 or ro[0] != 0 or (np.diff(ro) < 0).any() or ro[-1] > len(z['raw']):
-                    raise ValueError('signal offsets of a damaged container')
-                return z, meta, n, ro
-            for f5f in raw_files:
-                try:
-                    z, meta, n, ro = _open_container(f5f)
-                    if not use_move:
-                        eo = _c_arr(z['ev_off'], np.int64)
-                        if len(eo) != n + 1:
-                            raise ValueError('event offsets of a damaged container')
-                        ms = _c_arr(z['ev_model_state'], z['ev_model_state'].dtype)
-                        args = [_c_arr(z['ev_mean'], np.float64), _c_arr(z['ev_stdv'], np.float64), _c_arr(z['ev_start'], np.uint64),
-                                _c_arr(z['ev_length'], np.uint64)]
-                        mv = _c_arr(z['ev_move'], np.int64)
-                        opened.append((f5f, z, meta, n, eo, max(int(eo[-1]), 0), ms, args, mv, ro))
-                    elif not all(k in z for k in rawreads.MOVE_MEMBERS):
-                        opened_mv.append((f5f, z, meta, n, ro, None))
-                    else:
-                        if z['mv'].dtype != np.uint8 or z['fq'].dtype != np.uint8:
-                            raise ValueError('move tables of a damaged container')
-                        mvt, mvo, fst, fq, fqo = (_c_arr(z[k], dt) for k, dt in zip(rawreads.MOVE_MEMBERS, (np.uint8, np.int64, np.int64, np.uint8, np.int64)))
-                        # (dm_move_events checks the order of the offsets and their ends against the arrays)
-                        if len(mvo) != n + 1 or len(fqo) != n + 1 or len(fst) != n or (n and (mvo[0] != 0 or fqo[0] != 0)):
-                            raise ValueError('move offsets of a damaged container')
-                        opened_mv.append((f5f, z, meta, n, ro, (mvt, mvo, fst, fq, fqo)))
-                except Exception:
-                    out.errors["Cannot open fast5 or other errors"].append(f5f)
-                    print("Cannot open fast5 or other errors: {}".format(f5f))
-            # the merged event tables of the whole batch, written in place container after container (no per-container pieces to concatenate)
-            cap_ev = sum(o[5] for o in opened) + sum(len(o[5][3]) for o in opened_mv if o[5] is not None)
-            m_start, m_len, m_base = np.empty(max(cap_ev, 1), np.uint64), np.empty(max(cap_ev, 1), np.uint64), np.empty(max(cap_ev, 1), 'S1')
-            w = 0
-            for f5f, z, meta, n, eo, ne, ms, args, mv, ro in opened:
-                mev_off = np.empty(n + 1, np.int64)
-                # (the basecaller's mean / stdv are merged later and only if a read of the batch has an empty event: _fallback_values)
-                margs = (n, min(len(a) for a in args + [mv, ms]), eo.ctypes.data, args[0].ctypes.data, args[1].ctypes.data, args[2].ctypes.data, args[3].ctypes.data,
-                         ms.ctypes.data, ms.dtype.itemsize // 4, mv.ctypes.data, mev_off.ctypes.data)
-                got = lib.dm_events_merge(*margs, None, None, m_start.ctypes.data + 8 * w, m_len.ctypes.data + 8 * w, m_base.ctypes.data + w)
-                if got < 0:             # offsets that decrease or run past the table: a damaged container, the batch goes on without it
-                    out.errors["Cannot open fast5 or other errors"].append(f5f)
-                    print("Cannot open fast5 or other errors: {}".format(f5f))
-                    continue
-                merges.append((margs, ne, got, w, (eo, ms, mv, mev_off, args)))
-                per_read = mev_off[1:] - mev_off[:-1]
-                for i, m in enumerate(meta):
-                    rid = m['read_id'].replace(" ", ":::").replace("\t", "|||")
-                    if per_read[i] == 0:
-                        out.errors['No events data'].append(f5f)
-                        rid = None
-                    ids.append(rid)
-                    id_src.append(f5f)
-                raw_parts.append(z['raw'][:int(ro[-1])])          # samples behind the last read's end would shift every later container's offsets
-                raw_offs.extend((raw_offs[-1] + ro[1:]).tolist())
-                ev_offs.extend((ev_offs[-1] + mev_off[1:]).tolist())
-                w += got
-            for f5f, z, meta, n, ro, mvd in opened_mv:
-                if mvd is None:                 # a container without move data: the reference's reason, per read
-                    out.errors['No move data'].extend([f5f] * n)
-                    continue
-                mvt, mvo, fst, fq, fqo = mvd
-                mev_off, status = np.empty(n + 1, np.int64), np.empty(max(n, 1), np.int32)
-                got = lib.dm_move_events(n, len(mvt), mvt.ctypes.data, mvo.ctypes.data, fst.ctypes.data, ro.ctypes.data, len(fq), fq.ctypes.data, fqo.ctypes.data,
-                                         mev_off.ctypes.data, status.ctypes.data, m_start.ctypes.data + 8 * w, m_len.ctypes.data + 8 * w, m_base.ctypes.data + w)
-                if got < 0:
-                    out.errors["Cannot open fast5 or other errors"].append(f5f)
-                    print("Cannot open fast5 or other errors: {}".format(f5f))
-                    continue
-                keep.append(mvd)
-                good = np.flatnonzero(status[:n] == 0)
-                for i in np.flatnonzero(status[:n] != 0):       # where the reference is undefined the read fails (rawreads.py)
-                    out.errors["Cannot open fast5 or other errors"].append(f5f)
-                    print("Cannot open fast5 or other errors: {} (read {}: move table, status {})".format(f5f, meta[i]['read_id'], status[i]))
-                for i in good:
-                    ids.append(meta[i]['read_id'].replace(" ", ":::").replace("\t", "|||"))
-                    id_src.append(f5f)
-                if len(good) == n:              # the usual case: the container's arrays as they lie
-                    raw_parts.append(z['raw'][:int(ro[-1])])
-                    move_parts.append(mvt[:int(mvo[-1])])
-                    raw_offs.extend((raw_offs[-1] + ro[1:]).tolist())
-                    mv_offs.extend((mv_offs[-1] + mvo[1:]).tolist())
-                else:
-                    for i in good:
-                        raw_parts.append(z['raw'][int(ro[i]):int(ro[i + 1])])
-                        move_parts.append(mvt[int(mvo[i]):int(mvo[i + 1])])
-                        raw_offs.append(raw_offs[-1] + int(ro[i + 1] - ro[i]))
-                        mv_offs.append(mv_offs[-1] + int(mvo[i + 1] - mvo[i]))
-                firsts.extend(fst[good].tolist())
-                per_read = (mev_off[1:] - mev_off[:-1])[good]               # (a failed read has no events: mev_off is already the compacted table's)
-                ev_offs.extend((ev_offs[-1] + np.cumsum(per_read)).tolist())
-                w += got
-            t1 = time.perf_counter()
-            out.timing['load'] += t1 - t0
-            if ids:
-                cat = lambda parts, dt: np.concatenate(parts) if len(parts) > 1 else _c_arr(parts[0], dt)
-                m_start, m_len, m_base = m_start[:w], m_len[:w], m_base[:w]
-                m_mean = m_stdv = None
-
-                def _fallback_values():
-                    """The basecaller's mean / stdv of every merged event of the batch (getEvent's rounding): needed only for events at or behind a read's
-                    first empty event - the containers are merged once more, this time with the value columns."""
-                    if use_move:
-                        raise RuntimeError('a move read with an empty event: dm_move_events admits none')
-                    mm_, ms_ = np.empty(max(w, 1), np.float32), np.empty(max(w, 1), np.float32)
-                    for margs, ne, got, at, _keep in merges:
-                        a_, b_ = np.empty(ne, np.float32), np.empty(ne, np.float32)
-                        scratch = (np.empty(ne, np.uint64), np.empty(ne, np.uint64), np.empty(ne, 'S1'))
-                        if lib.dm_events_merge(*margs, a_.ctypes.data, b_.ctypes.data, scratch[0].ctypes.data, scratch[1].ctypes.data, scratch[2].ctypes.data) != got:
-                            raise _lib.DeepModHipError('dm_events_merge: ' + _lib.last_error())
-                        mm_[at:at + got], ms_[at:at + got] = a_[:got], b_[:got]
-                    return mm_[:w], ms_[:w]
-                raw_off, mev_off = np.array(raw_offs, np.int64), np.array(ev_offs, np.int64)
-                # resident form (round 6): a batch of raw containers only, whose rows are built on the device anyway - the signal request is POSTED
-                # (samples + event tables into the server's request file, no wait) and its statistics never come back: the feeder needs only
-                # first_empty (host arithmetic, dm_signal_plan_batch) to walk its alignments while the signal kernels run
-                want_resident = (hasattr(normalizer, 'post_arrays') and len(raw_files) == len(files)
-                                 and bool(moptions.get('select_base', os.environ.get('DEEPMOD_SELECT_BASE', '1') != '0'))
-                                 and bool(moptions.get('rows_on_device', os.environ.get('DEEPMOD_ROWS_ON_DEVICE', '1') != '0'))
-                                 and bool(moptions.get('stats_on_device', os.environ.get('DEEPMOD_STATS_ON_DEVICE', '1') != '0')))
-                try:
-                    if want_resident and use_move:
-                        # every event of a read that passed dm_move_events is non-empty: first_empty is the event count.  The move tables themselves are
-                        # posted (one byte per two samples instead of 16 per event) and segmented on the device; moptions['move_on_device'] = False /
-                        # DEEPMOD_MOVE_ON_DEVICE=0 posts the host-built tables through the event-table request instead
-                        first_empty = (mev_off[1:] - mev_off[:-1]).astype(np.int64)
-                        if hasattr(normalizer, 'post_move') and bool(moptions.get('move_on_device', os.environ.get('DEEPMOD_MOVE_ON_DEVICE', '1') != '0')):
-                            out.sig = normalizer.post_move(raw_parts, raw_off, move_parts, np.array(mv_offs, np.int64), np.array(firsts, np.int64), mev_off)
-                        else:
-                            out.sig = normalizer.post_arrays(raw_parts, raw_off, m_start, m_len, mev_off, first_empty, None, None)
-                        s_mean = s_stdv = None
-                    elif want_resident:
-                        first_empty = np.empty(len(raw_off) - 1, np.int64)
-                        _lib.check(lib.dm_signal_plan_batch(len(raw_off) - 1, raw_off.ctypes.data, mev_off.ctypes.data, m_start.ctypes.data, m_len.ctypes.data,
-                                                            first_empty.ctypes.data))
-                        if bool((first_empty < (mev_off[1:] - mev_off[:-1])).any()):
-                            m_mean, m_stdv = _fallback_values()
-                        out.sig = normalizer.post_arrays(raw_parts, raw_off, m_start, m_len, mev_off, first_empty, m_mean, m_stdv)
-                        s_mean = s_stdv = None
-                    else:
-                        s_mean, s_stdv, first_empty = normalizer.event_stats_arrays(raw_parts, raw_off, m_start, m_len, mev_off)
-                        if bool((np.asarray(first_empty) < (mev_off[1:] - mev_off[:-1])).any()):
-                            m_mean, m_stdv = _fallback_values()
-                except _lib.DeepModHipError:
-                    # a read the batched signal call cannot take (events covering no signal): the per-read Python path reports it
-                    lib.dm_rows_destroy(h)
-                    h = None
-                    return _prepare_batch_py(moptions, files, make_normalizer, alloc)
-                t2 = time.perf_counter()
-                out.timing['signal'] += t2 - t1
-                # alignment records: the reference's own aligner call when the binary is on PATH, else the side-car .sam files
-                f5data = {}
-                for gi, rid in enumerate(ids):
-                    if rid is None:
-                        continue
-                    if rid in f5data:
-                        print('Duplicate id', rid, id_src[gi])
-                    call = m_base[mev_off[gi]:mev_off[gi + 1]].tobytes().decode('ascii', 'replace') if moptions.get('Ref') else ''
-                    f5data[rid] = (call, gi, None, id_src[gi], (0, 0))
-                align_info = detect._alignment_lines(moptions, {'Error': out.errors}, raw_files, f5data)
-                if align_info is None:
-                    for f5k in sorted(f5data.keys()):
-                        out.errors["Cannot running aligment"].append(f5data[f5k][3])
-                else:
-                    sp_param = {'f5data': f5data, 'ref_info': {}, 'f5status': "", 'line': ""}
-                    f5align = readmap.parse_sam(moptions, {'Error': out.errors}, sp_param, align_info, f5data)
-                    recs = list(f5align.items())
-                    nrec = len(recs)
-                    seqs = readmap.read_fasta(moptions['Ref']) if moptions.get('Ref') else {}
-                    ref_bytes = _REF_BYTES.setdefault(moptions.get('Ref'), {})
-                    flag = np.zeros(nrec, np.int32); pos1 = np.zeros(nrec, np.int64); rlen = np.zeros(nrec, np.int64)
-                    cidx = np.full(nrec, -1, np.int32); ev_read = np.zeros(nrec, np.int32); skip = np.zeros(nrec, np.uint8)
-                    cig_b, seq_b = [], []
-                    for i, (qname, (mapq, fl, rname, ps, cigar, seq)) in enumerate(recs):
-                        flag[i], pos1[i], ev_read[i] = fl, ps, f5data[qname][1]
-                        cig_b.append(cigar.encode('ascii')); seq_b.append(seq.encode('ascii'))
-                        rlen[i] = len(seq_b[-1])
-                        if (not moptions.get('ConUnk', True)) and any(ch in rname for ch in '_-/:'):
-                            skip[i] = 1
-                        if rname not in contigs:
-                            contigs[rname] = len(contigs)
-                        cidx[i] = contigs[rname]
-                        if rname in seqs and rname not in ref_bytes:
-                            ref_bytes[rname] = seqs[rname].encode('ascii')
-                        if rname not in seqs:
-                            print('Fatal Error!!! cannot find the chrosome sequence %s' % rname)
-                    names = sorted(contigs, key=contigs.get)
-                    nct = len(names)
-                    ref_ptr = (ctypes.c_char_p * max(nct, 1))(*[ref_bytes.get(nm) for nm in names])
-                    ref_len = np.array([len(ref_bytes[nm]) if nm in ref_bytes else 0 for nm in names] or [0], np.int64)
-                    cig_ptr = (ctypes.c_char_p * max(nrec, 1))(*cig_b)
-                    seq_ptr = (ctypes.c_char_p * max(nrec, 1))(*seq_b)
-                    region = [mr for mr in moptions.get('region', [[None, None, None]])]
-                    any_all = any(mr[0] in ['', None] and mr[1] in ['', None] and mr[2] in ['', None] for mr in region)
-                    if any_all:
-                        region = []
-                    elif not region:
-                        skip[:] = 1          # an EMPTY region list matches nothing (myDetect.py:548-556 leaves isinreg False): n_region = 0 below means "no filter"
-                    rg_c = np.array([(-1 if mr[0] in ['', None] else contigs.get(mr[0], 0x7fffffff)) for mr in region] or [0], np.int32)   # a contig no record of the batch names: matches nothing
-                    rg_lo = np.array([(-1 if mr[1] in ['', None] else int(mr[1])) for mr in region] or [0], np.int64)
-                    rg_hi = np.array([(-1 if mr[2] in ['', None] else int(mr[2])) for mr in region] or [0], np.int64)
-                    keep.extend([flag, pos1, rlen, cidx, ev_read, skip, cig_b, seq_b, ref_ptr, ref_len, cig_ptr, seq_ptr, mev_off, m_mean, m_stdv,
-                                 m_len, m_base, s_mean, s_stdv, first_empty, rg_c, rg_lo, rg_hi])
-                    _lib.check(lib.dm_rows_add_raw(h, nrec, flag.ctypes.data, pos1.ctypes.data, cig_ptr, seq_ptr, rlen.ctypes.data, cidx.ctypes.data,
-                                                   ev_read.ctypes.data, skip.ctypes.data, nct, ref_ptr, ref_len.ctypes.data, len(mev_off) - 1, len(m_len), mev_off.ctypes.data,
-                                                   None if m_mean is None else m_mean.ctypes.data, None if m_stdv is None else m_stdv.ctypes.data,
-                                                   m_len.ctypes.data, m_base.ctypes.data,
-                                                   None if s_mean is None else s_mean.ctypes.data, None if s_stdv is None else s_stdv.ctypes.data,
-                                                   first_empty.ctypes.data, len(region), rg_c.ctypes.data, rg_lo.ctypes.data, rg_hi.ctypes.data))
-                    srcs.extend(f5data[q][3] for q, _ in recs)
-                    for nm in names:
-                        if nm in ref_bytes:
-                            out.contig_len[nm] = len(ref_bytes[nm])
-                out.timing['map+features'] += time.perf_counter() - t2
+        with _rows_handle(lib, moptions['Base']) as rows:
             t0 = time.perf_counter()
-        for cf in files:
-            if cf.endswith(rawreads.RAW_SUFFIX):
-                continue
-            try:
-                pk = predstore.load_packed(cf)
-            except Exception:
-                out.errors["Cannot open container"].append(cf)
-                continue
-            t1 = time.perf_counter()
-            out.timing['load'] += t1 - t0
-            meta = pk['reads']
-            n = len(meta)
-            if n:
-                for m in meta:
-                    if m['chr'] not in contigs:
-                        contigs[m['chr']] = len(contigs)
-                arrs = [_c_arr(pk['row_off'], np.int64), _c_arr(pk['bmi_off'], np.int64), _c_arr(pk['ev_off'], np.int64), _c_arr(pk['tx'], np.float32),
-                        _c_arr(pk['refbase'], 'S1'), _c_arr(pk['readbase'], 'S1'), _c_arr(pk['refbasei'], np.int64), _c_arr(pk['evbase'], 'S1'),
-                        np.array([m['start_clip'] for m in meta], np.int64), np.array([m['end_clip'] for m in meta], np.int64),
-                        np.array([contigs[m['chr']] for m in meta], np.int32), np.array([strands_c[m['strand']] for m in meta], np.int32)]
-                keep.append(arrs)
-                n_tab = min(len(arrs[4]), len(arrs[5]), len(arrs[6]))
-                if (min(len(arrs[0]), len(arrs[1]), len(arrs[2])) != n + 1 or arrs[3].ndim != 2 or arrs[3].shape[1] != 7 or
-                        lib.dm_rows_add_packed(h, n, len(arrs[3]), n_tab, len(arrs[7]), len(contigs), *[a.ctypes.data for a in arrs]) != 0):
-                    # offset tables that do not fit their arrays (a truncated / damaged container): the file is reported, the batch goes on
-                    out.errors["Cannot open container"].append(cf)
-                    print("Cannot open container: %s (%s)" % (cf, _lib.last_error() or 'offset tables of the wrong length'))
-                    continue
-                srcs.extend([cf] * n)
-            for c, ln in pk.get('contig_len', {}).items():
-                out.contig_len[c] = max(out.contig_len.get(c, 0), int(ln))
+            if raw_files:
+                normalizer = make_normalizer() if make_normalizer else None
+                if normalizer is None:
+                    from . import signal as dmsignal
+                    normalizer = dmsignal.SignalNormalizer(int(moptions.get('device', 0)))
+                batch = _raw_events(lib, out, raw_files, bool(moptions.get('move')))
+                t1 = time.perf_counter()
+                out.timing['load'] += t1 - t0
+                if batch.ids:
+                    stats = _signal_request(lib, moptions, normalizer, batch, len(raw_files) == len(files), compact, rows_on_device)
+                    out.sig = stats.sig
+                    t2 = time.perf_counter()
+                    out.timing['signal'] += t2 - t1
+                    _add_alignments(rows, out, moptions, raw_files, batch, stats)
+                    out.timing['map+features'] += time.perf_counter() - t2
+            _add_feature_containers(rows, out, files)
+            # ---- sizes, errors, then the arrays themselves (straight into the hand-over slot when alloc is given) ----
             t0 = time.perf_counter()
-            out.timing['rows'] += t0 - t1
-        # ---- sizes, errors, then the arrays themselves (straight into the hand-over slot when alloc is given) ----
-        nreads = len(srcs)
-        info = np.zeros((max(nreads, 1), 8), np.int64)
-        mism = np.zeros((20, 4), np.int64)
-        R, T, S, nm = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-        if lib.dm_rows_info(h, ctypes.byref(R), ctypes.byref(T), ctypes.byref(S), info.ctypes.data, mism.ctypes.data, 20, ctypes.byref(nm)) < 0:
-            raise _lib.DeepModHipError("dm_rows_info: " + _lib.last_error())
-        # compact form unless the caller wants every window classified (moptions['select_base'] = False / DEEPMOD_SELECT_BASE=0)
-        compact = bool(moptions.get('select_base', os.environ.get('DEEPMOD_SELECT_BASE', '1') != '0'))
-        for i in range(nreads):
-            st = int(info[i, 0])
-            if st in _ROWS_ERRORS:
-                out.errors[_ROWS_ERRORS[st]].append(srcs[i])
-            elif st == 3:
-                print("Errorfast5 " + srcs[i])
-                print('match-Error!!! no first and/or last match', srcs[i])
-        for j in range(min(int(nm.value), 20)):
-            print('Error Does not match: read %d of the batch (%s), table row %d, event %d, %d bases differ'
-                  % (mism[j, 0], srcs[int(mism[j, 0])], mism[j, 1], mism[j, 2], mism[j, 3]))
-        R, T, S = int(R.value), int(T.value), int(S.value)
-        if compact:
-            T = S + (T - R)                 # [S windows on a base of interest | extras]
-        ok = info[:nreads, 0] == 0
-        out.n_reads = int(ok.sum())
-        out.n_windows = int(info[:nreads, 3][ok].sum())
-        out.n_rows = R
-        # device form (round 5): a batch of raw reads only hands over (mean, stdv, length) per event, a class byte per row and a descriptor per
-        # read; the [R][7] matrix is built on the device.  moptions['rows_on_device'] = False / DEEPMOD_ROWS_ON_DEVICE=0: rows on the host as before
-        dev_form = None
-        resident = out.sig is not None
-        if R and compact and (resident or bool(moptions.get('rows_on_device', os.environ.get('DEEPMOD_ROWS_ON_DEVICE', '1') != '0'))):
-            ne, nr = ctypes.c_int64(), ctypes.c_int64()
-            if lib.dm_rows_device_info(h, ctypes.byref(ne), ctypes.byref(nr)) == 1:
-                dev_form = (0 if resident else int(ne.value), int(nr.value))
-        if resident and R and dev_form is None:
-            raise _lib.DeepModHipError('a batch whose statistics stay on the device must be a batch of raw reads')
-        if R:
-            if dev_form is not None:
-                E, NR = dev_form
-                if alloc is not None:
-                    out.ev3, out.code, out.rdesc, out.pos, out.flags, sel = alloc(R, T, S, dev=dev_form)
-                    out.sel = sel if S else np.zeros(0, np.int32)
-                else:
-                    out.ev3, out.code, out.rdesc = np.empty((max(E, 1), 3), np.float32), np.empty(R, np.uint8), np.empty((NR, 4), np.int64)
-                    out.pos, out.flags, out.sel = np.empty(T, np.int64), np.empty(T, np.uint8), np.empty(S, np.int32)
-                if resident:
-                    out.ev3 = None
-                out.rows = None
-            elif alloc is not None:
-                got = alloc(R, T, S) if compact else alloc(R, T)
-                out.rows, out.pos, out.flags = got[:3]
-                out.sel = (got[3] if S else np.zeros(0, np.int32)) if compact else None
-            else:
-                out.rows, out.pos, out.flags = np.empty((R, 7), np.float32), np.empty(T, np.int64), np.empty(T, np.uint8)
-                out.sel = np.empty(S, np.int32) if compact else None
-            names = sorted(contigs, key=contigs.get)
-            rank = np.empty(max(len(names), 1), np.int32)
-            rank[np.argsort(np.array(names, dtype=object), kind='stable') if names else []] = np.arange(len(names), dtype=np.int32)
-            clen = np.zeros(max(len(names), 1), np.int64)
-            groups = np.zeros((2 * max(len(names), 1), 8), np.int64)
-            in_range = ctypes.c_int32(1)
-            sel_dummy = np.zeros(1, np.int32)
-            sel_ptr = (out.sel.ctypes.data if S else sel_dummy.ctypes.data) if compact else None
-            if resident:
-                ng = lib.dm_rows_emit_resident(h, rank.ctypes.data, out.code.ctypes.data, out.rdesc.ctypes.data, sel_ptr, out.pos.ctypes.data,
-                                               out.flags.ctypes.data, groups.ctypes.data, len(groups), clen.ctypes.data, len(clen), ctypes.byref(in_range))
-            elif dev_form is not None:
-                ng = lib.dm_rows_emit_device(h, rank.ctypes.data, out.ev3.ctypes.data, out.code.ctypes.data, out.rdesc.ctypes.data, sel_ptr,
-                                             out.pos.ctypes.data, out.flags.ctypes.data, groups.ctypes.data, len(groups), clen.ctypes.data, len(clen),
-                                             ctypes.byref(in_range))
-            else:
-                ng = lib.dm_rows_emit(h, rank.ctypes.data, out.rows.ctypes.data, sel_ptr, out.pos.ctypes.data, out.flags.ctypes.data, groups.ctypes.data,
-                                      len(groups), clen.ctypes.data, len(clen), ctypes.byref(in_range))
-            if ng < 0:
-                raise _lib.DeepModHipError("dm_rows_emit: " + _lib.last_error())
-            out.groups = [(names[int(g[0])], '+-'[int(g[1])]) + tuple(int(v) for v in (g[2:8] if compact else g[2:6])) for g in groups[:ng]]
-            for i, nmn in enumerate(names):
-                if clen[i] > out.contig_len.get(nmn, 0):
-                    out.contig_len[nmn] = int(clen[i])        # lower bound when no reference length is known
-            out.f32 = not bool(in_range.value)
-        out.timing['rows'] += time.perf_counter() - t0
-        return out
-    finally:
-        if h:
-            lib.dm_rows_destroy(h)
-        del keep
+            R, T, S = _rows_info(rows, out, compact)
+            if R:
+                _allocate(rows, out, alloc, R, T, S, compact, rows_on_device)
+                _emit(rows, out, compact)
+            out.timing['rows'] += time.perf_counter() - t0
+            return out
+    except _BatchRefused:       # (the handle is gone by now)
+        return _prepare_batch_py(moptions, files, make_normalizer, alloc)
 
 
 def prepare_batch(moptions, files: List[str], make_normalizer=None, alloc=None) -> Prepared:
@@ -640,7 +754,7 @@ def prepare_batch(moptions, files: List[str], make_normalizer=None, alloc=None) 
     raw containers go through signal normalisation, alignment records, dm_map_read and get_Feature; feature containers
     enter at the prediction step.  Default: the compiled path (_prepare_batch_c); moptions['rows_in_c'] = False (or
     DEEPMOD_ROWS_IN_C=0) selects the per-read Python restatement."""
-    if moptions.get('rows_in_c', os.environ.get('DEEPMOD_ROWS_IN_C', '1') != '0'):
+    if _option_on(moptions, 'rows_in_c'):
         return _prepare_batch_c(moptions, files, make_normalizer, alloc)
     return _prepare_batch_py(moptions, files, make_normalizer, alloc)
 
@@ -701,6 +815,17 @@ def _prepare_batch_py(moptions, files: List[str], make_normalizer=None, alloc=No
 _ALIGN = 256
 
 
+def _layout(fields, align: int = 64):
+    """[(name, nbytes)] -> {name: byte offset, ..., 'end': size}: the fields back to back, each on a multiple of `align`.  A field of 0 bytes takes no
+    room: ('in_end', 0) marks the place where the inputs of a request end."""
+    o, pos = {}, 0
+    for name, nbytes in fields:
+        o[name] = pos
+        pos = -(-(pos + nbytes) // align) * align
+    o['end'] = pos
+    return o
+
+
 def _shm_layout(n_rows: int, n_pos: int, n_sel: int = 0):
     """byte offsets of [rows f32[n_rows][7] | pos i64[n_pos] | flags u8[n_pos] | sel i32[n_sel]] -> (o_pos, o_flags, end, o_sel)"""
     o_pos = -(-n_rows * 28 // _ALIGN) * _ALIGN
@@ -720,14 +845,9 @@ def _shm_views(buf, n_rows: int, n_pos: int, n_sel: int = 0):
 def _shm_layout_dev(n_rows: int, n_pos: int, n_sel: int, n_ev: int, n_reads: int):
     """byte offsets of the device form [ev3 f32[n_ev][3] | code u8[n_rows] | rdesc i64[n_reads][4] | pos i64[n_pos] | flags u8[n_pos] | sel i32[n_sel]]
     -> dict(ev3, code, rdesc, pos, flags, sel, end)"""
-    up = lambda v: -(-v // _ALIGN) * _ALIGN
-    o = {'ev3': 0}
-    o['code'] = up(12 * max(n_ev, 1))
-    o['rdesc'] = o['code'] + up(max(n_rows, 1))
-    o['pos'] = o['rdesc'] + up(32 * max(n_reads, 1))
-    o['flags'] = o['pos'] + up(8 * max(n_pos, 1))
-    o['sel'] = o['flags'] + up(max(n_pos, 1))
-    o['end'] = o['sel'] + 4 * max(n_sel, 1)
+    o = _layout((('ev3', 12 * max(n_ev, 1)), ('code', max(n_rows, 1)), ('rdesc', 32 * max(n_reads, 1)), ('pos', 8 * max(n_pos, 1)), ('flags', max(n_pos, 1)),
+                 ('sel', 4 * max(n_sel, 1))), _ALIGN)
+    o['end'] = o['sel'] + 4 * max(n_sel, 1)          # (the last array is not padded)
     return o
 
 
@@ -774,44 +894,37 @@ def shm_dir_for(moptions) -> str:
 # ---------------------------------------------------------------------------------------------
 def _sig_layout(n: int, n_raw: int, n_ev: int):
     """byte offsets of [raw i16 | raw_off i64 | ev_off i64 | ev_start u64 | ev_length u64 || mean f32 | stdv f32 | norm6 f64 | first_empty i64]"""
-    up = lambda v: -(-v // 64) * 64
-    o = {}
-    pos = 0
-    for name, nbytes in (('raw', 2 * n_raw), ('raw_off', 8 * (n + 1)), ('ev_off', 8 * (n + 1)), ('ev_start', 8 * n_ev), ('ev_length', 8 * n_ev)):
-        o[name] = pos
-        pos = up(pos + nbytes)
-    o['in_end'] = pos
-    for name, nbytes in (('mean', 4 * n_ev), ('stdv', 4 * n_ev), ('norm6', 48 * n), ('first_empty', 8 * n)):
-        o[name] = pos
-        pos = up(pos + nbytes)
-    o['end'] = pos
-    return o
+    return _layout((('raw', 2 * n_raw), ('raw_off', 8 * (n + 1)), ('ev_off', 8 * (n + 1)), ('ev_start', 8 * n_ev), ('ev_length', 8 * n_ev), ('in_end', 0),
+                    ('mean', 4 * n_ev), ('stdv', 4 * n_ev), ('norm6', 48 * n), ('first_empty', 8 * n)))
 
 
 def _sig_layout_res(n: int, n_raw: int, n_ev: int, with_fb: bool):
     """request of the resident form: [raw i16 | raw_off i64 | ev_off i64 | ev_start u64 | ev_length u64 | first_empty i64 | fb_mean f32 | fb_stdv f32]
     (the last two only when some read of the batch has an empty event) - inputs only: the statistics stay on the device"""
-    up = lambda v: -(-v // 64) * 64
-    o = {}
-    pos = 0
-    for name, nbytes in (('raw', 2 * n_raw), ('raw_off', 8 * (n + 1)), ('ev_off', 8 * (n + 1)), ('ev_start', 8 * n_ev), ('ev_length', 8 * n_ev),
-                         ('first_empty', 8 * n), ('fb_mean', 4 * n_ev if with_fb else 0), ('fb_stdv', 4 * n_ev if with_fb else 0)):
-        o[name] = pos
-        pos = up(pos + nbytes)
-    o['end'] = pos
-    return o
+    return _layout((('raw', 2 * n_raw), ('raw_off', 8 * (n + 1)), ('ev_off', 8 * (n + 1)), ('ev_start', 8 * n_ev), ('ev_length', 8 * n_ev),
+                    ('first_empty', 8 * n), ('fb_mean', 4 * n_ev if with_fb else 0), ('fb_stdv', 4 * n_ev if with_fb else 0)))
 
 
 def _sig_layout_move(n: int, n_raw: int, n_mv: int):
     """request of the resident form for move reads: [raw i16 | raw_off i64 | ev_off i64 | mv_off i64 | first i64 | move u8] - inputs only"""
-    up = lambda v: -(-v // 64) * 64
-    o = {}
-    pos = 0
-    for name, nbytes in (('raw', 2 * n_raw), ('raw_off', 8 * (n + 1)), ('ev_off', 8 * (n + 1)), ('mv_off', 8 * (n + 1)), ('first', 8 * n), ('move', n_mv)):
-        o[name] = pos
-        pos = up(pos + nbytes)
-    o['end'] = pos
-    return o
+    return _layout((('raw', 2 * n_raw), ('raw_off', 8 * (n + 1)), ('ev_off', 8 * (n + 1)), ('mv_off', 8 * (n + 1)), ('first', 8 * n), ('move', n_mv)))
+
+
+_SIG_DTYPES = {'raw': np.int16, 'move': np.uint8, 'ev_start': np.uint64, 'ev_length': np.uint64, 'fb_mean': np.float32, 'fb_stdv': np.float32}   # other inputs: int64
+
+
+def _map_request_file(path: str, nbytes: int, old=None):
+    """Create or grow a request file and map it -> (mapping, size): 1.5 x what is asked for, 4 MB at least; `old`, the mapping it replaces, is closed."""
+    import mmap
+    if old is not None:
+        old.close()
+    size = max(1 << 22, int(nbytes * 1.5))
+    fd = os.open(path, os.O_CREAT | os.O_RDWR, 0o600)
+    try:
+        os.ftruncate(fd, size)
+        return mmap.mmap(fd, size), size
+    finally:
+        os.close(fd)
 
 
 class SignalResults:
@@ -895,41 +1008,38 @@ class RemoteSignalNormalizer:
     # ---- resident form: post and go on ----
     def _request_file(self, seq: int, nbytes: int):
         """the request file of resident request `seq` (the file of request seq - 2, which the server must have copied), at least nbytes large"""
-        import mmap
         while seq - 2 > 0 and (seq - 2) not in self._acked:
             self._take_answer(block=True)
         self._acked.discard(seq - 2)
-        files = self._res_files
         slot = seq % 2
-        cur = files[slot]
+        cur = self._res_files[slot]
         if cur is None or cur[1] < nbytes:
-            if cur is not None:
-                cur[0].close()
-            size = max(1 << 22, int(nbytes * 1.5))
             path = self.path + '_r%d' % slot
-            fd = os.open(path, os.O_CREAT | os.O_RDWR, 0o600)
-            try:
-                os.ftruncate(fd, size)
-                cur = files[slot] = (mmap.mmap(fd, size), size, path)
-            finally:
-                os.close(fd)
+            cur = self._res_files[slot] = _map_request_file(path, nbytes, cur and cur[0]) + (path,)
         return cur
+
+    def _write(self, mm, o, **fields):
+        """Fill a request: every named array goes to its offset of layout `o` - a list of parts is concatenated straight into the mapping, None is left out."""
+        for name, a in fields.items():
+            if a is None:
+                continue
+            parts = [np.asarray(p) for p in a] if isinstance(a, (list, tuple)) else None
+            view = np.frombuffer(mm, _SIG_DTYPES.get(name, np.int64), len(a) if parts is None else sum(len(p) for p in parts), o[name])
+            if o[name] + view.nbytes > min([v for v in o.values() if v > o[name]] or [o['end']]):
+                raise ValueError('signal request: %s is larger than the layout says' % name)
+            if parts is None:
+                view[:] = a
+            elif len(view):
+                np.concatenate(parts, out=view, casting='same_kind')
 
     def post_move(self, raw_parts, raw_off, move_parts, mv_off, first, ev_off):
         """post_arrays for move reads (dm_signal_move_stats_device): the move tables travel instead of (start, length) tables - the server's kernels
         segment them.  ev_off: the cumulative Fastq lengths, the event count every read must have (the feeder has checked it: dm_move_events)."""
         seq = self._posted = self._posted + 1
-        n = len(raw_off) - 1
-        n_raw, n_ev, n_mv = int(raw_off[-1]), int(ev_off[-1]), int(mv_off[-1])
+        n, n_raw, n_ev, n_mv = len(raw_off) - 1, int(raw_off[-1]), int(ev_off[-1]), int(mv_off[-1])
         o = _sig_layout_move(n, n_raw, n_mv)
         mm, size, path = self._request_file(seq, o['end'])
-        np.concatenate([np.asarray(p) for p in raw_parts], out=np.frombuffer(mm, np.int16, n_raw, o['raw']), casting='same_kind')
-        np.frombuffer(mm, np.int64, n + 1, o['raw_off'])[:] = raw_off
-        np.frombuffer(mm, np.int64, n + 1, o['ev_off'])[:] = ev_off
-        np.frombuffer(mm, np.int64, n + 1, o['mv_off'])[:] = mv_off
-        np.frombuffer(mm, np.int64, n, o['first'])[:] = first
-        if n_mv:
-            np.concatenate([np.asarray(p) for p in move_parts], out=np.frombuffer(mm, np.uint8, n_mv, o['move']), casting='same_kind')
+        self._write(mm, o, raw=list(raw_parts), raw_off=raw_off, ev_off=ev_off, mv_off=mv_off, first=first, move=list(move_parts))
         self.requests.put(('mov', self.wid, path, size, n, n_raw, n_ev, seq, n_mv))
         return (self.wid, seq)
 
@@ -939,20 +1049,12 @@ class RemoteSignalNormalizer:
         for the file itself: request k reuses the file of request k - 2, which the server must have copied into its page-locked memory (its
         acknowledgement; usually long there)."""
         seq = self._posted = self._posted + 1
-        n = len(raw_off) - 1
-        n_raw, n_ev = int(raw_off[-1]), int(ev_off[-1])
+        n, n_raw, n_ev = len(raw_off) - 1, int(raw_off[-1]), int(ev_off[-1])
         with_fb = fb_mean is not None and fb_stdv is not None
         o = _sig_layout_res(n, n_raw, n_ev, with_fb)
         mm, size, path = self._request_file(seq, o['end'])
-        np.concatenate([np.asarray(p) for p in raw_parts], out=np.frombuffer(mm, np.int16, n_raw, o['raw']), casting='same_kind')
-        np.frombuffer(mm, np.int64, n + 1, o['raw_off'])[:] = raw_off
-        np.frombuffer(mm, np.int64, n + 1, o['ev_off'])[:] = ev_off
-        np.frombuffer(mm, np.uint64, n_ev, o['ev_start'])[:] = ev_start
-        np.frombuffer(mm, np.uint64, n_ev, o['ev_length'])[:] = ev_length
-        np.frombuffer(mm, np.int64, n, o['first_empty'])[:] = first_empty
-        if with_fb:
-            np.frombuffer(mm, np.float32, n_ev, o['fb_mean'])[:] = fb_mean
-            np.frombuffer(mm, np.float32, n_ev, o['fb_stdv'])[:] = fb_stdv
+        self._write(mm, o, raw=list(raw_parts), raw_off=raw_off, ev_off=ev_off, ev_start=ev_start, ev_length=ev_length, first_empty=first_empty,
+                    fb_mean=fb_mean if with_fb else None, fb_stdv=fb_stdv if with_fb else None)
         self.requests.put(('res', self.wid, path, size, n, n_raw, n_ev, seq, with_fb))
         return (self.wid, seq)
 
@@ -974,39 +1076,29 @@ class RemoteSignalNormalizer:
                 return got[1]
 
     def _ensure(self, nbytes: int):
-        import mmap
         if nbytes > self.size:
-            if self.mm is not None:
-                self.mm.close()
-            size = max(1 << 22, int(nbytes * 1.5))
-            fd = os.open(self.path, os.O_CREAT | os.O_RDWR, 0o600)
-            try:
-                os.ftruncate(fd, size)
-                self.mm = mmap.mmap(fd, size)
-            finally:
-                os.close(fd)
-            self.size = size
+            self.mm, self.size = _map_request_file(self.path, nbytes, self.mm)
+
+    def _ask(self, n: int, raw_off, ev_off, **columns):
+        """One synchronous request (raw, ev_start, ev_length in `columns`) -> (layout, mapping, events): the server's answer is in the mapping."""
+        from . import _lib
+        n_raw, n_ev = int(raw_off[-1]), int(ev_off[-1])
+        o = _sig_layout(n, n_raw, n_ev)
+        self._ensure(o['end'])
+        self._write(self.mm, o, raw_off=raw_off, ev_off=ev_off, **columns)
+        self.requests.put((self.wid, self.path, self.size, n, n_raw, n_ev))
+        err = self._wait_answer()
+        if err is not None:
+            raise _lib.DeepModHipError(err)
+        return o, self.mm, n_ev
 
     def event_stats_batch(self, reads):
-        from . import _lib
         if not reads:
             return []
         n = len(reads)
         raw_off = np.concatenate([[0], np.cumsum([len(r[0]) for r in reads])]).astype(np.int64)
         ev_off = np.concatenate([[0], np.cumsum([len(r[1]) for r in reads])]).astype(np.int64)
-        n_raw, n_ev = int(raw_off[-1]), int(ev_off[-1])
-        o = _sig_layout(n, n_raw, n_ev)
-        self._ensure(o['end'])
-        mm = self.mm
-        np.concatenate([np.asarray(r[0]) for r in reads], out=np.frombuffer(mm, np.int16, n_raw, o['raw']), casting='same_kind')
-        np.frombuffer(mm, np.int64, n + 1, o['raw_off'])[:] = raw_off
-        np.frombuffer(mm, np.int64, n + 1, o['ev_off'])[:] = ev_off
-        np.concatenate([np.asarray(r[1]) for r in reads], out=np.frombuffer(mm, np.uint64, n_ev, o['ev_start']), casting='same_kind')
-        np.concatenate([np.asarray(r[2]) for r in reads], out=np.frombuffer(mm, np.uint64, n_ev, o['ev_length']), casting='same_kind')
-        self.requests.put((self.wid, self.path, self.size, n, n_raw, n_ev))
-        err = self._wait_answer()
-        if err is not None:
-            raise _lib.DeepModHipError(err)
+        o, mm, n_ev = self._ask(n, raw_off, ev_off, raw=[r[0] for r in reads], ev_start=[r[1] for r in reads], ev_length=[r[2] for r in reads])
         mean = np.frombuffer(mm, np.float32, n_ev, o['mean']).copy()
         stdv = np.frombuffer(mm, np.float32, n_ev, o['stdv']).copy()
         norm6 = np.frombuffer(mm, np.float64, 6 * n, o['norm6']).reshape(n, 6)
@@ -1017,21 +1109,8 @@ class RemoteSignalNormalizer:
 
     def event_stats_arrays(self, raw_parts, raw_off, ev_start, ev_length, ev_off):
         """Same request as event_stats_batch, from arrays that are already back to back (see signal.SignalNormalizer.event_stats_arrays)."""
-        from . import _lib
         n = len(raw_off) - 1
-        n_raw, n_ev = int(raw_off[-1]), int(ev_off[-1])
-        o = _sig_layout(n, n_raw, n_ev)
-        self._ensure(o['end'])
-        mm = self.mm
-        np.concatenate([np.asarray(p) for p in raw_parts], out=np.frombuffer(mm, np.int16, n_raw, o['raw']), casting='same_kind')
-        np.frombuffer(mm, np.int64, n + 1, o['raw_off'])[:] = raw_off
-        np.frombuffer(mm, np.int64, n + 1, o['ev_off'])[:] = ev_off
-        np.frombuffer(mm, np.uint64, n_ev, o['ev_start'])[:] = ev_start
-        np.frombuffer(mm, np.uint64, n_ev, o['ev_length'])[:] = ev_length
-        self.requests.put((self.wid, self.path, self.size, n, n_raw, n_ev))
-        err = self._wait_answer()
-        if err is not None:
-            raise _lib.DeepModHipError(err)
+        o, mm, n_ev = self._ask(n, raw_off, ev_off, raw=list(raw_parts), ev_start=ev_start, ev_length=ev_length)
         return (np.frombuffer(mm, np.float32, n_ev, o['mean']).copy(), np.frombuffer(mm, np.float32, n_ev, o['stdv']).copy(),
                 np.frombuffer(mm, np.int64, n, o['first_empty']).copy())
 
@@ -1165,7 +1244,6 @@ def signal_server(requests, answers, device: int, stats=None, results: Optional[
             pinned.free()
         if norm is not None:
             norm.close()
-
 
 
 def feeder_process_main(moptions, work, ready, device: int, shm_dir: str, wid: int, free_slots=None, slot_bytes: int = 0,

@@ -726,3 +726,80 @@ def test_signal_results_registry():
     late.start()
     assert reg.take((3, 7), timeout=5.0) == (None, 0, 'signal stage: no device')
     late.join()
+
+
+def test_request_layouts_are_the_bytes_they_always_were():
+    """The layouts of the signal requests and of the device-form hand-over, as literals: feeder and server compute them with the same function, so a slip
+    in it is self-consistent and no round trip sees it - but it moves the int64 tables the server hands to the device from page-locked memory off their
+    64-byte boundaries.  (The values of the three hand-written loops these functions were before they shared one routine.)"""
+    assert stream._sig_layout(3, 1001, 37) == {'raw': 0, 'raw_off': 2048, 'ev_off': 2112, 'ev_start': 2176, 'ev_length': 2496, 'in_end': 2816, 'mean': 2816,
+                                                'stdv': 3008, 'norm6': 3200, 'first_empty': 3392, 'end': 3456}
+    res = {'raw': 0, 'raw_off': 2048, 'ev_off': 2112, 'ev_start': 2176, 'ev_length': 2496, 'first_empty': 2816, 'fb_mean': 2880}
+    assert stream._sig_layout_res(3, 1001, 37, False) == dict(res, fb_stdv=2880, end=2880)
+    assert stream._sig_layout_res(3, 1001, 37, True) == dict(res, fb_stdv=3072, end=3264)
+    assert stream._sig_layout_move(3, 1001, 500) == {'raw': 0, 'raw_off': 2048, 'ev_off': 2112, 'mv_off': 2176, 'first': 2240, 'move': 2304, 'end': 2816}
+    assert stream._sig_layout_move(0, 0, 0) == {'raw': 0, 'raw_off': 0, 'ev_off': 64, 'mv_off': 128, 'first': 192, 'move': 192, 'end': 192}
+    assert stream._shm_layout_dev(5, 9, 4, 37, 3) == {'ev3': 0, 'code': 512, 'rdesc': 768, 'pos': 1024, 'flags': 1280, 'sel': 1536, 'end': 1552}
+    for o in (stream._sig_layout(3, 1001, 37), stream._sig_layout_res(3, 1001, 37, True), stream._sig_layout_move(3, 1001, 500)):
+        assert list(o)[-1] == 'end' and list(o.values()) == sorted(o.values()) and all(v % 64 == 0 for v in o.values())
+
+
+def test_posted_move_requests_protocol(tmp_path):
+    """The twin of test_posted_signal_requests_protocol for post_move (detect --move, move tables segmented on the device): the bytes of the request file,
+    read back through stream._sig_layout_move.  Three reads whose sample bytes and move bytes are no multiples of 64, the largest move table a
+    non-contiguous slice; a request without a single move byte; the third request takes the first file again, and only once request 1 is acknowledged."""
+    import mmap
+    import threading
+    import time
+    requests, answers = queue.Queue(), queue.Queue()
+    norm = stream.RemoteSignalNormalizer(1, str(tmp_path), requests, answers)
+    rng = np.random.default_rng(7)
+
+    def off(parts):
+        return np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.int64)
+
+    raws = [rng.integers(300, 900, k).astype(np.int16) for k in (1001, 64, 4097)]
+    moves = [rng.integers(0, 2, 500).astype(np.uint8), rng.integers(0, 2, 32).astype(np.uint8), rng.integers(0, 2, 2 * 2048).astype(np.uint8)[::2]]
+    assert not moves[2].flags['C_CONTIGUOUS'] and sum(len(m) for m in moves) == 2580
+    first = np.array([3, 0, 17], np.int64)
+    ev_off = np.array([0, 211, 230, 1130], np.int64)
+
+    def read_request(req):
+        kind, wid, path, size, n, n_raw, n_ev, seq, n_mv = req
+        assert kind == 'mov' and wid == 1
+        with open(path, 'r+b') as fh:
+            mm = mmap.mmap(fh.fileno(), size)
+        o = stream._sig_layout_move(n, n_raw, n_mv)
+        assert o['end'] <= size
+        return path, {k: np.frombuffer(mm, dt, cnt, o[k]).copy() for k, dt, cnt in (('raw', np.int16, n_raw), ('raw_off', np.int64, n + 1), ('ev_off', np.int64, n + 1),
+                                                                                   ('mv_off', np.int64, n + 1), ('first', np.int64, n), ('move', np.uint8, n_mv))}
+
+    assert norm.post_move(raws, off(raws), moves, off(moves), first, ev_off) == (1, 1) and requests.qsize() == 1        # queued, nobody waited
+    req = requests.get()
+    assert req == ('mov', 1, req[2], req[3], 3, 5162, 1130, 1, 2580)
+    p1, r1 = read_request(req)
+    assert np.array_equal(r1['raw'], np.concatenate(raws)) and np.array_equal(r1['move'], np.concatenate(moves))
+    assert np.array_equal(r1['raw_off'], [0, 1001, 1065, 5162]) and np.array_equal(r1['mv_off'], [0, 500, 532, 2580])
+    assert np.array_equal(r1['ev_off'], ev_off) and np.array_equal(r1['first'], first)
+    # no move byte at all (n_mv == 0): written without error, the offsets read back
+    empty = [np.zeros(0, np.uint8)] * 3
+    assert norm.post_move(raws, off(raws), empty, off(empty), first, ev_off) == (1, 2)
+    req = requests.get()
+    assert req[0] == 'mov' and req[4:] == (3, 5162, 1130, 2, 0)
+    p2, r2 = read_request(req)
+    assert p2 != p1 and np.array_equal(r2['mv_off'], [0, 0, 0, 0]) and np.array_equal(r2['raw_off'], r1['raw_off']) and np.array_equal(r2['first'], first)
+    assert np.array_equal(r2['raw'], r1['raw']) and len(r2['move']) == 0
+    # request 3 wants the file of request 1: it blocks until that one is acknowledged
+    done = []
+    th = threading.Thread(target=lambda: done.append(norm.post_move(raws[:1], off(raws[:1]), moves[2:], off(moves[2:]), first[2:], ev_off[:2])), daemon=True)
+    th.start()
+    time.sleep(0.3)
+    assert not done and requests.empty()
+    answers.put(('ack', 1, None))
+    th.join(timeout=10)
+    assert done == [(1, 3)]
+    req = requests.get()
+    assert req[4:] == (1, 1001, 211, 3, 2048)
+    p3, r3 = read_request(req)
+    assert p3 == p1 and np.array_equal(r3['move'], moves[2]) and np.array_equal(r3['raw'], raws[0]) and np.array_equal(r3['first'], [17])
+    norm.close()
