@@ -1120,8 +1120,9 @@ int dm_model_mark(dm_model* m, int i) {
             break;
         }
     if (next < 0) {
-        // every slot is tied to a marker nobody waited for: keep writing the same slot (its launches are then reported with
-        // marker i as well as with the later one - conservative, never silent)
+        // every slot is tied to a marker nobody waited for (more than 2 DM_MARKS + 1 recordings without a wait): marker i gets no slot and
+        // the launches go on writing the current one.  dm_model_wait_mark(i) then reports nothing; what was queued before marker i is reported
+        // later - by the next marker that finds a free slot, or by dm_model_sync - and exactly once: never silent, but not at marker i
         m->mark_slot[i] = -1;
         return DM_OK;
     }
@@ -1137,7 +1138,7 @@ int dm_model_wait_mark(dm_model* m, int i) {
     if (!m->marks[i]) return DM_OK;
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipEventSynchronize(m->marks[i]));
-    if (m->mark_slot[i] < 0) return DM_OK;          // reported already (or shared with a later marker, see dm_model_mark)
+    if (m->mark_slot[i] < 0) return DM_OK;          // reported already (or left to a later marker / dm_model_sync, see dm_model_mark)
     const int sl = m->mark_slot[i];
     m->mark_slot[i] = -1;
     const bool bad = take_range_slot(m, sl);

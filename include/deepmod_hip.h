@@ -195,8 +195,11 @@ int dm_model_h2d_ahead(dm_model* m, void* dst, const void* src, size_t bytes);
  * set k % N while the device still works on batch k - 1; dm_model_mark(m, i) records a marker on the model's stream after the
  * launches that read set i, dm_model_wait_mark(m, i) blocks the host until that marker has passed (at once if it was never
  * recorded).  DM_ERANGE is tracked per marker: wait_mark(i) reports exactly the launches queued between the marker recorded before i and
- * marker i - a later batch still in flight is neither reported early nor cleared; dm_model_sync reports everything outstanding.  i in [0, DM_MARKS).  No reference counterpart: the reference feeds numpy arrays to session.run
- * (myDetect.py:796-822). */
+ * marker i - a later batch still in flight is neither reported early nor cleared; dm_model_sync reports everything outstanding.  i in [0, DM_MARKS).
+ * A marker recorded again before anybody waited for it leaves its earlier launches to dm_model_sync.  The library tracks 2 DM_MARKS + 2 such ranges: when
+ * markers are recorded that often without a wait, a further dm_model_mark(i) still orders host and device, but dm_model_wait_mark(i) reports nothing - the
+ * launches before it are reported by a later marker or by dm_model_sync instead, exactly once (tests/test_gpu_range_contract.py).  No reference counterpart:
+ * the reference feeds numpy arrays to session.run (myDetect.py:796-822). */
 #define DM_MARKS 8
 void* dm_host_alloc(int device, size_t bytes);
 int dm_host_free(int device, void* p);
