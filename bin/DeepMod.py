@@ -55,6 +55,10 @@ def build_parser():
                      help='0 (default): streaming detect - per-position counters stay on the GPUs, one RCCL reduce per contig x strand, '
                           'no per-read files; 1: also keep the per-read prediction tables and index files of the reference '
                           '(needed for a later --predDet 0 run)')
+    det.add_argument('--clusterCpG', nargs='?', const='', default=None, metavar='CKPT_PREFIX',
+                     help='--Base C with --Ref: after the mod_pos.* files, also write <outFolder>/<FileID>_clusterCpG.<chr>.C.bed per contig - the output of '
+                          'sum_chr_mod.py, generate_motif_pos.py (motif CG) and hm_cluster_predict.py on this run, computed from the counters on the GPU. '
+                          'CKPT_PREFIX: checkpoint prefix of the cluster model (default: DEEPMOD_CLUSTER_MODEL)')
     det.set_defaults(func=mDetect)
     for name in ('train', 'getfeatures'):
         p = sub.add_parser(name, help='not built: training-side, outside the accelerated path')
@@ -110,6 +114,12 @@ def mDetect(args):
             mr_sp = mr.split(':')
             mo['region'].append([mr_sp[0], int(mr_sp[1]) if len(mr_sp) > 1 else None, int(mr_sp[2]) if len(mr_sp) > 2 else None])
     mo['ConUnk'] = args.ConUnk not in (False, 'False', 'false', '0', 0)
+    mo['clusterCpG'] = None
+    if args.clusterCpG is not None:
+        try:
+            mo['clusterCpG'] = detect.cluster_cpg_prefix(args.clusterCpG, mo)
+        except ValueError as exc:
+            raise SystemExit('Error: --clusterCpG: %s' % exc)
     errs = []
     if mo['predDet'] == 1:
         if not mo['wrkBase'] or not os.path.isdir(mo['wrkBase']):

@@ -94,6 +94,9 @@ SIGNATURES = [
     ("dm_cluster_create", _vp, [_c.c_int, _vp, _c.c_size_t]),
     ("dm_cluster_destroy", None, [_vp]),
     ("dm_cluster_predict", _c.c_int, [_vp, _vp, _i64, _vp]),
+    ("dm_cluster_sites", _i64, [_vp, _vp, _vp, _c.c_int, _vp, _i64, _i64, _i64, _i64, _vp, _c.POINTER(_i64)]),
+    ("dm_cluster_sites_fetch", _c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    ("dm_cluster_bed_format", _i64, [_c.c_char_p, _c.c_char, _c.c_char, _vp, _vp, _vp, _vp, _i64, _vp, _i64]),
     ("dm_signal_create", _vp, [_c.c_int]),
     ("dm_signal_destroy", None, [_vp]),
     ("dm_map_read", _c.c_int, [_c.c_int, _i64, _c.c_char_p, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),

@@ -84,4 +84,51 @@ int64_t dm_bed_format(const char* chrom, char strand, char base, const int32_t* 
     return dm_bed_format_at(chrom, strand, base, 0, touch, cov, mod, length, out, cap);
 }
 
+// The lines of hm_cluster_predict.py's output for n sites of one strand (the records of dm_cluster_sites_fetch): the row sum_chr_mod.py:63
+// writes - "<chr> <pos> <pos+1> <Base> <min(cov,1000)> <strand>  <pos> <pos+1> 0,0,0 <cov> <int(mod*100/cov)> <mod>", two spaces after the
+// strand, no trailing space - then " <new>\n" (hm_cluster_predict.py:170).  Sized first like dm_bed_format_at: bound = n * (strlen(chrom) + 128).
+int64_t dm_cluster_bed_format(const char* chrom, char strand, char base, const int64_t* pos, const int32_t* cov, const int32_t* mod, const int32_t* new_pct,
+                              int64_t n, char* out, int64_t cap) {
+    if (!chrom || n < 0 || (n > 0 && (!pos || !cov || !mod || !new_pct))) return fail(DM_EINVAL, "dm_cluster_bed_format: bad input");
+    for (int64_t i = 0; i < n; ++i)
+        if (pos[i] < 0 || pos[i] >= (int64_t(1) << 40) || cov[i] < 0 || mod[i] < 0 || new_pct[i] < 0)      // (13-digit positions: a line stays below the bound)
+            return fail(DM_EINVAL, "dm_cluster_bed_format: value out of range in record %lld", (long long)i);
+    const size_t nchr = std::strlen(chrom);
+    const int64_t bound = n * int64_t(nchr + bedtext::LINE_EXTRA);
+    if (!out || cap < bound) return bound;
+    char* w = out;
+    for (int64_t i = 0; i < n; ++i) {
+        const unsigned long long p = (unsigned long long)pos[i];
+        const long long cv = cov[i], md = mod[i];
+        std::memcpy(w, chrom, nchr);
+        w += nchr;
+        *w++ = ' ';
+        w = bedtext::put_u64(w, p);
+        *w++ = ' ';
+        w = bedtext::put_u64(w, p + 1);
+        *w++ = ' ';
+        *w++ = base;
+        *w++ = ' ';
+        w = bedtext::put_u64(w, (unsigned long long)(cv < 1000 ? cv : 1000));
+        *w++ = ' ';
+        *w++ = strand;
+        *w++ = ' ';
+        *w++ = ' ';
+        w = bedtext::put_u64(w, p);
+        *w++ = ' ';
+        w = bedtext::put_u64(w, p + 1);
+        std::memcpy(w, " 0,0,0 ", 7);
+        w += 7;
+        w = bedtext::put_u64(w, (unsigned long long)cv);
+        *w++ = ' ';
+        w = bedtext::put_u64(w, (unsigned long long)(cv > 0 ? md * 100 / cv : 0));
+        *w++ = ' ';
+        w = bedtext::put_u64(w, (unsigned long long)md);
+        *w++ = ' ';
+        w = bedtext::put_u64(w, (unsigned long long)new_pct[i]);
+        *w++ = '\n';
+    }
+    return int64_t(w - out);
+}
+
 }  // extern "C"

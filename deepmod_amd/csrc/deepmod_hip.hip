@@ -1315,6 +1315,11 @@ struct dm_cluster {
     float* d_x = nullptr;
     float* d_out = nullptr;
     int64_t cap = 0;
+    // dm_cluster_sites (cluster_sites.hip.inc): device buffers of the last call, grown on demand, and its site counts
+    static constexpr int SITE_BUFFERS = 10;
+    void* site_buf[SITE_BUFFERS] = {};
+    int64_t site_cap[SITE_BUFFERS] = {};
+    int64_t n_sites = 0, n_plus = 0;
 };
 
 dm_cluster* dm_cluster_create(int device, const float* weights, size_t n_floats) {
@@ -1346,6 +1351,7 @@ void dm_cluster_destroy(dm_cluster* c) {
     (void)hipFree(c->d_w);
     (void)hipFree(c->d_x);
     (void)hipFree(c->d_out);
+    for (void* b : c->site_buf) (void)hipFree(b);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1662,3 +1668,4 @@ int dm_summary_fetch_slice(dm_summary* s, int32_t* touch, int32_t* cov, int32_t*
 #include "readmap.inc"
 #include "rowsbatch.inc"
 #include "bedtext.inc"
+#include "cluster_sites.hip.inc"

@@ -781,6 +781,24 @@ class _LazyManager:
         return self._m.Queue()
 
 
+def cluster_cpg_prefix(given, moptions) -> str:
+    """`detect --clusterCpG [CKPT_PREFIX]`: the checkpoint prefix of the cluster model for this run, or ValueError with the one line that
+    says why the run cannot have the stage.  Without a prefix the DEEPMOD_CLUSTER_MODEL variable names it, as for DeepMod_tools/hm_cluster_predict.py."""
+    if moptions.get('Base') != 'C':
+        raise ValueError('the CpG-cluster stage is defined for --Base C only (got --Base %s)' % moptions.get('Base'))
+    if moptions.get('storePred', 0) or moptions.get('predDet', 1) == 0:
+        raise ValueError('only the streaming mode holds both strands of a contig together (--storePred 1 / --predDet 0 summarise one strand per job): '
+                         'run sum_chr_mod.py, generate_motif_pos.py and hm_cluster_predict.py on the BED files instead')
+    if not moptions.get('Ref') or not os.path.isfile(moptions['Ref']):
+        raise ValueError('needs --Ref, the reference FASTA whose CG positions are the sites')
+    prefix = given or os.environ.get('DEEPMOD_CLUSTER_MODEL') or ''
+    if not prefix:
+        raise ValueError('no cluster-model checkpoint: give its prefix after the flag or set DEEPMOD_CLUSTER_MODEL')
+    if not os.path.isfile(prefix + '.index'):
+        raise ValueError('no cluster-model checkpoint at %r (no %s.index)' % (prefix, prefix))
+    return prefix
+
+
 def mDetect_manager(moptions):
     """The detect run (counterpart of myDetect.py:1124-1263): inputs -> worker batches -> detect -> per-position summary
     -> `<outFolder>.done`.  predDet == 1 runs the streaming mode unless `storePred` asks for the reference's per-read
@@ -789,6 +807,11 @@ def mDetect_manager(moptions):
         # the reference marks this branch of sum_handler "should not used now" (myDetect.py:1054-1087); neither run mode builds it,
         # and writing plain mod_pos.* files for a run that asked for cluster_mod_pos.* would be a silent change of meaning
         raise NotImplementedError("--mod_cluster 1 is not built (the reference marks that branch 'should not used now', myDetect.py:1054)")
+    if moptions.get('clusterCpG'):
+        try:
+            cluster_cpg_prefix(moptions['clusterCpG'], moptions)          # (callers that come past the command line)
+        except ValueError as exc:
+            raise SystemExit('Error: --clusterCpG: %s' % exc)
     moptions['_t_manager'] = time.time()
     ctx = multiprocessing.get_context('spawn')      # never fork a process that may hold a HIP context
     pmanager = _LazyManager(ctx)       # the stored-prediction paths share their queues through a manager like the reference (myDetect.py:1141)

@@ -29,7 +29,7 @@ import queue
 import threading
 import time
 from collections import defaultdict, namedtuple
-from typing import Dict, Iterable, List, Optional, Tuple
+from typing import Dict, Iterable, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -1545,6 +1545,122 @@ def finalize_threads(n_tables: int, longest: int, budget_positions: int = 250_00
     return max(1, min(8, n_tables, budget_positions // max(int(longest), 1)))
 
 
+class _ClusterStage:
+    """detect --clusterCpG: the CpG-cluster stage of a contig from its two counter tables while they are still on the device
+    (ClusterModel.sites: dm_cluster_sites) - what sum_chr_mod.py, generate_motif_pos.py and hm_cluster_predict.py compute from the BED
+    files of the run - written as `<outFolder>_clusterCpG.<chr>.<Base>.bed` (outFolder = `<command-line folder>/<FileID>`, the tools' prefix).
+    A contig without a site gets no file, as with the tools."""
+
+    class Table(NamedTuple):
+        """One strand's counters of the contig in work, kept open until its pair has been through the stage."""
+        summary: object
+        first: int                           # the positions this rank holds of it: [first, first + count)
+        count: int
+        edges: list                          # cluster.slice_edges of a slice (its first and last 26 cov | mod values); None for a whole table
+
+    def __init__(self, engine, gather, scattered: bool):
+        from . import cluster
+        self.eng, self.gather, self.cluster, self.scattered = engine, gather, cluster, scattered
+        self.mo = engine.mo
+        self._model = None
+        self.parts = {}                      # contig -> [bytes of this rank's '+' part, of its '-' part]
+        self.contig, self.tables = None, {}  # the contig in work and its Table per strand
+
+    @property
+    def model(self):
+        """Loaded by the first contig this rank computes: a rank that only hands its counters to rank 0 never loads it."""
+        if self._model is None:
+            self._model = self.cluster.ClusterModel.from_checkpoint(self.mo['clusterCpG'], getattr(self.eng.backend, 'device', 0))
+        return self._model
+
+    def path(self, chrom: str) -> str:
+        return '%s_clusterCpG.%s.%s.bed' % (self.mo['outFolder'].rstrip('/'), chrom, self.mo['Base'])
+
+    def _seq(self, chrom: str) -> str:
+        from . import readmap
+        seqs = readmap.read_fasta(self.mo['Ref'])          # (parsed once per process: the rank read it for the contig lengths, and this is that dict)
+        if chrom not in seqs:
+            raise RuntimeError('--clusterCpG: contig %r of the run is not in --Ref %s' % (chrom, self.mo['Ref']))
+        return seqs[chrom]
+
+    def keep(self, chrom: str, strand: str, summary, first: int = 0, count=None, cov=None, mod=None) -> None:
+        """Takes a table over instead of closing it.  Tables arrive contig by contig ('+' before '-'); the first table of the next contig sends the
+        pair before it through the stage.  cov, mod: the host copy of a slice, for its edges."""
+        if self.contig is not None and self.contig != chrom:
+            self.flush()
+        self.contig = chrom
+        edges = self.cluster.slice_edges(cov, mod, None, None)[0] if cov is not None else None
+        self.tables[strand] = self.Table(summary, int(first), int(summary.length if count is None else count), edges)
+
+    def flush(self) -> None:
+        """The pair in work through the stage, then its tables are closed.  A strand without a table counts as zeros."""
+        if self.contig is None:
+            return
+        chrom, plus, minus = self.contig, self.tables.get('+'), self.tables.get('-')
+        self.contig, self.tables = None, {}
+        some = plus or minus
+        if self.scattered:
+            self.sliced(chrom, plus and plus.summary, minus and minus.summary, some.first, some.count,
+                        [t.edges if t else [[[], []], [[], []]] for t in (plus, minus)])
+        elif self.eng.rank == 0:
+            self.whole(chrom, plus and plus.summary, minus and minus.summary)
+        for t in (plus, minus):
+            if t:
+                t.summary.close()
+
+    def finish(self) -> None:
+        self.flush()
+        if self.scattered:
+            self.join()
+        if self._model is not None:
+            self._model.close()
+
+    def whole(self, chrom: str, plus, minus) -> None:
+        """One rank holds the whole tables (either may be None)."""
+        res = self.model.sites(plus, minus, self._seq(chrom))
+        self.eng.stats['cluster_sites'] += len(res['pos'])
+        if len(res['pos']):
+            with open(self.path(chrom), 'wb') as fh:
+                fh.write(b''.join(self.cluster.site_text_parts(chrom, self.mo['Base'], res)))
+
+    def sliced(self, chrom: str, plus, minus, first: int, count: int, edges) -> None:
+        """After the reduce-scatter: this rank's slice [first, first + count) of both strands; the 26 counters beyond either end come from
+        the edges every rank publishes through the control plane, the bases from this rank's slice +- 27 of the sequence."""
+        mine = {"first": int(first), "count": int(count), "edges": edges}
+        everyone = self.gather({"cluster": mine}) if self.eng.world > 1 else [{"cluster": mine}]
+        halo = self.cluster.halo_from_edges(first, count, [e["cluster"] for e in everyone])
+        seq = self._seq(chrom)
+        lo, hi = max(0, first - self.cluster.HALO - 1), min(len(seq), first + count + self.cluster.HALO + 1)
+        res = self.model.sites(plus, minus, seq[lo:max(lo, hi)], first, count, from_slice=True, halo=halo, seq_first=lo)
+        self.eng.stats['cluster_sites'] += len(res['pos'])
+        sizes = []
+        for name, text in zip(('plus', 'minus'), self.cluster.site_text_parts(chrom, self.mo['Base'], res)):
+            with open('%s.%s.part%d' % (self.path(chrom), name, self.eng.rank), 'wb') as fh:
+                fh.write(text)
+            sizes.append(len(text))
+        self.parts[chrom] = sizes
+
+    def join(self) -> None:
+        """Rank 0: all '+' parts of a contig in rank order, then all '-' parts - the order of the tools' file."""
+        world = self.eng.world
+        sizes = self.gather({"cluster_parts": self.parts}) if world > 1 else [{"cluster_parts": self.parts}]
+        if self.eng.rank != 0:
+            return
+        for chrom in sorted(self.parts):
+            names = ['%s.%s.part%d' % (self.path(chrom), name, r) for name in ('plus', 'minus') for r in range(world)]
+            want = [sizes[r]["cluster_parts"].get(chrom, [0, 0])[k] for k in range(2) for r in range(world)]
+            if sum(want) > 0:
+                with open(self.path(chrom), 'wb') as out:
+                    for nm, size in zip(names, want):
+                        with open(nm, 'rb') as fh:
+                            data = fh.read()
+                        if len(data) != size:
+                            raise RuntimeError('clusterCpG part %s has %d bytes, its rank reported %d' % (nm, len(data), size))
+                        out.write(data)
+            for nm in names:
+                if os.path.exists(nm):
+                    os.remove(nm)
+
 class StreamEngine:
     """Rank-local streaming detect: pulls worker batches, keeps per contig x strand counters, merges at the end."""
 
@@ -1766,6 +1882,8 @@ class StreamEngine:
         # (moptions['force_scatter_merge']: the scatter form on a single rank too - how the GPU tests run this code path on one GPU)
         scattered = scatter_fn is not None and (self.world > 1 or bool(self.mo.get('force_scatter_merge')))
         out_path = lambda chrom, strand: '%s/mod_pos.%s%s.%s.bed' % (self.mo['outFolder'], chrom, strand, self.mo['Base'])
+        # --clusterCpG: both strands of a contig go through the cluster stage as a pair, before either table is closed
+        stage = _ClusterStage(self, gather, scattered) if (self.mo.get('clusterCpG') and write) else None
         def fetch_format_write(key):             # one rank, one table: download the counters, format, write (all outside the interpreter lock)
             chrom, strand = key.split("\t")
             s = self.summaries[(chrom, strand)]
@@ -1790,6 +1908,13 @@ class StreamEngine:
             for key in keys:
                 chrom, strand = key.split("\t")
                 self.summaries[(chrom, strand)].grow(max(self.summaries[(chrom, strand)].length, lens.get(chrom, 0)))
+            if stage is not None:
+                for chrom in sorted(set(key.split("\t")[0] for key in keys)):
+                    pair = [self.summaries.get((chrom, st)) for st in '+-']
+                    for s in pair:
+                        if s is not None:
+                            s.grow(max(t.length for t in pair if t is not None))      # one common length
+                    stage.whole(chrom, *pair)
             # a table in flight holds 3 x length int32 on the host plus its text: at most ~2.5e8 positions (3 GB of counters) at a time,
             # i.e. eight E. coli-sized tables side by side but one chr1-sized table after the other
             longest = max(self.summaries[tuple(key.split("\t"))].length for key in keys)
@@ -1801,6 +1926,8 @@ class StreamEngine:
         for key in keys:
             chrom, strand = key.split("\t")
             length = max([e["keys"].get(key, 0) for e in everyone] + [e["len"].get(chrom, 0) for e in everyone])
+            if stage is not None:
+                length = max([length] + [e["keys"].get("%s\t%s" % (chrom, st), 0) for e in everyone for st in '+-'])    # common to both strands
             s = self.summaries.get((chrom, strand))
             if s is None:                               # this rank saw no read of that contig x strand: zeros
                 s = self.summaries[(chrom, strand)] = self.backend.new_summary(length)
@@ -1809,6 +1936,8 @@ class StreamEngine:
                 s.sync()                                # every rank: positions this rank dropped as out of range fail the run here
                 first, count = scatter_fn(s)
                 touch, cov, mod = s.fetch_slice()
+                if stage is not None:
+                    stage.keep(chrom, strand, s, first, count, cov, mod)
                 if write:
                     parts[key] = 0
                     with open(out_path(chrom, strand) + '.part%d' % self.rank, 'wb') as fh:
@@ -1831,8 +1960,13 @@ class StreamEngine:
                     if write and len(bed) > 0:          # the reference writes no file for an empty table (myDetect.py:1109)
                         with open(out_path(chrom, strand), 'wb') as fh:
                             fh.write(bed)
-            s.close()
+                if stage is not None:
+                    stage.keep(chrom, strand, s)
+            if stage is None:
+                s.close()
         self.summaries = {}
+        if stage is not None:
+            stage.finish()
         if scattered and write:
             # every rank's parts are on disk once its sizes have been gathered; rank 0 joins them
             sizes = gather({"parts": parts}) if self.world > 1 else [{"parts": parts}]

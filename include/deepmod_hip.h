@@ -26,6 +26,10 @@
  *        (the reference merges BED files of separate runs; here: one RCCL reduce per contig x strand)
  *   dm_cluster_create / _predict / _destroy
  *        cluster MLP sess.run([output])         DeepMod_tools/hm_cluster_predict.py:94-103, :158-164
+ *   dm_cluster_sites / _sites_fetch / dm_cluster_bed_format
+ *        merged rows with mod > 0               DeepMod_tools/sum_chr_mod.py:37-66
+ *        CpG hits of the reference sequence     DeepMod_tools/generate_motif_pos.py:30-72
+ *        readpredmod + the 14 features + write  DeepMod_tools/hm_cluster_predict.py:43-72, :128-154, :165-171
  */
 #ifndef DEEPMOD_HIP_H
 #define DEEPMOD_HIP_H
@@ -297,6 +301,31 @@ typedef struct dm_cluster dm_cluster;
 dm_cluster* dm_cluster_create(int device, const float* weights, size_t n_floats);
 void dm_cluster_destroy(dm_cluster* c);
 int dm_cluster_predict(dm_cluster* c, const float* x, int64_t n, float* out);
+
+/* The cluster stage of one contig (or one rank's slice of it) from the counters where they are - no BED text in between.  Replaces
+ * sum_chr_mod.py:37-66 (rows with mod > 0 of both strands, pct = int(mod * 100 / cov)), generate_motif_pos.py:30-72 (CpG hits: '+' at p where
+ * the upper-cased sequence reads "CG" at p, '-' at p + 1) and hm_cluster_predict.py:43-72, :128-154 (the sites = rows on a hit; per site
+ * [frac, partner frac, n, 11-bin histogram / n] over the sites within +-25 bp, double arithmetic, cast to fp32), then runs the MLP above
+ * on the device feature rows.
+ *   plus, minus  the '+' and '-' counters of the contig; either may be NULL (all zero)
+ *   from_slice   0: the whole tables; positions [first, first + count) of them are the range (beyond a table's length: zero)
+ *                1: each summary's slice after dm_summary_reduce_scatter, which must be [first, first + count)
+ *   seq          host bytes of positions [seq_first, seq_first + seq_len), any case; positions outside hold no base.  A slice needs its own
+ *                positions +-27
+ *   halo         int32 [2 sides][2 strands][cov | mod][26]: the counters of positions first - 26 .. first - 1 (side 0) and
+ *                first + count .. first + count + 25 (side 1) - sites there are neighbours and partners, never output.  NULL: whole tables
+ *                are read beside the range themselves; beside a slice the counters are zero
+ * Returns the number of sites (< 0: error code); *n_plus of them are '+' sites.  Rows are ordered as the reference's file: '+' sites
+ * ascending, then '-' sites ascending.  The results stay on the device until the next call:
+ *   dm_cluster_sites_fetch   position, cov, mod, new = int(float32 p * 100) (hm_cluster_predict.py:170) and the [n][14] fp32 features per
+ *                            site (any may be NULL)
+ *   dm_cluster_bed_format    (host) the file's lines for n records of one strand: sum_chr_mod.py:63's row - two spaces after the strand,
+ *                            no trailing space - + " <new>\n".  Sized first like dm_bed_format_at; positions < 2^40 */
+int64_t dm_cluster_sites(dm_cluster* c, dm_summary* plus, dm_summary* minus, int from_slice, const uint8_t* seq, int64_t seq_first, int64_t seq_len,
+                         int64_t first, int64_t count, const int32_t* halo, int64_t* n_plus);
+int dm_cluster_sites_fetch(dm_cluster* c, int64_t* pos, int32_t* cov, int32_t* mod, int32_t* new_pct, float* features);
+int64_t dm_cluster_bed_format(const char* chrom, char strand, char base, const int64_t* pos, const int32_t* cov, const int32_t* mod,
+                              const int32_t* new_pct, int64_t n, char* out, int64_t cap);
 
 /* ---- raw-signal normalisation + per-event statistics ------------------------------------
  * Replaces myDetect.py:266-282 (mnormalized: median / MAD shift-scale over the event-covered slice, second
