@@ -4,8 +4,11 @@
 Keeps the `detect` sub-command of the reference's bin/DeepMod.py (flag names and defaults of
 bin/DeepMod.py:304-338) for the path this build implements: per-read BiLSTM modification calling on
 the GPU and the per-position BED summary.  `--wrkBase` holds feature containers (*.dmfeat.npz, see
-deepmod_amd/predstore.py) because FAST5 reading and alignment are out of scope here.  `train` and
-`getfeatures` are training-side and not built.
+deepmod_amd/predstore.py) because FAST5 reading and alignment are out of scope here.
+
+`train` (flags of bin/DeepMod.py:341-350 plus --seed and --batchsize) trains the BiLSTM on the GPU from the
+reference's *.xy.gz feature files and writes TF-bundle checkpoints `detect --modfile` loads
+(deepmod_amd/train.py).  `getfeatures` is not built.
 """
 import argparse
 import os
@@ -60,10 +63,70 @@ def build_parser():
                           'sum_chr_mod.py, generate_motif_pos.py (motif CG) and hm_cluster_predict.py on this run, computed from the counters on the GPU. '
                           'CKPT_PREFIX: checkpoint prefix of the cluster model (default: DEEPMOD_CLUSTER_MODEL)')
     det.set_defaults(func=mDetect)
-    for name in ('train', 'getfeatures'):
-        p = sub.add_parser(name, help='not built: training-side, outside the accelerated path')
-        p.set_defaults(func=lambda a, _n=name: sys.exit("'%s' is not part of this build (inference hot path only)" % _n))
+    trn = sub.add_parser('train', parents=[com], help='train a modification classifier on the GPU',
+                         description='Train the BiLSTM on *.xy.gz feature files (the format getfeatures of the reference writes): forward, backpropagation through '
+                                     'time and Adam as HIP kernels, fp32.  --wrkBase "a,b;c": groups separated by ;, folders of a group by , (the larger group leads). '
+                                     'The AUC of the progress line is the exact ROC statistic of the displayed batch, not the 200-threshold approximation of '
+                                     'tf.metrics.auc.  Initial values are TF1\'s distributions drawn from numpy (--seed): TensorFlow\'s own stream cannot be reproduced.')
+    trn.add_argument('--wrkBase2', help='accepted for compatibility (the reference parses and never reads it): name further groups in --wrkBase "a;b"')
+    trn.add_argument('--fnum', type=int, default=7, help='features per event')
+    trn.add_argument('--hidden', type=int, default=100, help='LSTM hidden units')
+    trn.add_argument('--modfile', default=None, help='accepted and ignored with a note: the reference never restores it')
+    trn.add_argument('--test', default=None, help="independent testing: 'E,a,b' leaves positions a..b (Mb) out, 'P,pct' uses pct %% of the files")
+    trn.add_argument('--outputlayer', default='', choices=['', 'sigmoid'], help="only '' is built")
+    trn.add_argument('--unbalanced', type=int, default=0, choices=[1, 0], help='1: class weights [0.1, 0.9] inside the loss')
+    trn.add_argument('--seed', type=int, default=0, help='seed of the initial values (numpy generator)')
+    trn.add_argument('--batchsize', type=int, default=2048, help='windows per training step (the reference fixes 2048): the leading group is cut into steps of batchsize .. 2 batchsize - 1 windows, a step of another group can be larger by a file; the device tape (158,400 B per window) is sized for 2 batchsize - 1 and grows to the largest step met')
+    trn.set_defaults(func=mTrain)
+    p = sub.add_parser('getfeatures', help='not built: training-side, outside the accelerated path')
+    p.set_defaults(func=lambda a: sys.exit("'getfeatures' is not part of this build (inference hot path only)"))
     return parser
+
+
+def train_options(args):
+    """moptions of `train` as bin/DeepMod.py:186-222 of the reference builds them; geometry and output layer are refused as detect refuses them."""
+    if args is None or not getattr(args, 'wrkBase', None):
+        raise SystemExit('Error: train: --wrkBase: the folders of the *.xy.gz feature files ("a,b;c")')
+    mo = {k: getattr(args, k) for k in ('outLevel', 'wrkBase', 'FileID', 'outFolder', 'recursive', 'windowsize', 'fnum', 'hidden', 'outputlayer',
+                                         'unbalanced', 'modfile', 'seed')}
+    for k in ('windowsize', 'fnum', 'hidden'):
+        non_negative(mo[k], k)
+    if (mo['fnum'], mo['hidden'], mo['windowsize']) != (7, 100, 21):
+        raise SystemExit('Error: this build supports fnum=7 hidden=100 windowsize=21 only (got %s)' % ((mo['fnum'], mo['hidden'], mo['windowsize']),))
+    if mo['outputlayer'] in ('sigmoid',):
+        raise SystemExit('Error: --outputlayer sigmoid is not used by any shipped model and is not built')
+    if args.batchsize < 1:
+        raise SystemExit('Error: --batchsize must be positive')
+    if not mo['outFolder'].endswith('/'):
+        mo['outFolder'] += '/'
+    if args.test is not None:                            # bin/DeepMod.py:212-222
+        mo['test'] = args.test.split(',')
+        if mo['test'][0] == 'E': mo['test'][0] = '-'
+        elif mo['test'][0] == 'P': mo['test'][0] = '0'
+        else:
+            raise SystemExit('Error: Unknown option for test: the first character must be E or P ' + args.test)
+        try:
+            if mo['test'][0] in ['-']:
+                mo['test'][1] = int(mo['test'][1]) * (10 ** 6)
+                mo['test'][2] = int(mo['test'][2]) * (10 ** 6)
+            else:
+                mo['test'][1] = int(mo['test'][1]) / 100.0
+        except (IndexError, ValueError):
+            raise SystemExit("Error: --test takes 'E,<from Mb>,<to Mb>' or 'P,<percent>' (got %r)" % args.test)
+    else:
+        mo['test'] = ['N', '100']
+    return mo
+
+
+def mTrain(args):
+    mo = train_options(args)
+    from deepmod_amd import _lib, train
+    if args.wrkBase2:
+        print('Note: --wrkBase2 %s is not read (the reference never reads it either): give further groups as --wrkBase "a;b"' % args.wrkBase2)
+    if _lib.load().dm_device_count() < 1:
+        raise SystemExit('Error: no gfx950 GPU visible (this build has no CPU path)')
+    os.makedirs(mo['outFolder'], exist_ok=True)
+    train.mMult_RNN_LSTM_train(mo, batchsize=args.batchsize)
 
 
 def kfd_gpu_count(base='/sys/class/kfd/kfd/topology/nodes'):

@@ -120,6 +120,14 @@ SIGNATURES = [
     ("dm_rows_emit_device", _i64, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _c.POINTER(_c.c_int32)]),
     ("dm_rows_emit_resident", _i64, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _c.POINTER(_c.c_int32)]),
     ("dm_rows_assemble", _c.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64]),
+    ("dm_trainer_create", _vp, [_c.c_int, _vp, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _i64]),
+    ("dm_trainer_destroy", None, [_vp]),
+    ("dm_trainer_grad", _c.c_int, [_vp, _vp, _vp, _i64, _c.c_int, _c.POINTER(_c.c_float), _vp, _vp]),
+    ("dm_trainer_adam", _c.c_int, [_vp, _vp]),
+    ("dm_trainer_step", _c.c_int, [_vp, _vp, _vp, _i64, _c.c_int, _c.POINTER(_c.c_float)]),
+    ("dm_trainer_get_state", _c.c_int, [_vp, _vp, _vp, _vp, _c.POINTER(_i64)]),
+    ("dm_trainer_set_state", _c.c_int, [_vp, _vp, _vp, _vp, _i64]),
+    ("dm_trainer_profile", _c.c_int, [_vp, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_i64)]),
 ]
 
 

@@ -1669,3 +1669,4 @@ int dm_summary_fetch_slice(dm_summary* s, int32_t* touch, int32_t* cov, int32_t*
 #include "rowsbatch.inc"
 #include "bedtext.inc"
 #include "cluster_sites.hip.inc"
+#include "train.hip.inc"

@@ -2,7 +2,7 @@
 TF1-Session-shaped adapter that makes the build's `mPredict1` a behavioural twin of the
 reference's (bin/DeepMod_scripts/myDetect.py:805-820).
 
-Mirrors, for the inference path only:
+Mirrors:
   * myMultiBiRNN.mCreateSession(num_input, num_hidden, timesteps, moptions)
         (bin/DeepMod_scripts/myMultiBiRNN.py:21-91) -> same 12-tuple arity, handles are tokens
   * tf.Session / tf.train.import_meta_graph / Saver.restore / tf.train.latest_checkpoint as used at
@@ -293,6 +293,7 @@ class Session:
         self.graph = graph
         self.device = device
         self.model: Optional[BiLSTMModel] = None
+        self._train = None                    # train.TrainSession, created by the first fetch of a training token
 
     # the command-line path (every model the detect command loads comes through here): DM_PREC_F16X3, the mode that meets the path's 1e-4
     # tolerance by construction (round 5: the int8 cross-term mode is opt-in again - its documented bound is 2e-4).  DEEPMOD_PRECISION =
@@ -317,6 +318,14 @@ class Session:
         flist = [fetches] if single else list(fetches)
         if all(f is self.graph.init_l or f is self.graph.init for f in flist):
             return None if single else [None] * len(flist)
+        tg = getattr(self.graph, "train", None)
+        if tg is not None and any(tg.is_train_token(f) for f in flist):
+            # loss_op / accuracy / train_op ... (myMultiBiRNN.py:180, :190): the trainer, from the seeded initial values at the first fetch
+            if self._train is None:
+                from . import train as _train
+                self._train = _train.TrainSession(tg, self.device)
+                self._train.run(tg.init)
+            return self._train.run(fetches, feed_dict)
         if self.model is None:
             raise _lib.DeepModHipError("Session.run before restore(): no weights loaded")
         if feed_dict is None or self.graph.X not in feed_dict:
@@ -339,13 +348,16 @@ class Session:
             elif f is self.graph.prediction:
                 out.append(prob)
             else:
-                raise ValueError("cannot fetch %r (inference-only build)" % (f,))
+                raise ValueError("cannot fetch %r" % (f,))
         return out[0] if single else out
 
     def close(self):
         if self.model is not None:
             self.model.close()
             self.model = None
+        if self._train is not None:
+            self._train.close()
+            self._train = None
 
 
 class Graph:
@@ -370,20 +382,29 @@ class Saver:
             raise ValueError("no checkpoint found (latest_checkpoint returned None)")
         sess.restore(save_path)
 
+    def save(self, sess: Session, save_path: str):
+        """`saver.save(sess, prefix)` of a session that has trained (myMultiBiRNN.py:214-225): variables + Adam slots as a TF bundle."""
+        if sess._train is None:
+            raise _lib.DeepModHipError("Saver.save: this session has not trained")
+        from . import train as _train
+        return _train.TrainSaver().save(sess._train, save_path)
+
 
 _last_graph: Optional[Graph] = None
 
 
 def mCreateSession(num_input, num_hidden, timesteps, moptions):
     """Same arity/positions as the reference's 12-tuple
-    (init, init_l, loss_op, accuracy, train_op, X, Y, saver, auc_op, mpre, mspf, mfpred);
-    training-side entries are None (inference-only build)."""
+    (init, init_l, loss_op, accuracy, train_op, X, Y, saver, auc_op, mpre, mspf, mfpred); the training-side entries are live
+    tokens of deepmod_amd.train: sess.run([train_op, loss_op], feed_dict={X: x, Y: y}) is one training step on the GPU."""
     global _last_graph
     if moptions.get("outputlayer", "") in ("sigmoid",):
         raise ValueError("--outputlayer sigmoid is not used by any shipped model and is not built")
     g = Graph(num_input, num_hidden, timesteps)
+    from . import train as _train
+    tg = g.train = _train.TrainGraph(num_input, num_hidden, timesteps, moptions, share=g)
     _last_graph = g
-    return (g.init, g.init_l, None, None, None, g.X, g.Y, g.saver, None, None, None, g.mfpred)
+    return (g.init, g.init_l, tg.loss_op, tg.accuracy, tg.train_op, g.X, g.Y, g.saver, tg.auc_op, tg.mpre, tg.mspf, g.mfpred)
 
 
 def import_meta_graph(meta_path: str) -> Saver:

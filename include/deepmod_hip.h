@@ -488,6 +488,32 @@ int64_t dm_rows_emit_resident(dm_rowsbatch* h, const int32_t* contig_rank, uint8
                               int64_t* groups, int64_t cap_groups, int64_t* contig_len, int64_t n_contig_len, int32_t* in_range);
 int dm_rows_assemble(dm_model* m, float* d_rows, const uint8_t* d_code, const float* d_ev3, const int64_t* d_rdesc, int64_t n_reads, int64_t n_rows);
 
+/* ------------------------------------------------------------------------- training -- */
+/*
+ * The other half of the reference: myMultiBiRNN.mCreateSession's loss_op / train_op (bin/DeepMod_scripts/myMultiBiRNN.py:21-91) and the
+ * sess.run([train_op, loss_op]) of train_save_model (:190).  fp32 throughout; forward with a tape, backpropagation through the 11 live
+ * steps of each direction, TF1 AdamOptimizer (lr 1e-3, beta1 0.9, beta2 0.999, eps 1e-8).  No float atomics: two runs are bit-identical.
+ *   weights, grad, m, v   the canonical DM_WEIGHT_FLOATS layout of dm_model_create
+ *   x [n][21][7], y [n][2]   host or device memory (detected); n <= max_batch, which sizes the tape once (158,400 B per window)
+ *   unbalanced == 1       the loss (only) is taken of logits * [0.1, 0.9] (:64-67); prob stays softmax(logits)
+ *   dm_trainer_grad       loss, prob [n][2] and the gradient blob (each of the last two may be NULL); the state does not change
+ *   dm_trainer_adam       one Adam step from a caller-supplied gradient blob
+ *   dm_trainer_step       grad + adam; nothing is downloaded but the loss
+ *   dm_trainer_get_state / _set_state   weights, Adam slots m and v (any may be NULL) and the step count t
+ * n == 0 is a no-op.  n > max_batch, NaN / Inf in x or y, or a non-finite loss return DM_EINVAL and leave the state unchanged.
+ */
+typedef struct dm_trainer dm_trainer;
+dm_trainer* dm_trainer_create(int device, const float* weights, size_t n_floats, int n_feat, int hidden, int window, int layers, int64_t max_batch);
+void dm_trainer_destroy(dm_trainer* t);
+int dm_trainer_grad(dm_trainer* t, const float* x, const float* y, int64_t n, int unbalanced, float* loss, float* prob, float* grad);
+int dm_trainer_adam(dm_trainer* t, const float* grad);
+int dm_trainer_step(dm_trainer* t, const float* x, const float* y, int64_t n, int unbalanced, float* loss);
+int dm_trainer_get_state(dm_trainer* t, float* weights, float* m, float* v, int64_t* step);
+int dm_trainer_set_state(dm_trainer* t, const float* weights, const float* m, const float* v, int64_t step);
+/* HIP events on the trainer's stream around every dm_trainer_step: reports the time summed and the steps counted since the last call (either may be
+ * NULL), then switches the bracketing on or off and clears both (tools/train_rate.py).  No reference counterpart. */
+int dm_trainer_profile(dm_trainer* t, int on, double* step_ms, int64_t* steps);
+
 #ifdef __cplusplus
 }
 #endif
