@@ -8,7 +8,14 @@ deepmod_amd/predstore.py) because FAST5 reading and alignment are out of scope h
 
 `train` (flags of bin/DeepMod.py:341-350 plus --seed and --batchsize) trains the BiLSTM on the GPU from the
 reference's *.xy.gz feature files and writes TF-bundle checkpoints `detect --modfile` loads
-(deepmod_amd/train.py).  `getfeatures` is not built.
+(deepmod_amd/train.py).
+
+`getfeatures` (flags and defaults of bin/DeepMod.py:354-375) writes those *.xy.gz / *.xy.ind files from raw
+containers (*.dmraw.npz, event tables or --move), a reference and known modified positions - a motif
+(--motifORPos 1) or position lists (--motifORPos 2): signal statistics, row selection and text on one GPU,
+alignment walk and gzip on --threads host threads (deepmod_amd/getfeatures.py).  Only --fnum 7 and
+--SignalGroup simple; --region takes a contig name; an --outFolder that already holds */*.xy.gz is refused
+(the reference deletes it).
 """
 import argparse
 import os
@@ -78,9 +85,74 @@ def build_parser():
     trn.add_argument('--seed', type=int, default=0, help='seed of the initial values (numpy generator)')
     trn.add_argument('--batchsize', type=int, default=2048, help='windows per training step (the reference fixes 2048): the leading group is cut into steps of batchsize .. 2 batchsize - 1 windows, a step of another group can be larger by a file; the device tape (158,400 B per window) is sized for 2 batchsize - 1 and grows to the largest step met')
     trn.set_defaults(func=mTrain)
-    p = sub.add_parser('getfeatures', help='not built: training-side, outside the accelerated path')
-    p.set_defaults(func=lambda a: sys.exit("'getfeatures' is not part of this build (inference hot path only)"))
+    gf = sub.add_parser('getfeatures', parents=[com], help='get labelled features of all raw reads for training',
+                        description='Write the *.xy.gz / *.xy.ind training files from raw containers (*.dmraw.npz), a reference and known modified positions: '
+                                    'per worker batch of --files_per_thread inputs a folder <outFolder>/<batch id>/.  One GPU; --threads host threads load, walk '
+                                    'alignments and gzip.  Inputs are taken in sorted order.  An --outFolder that already holds */*.xy.gz is refused (the reference '
+                                    'deletes the folder).')
+    gf.add_argument('--posneg', type=int, default=0, choices=[0, 1], help='the positive (1) or negative (0) class')
+    gf.add_argument('--size_per_batch', type=int, default=1, help='size (unit: 10^7 bytes at 80 bytes per row) of a feature file')
+    gf.add_argument('--fnum', type=int, default=7, help='features per event (only 7 is built)')
+    gf.add_argument('--region', type=str, help='contig of interest (the start:end part of the reference cannot work under Python 3 and is refused)')
+    gf.add_argument('--basecall_1d', default='Basecall_1D_000', help='accepted for compatibility')
+    gf.add_argument('--basecall_2strand', default='BaseCalled_template', help='accepted for compatibility')
+    gf.add_argument('--motifORPos', type=int, default=1, help='motif (1) or position lists (2) for the modified bases')
+    gf.add_argument('--motif', default='CG', type=str, help='the motif of interest')
+    gf.add_argument('--ModinMotif', default=0, type=int, help='position of the modified base in the motif')
+    gf.add_argument('--Ref', help='reference genome FASTA')
+    gf.add_argument('--fulmod', type=str, help='file pattern of completely modified positions (lines: chr strand pos)')
+    gf.add_argument('--anymod', type=str, help='file pattern of partially modified positions')
+    gf.add_argument('--nomod', type=str, help='file pattern of unmodified positions')
+    gf.set_defaults(func=mGetFeatures)
     return parser
+
+
+def getfeatures_options(args):
+    """moptions of `getfeatures` as bin/DeepMod.py:240-299 of the reference builds them; what this build does not do is refused with one line."""
+    if not args.wrkBase or not os.path.isdir(args.wrkBase):
+        raise SystemExit('Error: getfeatures: --wrkBase: input folder does not exist')
+    mo = {k: getattr(args, k) for k in ('outLevel', 'wrkBase', 'FileID', 'outFolder', 'recursive', 'threads', 'files_per_thread', 'windowsize', 'alignStr',
+                                         'SignalGroup', 'move', 'posneg', 'fnum', 'size_per_batch', 'basecall_1d', 'basecall_2strand', 'Ref', 'motifORPos')}
+    if mo['fnum'] != 7:
+        raise SystemExit('Error: getfeatures: this build supports --fnum 7 only (got %d)' % mo['fnum'])
+    if mo['SignalGroup'] != 'simple':
+        raise SystemExit('Error: getfeatures: --SignalGroup %s (event re-segmentation) is not built' % mo['SignalGroup'])
+    mo['threads'] = max(mo['threads'], 1)
+    mo['files_per_thread'] = max(mo['files_per_thread'], 2)          # bin/DeepMod.py:75-78
+    if mo['size_per_batch'] < 0.001:
+        mo['size_per_batch'] = 0.001                                 # bin/DeepMod.py:252
+    if not mo['outFolder'].endswith('/'):
+        mo['outFolder'] += '/'
+    mo['region'] = [None, None, None]
+    if not (args.region is None or args.region.strip() == ''):
+        rsp = [v.strip() for v in args.region.split(':')]
+        if any(v != '' for v in rsp[1:]):
+            raise SystemExit('Error: getfeatures: --region takes a contig name only (got %r): the reference compares the start and end with an int and raises TypeError' % args.region)
+        if rsp[0] != '':
+            mo['region'][0] = rsp[0]
+    if mo['Ref'] is None or not os.path.isfile(mo['Ref']):
+        raise SystemExit('Error: getfeatures: --Ref: reference file does not exist (%s)' % mo['Ref'])
+    if mo['motifORPos'] == 1:
+        mo['motif'] = [args.motif.upper(), args.ModinMotif]
+        if not 0 <= args.ModinMotif < len(args.motif):
+            raise SystemExit('Error: getfeatures: --ModinMotif %d is no position in the motif %s' % (args.ModinMotif, args.motif))
+    elif mo['motifORPos'] == 2:
+        missing = [k for k in ('fulmod', 'anymod', 'nomod') if getattr(args, k) is None]
+        if missing:
+            raise SystemExit('Error: getfeatures: --motifORPos 2 needs --fulmod, --anymod and --nomod (missing: %s)' % ', '.join('--' + k for k in missing))
+        mo.update(fulmod=args.fulmod, anymod=args.anymod, nomod=args.nomod)
+    else:
+        raise SystemExit('Error: getfeatures: --motifORPos %d is not supported (1: motif, 2: position lists)' % mo['motifORPos'])
+    from deepmod_amd import getfeatures
+    if getfeatures.existing_output(mo['outFolder']):
+        raise SystemExit('Error: getfeatures: --outFolder %s already holds */*.xy.gz files (the reference deletes the folder; this build does not)' % mo['outFolder'])
+    return mo
+
+
+def mGetFeatures(args):
+    mo = getfeatures_options(args)
+    from deepmod_amd import getfeatures
+    getfeatures.getFeature_manager(mo)
 
 
 def train_options(args):

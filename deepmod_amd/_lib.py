@@ -33,6 +33,9 @@ DM_OK, DM_EINVAL, DM_EDEVICE, DM_ENOMEM, DM_ESTATE, DM_ERCCL, DM_ERANGE = 0, -1,
 DM_MAP_INFO_LEN = 16
 DM_MAP_OK, DM_MAP_NO_MATCH, DM_MAP_NEED_ROWS = 0, 1, 2
 DM_MOVE_OK, DM_MOVE_COUNT, DM_MOVE_OUTSIDE = 0, 1, 2
+(DM_XY_OK, DM_XY_LESS_EVENT, DM_XY_NO_SITE, DM_XY_FILTERED, DM_XY_NO_MATCH, DM_XY_INDEX_ERROR, DM_XY_NEED_ROWS) = range(7)
+DM_XY_INFO_LEN = 8
+(DM_XY_STATUS, DM_XY_N_ROWS, DM_XY_STRAND, DM_XY_START_CLIP, DM_XY_END_CLIP, DM_XY_POS_AFTER_CLIP, DM_XY_EVENTS_AFTER_CLIP) = range(7)
 DM_WEIGHT_FLOATS = 408402
 
 _c = ctypes
@@ -128,6 +131,21 @@ SIGNATURES = [
     ("dm_trainer_get_state", _c.c_int, [_vp, _vp, _vp, _vp, _c.POINTER(_i64)]),
     ("dm_trainer_set_state", _c.c_int, [_vp, _vp, _vp, _vp, _i64]),
     ("dm_trainer_profile", _c.c_int, [_vp, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_i64)]),
+    ("dm_xy_sites_create", _vp, [_c.c_int32, _c.c_int, _c.c_int]),
+    ("dm_xy_sites_destroy", None, [_vp]),
+    ("dm_xy_sites_set", _c.c_int, [_vp, _c.c_int32, _c.c_int, _c.c_int, _vp, _i64]),
+    ("dm_xy_labels", _c.c_int, [_vp, _c.c_int32, _c.c_int, _c.c_char_p, _c.c_int, _c.c_int, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64,
+                                _i64, _vp, _vp]),
+    ("dm_xy_read", _c.c_int, [_vp, _c.c_int32, _c.c_int, _i64, _c.c_char_p, _c.c_char_p, _i64, _c.c_char_p, _i64, _i64, _c.c_char_p, _c.c_int, _c.c_int, _vp, _vp, _vp,
+                              _i64, _i64, _i64, _vp, _vp]),
+    ("dm_xy_format_host", _i64, [_vp, _i64, _vp, _i64]),
+    ("dm_xy_rows_host", _i64, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64]),
+    ("dm_xy_create", _vp, [_c.c_int]),
+    ("dm_xy_destroy", None, [_vp]),
+    ("dm_xy_rows", _i64, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _c.POINTER(_c.c_int32)]),
+    ("dm_xy_rows_fetch", _c.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    ("dm_xy_times", _c.c_int, [_vp, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
+    ("dm_xy_scan", _c.c_int, [_vp, _vp, _i64]),
 ]
 
 

@@ -1670,3 +1670,5 @@ int dm_summary_fetch_slice(dm_summary* s, int32_t* touch, int32_t* cov, int32_t*
 #include "bedtext.inc"
 #include "cluster_sites.hip.inc"
 #include "train.hip.inc"
+#include "xyrows.inc"
+#include "xyrows.hip.inc"

@@ -52,7 +52,7 @@ inline bool is_clip_op(char op) { return op == 'I' || op == 'D' || op == 'N' || 
 //   first_row  the final table is rows [*first_row, *first_row + info[DM_MAP_N_ROWS]) of the columns
 inline int map_read_core(int flag, int64_t pos1, const char* cigar, const char* readseq, int64_t readseq_len, const char* refseq, int64_t refseq_len,
                          int64_t n_events, char* refb, char* readb, int64_t* refi, uint64_t* readi, int64_t cap, int64_t* info, int64_t* first_row,
-                         int64_t* need_rows) {
+                         int64_t* need_rows, const bool cpg_swap = true) {
     for (int i = 0; i < DM_MAP_INFO_LEN; ++i) info[i] = 0;
     *first_row = 0;
     *need_rows = 0;
@@ -304,7 +304,8 @@ inline int map_read_core(int flag, int64_t pos1, const char* cigar, const char* 
     info[DM_MAP_LEFTCLIP] = leftclip;
     info[DM_MAP_RIGHTCLIP] = rightclip;
     // ---- CpG special alignment (:684-704), in place, ascending, later rows see earlier swaps ----
-    for (int64_t a = 0; a < n_rows; ++a) {
+    // (cpg_swap false: getfeatures with a motif other than CG or with position lists, myGetFeatureBasedPos.py:302 - xyrows.inc)
+    for (int64_t a = 0; cpg_swap && a < n_rows; ++a) {
         // (both cases need a gap right next to row a: one byte compare per row decides for nearly all of them)
         if (!((a + 1 < n_rows && qb[a + 1] == '-') || (a > 0 && qb[a - 1] == '-'))) continue;
         if (tb[a] == 'C' && qb[a] == 'C') {

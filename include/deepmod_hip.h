@@ -514,6 +514,76 @@ int dm_trainer_set_state(dm_trainer* t, const float* weights, const float* m, co
  * NULL), then switches the bracketing on or off and clears both (tools/train_rate.py).  No reference counterpart. */
 int dm_trainer_profile(dm_trainer* t, int on, double* step_ms, int64_t* steps);
 
+/* ---------------------------------------------------------------------- getfeatures -- */
+/*
+ * The reference's third sub-command (bin/DeepMod_scripts/myGetFeatureBasedPos.py): raw reads + a reference + known positions -> the labelled
+ * *.xy.gz text `train` reads.  A matrix row of get_Feature (:355-528) travels as (pos, lab, code) + the event it shows:
+ *   pos   int64  column 0, the reference position (0 outside the aligned part)
+ *   lab   uint8  0 none | 1 negative (column 1) | 2 positive (column 2)
+ *   code  uint8  the one-hot class dm_rows_assemble takes (columns 3..6)
+ *   rdesc int64 [reads][4]  dm_rows_assemble's descriptors: columns 7..9 are (mean, stdv, length) of event q + rdesc[1] of the ev3 block
+ * HOST (csrc/xyrows.inc):
+ *   dm_xy_sites_*   the position lists (fulmodlist / anymodlist / nomodlist, :653-701) as sorted arrays per contig x strand; has_any / has_no:
+ *                   the list is not None (--motifORPos 2).  Membership is by (strand, refbasei) value, as in the reference.
+ *   dm_xy_labels    the columns dm_map_read writes -> pos / lab / code of the read's matrix rows (n_events - end_clip - start_clip + 200 of them,
+ *                   written from index 0 of the arrays) and its descriptor for rows from row0 and events from ev0 of a batch.  motif: NULL
+ *                   without a motif (--motifORPos 2), else upper case; posneg as the reference's flag.
+ *   dm_xy_read      a SAM record -> the same, through the walk of dm_map_read with the CpG gap swap only for motif "CG" (:302); a base
+ *                   mismatch does not end the read (:462-464).  info[DM_XY_STATUS]:
+ */
+#define DM_XY_OK 0
+#define DM_XY_LESS_EVENT 1        /* fewer than 500 aligned events (:321-323) */
+#define DM_XY_NO_SITE 2           /* no listed position on the contig (:135-138) */
+#define DM_XY_FILTERED 3          /* region filter (:174-181; set by the caller, which knows the names) */
+#define DM_XY_NO_MATCH 4          /* no matching base (:245-250) */
+#define DM_XY_INDEX_ERROR 5       /* fewer aligned table rows than aligned events (the reference raises IndexError, :455) */
+#define DM_XY_NEED_ROWS 6         /* cap_rows < info[DM_XY_N_ROWS]: nothing written */
+#define DM_XY_INFO_LEN 8
+#define DM_XY_STATUS 0
+#define DM_XY_N_ROWS 1
+#define DM_XY_STRAND 2
+#define DM_XY_START_CLIP 3
+#define DM_XY_END_CLIP 4
+#define DM_XY_POS_AFTER_CLIP 5
+#define DM_XY_EVENTS_AFTER_CLIP 6
+typedef struct dm_xysites dm_xysites;
+dm_xysites* dm_xy_sites_create(int32_t n_contigs, int has_any, int has_no);
+void dm_xy_sites_destroy(dm_xysites* s);
+int dm_xy_sites_set(dm_xysites* s, int32_t contig, int strand, int kind, const int64_t* pos, int64_t n);
+int dm_xy_labels(const dm_xysites* s, int32_t contig, int strand, const char* motif, int motif_pos, int posneg, const char* refbase, const char* readbase,
+                 const uint64_t* refbasei, int64_t n_table_rows, int64_t n_events, int64_t start_clip, int64_t end_clip, int64_t mapped_start_pos,
+                 int64_t num_insertions, int64_t* pos, uint8_t* lab, uint8_t* code, int64_t cap_rows, int64_t row0, int64_t ev0, int64_t* rdesc,
+                 int64_t* info);
+int dm_xy_read(const dm_xysites* s, int32_t contig, int flag, int64_t pos1, const char* cigar, const char* readseq, int64_t readseq_len, const char* refseq,
+               int64_t refseq_len, int64_t n_events, const char* motif, int motif_pos, int posneg, int64_t* pos, uint8_t* lab, uint8_t* code,
+               int64_t cap_rows, int64_t row0, int64_t ev0, int64_t* rdesc, int64_t* info);
+/* The text: np.savetxt(fmt='%.3f') of rows [n][10] doubles - snprintf("%.3f") of the ten values joined by one space, then '\n' ('nan' without a
+ * sign).  -> the bytes of the text; written only if cap holds all of them.  dm_xy_rows_host: the device stage below on the host, from host
+ * statistics ev3 [n_events][3] (the rows of a batch are never materialised); keep, the offset tables and text are optional, text is written as far
+ * as cap reaches. */
+int64_t dm_xy_format_host(const double* rows, int64_t n_rows, char* out, int64_t cap);
+int64_t dm_xy_rows_host(const int64_t* pos, const uint8_t* lab, const uint8_t* code, const int64_t* rdesc, int64_t n_reads, int64_t n_rows, const float* ev3,
+                        int64_t n_events, uint8_t* keep, int64_t* read_row_off, int64_t* read_byte_off, char* text, int64_t cap);
+/* DEVICE (csrc/xyrows.hip.inc): row selection (:512-526) and text of a batch, statistics read where the signal stage left them (d_ev3, the block of
+ * dm_signal_event_stats_device / dm_signal_move_stats_device, [n_events][3]).  A row is kept if a labelled row of ITS read lies within +-25 rows;
+ * a read of n rows with 10 kept > 9 n keeps all, one with none gives nothing.  Plain launches on one stream, no atomics: two calls give the same bytes.
+ *   dm_xy_rows        pos / lab / code [n_rows], rdesc [n_reads][4]: host arrays, checked before use.  -> the bytes of the text (< 0: error code).
+ *                     *flag = 1: a mean or stdv of a kept row is not finite or >= 2^30 in magnitude, or a length is above 2^24 - the device
+ *                     formatter does not take those, and the call has computed the batch through dm_xy_rows_host on the downloaded block
+ *                     instead: the result is the reference's bytes either way.
+ *   dm_xy_rows_fetch  of the last call: the text, keep [n_rows], read_row_off / read_byte_off [n_reads + 1] (first output row / byte of every read,
+ *                     the totals last) - any may be NULL.
+ *   dm_xy_times       milliseconds the selection and the text kernels of the last call took on the device (HIP events).
+ *   dm_xy_scan        the stage's 64-bit exclusive scan on its own: values [n + 1] (host) <- the prefix sums of values [0 .. n) and their total. */
+typedef struct dm_xyrows dm_xyrows;
+dm_xyrows* dm_xy_create(int device);
+void dm_xy_destroy(dm_xyrows* h);
+int64_t dm_xy_rows(dm_xyrows* h, const int64_t* pos, const uint8_t* lab, const uint8_t* code, const int64_t* rdesc, int64_t n_reads, int64_t n_rows,
+                   const float* d_ev3, int64_t n_events, int32_t* flag);
+int dm_xy_rows_fetch(dm_xyrows* h, char* text, uint8_t* keep, int64_t* read_row_off, int64_t* read_byte_off);
+int dm_xy_times(dm_xyrows* h, double* keep_ms, double* text_ms);
+int dm_xy_scan(dm_xyrows* h, int64_t* values, int64_t n);
+
 #ifdef __cplusplus
 }
 #endif
