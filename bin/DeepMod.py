@@ -16,6 +16,11 @@ containers (*.dmraw.npz, event tables or --move), a reference and known modified
 alignment walk and gzip on --threads host threads (deepmod_amd/getfeatures.py).  Only --fnum 7 and
 --SignalGroup simple; --region takes a contig name; an --outFolder that already holds */*.xy.gz is refused
 (the reference deletes it).
+
+`predict` scores a checkpoint on labelled *.xy.gz files (the reference's unwired pred_entry / mPred): text parsing, row
+selection and the classifier on one GPU, gunzip on --threads host threads; --test takes the value `train` was given and
+evaluates what `train` left out.  Writes <outFolder>/<FileID>_mpred.txt (the reference's tp / fp / fn / tn lines) and
+<FileID>_mpred.json (deepmod_amd/predict.py).
 """
 import argparse
 import os
@@ -85,6 +90,17 @@ def build_parser():
     trn.add_argument('--seed', type=int, default=0, help='seed of the initial values (numpy generator)')
     trn.add_argument('--batchsize', type=int, default=2048, help='windows per training step (the reference fixes 2048): the leading group is cut into steps of batchsize .. 2 batchsize - 1 windows, a step of another group can be larger by a file; the device tape (158,400 B per window) is sized for 2 batchsize - 1 and grows to the largest step met')
     trn.set_defaults(func=mTrain)
+    prd = sub.add_parser('predict', parents=[com], help='score a trained model on labelled *.xy.gz feature files',
+                         description='Evaluate a checkpoint on labelled *.xy.gz files: per file the text is parsed, the labelled rows are selected and their '
+                                     'windows classified on one GPU (precision: DEEPMOD_PRECISION, as detect).  --wrkBase: folders separated by , or ; - files in '
+                                     'sorted order, no shuffle.  Writes <outFolder>/<FileID>_mpred.txt (tp= fp= fn= tn= per piece of at most 2048 windows) and '
+                                     '<FileID>_mpred.json (counts, accuracy, precision, recall, exact ROC AUC).')
+    prd.add_argument('--fnum', type=int, default=7, help='features per event')
+    prd.add_argument('--hidden', type=int, default=100, help='LSTM hidden units')
+    prd.add_argument('--modfile', default=None, help='checkpoint prefix of the trained model (TF bundle)')
+    prd.add_argument('--test', default=None, help="the value train was given: 'E,a,b' evaluates only positions a..b (Mb), 'P,pct' the files train did not use")
+    prd.add_argument('--outputlayer', default='', choices=['', 'sigmoid'], help="only '' is built")
+    prd.set_defaults(func=mPredict)
     gf = sub.add_parser('getfeatures', parents=[com], help='get labelled features of all raw reads for training',
                         description='Write the *.xy.gz / *.xy.ind training files from raw containers (*.dmraw.npz), a reference and known modified positions: '
                                     'per worker batch of --files_per_thread inputs a folder <outFolder>/<batch id>/.  One GPU; --threads host threads load, walk '
@@ -155,19 +171,19 @@ def mGetFeatures(args):
     getfeatures.getFeature_manager(mo)
 
 
-def train_options(args):
-    """moptions of `train` as bin/DeepMod.py:186-222 of the reference builds them; geometry and output layer are refused as detect refuses them."""
+def train_options(args, cmd='train', keys=('unbalanced', 'modfile', 'seed')):
+    """moptions of `train` as bin/DeepMod.py:186-222 of the reference builds them; geometry and output layer are refused as detect refuses them.
+    `predict` takes the same folders, geometry and --test (cmd, keys: its own options)."""
     if args is None or not getattr(args, 'wrkBase', None):
-        raise SystemExit('Error: train: --wrkBase: the folders of the *.xy.gz feature files ("a,b;c")')
-    mo = {k: getattr(args, k) for k in ('outLevel', 'wrkBase', 'FileID', 'outFolder', 'recursive', 'windowsize', 'fnum', 'hidden', 'outputlayer',
-                                         'unbalanced', 'modfile', 'seed')}
+        raise SystemExit('Error: %s: --wrkBase: the folders of the *.xy.gz feature files ("a,b;c")' % cmd)
+    mo = {k: getattr(args, k) for k in ('outLevel', 'wrkBase', 'FileID', 'outFolder', 'recursive', 'windowsize', 'fnum', 'hidden', 'outputlayer') + tuple(keys)}
     for k in ('windowsize', 'fnum', 'hidden'):
         non_negative(mo[k], k)
     if (mo['fnum'], mo['hidden'], mo['windowsize']) != (7, 100, 21):
         raise SystemExit('Error: this build supports fnum=7 hidden=100 windowsize=21 only (got %s)' % ((mo['fnum'], mo['hidden'], mo['windowsize']),))
     if mo['outputlayer'] in ('sigmoid',):
         raise SystemExit('Error: --outputlayer sigmoid is not used by any shipped model and is not built')
-    if args.batchsize < 1:
+    if cmd == 'train' and args.batchsize < 1:
         raise SystemExit('Error: --batchsize must be positive')
     if not mo['outFolder'].endswith('/'):
         mo['outFolder'] += '/'
@@ -199,6 +215,17 @@ def mTrain(args):
         raise SystemExit('Error: no gfx950 GPU visible (this build has no CPU path)')
     os.makedirs(mo['outFolder'], exist_ok=True)
     train.mMult_RNN_LSTM_train(mo, batchsize=args.batchsize)
+
+
+def mPredict(args):
+    mo = train_options(args, cmd='predict', keys=('modfile', 'threads'))
+    if not mo['modfile'] or not os.path.isfile(mo['modfile'] + '.index'):
+        raise SystemExit('Error: predict: --modfile: no TF checkpoint at %r' % mo['modfile'])
+    mo['threads'] = max(mo['threads'], 1)
+    from deepmod_amd import _lib, predict
+    if _lib.load().dm_device_count() < 1:
+        raise SystemExit('Error: no gfx950 GPU visible (this build has no CPU path)')
+    predict.pred_entry(mo)
 
 
 def kfd_gpu_count(base='/sys/class/kfd/kfd/topology/nodes'):

@@ -146,6 +146,20 @@ SIGNATURES = [
     ("dm_xy_rows_fetch", _c.c_int, [_vp, _vp, _vp, _vp, _vp]),
     ("dm_xy_times", _c.c_int, [_vp, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
     ("dm_xy_scan", _c.c_int, [_vp, _vp, _i64]),
+    ("dm_xyload_create", _vp, [_c.c_int]),
+    ("dm_xyload_destroy", None, [_vp]),
+    ("dm_xyload_parse", _c.c_int, [_vp, _vp, _i64, _c.POINTER(_i64), _c.POINTER(_c.c_int32), _c.POINTER(_i64)]),
+    ("dm_xyload_parse_host", _i64, [_vp, _i64, _vp, _i64, _c.POINTER(_c.c_int32), _c.POINTER(_i64)]),
+    ("dm_xyload_set_table", _c.c_int, [_vp, _vp, _i64]),
+    ("dm_xyload_select", _i64, [_vp, _c.c_int, _i64, _i64, _c.POINTER(_i64)]),
+    ("dm_xyload_set_selection", _c.c_int, [_vp, _vp, _vp, _i64]),
+    ("dm_xyload_device", _c.c_int, [_vp, _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_i64), _c.POINTER(_i64)]),
+    ("dm_xyload_fetch", _c.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    ("dm_xyload_classify", _c.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    ("dm_xyload_select_host", _i64, [_vp, _i64, _c.c_int, _i64, _i64, _vp, _vp, _i64, _c.POINTER(_i64)]),
+    ("dm_xyload_times", _c.c_int, [_vp, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
+    ("dm_xyload_tile_bytes", _c.c_int, []),
+    ("dm_xyload_scan_block", _c.c_int, []),
 ]
 
 

@@ -1,0 +1,531 @@
+// xyparse.hip.inc — predict, device part (included by deepmod_hip.hip after xyrows.hip.inc): the text of one .xy file -> its table, and the rows
+// whose windows are classified.  The inverse of xyrows.hip.inc (which writes this text) and the device statement of train.getDataFromFile_new
+// (np.loadtxt + the selection of myMultiBiRNN.py:306-343).
+//
+// The text: lines of ten fields `-?[0-9]+(\.[0-9]+)?` with at most 15 digit characters each, one space between fields, '\n' after the tenth (the
+// host appends a missing last one).  Anything else - nan, inf, an exponent, '+', a tab, two spaces, '\r', an empty line, '#', nine or eleven
+// fields, 16 digits, '.5', '5.' - marks its line and the file is loaded on the host instead (xyload.py: np.loadtxt): the result is np.loadtxt's
+// either way.
+// A field's value (parse_row, compiled for both sides: dm_xyload_parse_host runs it on the host): the digits as an integer m < 10^15 < 2^53, the
+// power 10^k of its k decimals as an integer <= 10^15 - both exact as doubles - ONE IEEE division, the sign last (-0.000 is -0.0), the cast to
+// float.  m / 10^k with exact operands is the correctly rounded double of the decimal (Clinger's exact case), i.e. what strtod and np.loadtxt
+// produce before their cast; contraction is off so that the division stays a division.
+// Plain launches on the stream of the handle's scan, no atomics, one writer per output element: two calls on the same bytes give the same bytes.
+//   xl_count_kernel   a tile of TILE bytes, 16 per lane (one dwordx4 load): newlines counted with one ballot per byte column -> count per tile
+//   xyk::scan_in_place  exclusive 64-bit scan of the tile counts: the first line of every tile, the row count R behind them
+//   xl_lines_kernel   the same loads again: a newline's rank = the tile's first line + the block scan of the lane counts -> the first byte of
+//                     every line
+//   xl_parse_kernel   one row per lane: parse_row -> head [R][3] (position, two labels), feats [R][7], a status byte
+//   xl_first_kernel   one block: the smallest row with a status byte set (-1: none)
+// Selection (xl_want_kernel, the scan, xl_compact_kernel): a row is wanted unless both labels are below 0.01f; under kind '-' not if
+// lo < int(position) < hi, under '+' only then (the float32 position truncated, as the reference's astype(int)); the wanted rows in ascending
+// order -> centre int32 [n] and label u8 [n] (1: int(column 2) == 1, myMultiBiRNN.py:407); a wanted row with fewer than 10 rows to an edge of the
+// file raises its status byte (xl_first_kernel: the first of them).  NaN cannot come out of parse_row, so the loader's NaN rule lives on the host
+// path only.  dm_xyload_select_host runs the same three rules (row_wanted, the edge, row_label) on a host table.
+// dm_xyload_classify: dm_predict_read_at on the resident table and centres, xl_prob1_kernel gathers column 1 of the probabilities; class,
+// probability and label come back as three plain copies, 6 bytes per window.
+
+namespace xlk {
+
+constexpr int THREADS = 256;
+constexpr int LANE_BYTES = 16;
+constexpr int TILE = THREADS * LANE_BYTES;          // dm_xyload_tile_bytes()
+constexpr int MAX_DIGITS = 15;
+constexpr int HALF = DM_WINDOW / 2;
+
+// One line p[0 .. n) (without its '\n') -> ten floats; false: outside the grammar (out is then unspecified).
+__host__ __device__ inline bool parse_row(const char* __restrict__ p, const long long n, float* __restrict__ out) {
+#pragma clang fp contract(off)
+    long long i = 0;
+    for (int f = 0; f < 10; ++f) {
+        const bool neg = i < n && p[i] == '-';
+        if (neg) ++i;
+        unsigned long long m = 0, scale = 1;
+        int digits = 0, whole = 0, decimals = 0;
+        bool point = false;
+        for (; i < n; ++i) {
+            const char c = p[i];
+            if (c >= '0' && c <= '9') {
+                if (++digits > MAX_DIGITS) return false;
+                m = m * 10ull + (unsigned long long)(c - '0');
+                if (point) {
+                    scale *= 10ull;
+                    ++decimals;
+                } else {
+                    ++whole;
+                }
+            } else if (c == '.' && !point && whole > 0) {
+                point = true;
+            } else {
+                break;
+            }
+        }
+        if (whole == 0 || (point && decimals == 0)) return false;
+        if (f < 9 ? !(i < n && p[i] == ' ') : i != n) return false;
+        ++i;
+        const double v = double(m) / double(scale);
+        out[f] = float(neg ? -v : v);
+    }
+    return true;
+}
+
+__device__ inline uint4 load_lane(const char* __restrict__ text, const long long off, const long long n_bytes) {
+    // the buffer holds whole 16-byte groups (dm_xyload_parse sizes it so); what lies behind n_bytes is masked by newline_mask
+    return off < n_bytes ? *reinterpret_cast<const uint4*>(text + off) : uint4{0u, 0u, 0u, 0u};
+}
+
+// bit j: byte j of the lane's 16 is a '\n' of the text
+__device__ inline unsigned newline_mask(const uint4 v, const long long off, const long long n_bytes) {
+    const unsigned w[4] = {v.x, v.y, v.z, v.w};
+    unsigned mask = 0;
+#pragma unroll
+    for (int j = 0; j < LANE_BYTES; ++j)
+        if (((w[j >> 2] >> (8 * (j & 3))) & 0xffu) == 0x0au && off + j < n_bytes) mask |= 1u << j;
+    return mask;
+}
+
+__global__ __launch_bounds__(THREADS) void xl_count_kernel(const char* __restrict__ text, const long long n_bytes, long long* __restrict__ count) {
+    __shared__ int wave_count[THREADS / 64];
+    const long long off = (long long)blockIdx.x * TILE + (long long)threadIdx.x * LANE_BYTES;
+    const unsigned mask = newline_mask(load_lane(text, off, n_bytes), off, n_bytes);
+    int c = 0;
+#pragma unroll
+    for (int j = 0; j < LANE_BYTES; ++j) c += __popcll(__ballot((mask >> j) & 1u));
+    if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long t = 0;
+        for (int k = 0; k < THREADS / 64; ++k) t += wave_count[k];
+        count[blockIdx.x] = t;
+    }
+}
+
+// start [R + 1]: start[r] = the first byte of line r, start[R] = the byte behind the last newline
+__global__ __launch_bounds__(THREADS) void xl_lines_kernel(const char* __restrict__ text, const long long n_bytes, const long long* __restrict__ tile_row,
+                                                          const long long n_rows, long long* __restrict__ start) {
+    __shared__ long long wave_total[THREADS / 64];
+    const long long off = (long long)blockIdx.x * TILE + (long long)threadIdx.x * LANE_BYTES;
+    const unsigned mask = newline_mask(load_lane(text, off, n_bytes), off, n_bytes);
+    long long total;
+    long long r = tile_row[blockIdx.x] + csites::block_exclusive_scan<THREADS>((long long)__popc(mask), wave_total, total);
+    if (blockIdx.x == 0 && threadIdx.x == 0) start[0] = 0;
+    for (int j = 0; j < LANE_BYTES; ++j)
+        if ((mask >> j) & 1u) {
+            ++r;                                                     // this newline ends line r - 1
+            if (r <= n_rows) start[r] = off + j + 1;
+        }
+}
+
+__global__ __launch_bounds__(THREADS) void xl_parse_kernel(const char* __restrict__ text, const long long* __restrict__ start, const long long n_rows,
+                                                          float* __restrict__ head, float* __restrict__ feats, unsigned char* __restrict__ status) {
+    const long long r = (long long)blockIdx.x * THREADS + threadIdx.x;
+    if (r >= n_rows) return;
+    const long long b = start[r], e = start[r + 1] - 1;              // text[e] is the line's '\n'
+    float v[10];
+    const bool ok = parse_row(text + b, e - b, v);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) head[3 * r + c] = ok ? v[c] : 0.0f;
+#pragma unroll
+    for (int c = 0; c < DM_NFEAT; ++c) feats[DM_NFEAT * r + c] = ok ? v[3 + c] : 0.0f;
+    status[r] = ok ? 0 : 1;
+}
+
+// out[0] = the smallest i with status[i] != 0, -1 if there is none
+__global__ __launch_bounds__(xyk::SUM_THREADS) void xl_first_kernel(const unsigned char* __restrict__ status, const long long n, long long* __restrict__ out) {
+    __shared__ long long wave_min[xyk::SUM_THREADS / 64];
+    const long long none = 0x7fffffffffffffffLL;
+    long long best = none;
+    for (long long i = threadIdx.x; i < n; i += xyk::SUM_THREADS)
+        if (status[i] && i < best) best = i;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) best = min(best, __shfl_xor(best, d, 64));
+    if ((threadIdx.x & 63) == 0) wave_min[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < xyk::SUM_THREADS / 64; ++k) best = min(best, wave_min[k]);
+        out[0] = best == none ? -1 : best;
+    }
+}
+
+__host__ __device__ inline bool row_wanted(const float* __restrict__ h /* position, label 0, label 1 */, const int kind, const long long lo, const long long hi) {
+    bool wanted = !(h[1] < 0.01f && h[2] < 0.01f);
+    if (kind != 0) {
+        const long long ipos = (long long)h[0];
+        const bool inside = lo < ipos && ipos < hi;
+        wanted = wanted && (kind < 0 ? !inside : inside);
+    }
+    return wanted;
+}
+
+// 1: int(column 2) == 1 (myMultiBiRNN.py:407 on labels.astype(int))
+__host__ __device__ inline unsigned char row_label(const float* __restrict__ h) { return (long long)h[2] == 1 ? 1 : 0; }
+
+__global__ __launch_bounds__(THREADS) void xl_want_kernel(const float* __restrict__ head, const long long n_rows, const int kind, const long long lo, const long long hi,
+                                                         long long* __restrict__ want, unsigned char* __restrict__ status) {
+    const long long r = (long long)blockIdx.x * THREADS + threadIdx.x;
+    if (r >= n_rows) return;
+    const bool w = row_wanted(head + 3 * r, kind, lo, hi);
+    want[r] = w ? 1 : 0;
+    status[r] = w && (r < HALF || r + HALF >= n_rows) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(THREADS) void xl_compact_kernel(const float* __restrict__ head, const long long* __restrict__ scan, const long long n_rows,
+                                                            int* __restrict__ centre, unsigned char* __restrict__ label) {
+    const long long r = (long long)blockIdx.x * THREADS + threadIdx.x;
+    if (r >= n_rows) return;
+    const long long at = scan[r];
+    if (scan[r + 1] == at) return;
+    centre[at] = int(r);
+    label[at] = row_label(head + 3 * r);
+}
+
+// column 1 of prob [n][2] -> prob1 [n]: what `predict` downloads is one contiguous copy
+__global__ __launch_bounds__(THREADS) void xl_prob1_kernel(const float* __restrict__ prob, const long long n, float* __restrict__ prob1) {
+    const long long i = (long long)blockIdx.x * THREADS + threadIdx.x;
+    if (i < n) prob1[i] = prob[2 * i + 1];
+}
+
+}  // namespace xlk
+
+struct dm_xyload {
+    dm_xyrows* xy = nullptr;                            // stream, the scan and its block sums
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    enum { TEXT, COUNT, START, HEAD, FEATS, STATUS, WANT, CENTRE, LABEL, OUT, PROB, PROB1, CLS, N_BUF };
+    void* buf[N_BUF] = {};
+    size_t cap[N_BUF] = {};
+    int64_t n_rows = -1, n = -1;                        // of the table on the device (-1: none) and of its selection (-1: none)
+    bool flagged = false;                               // the last text held a line outside the grammar: its table is not to be used
+    bool parse_timed = false, select_timed = false;
+};
+
+namespace xlk {
+
+int ensure(dm_xyload* h, int which, size_t bytes) {
+    if (h->cap[which] >= bytes && h->buf[which]) return DM_OK;
+    if (h->buf[which]) (void)hipFree(h->buf[which]);
+    h->buf[which] = nullptr;
+    h->cap[which] = 0;
+    const size_t want = bytes + (bytes >> 2) + 256;                  // grow-only, a quarter ahead
+    if (hipMalloc(&h->buf[which], want) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(DM_ENOMEM, "dm_xyload: hipMalloc(%zu) failed", want);
+    }
+    h->cap[which] = want;
+    return DM_OK;
+}
+
+template <class T>
+T* ptr(dm_xyload* h, int which) { return static_cast<T*>(h->buf[which]); }
+
+constexpr int64_t MAX_BYTES = int64_t(1) << 40;
+constexpr int64_t MAX_ROWS = 0x7fffffffLL - HALF;                     // centre is int32
+
+int table_buffers(dm_xyload* h, int64_t n_rows) {
+    int rc;
+    if ((rc = ensure(h, dm_xyload::HEAD, size_t(n_rows) * 12)) != DM_OK) return rc;
+    if ((rc = ensure(h, dm_xyload::FEATS, size_t(n_rows) * 4 * DM_NFEAT)) != DM_OK) return rc;
+    if ((rc = ensure(h, dm_xyload::STATUS, size_t(n_rows))) != DM_OK) return rc;
+    return ensure(h, dm_xyload::OUT, 16);
+}
+
+}  // namespace xlk
+
+extern "C" {
+
+int dm_xyload_tile_bytes(void) { return xlk::TILE; }
+int dm_xyload_scan_block(void) { return xyk::SCAN_TILE; }
+
+void dm_xyload_destroy(dm_xyload* h) {
+    if (!h) return;
+    if (h->xy) (void)hipSetDevice(h->xy->device);
+    for (void* b : h->buf)
+        if (b) (void)hipFree(b);
+    for (hipEvent_t e : h->ev)
+        if (e) (void)hipEventDestroy(e);
+    dm_xy_destroy(h->xy);
+    delete h;
+}
+
+dm_xyload* dm_xyload_create(int device) {
+    dm_xyrows* xy = dm_xy_create(device);
+    if (!xy) return nullptr;
+    dm_xyload* h = new dm_xyload;
+    h->xy = xy;
+    for (hipEvent_t& e : h->ev)
+        if (hipEventCreate(&e) != hipSuccess) {
+            fail(DM_EDEVICE, "dm_xyload_create: events on device %d", device);
+            dm_xyload_destroy(h);
+            return nullptr;
+        }
+    return h;
+}
+
+int64_t dm_xyload_parse_host(const char* text, int64_t n_bytes, float* table, int64_t cap_rows, int32_t* flag, int64_t* first_bad_line) {
+    if (n_bytes < 0 || (n_bytes > 0 && !text) || cap_rows < 0 || (cap_rows > 0 && !table)) return fail(DM_EINVAL, "dm_xyload_parse_host: null argument");
+    int64_t rows = 0, bad = 0;
+    float v[10];
+    for (int64_t b = 0; b < n_bytes;) {
+        const void* nl = std::memchr(text + b, '\n', size_t(n_bytes - b));
+        const int64_t e = nl ? static_cast<const char*>(nl) - text : n_bytes;          // a last line without '\n' ends with the text
+        const bool ok = xlk::parse_row(text + b, e - b, v);
+        if (!ok && bad == 0) bad = rows + 1;
+        if (rows < cap_rows)
+            for (int c = 0; c < 10; ++c) table[10 * rows + c] = ok ? v[c] : 0.0f;
+        ++rows;
+        b = e + 1;
+    }
+    if (flag) *flag = bad != 0;
+    if (first_bad_line) *first_bad_line = bad ? bad : -1;
+    return rows;
+}
+
+// the selection on the host, with the routines the kernels run (row_wanted, the edge rule, the label rule)
+int64_t dm_xyload_select_host(const float* table, int64_t n_rows, int kind, int64_t lo, int64_t hi, int32_t* centre, uint8_t* label, int64_t cap, int64_t* short_row) {
+    if (short_row) *short_row = -1;
+    if (n_rows < 0 || n_rows > xlk::MAX_ROWS || (n_rows > 0 && !table) || cap < 0 || (cap > 0 && (!centre || !label)))
+        return fail(DM_EINVAL, "dm_xyload_select_host: null argument or %lld rows", (long long)n_rows);
+    if (kind != 0 && kind != '-' && kind != '+') return fail(DM_EINVAL, "dm_xyload_select_host: kind %d (0, '-' or '+')", kind);
+    const int k = kind == 0 ? 0 : (kind == '-' ? -1 : 1);
+    int64_t n = 0;
+    for (int64_t r = 0; r < n_rows; ++r) {
+        if (!xlk::row_wanted(table + 10 * r, k, lo, hi)) continue;
+        if (r < xlk::HALF || r + xlk::HALF >= n_rows) {
+            if (short_row) *short_row = r;
+            return fail(DM_EINVAL, "dm_xyload_select_host: labelled row %lld is closer than %d rows to the edge of the table (%lld rows): no whole window", (long long)r,
+                        xlk::HALF, (long long)n_rows);
+        }
+        if (n < cap) {
+            centre[n] = int32_t(r);
+            label[n] = xlk::row_label(table + 10 * r);
+        }
+        ++n;
+    }
+    return n;
+}
+
+int dm_xyload_parse(dm_xyload* h, const char* text, int64_t n_bytes, int64_t* n_rows, int32_t* flag, int64_t* first_bad_line) {
+    if (!h) return fail(DM_EINVAL, "null handle");
+    h->n_rows = h->n = -1;
+    h->flagged = h->parse_timed = h->select_timed = false;
+    if (n_rows) *n_rows = 0;
+    if (flag) *flag = 0;
+    if (first_bad_line) *first_bad_line = -1;
+    if (n_bytes < 0 || n_bytes >= xlk::MAX_BYTES || (n_bytes > 0 && !text)) return fail(DM_EINVAL, "dm_xyload_parse: %lld bytes of text", (long long)n_bytes);
+    HIP_TRY(hipSetDevice(h->xy->device));
+    using B = dm_xyload;
+    int rc;
+    if (n_bytes == 0) {                                              // an empty file: a table of no rows
+        if ((rc = xlk::table_buffers(h, 0)) != DM_OK) return rc;
+        h->n_rows = 0;
+        return DM_OK;
+    }
+    const bool add_newline = text[n_bytes - 1] != '\n';
+    const int64_t n = n_bytes + (add_newline ? 1 : 0);
+    const int64_t tiles = (n + xlk::TILE - 1) / xlk::TILE;
+    if ((rc = xlk::ensure(h, B::TEXT, size_t(tiles) * xlk::TILE)) != DM_OK) return rc;    // whole 16-byte groups behind every lane offset below n
+    if ((rc = xlk::ensure(h, B::COUNT, size_t(tiles + 1) * 8)) != DM_OK) return rc;
+    if ((rc = xlk::ensure(h, B::OUT, 16)) != DM_OK) return rc;
+    hipStream_t s = h->xy->stream;
+    char* d_text = xlk::ptr<char>(h, B::TEXT);
+    long long* d_count = xlk::ptr<long long>(h, B::COUNT);
+    static const char newline = '\n';
+    HIP_TRY(hipMemcpyAsync(d_text, text, size_t(n_bytes), hipMemcpyHostToDevice, s));
+    if (add_newline) HIP_TRY(hipMemcpyAsync(d_text + n_bytes, &newline, 1, hipMemcpyHostToDevice, s));
+    const dim3 tile_grid{unsigned(tiles)}, block{xlk::THREADS};
+    HIP_TRY(hipEventRecord(h->ev[0], s));
+    hipLaunchKernelGGL(xlk::xl_count_kernel, tile_grid, block, 0, s, d_text, (long long)n, d_count);
+    HIP_TRY(hipGetLastError());
+    if ((rc = xyk::scan_in_place(h->xy, d_count, tiles)) != DM_OK) return rc;
+    long long rows = 0;
+    HIP_TRY(hipMemcpyAsync(&rows, d_count + tiles, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (rows < 1 || rows > n) return fail(DM_ESTATE, "dm_xyload_parse: %lld lines in %lld bytes", rows, (long long)n);
+    if (rows > xlk::MAX_ROWS) return fail(DM_EINVAL, "dm_xyload_parse: %lld rows (at most %lld)", rows, (long long)xlk::MAX_ROWS);
+    if ((rc = xlk::table_buffers(h, rows)) != DM_OK) return rc;
+    if ((rc = xlk::ensure(h, B::START, size_t(rows + 1) * 8)) != DM_OK) return rc;
+    long long* d_start = xlk::ptr<long long>(h, B::START);
+    unsigned char* d_status = xlk::ptr<unsigned char>(h, B::STATUS);
+    long long* d_out = xlk::ptr<long long>(h, B::OUT);
+    const dim3 row_grid{unsigned((rows + xlk::THREADS - 1) / xlk::THREADS)};
+    hipLaunchKernelGGL(xlk::xl_lines_kernel, tile_grid, block, 0, s, d_text, (long long)n, d_count, rows, d_start);
+    hipLaunchKernelGGL(xlk::xl_parse_kernel, row_grid, block, 0, s, d_text, d_start, rows, xlk::ptr<float>(h, B::HEAD), xlk::ptr<float>(h, B::FEATS), d_status);
+    hipLaunchKernelGGL(xlk::xl_first_kernel, dim3(1), dim3(xyk::SUM_THREADS), 0, s, d_status, rows, d_out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[1], s));
+    long long first = -1;
+    HIP_TRY(hipMemcpyAsync(&first, d_out, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    h->n_rows = rows;
+    h->flagged = first >= 0;
+    h->parse_timed = true;
+    if (n_rows) *n_rows = rows;
+    if (flag) *flag = first >= 0;
+    if (first_bad_line) *first_bad_line = first >= 0 ? first + 1 : -1;
+    return DM_OK;
+}
+
+int dm_xyload_set_table(dm_xyload* h, const float* table, int64_t n_rows) {
+    if (!h) return fail(DM_EINVAL, "null handle");
+    h->n_rows = h->n = -1;
+    h->flagged = h->parse_timed = h->select_timed = false;
+    if (n_rows < 0 || n_rows > xlk::MAX_ROWS || (n_rows > 0 && !table)) return fail(DM_EINVAL, "dm_xyload_set_table: %lld rows", (long long)n_rows);
+    HIP_TRY(hipSetDevice(h->xy->device));
+    int rc = xlk::table_buffers(h, n_rows);
+    if (rc) return rc;
+    std::vector<float> head(size_t(n_rows) * 3), feats(size_t(n_rows) * DM_NFEAT);
+    for (int64_t r = 0; r < n_rows; ++r) {
+        std::memcpy(&head[size_t(r) * 3], table + 10 * r, 12);
+        std::memcpy(&feats[size_t(r) * DM_NFEAT], table + 10 * r + 3, 4 * DM_NFEAT);
+    }
+    if (n_rows > 0) {
+        HIP_TRY(hipMemcpyAsync(h->buf[dm_xyload::HEAD], head.data(), head.size() * 4, hipMemcpyHostToDevice, h->xy->stream));
+        HIP_TRY(hipMemcpyAsync(h->buf[dm_xyload::FEATS], feats.data(), feats.size() * 4, hipMemcpyHostToDevice, h->xy->stream));
+        HIP_TRY(hipStreamSynchronize(h->xy->stream));
+    }
+    h->n_rows = n_rows;
+    return DM_OK;
+}
+
+int64_t dm_xyload_select(dm_xyload* h, int kind, int64_t lo, int64_t hi, int64_t* short_row) {
+    if (!h) return fail(DM_EINVAL, "null handle");
+    h->n = -1;
+    h->select_timed = false;
+    if (short_row) *short_row = -1;
+    if (h->n_rows < 0) return fail(DM_ESTATE, "dm_xyload_select: no table");
+    if (h->flagged) return fail(DM_ESTATE, "dm_xyload_select: the text was outside the device grammar; give the host's table with dm_xyload_set_table");
+    if (kind != 0 && kind != '-' && kind != '+') return fail(DM_EINVAL, "dm_xyload_select: kind %d (0, '-' or '+')", kind);
+    const int64_t rows = h->n_rows;
+    if (rows == 0) {
+        h->n = 0;
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(h->xy->device));
+    using B = dm_xyload;
+    int rc;
+    if ((rc = xlk::ensure(h, B::WANT, size_t(rows + 1) * 8)) != DM_OK) return rc;
+    hipStream_t s = h->xy->stream;
+    const float* d_head = xlk::ptr<float>(h, B::HEAD);
+    long long* d_want = xlk::ptr<long long>(h, B::WANT);
+    unsigned char* d_status = xlk::ptr<unsigned char>(h, B::STATUS);
+    long long* d_out = xlk::ptr<long long>(h, B::OUT);
+    const dim3 row_grid{unsigned((rows + xlk::THREADS - 1) / xlk::THREADS)}, block{xlk::THREADS};
+    HIP_TRY(hipEventRecord(h->ev[2], s));
+    hipLaunchKernelGGL(xlk::xl_want_kernel, row_grid, block, 0, s, d_head, (long long)rows, kind == 0 ? 0 : (kind == '-' ? -1 : 1), (long long)lo, (long long)hi, d_want,
+                       d_status);
+    hipLaunchKernelGGL(xlk::xl_first_kernel, dim3(1), dim3(xyk::SUM_THREADS), 0, s, d_status, (long long)rows, d_out);
+    HIP_TRY(hipGetLastError());
+    if ((rc = xyk::scan_in_place(h->xy, d_want, rows)) != DM_OK) return rc;
+    long long out[2] = {-1, 0};
+    HIP_TRY(hipMemcpyAsync(&out[0], d_out, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&out[1], d_want + rows, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (out[0] >= 0) {
+        if (short_row) *short_row = out[0];
+        return fail(DM_EINVAL, "dm_xyload_select: labelled row %lld is closer than %d rows to the edge of the table (%lld rows): no whole window", out[0], xlk::HALF,
+                    (long long)rows);
+    }
+    const int64_t n = out[1];
+    if (n < 0 || n > rows) return fail(DM_ESTATE, "dm_xyload_select: %lld of %lld rows", (long long)n, (long long)rows);
+    if (n > 0) {
+        if ((rc = xlk::ensure(h, B::CENTRE, size_t(n) * 4)) != DM_OK) return rc;
+        if ((rc = xlk::ensure(h, B::LABEL, size_t(n))) != DM_OK) return rc;
+        hipLaunchKernelGGL(xlk::xl_compact_kernel, row_grid, block, 0, s, d_head, d_want, (long long)rows, xlk::ptr<int>(h, B::CENTRE), xlk::ptr<unsigned char>(h, B::LABEL));
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(h->ev[3], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    h->n = n;
+    h->select_timed = true;
+    return n;
+}
+
+int dm_xyload_set_selection(dm_xyload* h, const int32_t* centre, const uint8_t* label, int64_t n) {
+    if (!h) return fail(DM_EINVAL, "null handle");
+    h->n = -1;
+    h->select_timed = false;
+    if (h->n_rows < 0) return fail(DM_ESTATE, "dm_xyload_set_selection: no table");
+    if (n < 0 || n > h->n_rows || (n > 0 && (!centre || !label))) return fail(DM_EINVAL, "dm_xyload_set_selection: %lld rows of %lld", (long long)n, (long long)h->n_rows);
+    for (int64_t i = 0; i < n; ++i)
+        if (centre[i] < xlk::HALF || centre[i] >= h->n_rows - xlk::HALF)
+            return fail(DM_EINVAL, "dm_xyload_set_selection: centre row %d +-%d outside the %lld rows", centre[i], xlk::HALF, (long long)h->n_rows);
+    HIP_TRY(hipSetDevice(h->xy->device));
+    if (n > 0) {
+        int rc;
+        if ((rc = xlk::ensure(h, dm_xyload::CENTRE, size_t(n) * 4)) != DM_OK) return rc;
+        if ((rc = xlk::ensure(h, dm_xyload::LABEL, size_t(n))) != DM_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(h->buf[dm_xyload::CENTRE], centre, size_t(n) * 4, hipMemcpyHostToDevice, h->xy->stream));
+        HIP_TRY(hipMemcpyAsync(h->buf[dm_xyload::LABEL], label, size_t(n), hipMemcpyHostToDevice, h->xy->stream));
+        HIP_TRY(hipStreamSynchronize(h->xy->stream));
+    }
+    h->n = n;
+    return DM_OK;
+}
+
+int dm_xyload_device(dm_xyload* h, const float** d_feats, const int32_t** d_centre, int64_t* n_rows, int64_t* n) {
+    if (!h) return fail(DM_EINVAL, "null handle");
+    if (h->n_rows < 0) return fail(DM_ESTATE, "dm_xyload_device: no table");
+    if (d_feats) *d_feats = xlk::ptr<const float>(h, dm_xyload::FEATS);
+    if (d_centre) *d_centre = h->n > 0 ? xlk::ptr<const int32_t>(h, dm_xyload::CENTRE) : nullptr;
+    if (n_rows) *n_rows = h->n_rows;
+    if (n) *n = h->n;
+    return DM_OK;
+}
+
+int dm_xyload_fetch(dm_xyload* h, float* feats, float* head, int32_t* centre, uint8_t* label) {
+    if (!h) return fail(DM_EINVAL, "null handle");
+    if (h->n_rows < 0) return fail(DM_ESTATE, "dm_xyload_fetch: no table");
+    if ((centre || label) && h->n < 0) return fail(DM_ESTATE, "dm_xyload_fetch: no selection");
+    HIP_TRY(hipSetDevice(h->xy->device));
+    hipStream_t s = h->xy->stream;
+    using B = dm_xyload;
+    if (feats && h->n_rows > 0) HIP_TRY(hipMemcpyAsync(feats, h->buf[B::FEATS], size_t(h->n_rows) * 4 * DM_NFEAT, hipMemcpyDeviceToHost, s));
+    if (head && h->n_rows > 0) HIP_TRY(hipMemcpyAsync(head, h->buf[B::HEAD], size_t(h->n_rows) * 12, hipMemcpyDeviceToHost, s));
+    if (centre && h->n > 0) HIP_TRY(hipMemcpyAsync(centre, h->buf[B::CENTRE], size_t(h->n) * 4, hipMemcpyDeviceToHost, s));
+    if (label && h->n > 0) HIP_TRY(hipMemcpyAsync(label, h->buf[B::LABEL], size_t(h->n), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return DM_OK;
+}
+
+int dm_xyload_classify(dm_xyload* h, dm_model* m, float* prob1, uint8_t* cls, uint8_t* label) {
+    if (!h || !m) return fail(DM_EINVAL, "null handle");
+    if (h->n_rows < 0 || h->n < 0) return fail(DM_ESTATE, "dm_xyload_classify: no selection");
+    if (m->device != h->xy->device) return fail(DM_EINVAL, "dm_xyload_classify: the model is on device %d, the table on device %d", m->device, h->xy->device);
+    if (h->n == 0) return DM_OK;
+    if (!prob1 || !cls) return fail(DM_EINVAL, "dm_xyload_classify: null output");
+    const int64_t n = h->n;
+    using B = dm_xyload;
+    int rc;
+    if ((rc = xlk::ensure(h, B::PROB, size_t(n) * 8)) != DM_OK) return rc;
+    if ((rc = xlk::ensure(h, B::PROB1, size_t(n) * 4)) != DM_OK) return rc;
+    if ((rc = xlk::ensure(h, B::CLS, size_t(n))) != DM_OK) return rc;
+    float* d_prob = xlk::ptr<float>(h, B::PROB);
+    if ((rc = dm_predict_read_at(m, xlk::ptr<const float>(h, B::FEATS), h->n_rows, xlk::ptr<const int32_t>(h, B::CENTRE), n, d_prob, xlk::ptr<uint8_t>(h, B::CLS))) != DM_OK)
+        return rc;
+    if ((rc = dm_model_sync(m)) != DM_OK) return rc;                 // a model in asynchronous mode has only queued the launch
+    hipStream_t s = h->xy->stream;
+    hipLaunchKernelGGL(xlk::xl_prob1_kernel, dim3(unsigned((n + xlk::THREADS - 1) / xlk::THREADS)), dim3(xlk::THREADS), 0, s, d_prob, (long long)n, xlk::ptr<float>(h, B::PROB1));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(prob1, h->buf[B::PROB1], size_t(n) * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(cls, h->buf[B::CLS], size_t(n), hipMemcpyDeviceToHost, s));
+    if (label) HIP_TRY(hipMemcpyAsync(label, h->buf[B::LABEL], size_t(n), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return DM_OK;
+}
+
+int dm_xyload_times(dm_xyload* h, double* parse_ms, double* select_ms) {
+    if (!h) return fail(DM_EINVAL, "null handle");
+    if (parse_ms) *parse_ms = 0.0;
+    if (select_ms) *select_ms = 0.0;
+    float a = 0.0f;
+    if (h->parse_timed && parse_ms) {
+        HIP_TRY(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
+        *parse_ms = double(a);
+    }
+    if (h->select_timed && select_ms) {
+        HIP_TRY(hipEventElapsedTime(&a, h->ev[2], h->ev[3]));
+        *select_ms = double(a);
+    }
+    return DM_OK;
+}
+
+}  // extern "C"

@@ -321,6 +321,17 @@ def getDataFromFile_new(fn, moptions, mfind0ld=None):
     rows with lo < position < hi, ['+', lo, hi] keeps only those.  A window that holds a NaN is dropped and the file is named once.  A
     labelled row without a whole window inside the file is an error that names file and row.  ([], [], None) when nothing is left."""
     table = np.loadtxt(fn, dtype=np.float32, ndmin=2)
+    rows = labelled_rows(table, moptions, fn)
+    if len(rows) == 0:
+        return ([], [], None)
+    half = int(moptions['windowsize'] / 2)
+    index = rows[:, None] + np.arange(-half, half + 1)[None, :]
+    return (np.ascontiguousarray(table[:, 3:][index]), table[rows, 1:3].astype(int), None)
+
+
+def labelled_rows(table, moptions, fn):
+    """The selection of getDataFromFile_new on a loaded table: the rows whose windows it returns, ascending (`predict` states its device
+    selection against this)."""
     position, labels, feats = table[:, 0], table[:, 1:3], table[:, 3:]
     half = int(moptions['windowsize'] / 2)
     wanted = ~((labels[:, 0] < 0.01) & (labels[:, 1] < 0.01))
@@ -335,16 +346,12 @@ def getDataFromFile_new(fn, moptions, mfind0ld=None):
         raise ValueError("%s: labelled row %d is closer than %d rows to the edge of the file (%d rows): no whole window" %
                          (fn, int(short[0]), half, len(feats)))
     if len(rows) == 0:
-        return ([], [], None)
+        return rows
     bad_before = np.concatenate(([0], np.cumsum(np.isnan(feats).any(axis=1))))
     clean = bad_before[rows + half + 1] == bad_before[rows - half]
     if not clean.all():
         print("Warning: NaN in a window of %s: such windows are dropped" % fn)
-    rows = rows[clean]
-    if len(rows) == 0:
-        return ([], [], None)
-    index = rows[:, None] + np.arange(-half, half + 1)[None, :]
-    return (np.ascontiguousarray(feats[index]), labels[rows].astype(int), None)
+    return rows[clean]
 
 
 # ---------------------------------------------------------------------------------------------

@@ -584,6 +584,55 @@ int dm_xy_rows_fetch(dm_xyrows* h, char* text, uint8_t* keep, int64_t* read_row_
 int dm_xy_times(dm_xyrows* h, double* keep_ms, double* text_ms);
 int dm_xy_scan(dm_xyrows* h, int64_t* values, int64_t n);
 
+/* -------------------------------------------------------------------------- predict -- */
+/*
+ * The inverse of the text stage above, for `DeepMod.py predict` (csrc/xyparse.hip.inc): the decompressed bytes of one .xy file -> its table on
+ * the device, bit-equal to np.loadtxt(dtype=float32, ndmin=2) of the same bytes (myMultiBiRNN.py:307), and the rows whose windows
+ * getDataFromFile_new (:306-343) would return.  The table is kept as head [R][3] (column 0 position, columns 1..2 the labels) and feats [R][7]
+ * (columns 3..9, contiguous: the `rows` of dm_predict_read_at).
+ * The device parses lines of ten fields -?[0-9]+(\.[0-9]+)? of at most 15 digit characters, separated by one space and ended by '\n' (a missing
+ * last '\n' is supplied).  A field is its digits as an integer divided once, in IEEE double, by the exact power of ten of its decimals, then the
+ * sign, then the cast to float: the correctly rounded double of strtod, cast as numpy casts it.  Any other line (nan, inf, exponents, '+', tabs,
+ * two spaces, '\r', empty lines, '#', nine or eleven fields, 16 digits, '.5', '5.') raises *flag; *first_bad_line is the 1-based number of the
+ * first such line (-1: none).  The table of a flagged text is not usable: the caller loads the file on the host and hands the result to
+ * dm_xyload_set_table (deepmod_amd/xyload.py does).  Plain launches on one stream, no atomics: two calls on the same bytes give the same bytes.
+ *   dm_xyload_parse          text: host bytes.  -> DM_OK, *n_rows = R.  Buffers grow and are kept between files; sizes are checked before a launch.
+ *   dm_xyload_parse_host     the same line routine compiled for the host (no GPU needed): table [cap_rows][10] receives the rows below cap_rows
+ *                            (a line outside the grammar as zeros).  -> R (< 0: error code).
+ *   dm_xyload_set_table      table [n_rows][10] host -> the handle's table, in place of a parse.
+ *   dm_xyload_select         kind 0: every labelled row; '-': not those with lo < int(position) < hi; '+': only those (the float32 position
+ *                            truncated, as the reference's astype(int)).  A row is labelled unless both labels are below 0.01f.  The selected rows
+ *                            in ascending order are centre int32 [n]; label u8 [n] is 1 where int(column 2) == 1 (:407).  -> n, or an error code;
+ *                            a selected row with fewer than 10 rows to an edge of the table is DM_EINVAL with *short_row = the first such row.
+ *   dm_xyload_set_selection  centre / label [n] host (checked: 10 <= centre < R - 10) in place of a selection: the host loader's rows of a file
+ *                            with NaN windows, which the device selection does not look for.
+ *   dm_xyload_device         the device addresses dm_predict_read_at takes (d_centre NULL while n <= 0), R and n (-1: no selection).
+ *   dm_xyload_fetch          feats [R][7], head [R][3], centre [n], label [n] to host arrays; any may be NULL.
+ *   dm_xyload_select_host    the same selection on a host table [n_rows][10], by the routines the kernels run (no GPU needed): centre / label receive
+ *                            the rows below cap.  -> n, or an error code with *short_row as above.
+ *   dm_xyload_classify       dm_predict_read_at of the model on the handle's table and selection; back come cls u8 [n], prob1 float [n] (the
+ *                            probability of class 1, gathered on the device into one contiguous block) and, unless NULL, label u8 [n]: 6 bytes per
+ *                            window, nothing of the table.  DM_ERANGE as dm_predict_read_at reports it.
+ *   dm_xyload_times          milliseconds between the HIP events around the kernels of the last parse / select (each interval holds one
+ *                            8-byte read-back the next launches are sized from); 0 for a call that launched nothing.
+ *   dm_xyload_tile_bytes     text bytes per block of the newline kernels; dm_xyload_scan_block: elements per block of the scan.  Tests build
+ *                            their boundary cases from them. */
+typedef struct dm_xyload dm_xyload;
+dm_xyload* dm_xyload_create(int device);
+void dm_xyload_destroy(dm_xyload* h);
+int dm_xyload_parse(dm_xyload* h, const char* text, int64_t n_bytes, int64_t* n_rows, int32_t* flag, int64_t* first_bad_line);
+int64_t dm_xyload_parse_host(const char* text, int64_t n_bytes, float* table, int64_t cap_rows, int32_t* flag, int64_t* first_bad_line);
+int dm_xyload_set_table(dm_xyload* h, const float* table, int64_t n_rows);
+int64_t dm_xyload_select(dm_xyload* h, int kind, int64_t lo, int64_t hi, int64_t* short_row);
+int64_t dm_xyload_select_host(const float* table, int64_t n_rows, int kind, int64_t lo, int64_t hi, int32_t* centre, uint8_t* label, int64_t cap, int64_t* short_row);
+int dm_xyload_set_selection(dm_xyload* h, const int32_t* centre, const uint8_t* label, int64_t n);
+int dm_xyload_device(dm_xyload* h, const float** d_feats, const int32_t** d_centre, int64_t* n_rows, int64_t* n);
+int dm_xyload_fetch(dm_xyload* h, float* feats, float* head, int32_t* centre, uint8_t* label);
+int dm_xyload_classify(dm_xyload* h, dm_model* m, float* prob1, uint8_t* cls, uint8_t* label);
+int dm_xyload_times(dm_xyload* h, double* parse_ms, double* select_ms);
+int dm_xyload_tile_bytes(void);
+int dm_xyload_scan_block(void);
+
 #ifdef __cplusplus
 }
 #endif
