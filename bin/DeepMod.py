@@ -8,7 +8,11 @@ deepmod_amd/predstore.py) because FAST5 reading and alignment are out of scope h
 
 `train` (flags of bin/DeepMod.py:341-350 plus --seed and --batchsize) trains the BiLSTM on the GPU from the
 reference's *.xy.gz feature files and writes TF-bundle checkpoints `detect --modfile` loads
-(deepmod_amd/train.py).
+(deepmod_amd/train.py).  Beside every checkpoint lies <prefix>.train.json, the schedule's position: --resume
+CKPT_PREFIX continues a stopped run from it, checkpoint for checkpoint the bytes of the uninterrupted run;
+--startFrom CKPT_PREFIX runs the whole schedule from an existing model's weights; --validate K (with --test)
+keeps K held-out windows on the GPU, scores them at every checkpoint (<prefix>.valid.json) and names the
+best one.
 
 `getfeatures` (flags and defaults of bin/DeepMod.py:354-375) writes those *.xy.gz / *.xy.ind files from raw
 containers (*.dmraw.npz, event tables or --move), a reference and known modified positions - a motif
@@ -89,6 +93,15 @@ def build_parser():
     trn.add_argument('--unbalanced', type=int, default=0, choices=[1, 0], help='1: class weights [0.1, 0.9] inside the loss')
     trn.add_argument('--seed', type=int, default=0, help='seed of the initial values (numpy generator)')
     trn.add_argument('--batchsize', type=int, default=2048, help='windows per training step (the reference fixes 2048): the leading group is cut into steps of batchsize .. 2 batchsize - 1 windows, a step of another group can be larger by a file; the device tape (158,400 B per window) is sized for 2 batchsize - 1 and grows to the largest step met')
+    trn.add_argument('--resume', default=None, metavar='CKPT_PREFIX',
+                     help='continue the run that wrote this checkpoint (its .train.json and bundle: weights, Adam slots, step count, reader positions) with the same '
+                          '--wrkBase, --test, --batchsize and --unbalanced: every later checkpoint is byte for byte the uninterrupted run\'s; --seed is not used')
+    trn.add_argument('--startFrom', default=None, metavar='CKPT_PREFIX',
+                     help='start the whole schedule from the 14 variables of this TF bundle (a published model, or a checkpoint of this command) instead of a fresh '
+                          'initialisation; Adam starts from zero; --seed is not used; excludes --resume')
+    trn.add_argument('--validate', type=int, default=0, metavar='K',
+                     help='with --test: keep at least K windows of the held-out data on the GPU (whole files, one per folder in turn) and score them at every checkpoint '
+                          'as predict would: <prefix>.valid.json, and <outFolder>/<FileID>_valid.json with the best checkpoint by AUC (default 0: off)')
     trn.set_defaults(func=mTrain)
     prd = sub.add_parser('predict', parents=[com], help='score a trained model on labelled *.xy.gz feature files',
                          description='Evaluate a checkpoint on labelled *.xy.gz files: per file the text is parsed, the labelled rows are selected and their '
@@ -203,6 +216,10 @@ def train_options(args, cmd='train', keys=('unbalanced', 'modfile', 'seed')):
             raise SystemExit("Error: --test takes 'E,<from Mb>,<to Mb>' or 'P,<percent>' (got %r)" % args.test)
     else:
         mo['test'] = ['N', '100']
+    if cmd == 'train':
+        mo.update(resume=getattr(args, 'resume', None), startFrom=getattr(args, 'startFrom', None), validate=getattr(args, 'validate', 0))
+        from deepmod_amd import train
+        train.check_run_options(mo)
     return mo
 
 

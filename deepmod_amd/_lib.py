@@ -160,6 +160,12 @@ SIGNATURES = [
     ("dm_xyload_times", _c.c_int, [_vp, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
     ("dm_xyload_tile_bytes", _c.c_int, []),
     ("dm_xyload_scan_block", _c.c_int, []),
+    ("dm_xyset_create", _vp, [_c.c_int, _i64]),
+    ("dm_xyset_destroy", None, [_vp]),
+    ("dm_xyset_append", _c.c_int, [_vp, _vp]),
+    ("dm_xyset_segments", _i64, [_vp, _vp, _vp, _i64]),
+    ("dm_xyset_classify", _c.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    ("dm_xyset_bytes", _i64, [_vp]),
 ]
 
 

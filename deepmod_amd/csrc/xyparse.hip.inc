@@ -529,3 +529,164 @@ int dm_xyload_times(dm_xyload* h, double* parse_ms, double* select_ms) {
 }
 
 }  // extern "C"
+
+// ---- the resident set: what dm_xyload holds after a file's load, for many files at once -------------------------------------------
+// `train --validate` scores the same held-out files at every checkpoint.  A loaded file that has windows becomes a SEGMENT: its feature rows
+// [R][7], its centres int32 [n] (relative to the segment's first row) and its labels u8 [n], appended to three growing device blocks by
+// device-to-device copies on the set's stream - 28 bytes per row + 5 per window, no text, no head columns, no scan scratch.  A segment is
+// classified exactly as dm_xyload_classify classifies its file (dm_predict_read_at on the segment's rows and centres, then xl_prob1_kernel),
+// so the results are the loader's byte for byte, and DM_ERANGE is a segment's own.
+struct dm_xyset {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    float* feats = nullptr;                             // [cap_rows][7]
+    int32_t* centre = nullptr;                          // [cap_centre], relative to the segment's first row
+    uint8_t* label = nullptr;                           // [cap_label]
+    int64_t cap_rows = 0, cap_centre = 0, cap_label = 0;
+    std::vector<int64_t> row_off{0}, win_off{0};        // segment s = rows [row_off[s], row_off[s+1]), windows [win_off[s], win_off[s+1])
+    float *prob = nullptr, *prob1 = nullptr;            // scratch of the largest segment classified so far
+    uint8_t* cls = nullptr;
+    int64_t cap_out = 0;
+};
+
+namespace xlk {
+
+// a block of `have` used and `cap` allocated elements of `elem` bytes is to hold `need`: at least doubled, the used part copied on the stream
+template <class T>
+int set_grow(dm_xyset* s, T*& block, int64_t& cap, int64_t have, int64_t need, size_t elem) {
+    if (need <= cap && block) return DM_OK;
+    const int64_t want = std::max<int64_t>(need, 2 * cap);
+    T* fresh = nullptr;
+    if (hipMalloc(&fresh, size_t(want) * elem + 256) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(DM_ENOMEM, "dm_xyset: hipMalloc(%zu) failed", size_t(want) * elem + 256);
+    }
+    if (block && have > 0 &&
+        (hipMemcpyAsync(fresh, block, size_t(have) * elem, hipMemcpyDeviceToDevice, s->stream) != hipSuccess || hipStreamSynchronize(s->stream) != hipSuccess)) {
+        (void)hipGetLastError();
+        (void)hipFree(fresh);
+        return fail(DM_EDEVICE, "dm_xyset: moving %lld elements to a larger block failed", (long long)have);
+    }
+    if (block) (void)hipFree(block);
+    block = fresh;
+    cap = want;
+    return DM_OK;
+}
+
+}  // namespace xlk
+
+extern "C" {
+
+void dm_xyset_destroy(dm_xyset* s) {
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    if (s->stream) (void)hipStreamSynchronize(s->stream);
+    for (void* b : {(void*)s->feats, (void*)s->centre, (void*)s->label, (void*)s->prob, (void*)s->prob1, (void*)s->cls})
+        if (b) (void)hipFree(b);
+    if (s->stream) (void)hipStreamDestroy(s->stream);
+    delete s;
+}
+
+dm_xyset* dm_xyset_create(int device, int64_t initial_rows) {
+    if (initial_rows < 0 || initial_rows > xlk::MAX_ROWS) {
+        fail(DM_EINVAL, "dm_xyset_create: %lld initial rows", (long long)initial_rows);
+        return nullptr;
+    }
+    if (hipSetDevice(device) != hipSuccess) {
+        (void)hipGetLastError();
+        fail(DM_EDEVICE, "dm_xyset_create: device %d", device);
+        return nullptr;
+    }
+    dm_xyset* s = new dm_xyset;
+    s->device = device;
+    const int64_t rows = std::max<int64_t>(initial_rows, 1);
+    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) {
+        (void)hipGetLastError();
+        fail(DM_EDEVICE, "dm_xyset_create: stream on device %d", device);
+        s->stream = nullptr;
+        dm_xyset_destroy(s);
+        return nullptr;
+    }
+    // one window in eight rows is the expectation the first blocks are sized by; every block grows on its own
+    if (xlk::set_grow(s, s->feats, s->cap_rows, 0, rows, sizeof(float) * DM_NFEAT) != DM_OK ||
+        xlk::set_grow(s, s->centre, s->cap_centre, 0, rows / 8 + 1, sizeof(int32_t)) != DM_OK ||
+        xlk::set_grow(s, s->label, s->cap_label, 0, rows / 8 + 1, 1) != DM_OK) {
+        std::string keep = g_err;
+        dm_xyset_destroy(s);
+        g_err = keep;
+        return nullptr;
+    }
+    return s;
+}
+
+int dm_xyset_append(dm_xyset* s, dm_xyload* h) {
+    if (!s || !h) return fail(DM_EINVAL, "null handle");
+    if (h->n_rows < 0 || h->n < 0) return fail(DM_ESTATE, "dm_xyset_append: the loader holds no selection");
+    if (h->xy->device != s->device) return fail(DM_EINVAL, "dm_xyset_append: the loader is on device %d, the set on device %d", h->xy->device, s->device);
+    if (h->n == 0) return DM_OK;                                     // a file without a window: no segment
+    if (h->n > h->n_rows) return fail(DM_ESTATE, "dm_xyset_append: %lld windows of %lld rows", (long long)h->n, (long long)h->n_rows);
+    HIP_TRY(hipSetDevice(s->device));
+    const int64_t rows = s->row_off.back(), wins = s->win_off.back(), R = h->n_rows, n = h->n;
+    int rc;
+    if ((rc = xlk::set_grow(s, s->feats, s->cap_rows, rows, rows + R, sizeof(float) * DM_NFEAT)) != DM_OK) return rc;
+    if ((rc = xlk::set_grow(s, s->centre, s->cap_centre, wins, wins + n, sizeof(int32_t))) != DM_OK) return rc;
+    if ((rc = xlk::set_grow(s, s->label, s->cap_label, wins, wins + n, 1)) != DM_OK) return rc;
+    using B = dm_xyload;
+    HIP_TRY(hipMemcpyAsync(s->feats + rows * DM_NFEAT, h->buf[B::FEATS], size_t(R) * 4 * DM_NFEAT, hipMemcpyDeviceToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->centre + wins, h->buf[B::CENTRE], size_t(n) * 4, hipMemcpyDeviceToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->label + wins, h->buf[B::LABEL], size_t(n), hipMemcpyDeviceToDevice, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));                        // the loader may take its next file, or be destroyed
+    s->row_off.push_back(rows + R);
+    s->win_off.push_back(wins + n);
+    return DM_OK;
+}
+
+int64_t dm_xyset_segments(dm_xyset* s, int64_t* rows, int64_t* windows, int64_t cap) {
+    if (!s) return fail(DM_EINVAL, "null handle");
+    const int64_t k = int64_t(s->row_off.size()) - 1;
+    if (cap < 0 || (cap > 0 && rows == nullptr && windows == nullptr)) return fail(DM_EINVAL, "dm_xyset_segments: null output");
+    for (int64_t i = 0; i < k && i < cap; ++i) {
+        if (rows) rows[i] = s->row_off[i + 1] - s->row_off[i];
+        if (windows) windows[i] = s->win_off[i + 1] - s->win_off[i];
+    }
+    return k;
+}
+
+int64_t dm_xyset_bytes(dm_xyset* s) {
+    if (!s) return fail(DM_EINVAL, "null handle");
+    return s->row_off.back() * 4 * DM_NFEAT + s->win_off.back() * 5;
+}
+
+int dm_xyset_classify(dm_xyset* s, dm_model* m, int64_t segment, float* prob1, uint8_t* cls, uint8_t* label) {
+    if (!s || !m) return fail(DM_EINVAL, "null handle");
+    if (segment < 0 || segment + 1 >= int64_t(s->row_off.size())) return fail(DM_EINVAL, "dm_xyset_classify: segment %lld of %lld", (long long)segment, (long long)s->row_off.size() - 1);
+    if (m->device != s->device) return fail(DM_EINVAL, "dm_xyset_classify: the model is on device %d, the set on device %d", m->device, s->device);
+    if (!prob1 || !cls) return fail(DM_EINVAL, "dm_xyset_classify: null output");
+    const int64_t row0 = s->row_off[segment], R = s->row_off[segment + 1] - row0, win0 = s->win_off[segment], n = s->win_off[segment + 1] - win0;
+    HIP_TRY(hipSetDevice(s->device));
+    if (n > s->cap_out) {
+        for (void* b : {(void*)s->prob, (void*)s->prob1, (void*)s->cls})
+            if (b) (void)hipFree(b);
+        s->prob = s->prob1 = nullptr;
+        s->cls = nullptr;
+        s->cap_out = 0;
+        const int64_t want = n + (n >> 2) + 64;
+        if (hipMalloc(&s->prob, size_t(want) * 8) != hipSuccess || hipMalloc(&s->prob1, size_t(want) * 4) != hipSuccess || hipMalloc(&s->cls, size_t(want)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(DM_ENOMEM, "dm_xyset_classify: hipMalloc for %lld windows failed", (long long)want);
+        }
+        s->cap_out = want;
+    }
+    int rc;
+    if ((rc = dm_predict_read_at(m, s->feats + row0 * DM_NFEAT, R, s->centre + win0, n, s->prob, s->cls)) != DM_OK) return rc;
+    if ((rc = dm_model_sync(m)) != DM_OK) return rc;                 // a model in asynchronous mode has only queued the launch
+    hipLaunchKernelGGL(xlk::xl_prob1_kernel, dim3(unsigned((n + xlk::THREADS - 1) / xlk::THREADS)), dim3(xlk::THREADS), 0, s->stream, s->prob, (long long)n, s->prob1);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(prob1, s->prob1, size_t(n) * 4, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(cls, s->cls, size_t(n), hipMemcpyDeviceToHost, s->stream));
+    if (label) HIP_TRY(hipMemcpyAsync(label, s->label + win0, size_t(n), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return DM_OK;
+}
+
+}  // extern "C"

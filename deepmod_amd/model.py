@@ -387,7 +387,20 @@ class Saver:
         if sess._train is None:
             raise _lib.DeepModHipError("Saver.save: this session has not trained")
         from . import train as _train
-        return _train.TrainSaver().save(sess._train, save_path)
+        saver = _train.TrainSaver()
+        out = saver.save(sess._train, save_path)
+        self.last_saved = saver.last_saved               # (weights blob, t): what `train --validate` scores
+        return out
+
+    def restore_training(self, sess: Session, save_path: str, t: int, slots: bool):
+        """`train --resume` (slots: variables, Adam slots and step count t) / `--startFrom` (the variables only) into the session's trainer,
+        which is created first if no training token has been fetched yet."""
+        from . import train as _train
+        tg = sess.graph.train
+        if sess._train is None:
+            sess._train = _train.TrainSession(tg, sess.device)
+            sess._train.run(tg.init)
+        _train.TrainSaver().restore_training(sess._train, save_path, t, slots)
 
 
 _last_graph: Optional[Graph] = None

@@ -60,6 +60,20 @@ def piece_lines(cls, label, name):
     return lines, total
 
 
+def finish_stats(stats, total, probs, labels, model):
+    """mPred's summary from the counts [tp, fp, fn, tn] and the per-file probabilities and labels, in file order (`train --validate` writes the
+    same figures): accuracy, precision, recall, the exact ROC AUC (None unless both labels occur) and the precision the model ran."""
+    from . import model as _model
+    tp, fp, fn_, tn = (int(v) for v in total)
+    stats.update(tp=tp, fp=fp, fn=fn_, tn=tn, accuracy=(tp + tn) / max(stats['windows'], 1), precision=tp / max(tp + fp, 1), recall=tp / max(tp + fn_, 1))
+    lab = np.concatenate(labels) if labels else np.zeros(0, np.uint8)
+    both = 0 < int(lab.sum()) < len(lab)
+    stats['auc'] = float(roc_auc(lab, np.concatenate(probs))) if both else None
+    names = {v: k for k, v in _model.BiLSTMModel.PRECISIONS.items()}
+    stats['precision_mode'] = names.get(model.get_info(_lib.DM_INFO_PRECISION), 'unknown')
+    return stats
+
+
 def read_text(fn):
     with open(fn, 'rb') as fh:
         return gzip.decompress(fh.read())               # zlib releases the GIL
@@ -99,14 +113,7 @@ def mPred(mfbase, mffolder, accuracy, X, Y, test_gzfile2, pf, num_input, auc_op,
                 stats['windows'] += n
                 probs.append(prob1)
                 labels.append(label)
-        tp, fp, fn_, tn = (int(v) for v in total)
-        stats.update(tp=tp, fp=fp, fn=fn_, tn=tn, accuracy=(tp + tn) / max(stats['windows'], 1), precision=tp / max(tp + fp, 1), recall=tp / max(tp + fn_, 1))
-        lab = np.concatenate(labels) if labels else np.zeros(0, np.uint8)
-        both = 0 < int(lab.sum()) < len(lab)
-        stats['auc'] = float(roc_auc(lab, np.concatenate(probs))) if both else None
-        names = {v: k for k, v in _model.BiLSTMModel.PRECISIONS.items()}
-        stats['precision_mode'] = names.get(sess.model.get_info(_lib.DM_INFO_PRECISION), 'unknown')
-        return stats
+        return finish_stats(stats, total, probs, labels, sess.model)
     finally:
         if loader is not None:
             loader.close()

@@ -13,11 +13,18 @@ Initialisation is TF1's (glorot-uniform kernels, zero biases, truncated-normal h
 TensorFlow's own random stream cannot be reproduced, so a run here and a run of the reference start from different draws of the same
 distributions.  Checkpoints are TF bundles with the variables, the Adam slots and beta1_power / beta2_power under the names and shapes of
 the reference's .index files, plus the `checkpoint` state file; no .meta is written (a serialized graph this build's detect does not need).
+
+Beside every checkpoint the schedule writes <prefix>.train.json: its own position (epoch, reader positions, step count t) and what it depends on
+(batchsize, unbalanced, test, a digest of the file lists).  --resume reads it and the bundle back and continues: every later checkpoint is byte
+for byte the uninterrupted run's.  --startFrom takes only the 14 variables of a bundle and runs the whole schedule.  --validate K keeps at least
+K windows of the files --test held out on the device (xyload.XYSet) and scores them at every checkpoint as `predict` would (<prefix>.valid.json).
 """
 from __future__ import annotations
 
 import ctypes
 import glob
+import hashlib
+import json
 import os
 import sys
 import time
@@ -172,10 +179,51 @@ def checkpoint_tensors(w: np.ndarray, m: np.ndarray, v: np.ndarray, t: int) -> D
 class TrainSaver:
     """saver.save(sess, prefix): a TF bundle (tfbundle.write_bundle) + the `checkpoint` state file; no .meta."""
 
+    last_saved = None                                   # (weights blob, t) of the last save: --validate scores what was written
+
     def save(self, sess: "TrainSession", prefix: str):
         w, m, v, t = sess.trainer.get_state()
         tfbundle.write_bundle(prefix, checkpoint_tensors(w, m, v, t))
+        self.last_saved = (w, t)
         return prefix
+
+    def restore_training(self, sess: "TrainSession", prefix: str, t: int, slots: bool):
+        """The trainer's state from the bundle at prefix: the 14 variables, and with slots (--resume) the Adam slots and step count t;
+        without (--startFrom) m = v = 0 and t = 0."""
+        w, m, v = load_training_state(prefix, t, slots)
+        if sess.trainer is None:
+            sess.run(sess.graph.init)
+        sess.trainer.set_state(w, m, v, t if slots else 0)
+
+
+def load_training_state(prefix: str, t: int, slots: bool):
+    """-> (w, m, v) blobs of the bundle at prefix.  Refused in one line: a bundle that is not there, a tensor that is missing or has another
+    shape, and with slots beta1_power / beta2_power that are not those of step count t."""
+    what = "--resume" if slots else "--startFrom"
+    if not os.path.isfile(prefix + ".index"):
+        raise SystemExit("Error: %s: no TF checkpoint at %r" % (what, prefix))
+    entries = tfbundle.read_index(prefix + ".index")
+    suffixes = ("", "/Adam", "/Adam_1") if slots else ("",)
+    for suffix in suffixes:
+        for name, shape in blob_names():
+            if name + suffix not in entries:
+                raise SystemExit("Error: %s: %s holds no tensor %r" % (what, prefix, name + suffix))
+            if tuple(entries[name + suffix].shape) != tuple(shape):
+                raise SystemExit("Error: %s: tensor %r of %s has shape %s, this model needs %s" %
+                                 (what, name + suffix, prefix, tuple(entries[name + suffix].shape), tuple(shape)))
+    powers = ("beta1_power", "beta2_power") if slots else ()
+    for name in powers:
+        if name not in entries:
+            raise SystemExit("Error: %s: %s holds no tensor %r" % (what, prefix, name))
+    tensors = tfbundle.load_bundle(prefix, [name + suffix for suffix in suffixes for name, _ in blob_names()] + list(powers))
+    for name, beta in zip(powers, (BETA1, BETA2)):
+        want = np.float32(beta ** (t + 1))
+        if np.float32(tensors[name]) != want:
+            raise SystemExit("Error: %s: %s of %s is %r, step count t = %d of its .train.json gives %r" %
+                             (what, name, prefix, float(tensors[name]), t, float(want)))
+    blobs = [flatten_weights({name: tensors[name + suffix] for name, _ in blob_names()}) for suffix in suffixes]
+    zero = np.zeros(_lib.DM_WEIGHT_FLOATS, np.float32)
+    return (blobs[0], blobs[1], blobs[2]) if slots else (blobs[0], zero, zero.copy())
 
 
 # ---------------------------------------------------------------------------------------------
@@ -411,7 +459,152 @@ def _mid_epoch_folder(percent, single_group):
     return None
 
 
-def train_save_model(filelists, num_input, mhidden, timesteps, moptions, batchsize: int = batchsize, session_factory=None):
+STATE_VERSION = 1
+
+
+def wrkbase_folders(moptions) -> List[str]:
+    """Every folder --wrkBase names, groups and their folders in the order given."""
+    return [folder for folder in moptions['wrkBase'].replace(';', ',').split(',') if folder]
+
+
+def _relative(fn, folders):
+    """'<index of the --wrkBase folder>:<path below it>' of a file (the longest folder that holds it), so that a data set that moved is the same."""
+    best = None
+    for i, folder in enumerate(folders):
+        base = os.path.join(os.path.abspath(folder), "")
+        if os.path.abspath(fn).startswith(base) and (best is None or len(base) > len(best[1])):
+            best = (i, base)
+    if best is None:
+        return os.path.abspath(fn)
+    return "%d:%s" % (best[0], os.path.abspath(fn)[len(best[1]):].replace(os.sep, "/"))
+
+
+def filelists_digest(filelists, moptions) -> str:
+    """SHA-256 of the ordered file lists (after file_groups: --test P slicing, shuffle, the largest group first), paths relative to their
+    --wrkBase folder."""
+    folders = wrkbase_folders(moptions) if moptions.get('wrkBase') else []
+    text = json.dumps([[_relative(fn, folders) for fn in files] for files in filelists])
+    return hashlib.sha256(text.encode("utf-8")).hexdigest()
+
+
+def _json_form(value):
+    return json.loads(json.dumps(value))
+
+
+def schedule_state(epoch, closed, readers, t, batchsize, moptions, digest):
+    """What <prefix>.train.json holds: the schedule's position at a save and what the schedule depends on."""
+    return {"version": STATE_VERSION, "epoch": int(epoch), "epoch_closed": bool(closed), "next": [int(r.next) for r in readers], "t": int(t),
+            "batchsize": int(batchsize), "unbalanced": int(moptions.get('unbalanced') or 0), "test": _json_form(list(moptions['test'])),
+            "files_digest": digest}
+
+
+def write_json(path, obj):
+    with open(path, 'w') as fh:
+        json.dump(obj, fh, indent=1, sort_keys=True)
+        fh.write('\n')
+
+
+def read_schedule_state(prefix, n_readers, batchsize, moptions, digest):
+    """<prefix>.train.json for --resume; refused in one line that names the difference when the file is missing or was written by another
+    command line (batchsize, unbalanced, test, the file lists)."""
+    path = prefix + ".train.json"
+    if not os.path.isfile(path):
+        raise SystemExit("Error: --resume: no state file %s (checkpoints written before the schedule kept its state cannot be resumed; "
+                         "--startFrom takes their weights)" % path)
+    with open(path) as fh:
+        state = json.load(fh)
+    if state.get("version") != STATE_VERSION:
+        raise SystemExit("Error: --resume: %s has format version %r, this build reads version %d" % (path, state.get("version"), STATE_VERSION))
+    now = schedule_state(0, False, [], 0, batchsize, moptions, digest)
+    for key, flag in (("batchsize", "--batchsize"), ("unbalanced", "--unbalanced"), ("test", "--test")):
+        if state.get(key) != now[key]:
+            raise SystemExit("Error: --resume: %s differs: the checkpoint was written with %r, this command line gives %r" % (flag, state.get(key), now[key]))
+    if state.get("files_digest") != digest:
+        raise SystemExit("Error: --resume: the feature files under --wrkBase differ from those the checkpoint was trained on "
+                         "(digest of the ordered file lists %s..., now %s...)" % (str(state.get("files_digest"))[:12], digest[:12]))
+    if len(state.get("next", [])) != n_readers:
+        raise SystemExit("Error: --resume: %s holds %d reader positions, --wrkBase gives %d groups" % (path, len(state.get("next", [])), n_readers))
+    return state
+
+
+def check_run_options(moptions):
+    """The combinations of --resume / --startFrom / --validate that are refused, each in one line."""
+    if moptions.get('resume') and moptions.get('startFrom'):
+        raise SystemExit("Error: --resume and --startFrom exclude each other: one continues a run, the other starts a new one from a model's weights")
+    if int(moptions.get('validate') or 0) < 0:
+        raise SystemExit("Error: --validate must be non-negative (got %d)" % moptions['validate'])
+    if int(moptions.get('validate') or 0) > 0 and moptions['test'][0] not in ('-', '0'):
+        raise SystemExit("Error: --validate needs --test: without it no data is held out")
+
+
+class HeldOut:
+    """--validate K: at least K windows of the data --test holds out, on the device.  The files are predict.predict_files of every --wrkBase
+    folder, taken one per folder in turn - whole files, until K windows are held - each through XYLoader.load under predict.loader_options and
+    then appended to an xyload.XYSet.  score() is what `predict` computes for the same files: same kernels, same inputs per file."""
+
+    def __init__(self, moptions, k, device: int = 0, initial_rows: int = 1 << 16):
+        from . import predict, xyload
+        self.device = device
+        folders = wrkbase_folders(moptions)
+        per_folder = [predict.predict_files(folder, moptions) for folder in folders]
+        order = [files[i] for i in range(max([len(f) for f in per_folder] + [0])) for files in per_folder if i < len(files)]
+        lopt = predict.loader_options(moptions)
+        self.files, self.names, self.seg_names = [], [], []
+        self.base = dict(files=0, fallback_files=0, rows=0, windows=0)
+        self.set = xyload.XYSet(device, initial_rows)
+        loader = xyload.XYLoader(device)
+        try:
+            for fn in order:
+                if self.base['windows'] >= k:
+                    break
+                rows, n, fallback = loader.load(predict.read_text(fn), lopt, fn)
+                self.files.append(fn)
+                self.names.append(_relative(fn, folders))
+                self.base['files'] += 1
+                self.base['rows'] += rows
+                self.base['fallback_files'] += int(fallback)
+                if n < 1:
+                    continue
+                self.set.append(loader)
+                self.seg_names.append(fn)
+                self.base['windows'] += n
+        finally:
+            loader.close()
+        self.seg_windows = [int(n) for n in self.set.segments()[1]]
+        print("validate: %d windows of %d held-out files (%d rows) stay on the device: %d bytes" %
+              (self.base['windows'], self.base['files'], self.base['rows'], self.set.nbytes()))
+        sys.stdout.flush()
+
+    def close(self):
+        self.set.close()
+
+    def score(self, w):
+        """The held-out windows through a model of the weight blob w -> predict's stats."""
+        from . import model as _model, predict
+        model = _model.BiLSTMModel(unflatten_weights(w), self.device, precision=os.environ.get("DEEPMOD_PRECISION", "f16x3"))
+        try:
+            total, probs, labels = np.zeros(4, np.int64), [], []
+            for seg, (fn, n) in enumerate(zip(self.seg_names, self.seg_windows)):
+                prob1, cls, label = self.set.classify(model, seg, n)
+                total += predict.piece_lines(cls, label, fn)[1]
+                probs.append(prob1)
+                labels.append(label)
+            return predict.finish_stats(dict(self.base), total, probs, labels, model)
+        finally:
+            model.close()
+
+
+def best_checkpoint(table):
+    """The entry with the largest AUC; ties go to the earliest, an AUC of None ranks last."""
+    best = None
+    for entry in table:
+        if best is None or (entry['auc'] is not None and (best['auc'] is None or entry['auc'] > best['auc'])):
+            best = entry
+    return best
+
+
+def train_save_model(filelists, num_input, mhidden, timesteps, moptions, batchsize: int = batchsize, session_factory=None, resume=None,
+                     start_from=None, validate: int = 0):
     """Four epochs over the file groups; filelists[0] leads.  One round of an epoch:
       * the leading group reads files until it has 25 * batchsize windows (or runs out) and cuts them into int(windows / batchsize) equal
         steps (np.array_split: batchsize .. 2 batchsize - 1 windows each); a round that cannot fill one step is skipped with a note;
@@ -422,29 +615,75 @@ def train_save_model(filelists, num_input, mhidden, timesteps, moptions, batchsi
         <outFolder><epoch - 1>0.1 ... 0.9, and <outFolder><epoch>/<FileID> after every epoch.
     A step larger than the trainer's tape makes the session grow it (TrainSession).  The progress line shows loss, accuracy, precision, recall
     and the exact ROC AUC (siteperf.roc_auc) of the round's first step of the last group, not tf.metrics.auc's 200-threshold figure.
-    session_factory(init) -> a session-like object (tests record with it); it may bring its own `saver`."""
+    session_factory(init) -> a session-like object (tests record with it); it may bring its own `saver`.
+    Every save also writes <prefix>.train.json (schedule_state; t counts the steps fed so far).  resume: a checkpoint prefix of an earlier run
+    of the same command line - the schedule takes its position from the .train.json, the saver (restore_training, if it has one) the trainer's
+    state from the bundle, and the run goes on: inside the epoch of a mid-epoch checkpoint, with the next epoch after an epoch's last, not at
+    all after the run's last.  start_from: a bundle whose 14 variables replace the initial values; the schedule is the whole one.
+    validate: HeldOut of that many windows, scored at every save of a GPU session (<prefix>.valid.json, <outFolder><FileID>_valid.json)."""
     from . import model as _model
+    check_run_options(dict(moptions, resume=resume, startFrom=start_from, validate=validate))
     graph_options = dict(moptions, max_batch=2 * batchsize - 1)
     init, init_l, loss_op, accuracy, train_op, X, Y, saver, auc_op, mpre, mspf, mfpred = \
         _model.mCreateSession(num_input, mhidden, timesteps, graph_options)
-    sess = session_factory(init) if session_factory else _model.new_session(int(moptions.get("device", 0)))
-    saver = getattr(sess, "saver", saver)
+    tokens = (accuracy, X, Y, auc_op, mpre, mspf, init_l, mfpred)
     readers = [_GroupReader(files, moptions) for files in filelists]
     lead, others = readers[0], readers[1:]
     every = _progress_interval(len(lead.files))
     full_round = SUMPSIZE
+    digest = filelists_digest(filelists, moptions)
+    t, first_epoch, inside = 0, 1, False
+    if resume is not None:
+        state = read_schedule_state(resume, len(readers), batchsize, moptions, digest)
+        for reader, position in zip(readers, state["next"]):
+            if not 0 <= position <= len(reader.files):
+                raise SystemExit("Error: --resume: reader position %d outside the %d files of its group" % (position, len(reader.files)))
+            reader.next = position
+        t, inside = state["t"], not state["epoch_closed"]
+        first_epoch = state["epoch"] if inside else state["epoch"] + 1
+        if first_epoch > TRAINING_STEPS:
+            print("--resume %s: this is the last checkpoint of its run (epoch %d of %d closed): the run is complete, nothing is written" %
+                  (resume, state["epoch"], TRAINING_STEPS))
+            return tokens
+        print("--resume %s: step count %d, going on %s epoch %d" % (resume, t, "inside" if inside else "with", first_epoch))
+    if (resume is not None or start_from is not None) and 'seed' in moptions:
+        print("Note: --seed %s is not used: the weights come from %s" % (moptions['seed'], resume or start_from))
+    sess = session_factory(init) if session_factory else _model.new_session(int(moptions.get("device", 0)))
+    saver = getattr(sess, "saver", saver)
+    held, table = None, []
 
-    def save(folder):
+    def save(folder, epoch, closed):
         os.makedirs(folder, exist_ok=True)
-        saver.save(sess, folder + '/' + moptions['FileID'])
+        prefix = folder + '/' + moptions['FileID']
+        saver.save(sess, prefix)
+        write_json(prefix + ".train.json", schedule_state(epoch, closed, readers, t, batchsize, moptions, digest))
+        if held is not None:
+            if saver.last_saved[1] != t:
+                raise _lib.DeepModHipError("the trainer has made %d steps, the schedule has fed %d" % (saver.last_saved[1], t))
+            stats = held.score(saver.last_saved[0])
+            stats.update(checkpoint=os.path.relpath(prefix, moptions['outFolder']).replace(os.sep, "/"), t=t)
+            write_json(prefix + ".valid.json", stats)
+            table.append(stats)
+            print("validate %s: t=%d windows=%d acc=%.4f p=%.4f r=%.4f AUC=%s" % (stats['checkpoint'], t, stats['windows'], stats['accuracy'],
+                  stats['precision'], stats['recall'], "none" if stats['auc'] is None else "%.4f" % stats['auc']))
+            sys.stdout.flush()
 
     started = time.time()
     try:
         sess.run(init)
-        for epoch in range(1, TRAINING_STEPS + 1):
+        restore = getattr(saver, "restore_training", None)
+        if restore is not None and resume is not None:
+            restore(sess, resume, t, True)
+        elif restore is not None and start_from is not None:
+            restore(sess, start_from, 0, False)
+        if validate > 0 and session_factory is None:
+            held = HeldOut(moptions, validate, int(moptions.get("device", 0)))
+        for epoch in range(first_epoch, TRAINING_STEPS + 1):
             print("epoch %d of %d" % (epoch, TRAINING_STEPS))
             sys.stdout.flush()
-            lead.next = 0
+            if not inside:
+                lead.next = 0
+            inside = False
             shown_at = -1
             while not lead.exhausted():
                 x0, y0 = lead.pool(batchsize * full_round, wrap=False)
@@ -471,15 +710,28 @@ def train_save_model(filelists, num_input, mhidden, timesteps, moptions, batchsi
                 for i in range(steps):
                     for px, py in pieces:
                         sess.run([train_op, loss_op], feed_dict={X: px[i], Y: py[i]})
+                        t += 1
                 suffix = _mid_epoch_folder(int(lead.next * 100 / float(len(lead.files))), not others)
                 if suffix is not None:
-                    save(moptions['outFolder'] + str(epoch - 1) + suffix)
-            save(moptions['outFolder'] + str(epoch))
+                    save(moptions['outFolder'] + str(epoch - 1) + suffix, epoch, False)
+            save(moptions['outFolder'] + str(epoch), epoch, True)
         print("Training Finished!")
+        if held is not None:
+            best = best_checkpoint(table)
+            for entry in table:
+                print("%s %-24s t=%-8d acc=%.4f AUC=%s" % ("*" if entry is best else " ", entry['checkpoint'], entry['t'], entry['accuracy'],
+                      "none" if entry['auc'] is None else "%.4f" % entry['auc']))
+            if best is not None:
+                print("best checkpoint by AUC on the held-out windows: %s" % best['checkpoint'])
+            write_json(moptions['outFolder'] + moptions['FileID'] + '_valid.json',
+                       dict(checkpoints=table, best=None if best is None else best['checkpoint'], held_out_files=held.names,
+                            resident_bytes=held.set.nbytes()))
     finally:
+        if held is not None:
+            held.close()
         if hasattr(sess, "close"):
             sess.close()
-    return (accuracy, X, Y, auc_op, mpre, mspf, init_l, mfpred)
+    return tokens
 
 
 def file_groups(moptions) -> List[List[str]]:
@@ -501,10 +753,12 @@ def file_groups(moptions) -> List[List[str]]:
 
 
 def mMult_RNN_LSTM_train(moptions, batchsize: int = batchsize, session_factory=None):
+    check_run_options(moptions)
     filelists = file_groups(moptions)
     if moptions.get('modfile') is not None:
         print("Note: --modfile %s is accepted and ignored: training always starts from a fresh initialisation" % (moptions['modfile'],))
     if len(filelists[0]) == 0:
         raise SystemExit("Error: no *.xy.gz feature file under --wrkBase %r" % (moptions['wrkBase'],))
     return train_save_model(filelists, moptions['fnum'], moptions['hidden'], moptions['windowsize'], moptions, batchsize=batchsize,
-                            session_factory=session_factory)
+                            session_factory=session_factory, resume=moptions.get('resume'), start_from=moptions.get('startFrom'),
+                            validate=int(moptions.get('validate') or 0))

@@ -189,3 +189,64 @@ class XYLoader:
         self.set_table(table)
         self.set_selection(sel, table[sel, 2].astype(int) == 1)
         return len(table), len(sel), True
+
+
+class XYSet:
+    """One dm_xyset on one GPU: loaded files kept on the device as segments (feature rows [R][7], centres int32 [n], labels u8 [n] - 28 bytes per
+    row + 5 per window), classified again and again without their text being read a second time (`train --validate`)."""
+
+    def __init__(self, device: int = 0, initial_rows: int = 1 << 16):
+        self._lib = _lib.load()
+        self.device = device
+        self._h = self._lib.dm_xyset_create(device, int(initial_rows))
+        if not self._h:
+            raise _lib.DeepModHipError("dm_xyset_create: " + _lib.last_error())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.dm_xyset_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def append(self, loader: XYLoader) -> bool:
+        """The loader's table and selection become the next segment -> whether one was added (a file without a window adds none)."""
+        _lib.check(self._lib.dm_xyset_append(self._h, loader._h))
+        return loader.n > 0
+
+    def segments(self) -> Tuple[np.ndarray, np.ndarray]:
+        """-> (rows int64 [k], windows int64 [k]) of the k segments"""
+        k = int(self._lib.dm_xyset_segments(self._h, None, None, 0))
+        if k < 0:
+            _lib.check(k)
+        rows, windows = np.zeros(k, np.int64), np.zeros(k, np.int64)
+        if k:
+            self._lib.dm_xyset_segments(self._h, rows.ctypes.data, windows.ctypes.data, k)
+        return rows, windows
+
+    def nbytes(self) -> int:
+        return int(self._lib.dm_xyset_bytes(self._h))
+
+    def classify(self, model, segment: int, n: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Segment `segment` through model -> (probability of class 1 float32 [n], class u8 [n], label u8 [n]), as XYLoader.classify gives them
+        for the segment's file: a segment the split-f16 kernel cannot represent is computed by the fp32 kernel, that segment alone."""
+        if n is None:
+            n = int(self.segments()[1][segment])
+        prob1, cls, label = np.empty(n, np.float32), np.empty(n, np.uint8), np.empty(n, np.uint8)
+
+        def run():
+            _lib.check(self._lib.dm_xyset_classify(self._h, model._h, int(segment), prob1.ctypes.data, cls.ctypes.data, label.ctypes.data))
+        try:
+            run()
+        except _lib.DeepModRangeError:
+            keep = model.get_info(_lib.DM_INFO_PRECISION)
+            model.set_option(_lib.DM_OPT_PRECISION, _lib.DM_PREC_F32)
+            try:
+                run()
+            finally:
+                model.set_option(_lib.DM_OPT_PRECISION, keep)
+        return prob1, cls, label

@@ -633,6 +633,25 @@ int dm_xyload_times(dm_xyload* h, double* parse_ms, double* select_ms);
 int dm_xyload_tile_bytes(void);
 int dm_xyload_scan_block(void);
 
+/* The RESIDENT SET: the files `train --validate` scores at every checkpoint, kept on the device after one load each.  No reference counterpart
+ * (the reference's train never looks at the data --test holds out).  A segment is what dm_xyload holds after a file's parse and selection -
+ * feature rows [R][7], centres int32 [n] relative to the segment's first row, labels u8 [n]: 28 bytes per row + 5 per window.
+ *   dm_xyset_create    initial_rows sizes the first blocks (rows; one window per eight rows); every block at least doubles when it is full.
+ *   dm_xyset_append    the loader's table and selection become the next segment: three device-to-device copies on the set's stream, complete
+ *                      on return (the loader may load its next file or be destroyed).  A loader with n == 0 adds no segment.
+ *   dm_xyset_segments  -> the number of segments; rows / windows [cap] receive R and n of the segments below cap (either may be NULL).
+ *   dm_xyset_classify  one segment as dm_xyload_classify classifies its file: dm_predict_read_at on the segment's rows and centres; prob1 float [n],
+ *                      cls u8 [n] and, unless NULL, label u8 [n] come back (host arrays).  DM_ERANGE is the segment's own: the caller repeats that
+ *                      segment with DM_PREC_F32, as for a file.  Results equal the loader's byte for byte.
+ *   dm_xyset_bytes     28 * (rows of all segments) + 5 * (windows of all segments): what the set keeps for its files. */
+typedef struct dm_xyset dm_xyset;
+dm_xyset* dm_xyset_create(int device, int64_t initial_rows);
+void dm_xyset_destroy(dm_xyset* s);
+int dm_xyset_append(dm_xyset* s, dm_xyload* h);
+int64_t dm_xyset_segments(dm_xyset* s, int64_t* rows, int64_t* windows, int64_t cap);
+int dm_xyset_classify(dm_xyset* s, dm_model* m, int64_t segment, float* prob1, uint8_t* cls, uint8_t* label);
+int64_t dm_xyset_bytes(dm_xyset* s);
+
 #ifdef __cplusplus
 }
 #endif
