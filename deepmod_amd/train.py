@@ -121,12 +121,13 @@ class Trainer:
         return x, y
 
     def grad(self, x, y, unbalanced: bool = False, want_prob: bool = True, want_grad: bool = True):
-        """-> (loss, prob float32[n,2] or None, gradient blob float32[408402] or None); the state does not change."""
+        """-> (loss, prob float32[n,2] or None, gradient blob float32[408402] or None); the state does not change.  An empty batch gives loss 0 and
+        a zero gradient."""
         x, y = self._xy(x, y)
         n = x.shape[0]
         loss = ctypes.c_float(0.0)
         prob = np.empty((n, 2), np.float32) if want_prob else None
-        grad = np.empty(_lib.DM_WEIGHT_FLOATS, np.float32) if want_grad else None
+        grad = (np.empty if n else np.zeros)(_lib.DM_WEIGHT_FLOATS, np.float32) if want_grad else None       # n = 0: the library writes nothing
         _lib.check(self._lib.dm_trainer_grad(self._h, x.ctypes.data, y.ctypes.data, n, 1 if unbalanced else 0, ctypes.byref(loss),
                                              prob.ctypes.data if want_prob else None, grad.ctypes.data if want_grad else None))
         return loss.value, prob, grad

@@ -15,6 +15,31 @@ R_L = 266   measured 2026-10-18: the worst (|loss_gpu - loss64| - 2^-23 loss64) 
             float64 one, the float32 one within 1.4e-7 - the float32 run lies within the resolution of a float32 loss at most steps, which is what
             makes the ratio large.  The first Adam steps divide by sqrt(v) + eps with v ~ g^2: where |g| is near eps / sqrt(1 - beta2) = 3e-7 the
             update has slope lr (1 - beta1) / eps = 1e4 in g, so an absolute gradient error of 1e-8 moves a weight by 1e-4.
+
+A tensor's maximum is set by its largest rows (the event-length row of a layer-0 kernel carries gradients 30 to 1,000 times those of the other
+rows), so the rule above holds a small row group, gate or the partial unit tile 96..99 only to per cent of its own scale.  The block rule holds
+each of the 195 blocks B of train_oracle.BLOCKS (row group x gate x unit group) to its own scale:
+
+        e_gpu(B) <= R_B * e32*(B) + 2^-23
+
+where e32*(B) is the largest e32 of the block over three float32 evaluations of the oracle in three summation orders (the batch as given,
+reversed, in two halves): one evaluation's error of a 4-element block can be luckily small.  tests/test_train_host.py checks on the CPU that
+every case gives every block a float64 gradient and a yardstick above zero, and that the rule rejects what the tensor rule accepts.
+
+R_B = 41    measured 2026-10-19 on one MI355X: the worst (e_gpu(B) - 2^-23) / e32*(B) over all blocks of all cases below was 26.87 (trained-like
+            weights, synthetic windows, n = 2,049, unbalanced, bw2/bias[o,u96-99]: e_gpu 5.07e-6 against e32* 1.84e-7; absolute error 4.35e-9 on a
+            block maximum of 8.6e-4, in a tensor whose maximum is 0.77), x 1.5 = 40.3, rounded up.  At n = 2,049 the median block ratio is 2.9
+            (dw_kernel adds the 2,049 windows on one accumulator chain of 513 MFMAs, torch sums in blocks; at n <= 129 the median is at most 1.2),
+            the four terms of this block cancel to a tenth of sum|term| (6 to 12 per unit, from the float64 oracle), and the next blocks are 13.4,
+            12.1 (the same gate's units 0..95) and 12.1.  The second (the smaller call on a used handle, n = 1, bw0/kernel[mean,f,u96-99]): 22.57,
+            e_gpu 4.91e-7 - four units round-off - against e32* 1.65e-8, a single draw at n = 1 where the three evaluations coincide; that call's
+            median block ratio is 0.9.  Over all cases units 96..99 and units 0..95, the four gates and the row groups have the same median e_gpu
+            (2.7e-7 and 2.8e-7 for the unit groups): no operand segment, gate or tile edge stands out.  The yardstick is the CPU's: with the
+            float32 oracle run on 8 threads in place of 16 the same GPU gradients give 37.3 at n = 2,049 (fw0/bias[i,u96-99]) and 6.3 on
+            the n = 1 call, at most 12.4 elsewhere.  Worst per family: synthetic windows
+            n <= 129 10.29, n = 2,049 26.87, read-shaped 11.08, saturating weights 4.19, one class 7.44, shrinking batches 22.57, Session 2.96.
+prob        max|prob - prob64| <= R max|prob32 - prob64| + 2^-23 with the R above: the worst (max|prob - prob64| - 2^-23) / max|prob32 - prob64|
+            measured 2026-10-19 was 1.84 (read-shaped windows, n = 129: 7.7e-7 against 3.5e-7).
 """
 import importlib.util
 import os
@@ -30,11 +55,13 @@ pytestmark = pytest.mark.gpu
 
 R = 18
 R_L = 266
+R_B = 41
 U = 2.0 ** -23
 TOL = 1e-4                 # the project's probability tolerance (tests/test_gpu_parity.py)
 MAX_BATCH = 2049
 
 GRAD_NS = (1, 15, 16, 17, 33, 129)      # row-tile edges; 11 n off a multiple of 4; and one n = 2,049 below (one past the nominal batch)
+assert GRAD_NS == oracle.GRAD_NS and oracle.BIG_CASE == ("synth", "trained", MAX_BATCH, True)
 
 
 def _weights(which):
@@ -62,16 +89,46 @@ def trainers(gpu_device):
 
 def gradient_case(tr, which, n, unbalanced):
     """-> (e_gpu, e32) dicts over the 14 tensors plus 'loss'."""
-    flat = _weights(which)
-    x, y = _batch(n, 1000 + n)
-    l64, g64, _ = oracle.loss_and_grad(flat, x, y, unbalanced, oracle.torch.float64)
-    l32, g32, _ = oracle.loss_and_grad(flat, x, y, unbalanced, oracle.torch.float32)
-    loss, _, g = tr.grad(x, y, unbalanced, want_prob=False)
+    ref = oracle.reference(("synth", which, n, unbalanced))
+    l64, g64, l32 = ref["l64"], ref["g64"], ref["l32"]
+    loss, _, g = tr.grad(ref["x"], ref["y"], unbalanced, want_prob=False)
     e_gpu = oracle.tensor_errors(g.astype(np.float64), g64)
-    e_32 = oracle.tensor_errors(g32, g64)
+    e_32 = oracle.tensor_errors(ref["g32"].astype(np.float64), g64)
     e_gpu["loss"] = abs(loss - l64) / abs(l64)
     e_32["loss"] = abs(l32 - l64) / abs(l64)
     return e_gpu, e_32
+
+
+def blocks_and_prob(case, prob, g):
+    """The block rule and the prob rule of one call against the case's reference: prints the worst block, then asserts every block and prob."""
+    ref = oracle.reference(case)
+    e_gpu, e_32 = oracle.block_errors(g, ref["g64"]), ref["e32_blocks"]
+    ratio, name = max(((e_gpu[k] - U) / e_32[k], k) for k in e_gpu)
+    a = np.abs(ref["g64"])
+    idx = next(i for k, _, i in oracle.BLOCKS if k == name)
+    print("blocks %s worst %s e_gpu=%.3g e32*=%.3g ratio=%.3g (abs err %.3g, block max|g64| %.3g, tensor max|g64| %.3g)" %
+          (oracle.case_id(case), name, e_gpu[name], e_32[name], ratio, e_gpu[name] * a[idx].max(), a[idx].max(),
+           max(a[lo:hi].max() for t, lo, hi, _ in oracle.SLICES if t == name.split("[")[0])))
+    dp, dp32 = float(np.abs(prob - ref["p64"]).max()), ref["e32_prob"]
+    print("prob   %s max|p - p64|=%.3g max|p32 - p64|=%.3g ratio=%.3g" % (oracle.case_id(case), dp, dp32, (dp - U) / max(dp32, 1e-300)))
+    assert prob.shape == ref["p64"].shape and prob.dtype == np.float32
+    for k in e_gpu:
+        assert e_gpu[k] <= R_B * e_32[k] + U, k
+    assert dp <= R * dp32 + U
+
+
+def held_to_the_oracle(case, loss, prob, g):
+    """Every rule on one call: loss and the 14 tensors by R, the 195 blocks by R_B, prob by R."""
+    ref = oracle.reference(case)
+    e_gpu = oracle.tensor_errors(g.astype(np.float64), ref["g64"])
+    e_32 = oracle.tensor_errors(ref["g32"].astype(np.float64), ref["g64"])
+    e_gpu["loss"] = abs(loss - ref["l64"]) / abs(ref["l64"])
+    e_32["loss"] = abs(ref["l32"] - ref["l64"]) / abs(ref["l64"])
+    ratio, name = max(((e_gpu[k] - U) / max(e_32[k], 1e-300), k) for k in e_gpu)
+    print("grad   %s worst %s e_gpu=%.3g e32=%.3g ratio=%.3g" % (oracle.case_id(case), name, e_gpu[name], e_32[name], ratio))
+    for name in e_gpu:
+        assert e_gpu[name] <= R * e_32[name] + U, name
+    blocks_and_prob(case, prob, g)
 
 
 @pytest.mark.parametrize("n", (1, 17, 129))
@@ -108,6 +165,147 @@ def test_gradients_one_past_the_nominal_batch(trainers):
               (name, e_gpu[name], e_32[name], (e_gpu[name] - U) / max(e_32[name], 1e-300)))
     for name in e_gpu:
         assert e_gpu[name] <= R * e_32[name] + U, name
+
+
+@pytest.mark.parametrize("unbalanced", (False, True))
+@pytest.mark.parametrize("which", ("synthetic", "trained"))
+@pytest.mark.parametrize("n", GRAD_NS)
+def test_gradient_blocks_and_prob_against_float64_autograd(trainers, which, n, unbalanced):
+    case = ("synth", which, n, unbalanced)
+    ref = oracle.reference(case)
+    _, prob, g = trainers(which).grad(ref["x"], ref["y"], unbalanced)
+    blocks_and_prob(case, prob, g)
+
+
+def test_gradient_blocks_and_prob_one_past_the_nominal_batch(trainers):
+    ref = oracle.reference(oracle.BIG_CASE)
+    _, prob, g = trainers("trained").grad(ref["x"], ref["y"], ref["unbalanced"])
+    blocks_and_prob(oracle.BIG_CASE, prob, g)
+
+
+@pytest.mark.parametrize("case", oracle.TAIL_CASES, ids=oracle.case_id)
+def test_read_shaped_gradients_against_float64_autograd(gpu_device, case):
+    """Windows of tests/golden/trained_like_tail_case.npz (event lengths up to 26,984, means on the +-5 clip) with seeded labels: trained-like
+    weights unbalanced at n = 1, 17, 129; saturating weights (scale 4) balanced at n = 33; 16 windows of one class, each class."""
+    ref = oracle.reference(case)
+    tr = train.Trainer(ref["flat"], device=gpu_device, max_batch=len(ref["x"]))
+    try:
+        loss, prob, g = tr.grad(ref["x"], ref["y"], ref["unbalanced"])
+    finally:
+        tr.close()
+    held_to_the_oracle(case, loss, prob, g)
+
+
+def test_smaller_batches_after_a_larger_one_on_one_handle(gpu_device):
+    """n = 129, 1, 17, 16, 129 on one Trainer(max_batch=129), each call with other windows, other labels and the other `unbalanced`: what the
+    larger call left in the tape, dh and dc is wrong for the smaller one, so a stale entry that is read shows against the float64 oracle."""
+    ref0 = oracle.reference(oracle.SHRINK_CASES[0])
+    tr = train.Trainer(ref0["flat"], device=gpu_device, max_batch=max(oracle.SHRINK_NS))
+    try:
+        got = []
+        for case in oracle.SHRINK_CASES:
+            ref = oracle.reference(case)
+            assert len(ref["x"]) == oracle.SHRINK_NS[case[1]] and np.array_equal(ref["flat"], ref0["flat"])
+            got.append(tr.grad(ref["x"], ref["y"], ref["unbalanced"]))
+    finally:
+        tr.close()
+    for case, (loss, prob, g) in zip(oracle.SHRINK_CASES, got):
+        held_to_the_oracle(case, loss, prob, g)
+
+
+def test_session_fetch_after_a_larger_one_is_held_to_the_oracle(gpu_device):
+    """model.Session with a tape of 16 windows: a 40-window fetch makes the trainer grow, the 9-window fetch after it is held to float64 - loss and
+    prob as the session returns them, the gradient from the session's own trainer."""
+    init, init_l, loss_op, accuracy, train_op, X, Y, saver, auc_op, mpre, mspf, mfpred = \
+        model.mCreateSession(7, 100, 21, {"outputlayer": "", "unbalanced": 0, "seed": oracle.SESSION_SEED, "max_batch": 16})
+    sess = model.new_session(gpu_device)
+    try:
+        sess.run(init)
+        for case in oracle.SESSION_CASES:
+            ref = oracle.reference(case)
+            loss, prob = sess.run([loss_op, sess.graph.prediction], feed_dict={X: ref["x"], Y: ref["y"]})
+            tr = sess._train.trainer
+            assert tr.max_batch >= max(oracle.SESSION_NS[:case[1] + 1])
+            assert np.array_equal(tr.get_state()[0], ref["flat"])
+            loss2, prob2, g = tr.grad(ref["x"], ref["y"], False)
+            assert np.float32(loss).tobytes() == np.float32(loss2).tobytes() and np.array_equal(prob, prob2)
+            held_to_the_oracle(case, float(loss), prob, g)
+    finally:
+        sess.close()
+
+
+def test_unbalanced_reaches_the_kernel_through_the_session(gpu_device):
+    init, init_l, loss_op, accuracy, train_op, X, Y, saver, auc_op, mpre, mspf, mfpred = \
+        model.mCreateSession(7, 100, 21, {"outputlayer": "", "unbalanced": 1, "seed": 2, "max_batch": 16})
+    sess = model.new_session(gpu_device)
+    weighted, plain = (train.Trainer(train.initial_weights(2), device=gpu_device, max_batch=16) for _ in range(2))
+    bits = lambda v: np.float32(v).tobytes()
+    try:
+        sess.run(init)
+        x, y = _batch(16, 410)
+        got = sess.run([train_op, loss_op], feed_dict={X: x, Y: y})
+        assert bits(got[1]) == bits(weighted.step(x, y, unbalanced=True))
+        assert bits(got[1]) != bits(plain.step(x, y, unbalanced=False))
+        assert _same_state(sess._train.trainer.get_state(), weighted.get_state())
+        assert not np.array_equal(sess._train.trainer.get_state()[0], plain.get_state()[0])
+        plain.set_state(*weighted.get_state())
+        x, y = _batch(9, 411)
+        loss = sess.run(loss_op, feed_dict={X: x, Y: y})              # the loss-only fetch: dm_trainer_grad
+        assert bits(loss) == bits(weighted.grad(x, y, True, want_grad=False)[0])
+        assert bits(loss) != bits(plain.grad(x, y, False, want_grad=False)[0])
+    finally:
+        sess.close()
+        weighted.close()
+        plain.close()
+
+
+def test_a_loss_that_is_not_finite_is_refused_and_the_state_kept(gpu_device):
+    """out/W of +-3e38 on hidden states of order 1: the logits overflow, the loss is NaN or Inf.  step and grad refuse, Adam does not run."""
+    from deepmod_amd import _lib
+    tr = train.Trainer(_weights("trained"), device=gpu_device, max_batch=32)
+    try:
+        x, y = _batch(20, 9)
+        tr.step(x, y)
+        good = tr.get_state()
+        bad = good[0].copy()
+        a, b = oracle.SLICES[12][1:3]
+        bad[a:b] = np.float32(3e38) * np.random.default_rng(5).choice([-1.0, 1.0], b - a).astype(np.float32)
+        tr.set_state(bad, good[1], good[2], good[3])
+        before = tr.get_state()
+        assert _same_state(before, (bad, good[1], good[2], good[3]))
+        for unbalanced in (False, True):
+            with pytest.raises(_lib.DeepModHipError) as exc:
+                tr.step(x, y, unbalanced)
+            assert "not finite" in str(exc.value)
+            with pytest.raises(_lib.DeepModHipError) as exc:
+                tr.grad(x, y, unbalanced)
+            assert "not finite" in str(exc.value)
+            assert _same_state(before, tr.get_state())
+        tr.set_state(*good)
+        tr.step(x, y)
+        after = tr.get_state()
+        assert after[3] == 2 and np.isfinite(after[0]).all() and not np.array_equal(after[0], good[0])
+    finally:
+        tr.close()
+
+
+def test_an_empty_batch_gives_a_zero_gradient(gpu_device):
+    tr = train.Trainer(_weights("synthetic"), device=gpu_device, max_batch=16)
+    try:
+        x, y = _batch(4, 3)
+        tr.step(x, y)
+        before = tr.get_state()
+        for _ in range(2):                                    # np.empty would hand back the freed gradient of the call before
+            big = tr.grad(x, y)[2]
+            assert np.abs(big).max() > 0
+            del big
+            loss, prob, g = tr.grad(x[:0], y[:0])
+            assert loss == 0.0 and prob.shape == (0, 2) and prob.dtype == np.float32
+            assert g.shape == (oracle.NW,) and g.dtype == np.float32 and not g.any()
+        assert tr.grad(x[:0], y[:0], want_prob=False, want_grad=False) == (0.0, None, None)
+        assert _same_state(before, tr.get_state())
+    finally:
+        tr.close()
 
 
 def _adam_blobs(rng):

@@ -1,5 +1,6 @@
 """CPU: the host side of `train` (deepmod_amd/train.py, bin/DeepMod.py train) against recordings of the reference's own Python
-(tests/golden/make_golden_train.py -> tests/golden/train/), and the teeth of the gradient oracle (tests/train_oracle.py)."""
+(tests/golden/make_golden_train.py -> tests/golden/train/), and the teeth of the gradient oracle (tests/train_oracle.py): of the per-tensor rule, and
+of the block rule with the conditions its GPU cases must meet."""
 import contextlib
 import importlib.util
 import io
@@ -221,3 +222,110 @@ def test_a_round_that_cannot_fill_a_step_is_skipped(tmp_path):
     with contextlib.redirect_stdout(io.StringIO()):
         train.mMult_RNN_LSTM_train(dict(mo), batchsize=5, session_factory=lambda init: RecordingSession(log, saves, out_folder))
     assert [s[0] for s in log] == [5] * 4 and saves == ["1/m", "2/m", "3/m", "4/m"]
+
+
+# ---------------------------------------------------------------------------------------------
+# the block rule of tests/test_gpu_train.py, on the reference alone
+# ---------------------------------------------------------------------------------------------
+def _gpu_test_constant(name):
+    import re
+    return float(re.search(r"^%s = ([0-9.]+)$" % name, open(os.path.join(ROOT, "tests", "test_gpu_train.py")).read(), re.M).group(1))
+
+
+def test_blocks_are_a_partition_of_the_blob():
+    import train_oracle as oracle
+    assert len(oracle.BLOCKS) == 195 and len({name for name, _, _ in oracle.BLOCKS}) == 195
+    seen = np.zeros(oracle.NW, np.int64)
+    spans = {name: (a, b) for name, a, b, _ in oracle.SLICES}
+    for name, tensor, idx in oracle.BLOCKS:
+        assert idx.ndim == 1 and idx.size > 0, name
+        np.add.at(seen, idx, 1)
+        a, b = spans[tensor]
+        assert a <= idx.min() and idx.max() < b, name            # inside one tensor
+    assert np.array_equal(seen, np.ones(oracle.NW, np.int64))    # every index once, the union is range(NW)
+    sizes = {name: idx.size for name, _, idx in oracle.BLOCKS}
+    assert sizes["fw0/kernel[length,i,u96-99]"] == 4 and sizes["bw0/kernel[recurrent,o,u0-95]"] == 9600 and sizes["fw2/kernel[input,j,u96-99]"] == 400
+    assert sizes["bw1/bias[f,u0-95]"] == 96 and sizes["out/W[fw]"] == sizes["out/W[bw]"] == 200 and sizes["out/b"] == 2
+    # a gate block holds that gate's columns: the forget-gate block of a bias is where BasicLSTMCell's kernel columns 200..299 land
+    name, _, idx = next(b for b in oracle.BLOCKS if b[0] == "fw0/bias[f,u96-99]")
+    assert idx.tolist() == [107 * 400 + 296 + i for i in range(4)]
+
+
+def test_block_errors_resolve_what_tensor_errors_average_away():
+    import train_oracle as oracle
+    g64 = np.random.default_rng(0).standard_normal(oracle.NW)
+    g = g64.copy()
+    i = next(idx for name, _, idx in oracle.BLOCKS if name == "bw1/kernel[recurrent,o,u96-99]")[7]
+    g[i] += 0.5
+    eb, et = oracle.block_errors(g, g64), oracle.tensor_errors(g, g64)
+    assert [k for k, v in eb.items() if v > 0] == ["bw1/kernel[recurrent,o,u96-99]"] and [k for k, v in et.items() if v > 0] == ["bw1/kernel"]
+    assert eb["bw1/kernel[recurrent,o,u96-99]"] > et["bw1/kernel"]
+
+
+@pytest.mark.parametrize("case", __import__("train_oracle").ALL_CASES, ids=__import__("train_oracle").case_id)
+def test_every_gpu_gradient_case_resolves_every_block(case):
+    """What the block rule of tests/test_gpu_train.py needs from a case, on the reference alone: no block of the float64 gradient is all zero and
+    every block has a yardstick > 0 (the largest e32 of three float32 evaluations in three summation orders) - for all 195 blocks, none skipped
+    or merged.  A case that fails this gets another seed or n."""
+    import train_oracle as oracle
+    ref = oracle.reference(case)
+    a = np.abs(ref["g64"])
+    assert np.isfinite(ref["l64"]) and np.isfinite(a).all()
+    for name, _, idx in oracle.BLOCKS:
+        assert a[idx].max() > 0, name
+        assert 0 < ref["e32_blocks"][name] < np.inf, name
+    assert ref["e32_prob"] > 0 or ref["p64"].shape[0] == 1
+    assert ref["x"].shape[0] == ref["p64"].shape[0] == ref["p32"].shape[0]
+
+
+def test_train_command_line_unbalanced_reaches_the_graph():
+    p = cli.build_parser()
+    for flag, want in (([], False), (["--unbalanced", "0"], False), (["--unbalanced", "1"], True)):
+        mo = cli.train_options(p.parse_args(["train", "--wrkBase", "a"] + flag))
+        assert train.TrainGraph(mo["fnum"], mo["hidden"], mo["windowsize"], mo).unbalanced is want, flag
+
+
+TEETH = (  # (case, delta, the per-tensor rule accepts it)
+    (("tail", 1), 1e-3, True),
+    (("tail", 17), 5e-4, True),
+    (("synth", "synthetic", 1, False), 1e-3, False),
+)
+
+
+@pytest.mark.parametrize("case,delta,accepted", TEETH, ids=lambda v: __import__("train_oracle").case_id(v) if isinstance(v, tuple) else str(v))
+def test_the_block_rule_has_teeth_where_the_tensor_rule_has_none(case, delta, accepted):
+    """Two wrong gradients a dW kernel could produce - the recurrent rows of fw0/kernel (one operand segment) and units 96..99 of the forget gate
+    of bw2/kernel (the last, partial 16-unit tile) scaled by 1 + delta - stay inside the per-tensor bound R e32(T) + 2^-23 in every tensor and
+    miss the block bound R_B e32*(B) + 2^-23 by at least 10 times in a block of the mutated rows or units.  On read-shaped windows the length row
+    is 100 to 500 times the mutated blocks (the tensor rule accepts delta up to 1.5e-3 at n = 1, 1.7e-3 at n = 17).  On the synthetic n = 1 case
+    it is 10 to 15 times, and the tensor rule accepts delta only up to 8e-5 and 4e-5: there delta = 1e-3 is rejected by both rules, by the
+    block rule by the wider margin (fw0/kernel: 6.6e-5 against the tensor bound 5.2e-6; 1e-3 against a block bound of 6e-6)."""
+    import train_oracle as oracle
+    R, R_B, U = _gpu_test_constant("R"), _gpu_test_constant("R_B"), 2.0 ** -23
+    ref = oracle.reference(case)
+    g64 = ref["g64"]
+    tensor_bound = {k: R * e + U for k, e in oracle.tensor_errors(ref["g32"].astype(np.float64), g64).items()}
+    block_bound = {k: R_B * e + U for k, e in ref["e32_blocks"].items()}
+    spans = {name: (a, b, shape) for name, a, b, shape in oracle.SLICES}
+    mutants = {}
+    a, b, shape = spans["fw0/kernel"]
+    g = g64.copy()
+    g[a:b].reshape(shape)[oracle.NFEAT:, :] *= 1.0 + delta
+    mutants["fw0/kernel recurrent rows"] = (g, "fw0/kernel[recurrent")
+    a, b, shape = spans["bw2/kernel"]
+    g = g64.copy()
+    g[a:b].reshape(shape)[:, 2 * oracle.HID + 96:3 * oracle.HID] *= 1.0 + delta
+    mutants["bw2/kernel forget gate units 96..99"] = (g, "bw2/kernel[")
+    for what, (g, prefix) in mutants.items():
+        et, eb = oracle.tensor_errors(g, g64), oracle.block_errors(g, g64)
+        worst = max((eb[k] / block_bound[k], k) for k in eb)
+        worst_tensor = max(et[k] / tensor_bound[k] for k in et)
+        print("%s %s delta=%g: tensor %.3g of its bound, worst block %s at %.3g times its bound" %
+              (oracle.case_id(case), what, delta, worst_tensor, worst[1], worst[0]))
+        assert [k for k, v in eb.items() if v > 0 and not k.startswith(prefix)] == []       # the mutation is where it was put
+        if accepted:
+            for k in et:
+                assert et[k] <= tensor_bound[k], (what, k)          # today's rule accepts it
+        else:
+            assert worst_tensor < worst[0]
+        assert worst[0] >= 10 and worst[1].startswith(prefix), (what, worst)
