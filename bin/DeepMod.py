@@ -12,7 +12,8 @@ reference's *.xy.gz feature files and writes TF-bundle checkpoints `detect --mod
 CKPT_PREFIX continues a stopped run from it, checkpoint for checkpoint the bytes of the uninterrupted run;
 --startFrom CKPT_PREFIX runs the whole schedule from an existing model's weights; --validate K (with --test)
 keeps K held-out windows on the GPU, scores them at every checkpoint (<prefix>.valid.json) and names the
-best one.
+best one.  --resident 1 loads the training files once through the GPU parser and keeps them on the GPU: a step
+sends window ids, not windows, and the checkpoints are the default run's byte for byte.
 
 `getfeatures` (flags and defaults of bin/DeepMod.py:354-375) writes those *.xy.gz / *.xy.ind files from raw
 containers (*.dmraw.npz, event tables or --move), a reference and known modified positions - a motif
@@ -102,6 +103,12 @@ def build_parser():
     trn.add_argument('--validate', type=int, default=0, metavar='K',
                      help='with --test: keep at least K windows of the held-out data on the GPU (whole files, one per folder in turn) and score them at every checkpoint '
                           'as predict would: <prefix>.valid.json, and <outFolder>/<FileID>_valid.json with the best checkpoint by AUC (default 0: off)')
+    trn.add_argument('--resident', type=int, default=0, choices=[0, 1],
+                     help='1: load every training file once, before the first step, through the GPU parser (as predict loads its files; gunzip on --threads host '
+                          'threads) and keep it on the GPU at 28 B per row + 5 B per window; every step then gathers its windows there from 8 B of window id '
+                          'each.  Checkpoints and .train.json are byte for byte those of the default (0: files are read on the host, round by round, in every '
+                          'epoch).  A labelled row without a whole window is reported while loading.  DEEPMOD_RESIDENT_BYTES=N ends the run before its first '
+                          'step when the files need more than N bytes')
     trn.set_defaults(func=mTrain)
     prd = sub.add_parser('predict', parents=[com], help='score a trained model on labelled *.xy.gz feature files',
                          description='Evaluate a checkpoint on labelled *.xy.gz files: per file the text is parsed, the labelled rows are selected and their '
@@ -217,7 +224,8 @@ def train_options(args, cmd='train', keys=('unbalanced', 'modfile', 'seed')):
     else:
         mo['test'] = ['N', '100']
     if cmd == 'train':
-        mo.update(resume=getattr(args, 'resume', None), startFrom=getattr(args, 'startFrom', None), validate=getattr(args, 'validate', 0))
+        mo.update(resume=getattr(args, 'resume', None), startFrom=getattr(args, 'startFrom', None), validate=getattr(args, 'validate', 0),
+                  resident=getattr(args, 'resident', 0), threads=max(getattr(args, 'threads', 1) or 1, 1))
         from deepmod_amd import train
         train.check_run_options(mo)
     return mo

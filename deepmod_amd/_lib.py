@@ -166,6 +166,9 @@ SIGNATURES = [
     ("dm_xyset_segments", _i64, [_vp, _vp, _vp, _i64]),
     ("dm_xyset_classify", _c.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     ("dm_xyset_bytes", _i64, [_vp]),
+    ("dm_xyset_gather", _c.c_int, [_vp, _vp, _i64, _vp]),
+    ("dm_trainer_step_set", _c.c_int, [_vp, _vp, _vp, _vp, _i64, _c.c_int, _c.POINTER(_c.c_float)]),
+    ("dm_trainer_grad_set", _c.c_int, [_vp, _vp, _vp, _vp, _i64, _c.c_int, _c.POINTER(_c.c_float), _vp, _vp]),
 ]
 
 

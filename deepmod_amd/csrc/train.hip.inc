@@ -388,7 +388,8 @@ struct dm_trainer {
     float *d_G = nullptr, *d_C = nullptr, *d_H = nullptr;           // the tape
     float *d_x = nullptr, *d_y = nullptr, *d_prob = nullptr, *d_lossw = nullptr, *d_dz = nullptr, *d_loss = nullptr;
     float *d_dh = nullptr, *d_dc = nullptr;                       // [2][3][max_batch][100]
-    int* d_flag = nullptr;
+    int* d_flag = nullptr;                                        // 16 bytes: the finite check's flag, and at byte 8 the id word of a step from a set
+    long long* d_ids = nullptr;                                   // [max_batch]: the window ids of a step from a set (xygather.hip.inc)
     int64_t t = 0;
     // dm_trainer_profile: HIP events around every dm_trainer_step (uploads, the two host round trips for the input check and the loss, Adam)
     bool profile = false, in_step = false;
@@ -408,24 +409,25 @@ int trainer_download(dm_trainer* tr, float* dst, const float* src, size_t floats
     return DM_OK;
 }
 
-// checks, staging, forward, backward: leaves loss, prob and the gradient on the device and *loss on the host.  Nothing is launched past an error.
-int trainer_grad_device(dm_trainer* tr, const float* x, const float* y, int64_t n, int unbalanced, float* loss) {
+// d_x and d_y are staged on the stream: finite check, forward, backward: leaves loss, prob and the gradient on the device and *loss on the host.
+// Nothing is launched past an error.  bad_id (dm_trainer_step_set, xygather.hip.inc): the word behind the finite flag, which the gather raised
+// for an id outside the set, comes back in the same copy.
+int trainer_grad_staged(dm_trainer* tr, int64_t n, int unbalanced, float* loss, long long* bad_id = nullptr) {
     using namespace dmtrain;
-    if (!x || !y) return fail(DM_EINVAL, "dm_trainer: null x or y");
-    if (n > tr->max_batch) return fail(DM_EINVAL, "dm_trainer: %lld windows exceed max_batch = %lld", (long long)n, (long long)tr->max_batch);
-    HIP_TRY(hipSetDevice(tr->device));
     hipStream_t s = tr->stream;
-    int rc = trainer_upload(tr, tr->d_x, x, size_t(n) * WIN * NFEAT);
-    if (rc) return rc;
-    rc = trainer_upload(tr, tr->d_y, y, size_t(n) * 2);
-    if (rc) return rc;
     HIP_TRY(hipMemsetAsync(tr->d_flag, 0, sizeof(int), s));
     hipLaunchKernelGGL(finite_check_kernel, dim3(unsigned(std::min<int64_t>((n * WIN * NFEAT + 255) / 256, 1024))), dim3(256), 0, s, tr->d_x,
                        (long long)n * WIN * NFEAT, tr->d_y, (long long)n * 2, tr->d_flag);
     HIP_TRY(hipGetLastError());
-    int flag = 0;
-    HIP_TRY(hipMemcpyAsync(&flag, tr->d_flag, sizeof(int), hipMemcpyDeviceToHost, s));
+    long long back[2] = {0, 0};                                      // the flag in the first int; the id word at byte 8
+    HIP_TRY(hipMemcpyAsync(back, tr->d_flag, bad_id ? 16 : sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    if (bad_id) {
+        *bad_id = back[1];
+        if (back[1] != 0) return DM_EINVAL;                          // the caller words it
+    }
+    int flag = 0;
+    std::memcpy(&flag, back, sizeof(int));
     if (flag) return fail(DM_EINVAL, "dm_trainer: NaN or Inf in x or y (%lld windows); nothing was computed", (long long)n);
 
     const long long nn = n, cap = tr->max_batch;
@@ -468,6 +470,19 @@ int trainer_grad_device(dm_trainer* tr, const float* x, const float* y, int64_t 
     return DM_OK;
 }
 
+// checks and staging of host or device x and y, then trainer_grad_staged
+int trainer_grad_device(dm_trainer* tr, const float* x, const float* y, int64_t n, int unbalanced, float* loss) {
+    using namespace dmtrain;
+    if (!x || !y) return fail(DM_EINVAL, "dm_trainer: null x or y");
+    if (n > tr->max_batch) return fail(DM_EINVAL, "dm_trainer: %lld windows exceed max_batch = %lld", (long long)n, (long long)tr->max_batch);
+    HIP_TRY(hipSetDevice(tr->device));
+    int rc = trainer_upload(tr, tr->d_x, x, size_t(n) * WIN * NFEAT);
+    if (rc) return rc;
+    rc = trainer_upload(tr, tr->d_y, y, size_t(n) * 2);
+    if (rc) return rc;
+    return trainer_grad_staged(tr, n, unbalanced, loss);
+}
+
 int trainer_adam_device(dm_trainer* tr) {
     const int64_t t = tr->t + 1;
     const double lr = 1e-3 * std::sqrt(1.0 - std::pow(0.999, double(t))) / (1.0 - std::pow(0.9, double(t)));
@@ -478,6 +493,27 @@ int trainer_adam_device(dm_trainer* tr) {
     HIP_TRY(hipStreamSynchronize(tr->stream));
     tr->t = t;
     return DM_OK;
+}
+
+// the two ends of a step (dm_trainer_step, dm_trainer_step_set): the profile's bracket, Adam behind the gradient
+int trainer_step_begin(dm_trainer* tr) {
+    if (tr->profile) {
+        HIP_TRY(hipSetDevice(tr->device));
+        HIP_TRY(hipEventRecord(tr->ev0, tr->stream));
+    }
+    return DM_OK;
+}
+int trainer_step_finish(dm_trainer* tr) {
+    tr->in_step = tr->profile;
+    const int rc = trainer_adam_device(tr);
+    tr->in_step = false;
+    if (rc == DM_OK && tr->profile) {
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, tr->ev0, tr->ev1));
+        tr->prof_ms += ms;
+        ++tr->prof_steps;
+    }
+    return rc;
 }
 
 int trainer_init(dm_trainer* tr, const float* weights) {
@@ -505,7 +541,8 @@ int trainer_init(dm_trainer* tr, const float* weights) {
     HIP_TRY(hipMalloc(&tr->d_loss, f));
     HIP_TRY(hipMalloc(&tr->d_dh, size_t(6) * cap * HID * f));
     HIP_TRY(hipMalloc(&tr->d_dc, size_t(6) * cap * HID * f));
-    HIP_TRY(hipMalloc(&tr->d_flag, sizeof(int)));
+    HIP_TRY(hipMalloc(&tr->d_flag, 16));
+    HIP_TRY(hipMalloc(&tr->d_ids, cap * sizeof(long long)));
     HIP_TRY(hipMemcpy(tr->d_w, weights, NW * f, hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(tr->d_m, 0, NW * f));
     HIP_TRY(hipMemset(tr->d_v, 0, NW * f));
@@ -554,6 +591,7 @@ void dm_trainer_destroy(dm_trainer* tr) {
                      tr->d_dz, tr->d_loss, tr->d_dh, tr->d_dc};
     for (float* p : bufs) (void)hipFree(p);
     (void)hipFree(tr->d_flag);
+    (void)hipFree(tr->d_ids);
     if (tr->ev0) (void)hipEventDestroy(tr->ev0);
     if (tr->ev1) (void)hipEventDestroy(tr->ev1);
     if (tr->stream) (void)hipStreamDestroy(tr->stream);
@@ -591,22 +629,11 @@ int dm_trainer_step(dm_trainer* tr, const float* x, const float* y, int64_t n, i
     if (!tr) return fail(DM_EINVAL, "null trainer");
     if (n < 0) return fail(DM_EINVAL, "negative window count");
     if (n == 0) return DM_OK;
-    if (tr->profile) {
-        HIP_TRY(hipSetDevice(tr->device));
-        HIP_TRY(hipEventRecord(tr->ev0, tr->stream));
-    }
-    int rc = trainer_grad_device(tr, x, y, n, unbalanced, loss);
+    int rc = trainer_step_begin(tr);
     if (rc) return rc;
-    tr->in_step = tr->profile;
-    rc = trainer_adam_device(tr);
-    tr->in_step = false;
-    if (rc == DM_OK && tr->profile) {
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, tr->ev0, tr->ev1));
-        tr->prof_ms += ms;
-        ++tr->prof_steps;
-    }
-    return rc;
+    rc = trainer_grad_device(tr, x, y, n, unbalanced, loss);
+    if (rc) return rc;
+    return trainer_step_finish(tr);
 }
 
 int dm_trainer_profile(dm_trainer* tr, int on, double* step_ms, int64_t* steps) {

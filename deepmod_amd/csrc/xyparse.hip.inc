@@ -547,6 +547,13 @@ struct dm_xyset {
     float *prob = nullptr, *prob1 = nullptr;            // scratch of the largest segment classified so far
     uint8_t* cls = nullptr;
     int64_t cap_out = 0;
+    // the gather by window id (xygather.hip.inc): the segment table on the device and dm_xyset_gather's scratch
+    long long* d_off = nullptr;                         // win_off [S + 1], row_off [S + 1] of the d_off_segs segments it was uploaded for
+    size_t cap_off = 0;
+    int64_t d_off_segs = -1;
+    std::vector<long long> off_host;
+    void *g_ids = nullptr, *g_x = nullptr, *g_bad = nullptr;
+    size_t cap_g_ids = 0, cap_g_x = 0;
 };
 
 namespace xlk {
@@ -581,7 +588,7 @@ void dm_xyset_destroy(dm_xyset* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
-    for (void* b : {(void*)s->feats, (void*)s->centre, (void*)s->label, (void*)s->prob, (void*)s->prob1, (void*)s->cls})
+    for (void* b : {(void*)s->feats, (void*)s->centre, (void*)s->label, (void*)s->prob, (void*)s->prob1, (void*)s->cls, (void*)s->d_off, s->g_ids, s->g_x, s->g_bad})
         if (b) (void)hipFree(b);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;

@@ -144,6 +144,32 @@ class Trainer:
         _lib.check(self._lib.dm_trainer_step(self._h, x.ctypes.data, y.ctypes.data, x.shape[0], 1 if unbalanced else 0, ctypes.byref(loss)))
         return loss.value
 
+    @staticmethod
+    def _ids_y(ids, y):
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        y = np.ascontiguousarray(y, dtype=np.float32)
+        if ids.ndim != 1 or y.shape != (ids.shape[0], 2):
+            raise ValueError("expected ids [n] and y [n,2], got %s and %s" % (ids.shape, y.shape))
+        return ids, y
+
+    def grad_set(self, xyset, ids, y, unbalanced: bool = False, want_prob: bool = True, want_grad: bool = True):
+        """grad() of the windows `ids` of an xyload.XYSet on this device, gathered there: 8 B of id and 8 B of y per window go up."""
+        ids, y = self._ids_y(ids, y)
+        n = ids.shape[0]
+        loss = ctypes.c_float(0.0)
+        prob = np.empty((n, 2), np.float32) if want_prob else None
+        grad = (np.empty if n else np.zeros)(_lib.DM_WEIGHT_FLOATS, np.float32) if want_grad else None
+        _lib.check(self._lib.dm_trainer_grad_set(self._h, xyset._h, ids.ctypes.data, y.ctypes.data, n, 1 if unbalanced else 0, ctypes.byref(loss),
+                                                 prob.ctypes.data if want_prob else None, grad.ctypes.data if want_grad else None))
+        return loss.value, prob, grad
+
+    def step_set(self, xyset, ids, y, unbalanced: bool = False) -> float:
+        """step() of the windows `ids` of an xyload.XYSet on this device: the host-fed step's results bit for bit."""
+        ids, y = self._ids_y(ids, y)
+        loss = ctypes.c_float(0.0)
+        _lib.check(self._lib.dm_trainer_step_set(self._h, xyset._h, ids.ctypes.data, y.ctypes.data, ids.shape[0], 1 if unbalanced else 0, ctypes.byref(loss)))
+        return loss.value
+
     def profile(self, on: bool = True):
         """-> (ms, steps) of the dm_trainer_step calls since the last call (HIP events on the trainer's stream), then switches the bracketing."""
         ms, steps = ctypes.c_double(0.0), ctypes.c_int64(0)
@@ -261,11 +287,22 @@ class TrainGraph:
         return any(f is t for t in (self.loss_op, self.accuracy, self.train_op, self.auc_op[1], self.mpre[1], self.mspf[1]))
 
 
+class SetWindows:
+    """X of a feed whose windows are not on the host: the ids of windows of an xyload.XYSet (TrainSession.run gathers them on the device)."""
+
+    def __init__(self, xyset, ids):
+        self.set, self.ids = xyset, np.ascontiguousarray(ids, dtype=np.int64)
+
+    def __len__(self):
+        return len(self.ids)
+
+
 class TrainSession:
     """The training side of model.Session (which creates one at the first fetch of a training token): run(init) creates the trainer from the
     seeded initial values, run([train_op, loss_op], feed) is one dm_trainer_step, a fetch without train_op is one dm_trainer_grad (loss,
     accuracy, precision, recall, AUC of that batch: the metrics are reset before every progress line, so they are the batch's own).  A
-    batch larger than the tape makes the trainer grow, state kept."""
+    batch larger than the tape makes the trainer grow, state kept.  An X that is a SetWindows routes to dm_trainer_step_set / _grad_set; the
+    set is not the trainer's, so it outlives a growth."""
 
     def __init__(self, graph: TrainGraph, device: int = 0):
         self.graph, self.device = graph, device
@@ -303,13 +340,18 @@ class TrainSession:
             raise _lib.DeepModHipError("TrainSession.run before run(init)")
         if feed_dict is None or g.X not in feed_dict or g.Y not in feed_dict:
             raise ValueError("feed_dict must provide X and Y")
-        x, y = np.asarray(feed_dict[g.X]), np.asarray(feed_dict[g.Y])
+        x, y = feed_dict[g.X], np.asarray(feed_dict[g.Y])
+        from_set = isinstance(x, SetWindows)            # `train --resident 1`: the windows stay on the device, the feed names them by id
+        if not from_set:
+            x = np.asarray(x)
         self._fit(len(x))
         prob = None
         if any(f is g.train_op for f in flist):
             if any(f is not g.train_op and f is not g.loss_op for f in flist):
                 raise ValueError("train_op can be fetched together with loss_op only")
-            loss = self.trainer.step(x, y, g.unbalanced)
+            loss = self.trainer.step_set(x.set, x.ids, y, g.unbalanced) if from_set else self.trainer.step(x, y, g.unbalanced)
+        elif from_set:
+            loss, prob, _ = self.trainer.grad_set(x.set, x.ids, y, g.unbalanced, want_prob=True, want_grad=False)
         else:
             loss, prob, _ = self.trainer.grad(x, y, g.unbalanced, want_prob=True, want_grad=False)
         out = []
@@ -438,6 +480,127 @@ class _GroupReader:
         if not xs:
             return np.zeros((0, WIN, NFEAT), np.float32), np.zeros((0, 2), int)
         return np.concatenate(xs, axis=0), np.concatenate(ys, axis=0)
+
+
+class ResidentCatalogue:
+    """What `train --resident 1` knows of its files once they are loaded: per file its number of windows, its first window id in the set
+    (-1: the file has no window and therefore no segment) and y int [k,2] of its windows.  A window's id is its index over the concatenated
+    segments, in load order.  Host data only."""
+
+    def __init__(self):
+        self.windows, self.first, self.y, self.total = {}, {}, {}, 0
+
+    def __contains__(self, fn):
+        return fn in self.windows
+
+    def add(self, fn, y):
+        k = len(y)
+        self.windows[fn] = k
+        self.first[fn] = self.total if k > 0 else -1
+        self.y[fn] = np.asarray(y, dtype=int).reshape(k, 2)
+        self.total += k
+
+
+class _ResidentReader:
+    """_GroupReader on a catalogue: pool() names the windows it would have read - (ids int64 [k], y int [k,2]) - with the same file order,
+    position, recycling and errors."""
+
+    def __init__(self, files, catalogue):
+        self.files, self.catalogue, self.next = list(files), catalogue, 0
+
+    def exhausted(self):
+        return self.next >= len(self.files)
+
+    def pool(self, windows_wanted, wrap):
+        ids, ys, have, idle = [], [], 0, 0
+        while have < windows_wanted:
+            if self.exhausted():
+                if not wrap:
+                    break
+                self.next = 0
+            fn = self.files[self.next]
+            self.next += 1
+            k = self.catalogue.windows[fn]
+            if k > 0:
+                first = self.catalogue.first[fn]
+                ids.append(np.arange(first, first + k, dtype=np.int64))
+                ys.append(self.catalogue.y[fn])
+                have += k
+                idle = 0
+            else:
+                idle += 1
+                if idle > len(self.files):
+                    raise ValueError("no labelled window in any of the %d files of a group (first: %s)" % (len(self.files), self.files[0]))
+        if not ids:
+            return np.zeros(0, np.int64), np.zeros((0, 2), int)
+        return np.concatenate(ids), np.concatenate(ys, axis=0)
+
+
+RESIDENT_BYTES = "DEEPMOD_RESIDENT_BYTES"
+
+
+class ResidentData:
+    """--resident 1: every file of every group, once through XYLoader.load under the run's moptions['test'] (device parser and selection, host
+    fallback with its note) and appended to one xyload.XYSet; gunzip runs ahead on --threads host threads.  A labelled row without a whole
+    window is the loader's error, raised here and not when the schedule reaches the file.  The set larger than DEEPMOD_RESIDENT_BYTES, or a
+    device allocation that fails, ends the run in one line before its first step."""
+
+    def __init__(self, filelists, moptions, device: int = 0, initial_rows: int = 1 << 16):
+        from concurrent.futures import ThreadPoolExecutor
+        from . import predict, xyload
+        self.catalogue = ResidentCatalogue()
+        files = list(dict.fromkeys(fn for group in filelists for fn in group))
+        budget = os.environ.get(RESIDENT_BYTES)
+        budget = int(budget) if budget not in (None, "") else None
+        threads = max(int(moptions.get('threads') or 1), 1)
+        started = time.time()
+        rows_total = 0
+        self.set = xyload.XYSet(device, initial_rows)
+        loader = xyload.XYLoader(device)
+
+        def too_large(fn, why):
+            return SystemExit("Error: --resident: %s at %s (file %d of %d) with %d bytes held%s: run without --resident" %
+                              (why, fn, len(self.catalogue.windows) + 1, len(files), self.set.nbytes(),
+                               "" if budget is None else ", budget %s=%d" % (RESIDENT_BYTES, budget)))
+        try:
+            with ThreadPoolExecutor(threads) as pool:
+                ahead, nxt = [], 0                      # at most 2 * threads texts in flight
+                for _ in files:
+                    while nxt < len(files) and len(ahead) < 2 * threads:
+                        ahead.append((files[nxt], pool.submit(predict.read_text, files[nxt])))
+                        nxt += 1
+                    fn, fut = ahead.pop(0)
+                    try:
+                        rows, n, _ = loader.load(fut.result(), moptions, fn)
+                        y = np.zeros((0, 2), int)
+                        if n > 0:
+                            y = loader.fetch_head()[loader.fetch_selection()[0], 1:3].astype(int)
+                            self.set.append(loader)
+                    except _lib.DeepModHipError as exc:
+                        if exc.code != _lib.DM_ENOMEM:
+                            raise
+                        for _, other in ahead:
+                            other.cancel()
+                        raise too_large(fn, "the device has no room for the training files")
+                    if budget is not None and self.set.nbytes() > budget:
+                        for _, other in ahead:
+                            other.cancel()
+                        raise too_large(fn, "the training files pass the budget")
+                    self.catalogue.add(fn, y)
+                    rows_total += rows
+        except BaseException:
+            self.close()
+            raise
+        finally:
+            loader.close()
+        print("resident: %d files, %d rows, %d windows stay on the device: %d bytes (%.2f s)" %
+              (len(files), rows_total, self.catalogue.total, self.set.nbytes(), time.time() - started))
+        sys.stdout.flush()
+
+    def close(self):
+        if getattr(self, "set", None) is not None:
+            self.set.close()
+            self.set = None
 
 
 def _progress_interval(n_files):
@@ -605,7 +768,7 @@ def best_checkpoint(table):
 
 
 def train_save_model(filelists, num_input, mhidden, timesteps, moptions, batchsize: int = batchsize, session_factory=None, resume=None,
-                     start_from=None, validate: int = 0):
+                     start_from=None, validate: int = 0, resident: bool = False):
     """Four epochs over the file groups; filelists[0] leads.  One round of an epoch:
       * the leading group reads files until it has 25 * batchsize windows (or runs out) and cuts them into int(windows / batchsize) equal
         steps (np.array_split: batchsize .. 2 batchsize - 1 windows each); a round that cannot fill one step is skipped with a note;
@@ -621,9 +784,13 @@ def train_save_model(filelists, num_input, mhidden, timesteps, moptions, batchsi
     of the same command line - the schedule takes its position from the .train.json, the saver (restore_training, if it has one) the trainer's
     state from the bundle, and the run goes on: inside the epoch of a mid-epoch checkpoint, with the next epoch after an epoch's last, not at
     all after the run's last.  start_from: a bundle whose 14 variables replace the initial values; the schedule is the whole one.
-    validate: HeldOut of that many windows, scored at every save of a GPU session (<prefix>.valid.json, <outFolder><FileID>_valid.json)."""
+    validate: HeldOut of that many windows, scored at every save of a GPU session (<prefix>.valid.json, <outFolder><FileID>_valid.json).
+    resident: ResidentData holds every training file on the device from before the first step; the readers answer from its catalogue and a
+    step's X is a SetWindows of window ids.  The schedule, and with it every checkpoint and .train.json, is the host-fed run's."""
     from . import model as _model
     check_run_options(dict(moptions, resume=resume, startFrom=start_from, validate=validate))
+    if resident and session_factory is not None:
+        raise SystemExit("Error: --resident needs the GPU session: it cannot run with a session_factory")
     graph_options = dict(moptions, max_batch=2 * batchsize - 1)
     init, init_l, loss_op, accuracy, train_op, X, Y, saver, auc_op, mpre, mspf, mfpred = \
         _model.mCreateSession(num_input, mhidden, timesteps, graph_options)
@@ -649,6 +816,17 @@ def train_save_model(filelists, num_input, mhidden, timesteps, moptions, batchsi
         print("--resume %s: step count %d, going on %s epoch %d" % (resume, t, "inside" if inside else "with", first_epoch))
     if (resume is not None or start_from is not None) and 'seed' in moptions:
         print("Note: --seed %s is not used: the weights come from %s" % (moptions['seed'], resume or start_from))
+    data = None
+    if resident:
+        data = ResidentData(filelists, moptions, int(moptions.get("device", 0)))
+        for i, reader in enumerate(readers):
+            readers[i] = _ResidentReader(reader.files, data.catalogue)
+            readers[i].next = reader.next
+        lead, others = readers[0], readers[1:]
+
+    def windows(x):
+        return x if data is None else SetWindows(data.set, x)
+
     sess = session_factory(init) if session_factory else _model.new_session(int(moptions.get("device", 0)))
     saver = getattr(sess, "saver", saver)
     held, table = None, []
@@ -703,14 +881,14 @@ def train_save_model(filelists, num_input, mhidden, timesteps, moptions, batchsi
                 if report:
                     px, py = pieces[min(3, len(pieces) - 1)]
                     sess.run(init_l)
-                    loss, auc, acc, prec, rec = sess.run([loss_op, auc_op[1], accuracy, mpre[1], mspf[1]], feed_dict={X: px[0], Y: py[0]})
+                    loss, auc, acc, prec, rec = sess.run([loss_op, auc_op[1], accuracy, mpre[1], mspf[1]], feed_dict={X: windows(px[0]), Y: py[0]})
                     print("files %d/%d: loss=%.3f AUC=%.3f acc=%.3f p=%.3f r=%.3f (%d s)" %
                           (lead.next, len(lead.files), loss, auc, acc, prec, rec, time.time() - started))
                     sys.stdout.flush()
                     shown_at = (lead.next + 1) - ((lead.next + 1) % every)
                 for i in range(steps):
                     for px, py in pieces:
-                        sess.run([train_op, loss_op], feed_dict={X: px[i], Y: py[i]})
+                        sess.run([train_op, loss_op], feed_dict={X: windows(px[i]), Y: py[i]})
                         t += 1
                 suffix = _mid_epoch_folder(int(lead.next * 100 / float(len(lead.files))), not others)
                 if suffix is not None:
@@ -730,6 +908,8 @@ def train_save_model(filelists, num_input, mhidden, timesteps, moptions, batchsi
     finally:
         if held is not None:
             held.close()
+        if data is not None:
+            data.close()
         if hasattr(sess, "close"):
             sess.close()
     return tokens
@@ -762,4 +942,4 @@ def mMult_RNN_LSTM_train(moptions, batchsize: int = batchsize, session_factory=N
         raise SystemExit("Error: no *.xy.gz feature file under --wrkBase %r" % (moptions['wrkBase'],))
     return train_save_model(filelists, moptions['fnum'], moptions['hidden'], moptions['windowsize'], moptions, batchsize=batchsize,
                             session_factory=session_factory, resume=moptions.get('resume'), start_from=moptions.get('startFrom'),
-                            validate=int(moptions.get('validate') or 0))
+                            validate=int(moptions.get('validate') or 0), resident=bool(int(moptions.get('resident') or 0)))

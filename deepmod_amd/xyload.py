@@ -143,6 +143,12 @@ class XYLoader:
         _lib.check(self._lib.dm_xyload_fetch(self._h, feats.ctypes.data, head.ctypes.data, None, None))
         return feats, head
 
+    def fetch_head(self) -> np.ndarray:
+        """-> head [R,3] (position, two labels) alone: 12 bytes per row (`train --resident` takes its y from it)."""
+        head = np.empty((self.n_rows, 3), np.float32)
+        _lib.check(self._lib.dm_xyload_fetch(self._h, None, head.ctypes.data, None, None))
+        return head
+
     def fetch_selection(self) -> Tuple[np.ndarray, np.ndarray]:
         """-> (centre int32 [n], label u8 [n])"""
         centre, label = np.empty(max(self.n, 0), np.int32), np.empty(max(self.n, 0), np.uint8)
@@ -193,7 +199,8 @@ class XYLoader:
 
 class XYSet:
     """One dm_xyset on one GPU: loaded files kept on the device as segments (feature rows [R][7], centres int32 [n], labels u8 [n] - 28 bytes per
-    row + 5 per window), classified again and again without their text being read a second time (`train --validate`)."""
+    row + 5 per window), classified again and again without their text being read a second time (`train --validate`), or the source of a
+    training step's windows by id (`train --resident 1`: gather, Trainer.step_set)."""
 
     def __init__(self, device: int = 0, initial_rows: int = 1 << 16):
         self._lib = _lib.load()
@@ -230,6 +237,14 @@ class XYSet:
 
     def nbytes(self) -> int:
         return int(self._lib.dm_xyset_bytes(self._h))
+
+    def gather(self, ids) -> np.ndarray:
+        """The windows of ids (a window's id is its index over the concatenated segments) -> float32 [n,21,7], gathered on the device: what
+        train.getDataFromFile_new returns for those windows of the segments' files."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        x = np.empty((len(ids), 21, 7), np.float32)
+        _lib.check(self._lib.dm_xyset_gather(self._h, ids.ctypes.data, len(ids), x.ctypes.data))
+        return x
 
     def classify(self, model, segment: int, n: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Segment `segment` through model -> (probability of class 1 float32 [n], class u8 [n], label u8 [n]), as XYLoader.classify gives them

@@ -652,6 +652,21 @@ int64_t dm_xyset_segments(dm_xyset* s, int64_t* rows, int64_t* windows, int64_t 
 int dm_xyset_classify(dm_xyset* s, dm_model* m, int64_t segment, float* prob1, uint8_t* cls, uint8_t* label);
 int64_t dm_xyset_bytes(dm_xyset* s);
 
+/* TRAINING FROM THE SET (`train --resident 1`): the training files are segments of a set as well, and a step names its windows by id.  A window's
+ * id is its index over the concatenated segments: segment s holds the ids [sum of the windows before s, + its own n), in its centres' order.
+ *   dm_xyset_gather      x [n][21][7] (host or device, detected) receives the windows of ids int64 [n] (host or device): the 147 contiguous
+ *                        floats feats[(centre - 10) * 7 .. (centre + 11) * 7) of each - what getDataFromFile_new's table[:, 3:][index] holds.
+ *                        One kernel on the set's stream resolves every id by a binary search over the segments' window prefix sums.
+ *   dm_trainer_step_set  dm_trainer_step whose x is gathered on the device into the trainer's input block: the host sends 8 B of id and 8 B of y
+ *   dm_trainer_grad_set  per window.  From the gather on it is dm_trainer_step / dm_trainer_grad's own code: same finite check, same kernels, same
+ *                        two host round trips (the id check comes back with the finite check's flag), results bit for bit.  ids and y: host arrays.
+ * An id outside [0, windows of the set) returns DM_EINVAL, dm_last_error names the first such id and its position; nothing is launched past
+ * the check and the trainer's state is unchanged.  A set on another device than the trainer, n > max_batch and null handles are refused likewise.
+ * The set must not be appended to while a call is running on it (one host thread drives both). */
+int dm_xyset_gather(dm_xyset* s, const int64_t* ids, int64_t n, float* x);
+int dm_trainer_step_set(dm_trainer* t, dm_xyset* s, const int64_t* ids, const float* y, int64_t n, int unbalanced, float* loss);
+int dm_trainer_grad_set(dm_trainer* t, dm_xyset* s, const int64_t* ids, const float* y, int64_t n, int unbalanced, float* loss, float* prob, float* grad);
+
 #ifdef __cplusplus
 }
 #endif
