@@ -26,6 +26,11 @@ alignment walk and gzip on --threads host threads (deepmod_amd/getfeatures.py). 
 selection and the classifier on one GPU, gunzip on --threads host threads; --test takes the value `train` was given and
 evaluates what `train` left out.  Writes <outFolder>/<FileID>_mpred.txt (the reference's tp / fp / fn / tn lines) and
 <FileID>_mpred.json (deepmod_amd/predict.py).
+
+`traincluster --predFile <prefix> --motifFolder <dir> --truth <bedMethyl[,..]> [--chr chr1[,..]] [--heldout chrN[,..]] [--cov 5]
+[--keep_prob 0.7] [--epochs 1] [--batchsize 4096] [--seed 0]` fits the CpG-cluster model of `detect --clusterCpG` /
+hm_cluster_predict.py on the sites that have bisulfite truth: the training graph the reference ships, on one GPU; row order,
+epochs, dropout stream and initial draw are this project's own, fixed by --seed (deepmod_amd/cluster_train.py).
 """
 import argparse
 import os
@@ -140,7 +145,32 @@ def build_parser():
     gf.add_argument('--anymod', type=str, help='file pattern of partially modified positions')
     gf.add_argument('--nomod', type=str, help='file pattern of unmodified positions')
     gf.set_defaults(func=mGetFeatures)
+    tcl = sub.add_parser('traincluster', parents=[com], help='fit the CpG-cluster model (detect --clusterCpG, hm_cluster_predict.py) on the GPU',
+                         description='Fit the second-stage MLP 14 -> 100 -> 20 -> 1 on the sites of a DeepMod BED that have bisulfite truth: the training graph the '
+                                     'reference ships (dropout, mean squared error, Adam) on one GPU.  The order of the rows, the number of epochs, the dropout random '
+                                     'stream and the draw of the initial values are this project\'s own, all fixed by --seed (the reference ships no training '
+                                     'script and TensorFlow\'s random stream cannot be reproduced).  Writes <outFolder>/Cg.cov<cov>.nb25-<epoch> (TF bundles with the '
+                                     'Adam slots, loadable by detect --clusterCpG and hm_cluster_predict.py) after every epoch and <outFolder>/<FileID>_cluster_train.json.')
+    tcl.add_argument('--predFile', default=None, help='prefix of the DeepMod BED files, as the first argument of hm_cluster_predict.py: <prefix>.<chr>.C.bed')
+    tcl.add_argument('--motifFolder', default=None, help='folder with motif_<chr>_C.bed (generate_motif_pos.py)')
+    tcl.add_argument('--truth', default=None, help='bisulfite bedMethyl file(s), separated by commas (11 columns; the first line is skipped)')
+    tcl.add_argument('--chr', default='chr1', help='contigs to train on, separated by commas (default chr1, as the shipped model)')
+    tcl.add_argument('--heldout', default='', help='contigs scored after every epoch at keep_prob 1 (MSE, Pearson r), never trained on')
+    tcl.add_argument('--cov', type=int, default=5, help='least coverage of a truth row (hm_cluster_predict.py:18)')
+    tcl.add_argument('--keep_prob', type=float, default=0.7, help='dropout keep probability in (0, 1] (the shipped model: 0.7)')
+    tcl.add_argument('--epochs', type=int, default=1, help='passes over the rows (the project\'s own choice; default 1)')
+    tcl.add_argument('--batchsize', type=int, default=4096, help='rows per step (hm_cluster_predict.py:16)')
+    tcl.add_argument('--seed', type=int, default=0, help='seeds the initial values, the order of the rows and the dropout masks: the same seed gives the same bytes')
+    tcl.set_defaults(func=mTrainCluster)
     return parser
+
+
+def mTrainCluster(args):
+    from deepmod_amd import cluster_train
+    mo = {k: getattr(args, k) for k in ('outLevel', 'FileID', 'outFolder', 'predFile', 'motifFolder', 'cov', 'keep_prob', 'epochs', 'batchsize', 'seed')}
+    for key in ('truth', 'chr', 'heldout'):
+        mo[key] = [c for c in (getattr(args, key) or '').split(',') if c]
+    cluster_train.train_cluster(mo)
 
 
 def getfeatures_options(args):

@@ -169,6 +169,16 @@ SIGNATURES = [
     ("dm_xyset_gather", _c.c_int, [_vp, _vp, _i64, _vp]),
     ("dm_trainer_step_set", _c.c_int, [_vp, _vp, _vp, _vp, _i64, _c.c_int, _c.POINTER(_c.c_float)]),
     ("dm_trainer_grad_set", _c.c_int, [_vp, _vp, _vp, _vp, _i64, _c.c_int, _c.POINTER(_c.c_float), _vp, _vp]),
+    ("dm_cluster_trainer_create", _vp, [_c.c_int, _vp, _c.c_size_t, _i64]),
+    ("dm_cluster_trainer_destroy", None, [_vp]),
+    ("dm_cluster_trainer_set_data", _c.c_int, [_vp, _vp, _vp, _i64]),
+    ("dm_cluster_trainer_grad", _c.c_int, [_vp, _vp, _vp, _i64, _c.c_float, _vp, _c.c_uint64, _i64, _c.POINTER(_c.c_float), _vp, _vp]),
+    ("dm_cluster_trainer_adam", _c.c_int, [_vp, _vp]),
+    ("dm_cluster_trainer_step", _c.c_int, [_vp, _vp, _i64, _c.c_float, _c.c_uint64]),
+    ("dm_cluster_trainer_losses", _c.c_int, [_vp, _i64, _i64, _vp]),
+    ("dm_cluster_trainer_mask", _c.c_int, [_vp, _c.c_uint64, _i64, _i64, _c.c_float, _vp]),
+    ("dm_cluster_trainer_get_state", _c.c_int, [_vp, _vp, _vp, _vp, _c.POINTER(_i64)]),
+    ("dm_cluster_trainer_set_state", _c.c_int, [_vp, _vp, _vp, _vp, _i64]),
 ]
 
 

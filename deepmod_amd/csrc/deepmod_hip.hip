@@ -1670,6 +1670,7 @@ int dm_summary_fetch_slice(dm_summary* s, int32_t* touch, int32_t* cov, int32_t*
 #include "bedtext.inc"
 #include "cluster_sites.hip.inc"
 #include "train.hip.inc"
+#include "cluster_train.hip.inc"
 #include "xyrows.inc"
 #include "xyrows.hip.inc"
 #include "xyparse.hip.inc"

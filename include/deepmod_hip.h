@@ -514,6 +514,45 @@ int dm_trainer_set_state(dm_trainer* t, const float* weights, const float* m, co
  * NULL), then switches the bracketing on or off and clears both (tools/train_rate.py).  No reference counterpart. */
 int dm_trainer_profile(dm_trainer* t, int on, double* step_ms, int64_t* steps);
 
+/* ------------------------------------------------------- training the CpG-cluster model -- */
+/*
+ * The training graph the reference ships with its cluster checkpoint (train_deepmod/na12878_cluster_train_mod-keep_prob0.7-nb25-chr1/
+ * Cg.cov5.nb25.meta): the MLP of dm_cluster_predict with TF1 dropout behind both hidden layers (a / keep_prob * floor(keep_prob + U[0,1))),
+ * loss = mean((output - y)^2) over the n rows, AdamOptimizer (lr 1e-3, beta1 0.9, beta2 0.999, eps 1e-8).  fp32 throughout, no float atomics: two
+ * runs are bit-identical.  The dropout mask is this library's own counter-based generator keyed by (seed, step, row in batch, unit 0..119; units
+ * 0..99 = layer 1, 100..119 = layer 2), defined by deepmod_amd/cluster_train.py:dropout_keep; TensorFlow's stream cannot be reproduced.
+ *   weights, grad, m, v   the DM_CLUSTER_WEIGHT_FLOATS layout of dm_cluster_create; a dm_cluster can be created from get_state's weights as they are
+ *   all pointers          host memory
+ *   max_batch             in [1, 65536]; n > max_batch is refused (DM_EINVAL), nothing grows
+ *   _set_data             x [n_rows][14], y [n_rows]: one resident copy on the device, replacing the last
+ *   _grad                 host rows x [n][14], y [n]; keep: uint8 [n][120] of 0 / 1, or NULL: the mask generated for (seed, step).  loss, out [n]
+ *                         and the gradient blob (each may be NULL); the state does not change
+ *   _adam                 one Adam step from a caller-supplied gradient blob
+ *   _step                 rows ids [n] (int64, each in [0, n_rows), repeats allowed) of the resident data, the mask generated for (seed, the handle's
+ *                         step count t), grad + adam: exactly the state of _grad on those rows with that mask followed by _adam.  Three kernel
+ *                         launches, nothing is downloaded and the host does not wait; the step's loss is recorded on the device
+ *   _losses               the recorded losses of steps [first_step, first_step + count) - step numbers are values of t before the step; the record
+ *                         starts at creation and again behind every _set_state and _adam.  Waits for those steps
+ *   _mask                 the generated mask uint8 [n][120] (n <= max_batch)
+ *   _get_state / _set_state   weights, Adam slots m and v (any may be NULL) and the step count t
+ * n == 0 is a no-op.  NaN / Inf in x or y, keep_prob outside (0, 1], an id outside the data, _step before _set_data, or a non-finite loss in _grad
+ * return DM_EINVAL with dm_last_error set and leave the state unchanged.  The loss of a _step is looked at only in _losses: it returns DM_EINVAL for
+ * a non-finite one (the values are still written), and by then that step and every later one HAVE been applied - the weights are no longer
+ * usable; keep a _get_state copy from before (cluster_train.py keeps the last epoch's) to go back to.
+ */
+typedef struct dm_cluster_trainer dm_cluster_trainer;
+dm_cluster_trainer* dm_cluster_trainer_create(int device, const float* weights, size_t n_floats, int64_t max_batch);
+void dm_cluster_trainer_destroy(dm_cluster_trainer* t);
+int dm_cluster_trainer_set_data(dm_cluster_trainer* t, const float* x, const float* y, int64_t n_rows);
+int dm_cluster_trainer_grad(dm_cluster_trainer* t, const float* x, const float* y, int64_t n, float keep_prob, const uint8_t* keep, uint64_t seed,
+                            int64_t step, float* loss, float* out, float* grad);
+int dm_cluster_trainer_adam(dm_cluster_trainer* t, const float* grad);
+int dm_cluster_trainer_step(dm_cluster_trainer* t, const int64_t* ids, int64_t n, float keep_prob, uint64_t seed);
+int dm_cluster_trainer_losses(dm_cluster_trainer* t, int64_t first_step, int64_t count, float* losses);
+int dm_cluster_trainer_mask(dm_cluster_trainer* t, uint64_t seed, int64_t step, int64_t n, float keep_prob, uint8_t* keep);
+int dm_cluster_trainer_get_state(dm_cluster_trainer* t, float* weights, float* m, float* v, int64_t* step);
+int dm_cluster_trainer_set_state(dm_cluster_trainer* t, const float* weights, const float* m, const float* v, int64_t step);
+
 /* ---------------------------------------------------------------------- getfeatures -- */
 /*
  * The reference's third sub-command (bin/DeepMod_scripts/myGetFeatureBasedPos.py): raw reads + a reference + known positions -> the labelled
