@@ -204,6 +204,7 @@ struct dm_model {
     int64_t plogit_tiles = 0;
     float bout[2] = {0, 0};
     int grid_cap = 0;
+    int last_grid = 0;                    // DM_INFO_LAST_GRID: workgroups of the last classifier launch (launch_bilstm)
     std::vector<float> host_weights;      // canonical blob, kept for lazy packing of other precisions
     // staging for host-pointer callers
     static constexpr int64_t STAGE_WINDOWS = 65536;
@@ -393,6 +394,7 @@ int launch_bilstm(dm_model* m, const float* d_x, long long xstride, int64_t n, f
         const int rounds = (2 * ntiles + m->grid_cap - 1) / m->grid_cap;
         grid = (2 * ntiles + rounds - 1) / rounds;
     }
+    m->last_grid = grid;
     if (m->precision == DM_PREC_F16X3 || m->precision == DM_PREC_F16I8 || m->precision == DM_PREC_F16X3_ROLES) {
         const bool i8 = m->precision == DM_PREC_F16I8;
         const bool q16 = m->precision == DM_PREC_F16X3 && m->f16_q;
@@ -995,6 +997,8 @@ int dm_model_get_info(dm_model* m, int key, int64_t* value) {
         case DM_INFO_F16_REPRESENTABLE: *value = m->f16_ok ? 1 : 0; return DM_OK;
         case DM_INFO_F16_LENGTH_SHIFT: *value = m->len_shift; return DM_OK;
         case DM_INFO_DEVICE: *value = m->device; return DM_OK;
+        case DM_INFO_GRID_CAP: *value = m->grid_cap; return DM_OK;
+        case DM_INFO_LAST_GRID: *value = m->last_grid; return DM_OK;
         case DM_INFO_HAS_F16S:
 #ifdef DM_WITH_F16S
             *value = 1;

@@ -194,6 +194,11 @@ class BiLSTMModel:
         _lib.check(self._lib.dm_model_get_info(self._h, key, ctypes.byref(v)))
         return v.value
 
+    def launch_geometry(self) -> Tuple[int, int]:
+        """(grid cap in effect: CUs - DM_OPT_RESERVED_CUS, workgroups of the last classifier launch).  Workgroup b of a grid g runs the work
+        items b, b + g, ... below 2 * ceil(n / 128); item w is tile w // 2 in direction w % 2 (0 forward, 1 backward)."""
+        return self.get_info(_lib.DM_INFO_GRID_CAP), self.get_info(_lib.DM_INFO_LAST_GRID)
+
     def upload_async(self, dst_ptr: int, arr: np.ndarray):
         """Host array -> device address, queued on the model's stream (keep `arr` alive until the next sync())."""
         _lib.check(self._lib.dm_model_h2d_async(self._h, dst_ptr, arr.ctypes.data, arr.nbytes))

@@ -107,6 +107,10 @@ extern "C" {
 #define DM_INFO_DEVICE 4
 #define DM_INFO_HAS_F16X3_ROLES 5    /* 1 if the library was built with the wave-pair experiment kernel */
 #define DM_INFO_HAS_F16S 6           /* 1 if the library was built with the 32x32x16 kernels of rounds 2-3 (experiment builds: DM_WITH_F16S=1) */
+#define DM_INFO_GRID_CAP 7           /* most workgroups a classifier launch may use: the device's CUs minus DM_OPT_RESERVED_CUS */
+#define DM_INFO_LAST_GRID 8          /* workgroups of the last classifier launch of this model (0 before the first).  A workgroup b of a grid g
+                                        over T = ceil(n / 128) tiles runs the work items b, b + g, b + 2 g, ... < 2 T; item w is tile w / 2 in
+                                        direction w % 2 (0 forward, 1 backward).  Read-only: what the tests derive items per workgroup from. */
 
 typedef struct dm_model dm_model;
 typedef struct dm_summary dm_summary;

@@ -21,6 +21,9 @@ Three figures per case, over ALL windows (no class is compared, so nothing is ex
     err   = max |recover_z(prob_kernel) - z_64|
 
 and the assertion of tests/test_gpu_hidden_parity.py is err <= R * yard + 2 * floor.
+
+A call that repeats K distinct windows n times over (tests/test_gpu_work_items.py: enough tiles for every workgroup to run three or four work
+items) is reported through Reference.view(index): the oracles cost K windows, and yard and floor are those of the windows the call uses.
 """
 from __future__ import annotations
 
@@ -136,20 +139,70 @@ class Reference:
         """The C oracle's probabilities under the probe head, from its own hcat (c_head_prob): the C oracle is not run again for every head."""
         return c_head_prob(self.h32f, head)
 
-    def _cached(self, what: str, head: np.ndarray, compute) -> float:
+    def _cached(self, what: str, head: np.ndarray, compute):
         key = (what, np.ascontiguousarray(head, np.float32).tobytes())
         if key not in self._figures:
             self._figures[key] = compute()
         return self._figures[key]
 
+    def yards(self, head: np.ndarray) -> np.ndarray:
+        """|z_c32 - z_64| per window."""
+        return self._cached("yards", head, lambda: np.abs(self.z32(head) - self.z64(head)))
+
+    def floors(self, head: np.ndarray) -> np.ndarray:
+        """|recover_z(prob_c32) - z_c32| per window."""
+        return self._cached("floors", head, lambda: np.abs(recover_z(self.prob_c32(head)) - self.z32(head)))
+
     def yard(self, head: np.ndarray) -> float:
-        return self._cached("yard", head, lambda: float(np.abs(self.z32(head) - self.z64(head)).max()))
+        return self._cached("yard", head, lambda: float(self.yards(head).max()))
 
     def floor(self, head: np.ndarray) -> float:
-        return self._cached("floor", head, lambda: float(np.abs(recover_z(self.prob_c32(head)) - self.z32(head)).max()))
+        return self._cached("floor", head, lambda: float(self.floors(head).max()))
 
     def err(self, prob: np.ndarray, head: np.ndarray) -> np.ndarray:
         """|recover_z(prob) - z_64| per window."""
+        return np.abs(recover_z(prob) - self.z64(head))
+
+    def view(self, index: np.ndarray) -> "IndexedReference":
+        return IndexedReference(self, index)
+
+
+class IndexedReference:
+    """A Reference over K distinct windows seen through an index map [n] -> [0, K): what report() needs for a kernel call whose window i is
+    window index[i] of the Reference.  A window's arithmetic does not depend on where in a call it sits, so a call of n windows that repeats
+    K distinct ones costs the CPU oracles K windows; yard and floor are taken over the distinct windows the call USES, so windows of the
+    Reference that the call leaves out lend it no allowance.  view(arange(K)) reports what the Reference itself reports."""
+
+    def __init__(self, ref: Reference, index: np.ndarray):
+        index = np.ascontiguousarray(index, np.int64)
+        k = ref.x.shape[0]
+        assert index.ndim == 1 and index.size > 0 and int(index.min()) >= 0 and int(index.max()) < k, (index.shape, k)
+        self.ref, self.index, self.used = ref, index, np.unique(index)
+        self.w = ref.w
+
+    @property
+    def x(self) -> np.ndarray:
+        """The call's windows, materialised: float32 [n, 21, 7]."""
+        return np.ascontiguousarray(self.ref.x[self.index])
+
+    def z64(self, head: np.ndarray) -> np.ndarray:
+        return self.ref.z64(head)[self.index]
+
+    def z32(self, head: np.ndarray) -> np.ndarray:
+        return self.ref.z32(head)[self.index]
+
+    def prob_c32(self, head: np.ndarray) -> np.ndarray:
+        return self.ref.prob_c32(head)[self.index]
+
+    def yard(self, head: np.ndarray) -> float:
+        return float(self.ref.yards(head)[self.used].max())
+
+    def floor(self, head: np.ndarray) -> float:
+        return float(self.ref.floors(head)[self.used].max())
+
+    def err(self, prob: np.ndarray, head: np.ndarray) -> np.ndarray:
+        prob = np.asarray(prob)
+        assert prob.shape == (self.index.size, 2), (prob.shape, self.index.size)
         return np.abs(recover_z(prob) - self.z64(head))
 
 
@@ -159,8 +212,9 @@ def reference_z(w: Dict[str, np.ndarray], x: np.ndarray, head: np.ndarray):
     return ref.z64(head), ref.z32(head)
 
 
-def report(ref: Reference, prob: np.ndarray, head: np.ndarray) -> Dict[str, float]:
-    """yard, floor and err of one case; ratio = (err - 2 floor) / yard is what the allowance R is measured as."""
+def report(ref, prob: np.ndarray, head: np.ndarray) -> Dict[str, float]:
+    """yard, floor and err of one case; ratio = (err - 2 floor) / yard is what the allowance R is measured as.  ref: a Reference, or an
+    IndexedReference (Reference.view(index)) for a kernel output of n windows that are windows index[0..n) of the Reference."""
     yard, floor = ref.yard(head), ref.floor(head)
     e = ref.err(prob, head)
     worst = int(np.argmax(e)) if len(e) else -1

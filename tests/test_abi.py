@@ -43,7 +43,8 @@ def test_header_constants_equal_the_bindings():
     drifts between the two would select another kernel or misread an error without any symbol going missing)."""
     text = open(os.path.join(ROOT, "include", "deepmod_hip.h")).read()
     defines = {n: int(v) for n, v in re.findall(r"^#define\s+(DM_(?:OPT|PREC|INFO|OK|E[A-Z]+|MAP|ROWS)[A-Z0-9_]*)\s+\(?(-?\d+)\)?", text, flags=re.M)}
-    assert {"DM_OPT_PRECISION", "DM_OPT_F16X3_SHAPE", "DM_PREC_F16X3", "DM_PREC_F16I8", "DM_PREC_F16X3_ROLES", "DM_INFO_HAS_F16X3_ROLES", "DM_ERANGE"} <= set(defines)
+    assert {"DM_OPT_PRECISION", "DM_OPT_F16X3_SHAPE", "DM_PREC_F16X3", "DM_PREC_F16I8", "DM_PREC_F16X3_ROLES", "DM_INFO_HAS_F16X3_ROLES", "DM_INFO_GRID_CAP", "DM_INFO_LAST_GRID", "DM_ERANGE"} <= set(defines)
+    assert all(hasattr(_lib, n) for n in defines if n.startswith("DM_INFO_")), [n for n in defines if n.startswith("DM_INFO_") and not hasattr(_lib, n)]
     checked = 0
     for name, value in defines.items():
         if hasattr(_lib, name):
