@@ -31,6 +31,12 @@ evaluates what `train` left out.  Writes <outFolder>/<FileID>_mpred.txt (the ref
 [--keep_prob 0.7] [--epochs 1] [--batchsize 4096] [--seed 0]` fits the CpG-cluster model of `detect --clusterCpG` /
 hm_cluster_predict.py on the sites that have bisulfite truth: the training graph the reference ships, on one GPU; row order,
 epochs, dropout stream and initial draw are this project's own, fixed by --seed (deepmod_amd/cluster_train.py).
+
+`siteperf --predFolder RUN --control C1[,C2..] --Ref genome.fa --motif Cg --ModinMotif 0 [--chr NAME] [--start S --end E] [--cov 1,5]
+--outFolder O --FileID id` is DeepMod_tools/cal_EcoliDetPerf.py: per-site ROC AUC and average precision of a modified run against control
+runs, for every site category and for motif sites only, at each coverage threshold.  The BED lines are parsed, classified and counted on one
+GPU into integer histograms; the numbers are exact functions of those (deepmod_amd/siteperf.py).  Writes <O>/<id>_siteperf.txt (the
+reference's lines) and <O>/<id>_siteperf.json (the curves); no plots.
 """
 import argparse
 import os
@@ -162,7 +168,43 @@ def build_parser():
     tcl.add_argument('--batchsize', type=int, default=4096, help='rows per step (hm_cluster_predict.py:16)')
     tcl.add_argument('--seed', type=int, default=0, help='seeds the initial values, the order of the rows and the dropout masks: the same seed gives the same bytes')
     tcl.set_defaults(func=mTrainCluster)
+    spf = sub.add_parser('siteperf', parents=[com], help='site-level ROC / PR of a run against control runs (cal_EcoliDetPerf.py) on the GPU',
+                         description='Per-site ROC AUC and average precision of the methylation percentage of a modified run against control runs, as '
+                                     'DeepMod_tools/cal_EcoliDetPerf.py prints them: for all seven site categories and for motif sites only, at every coverage '
+                                     'threshold.  Writes <outFolder>/<FileID>_siteperf.txt (the reference\'s lines; the PNG names are labels, nothing is drawn) and '
+                                     '<outFolder>/<FileID>_siteperf.json (counts, curves, histograms).')
+    spf.add_argument('--predFolder', default=None, help='folder of the modified run: mod_pos.*.<B>.bed in it, one or two levels below')
+    spf.add_argument('--control', default=None, help='folder(s) of the control runs, separated by commas; their coverage is summed per site')
+    spf.add_argument('--Ref', help='reference genome FASTA')
+    spf.add_argument('--motif', default='Cg', help='motif, as the reference types it (default Cg)')
+    spf.add_argument('--ModinMotif', type=int, default=0, help='offset of the modified base in the motif; the base there names the files and must be upper case')
+    spf.add_argument('--chr', default=None, help='evaluate this contig only (default: every contig of the FASTA)')
+    spf.add_argument('--start', type=int, default=None, help='first position of the region (inclusive; needs --chr)')
+    spf.add_argument('--end', type=int, default=None, help='last position of the region (inclusive; needs --chr)')
+    spf.add_argument('--cov', default='1,5', help='coverage thresholds, ascending, at most 8 (default 1,5)')
+    spf.set_defaults(func=mSitePerf)
     return parser
+
+
+def mSitePerf(args):
+    from deepmod_amd import siteperf
+    try:
+        cov = tuple(int(v) for v in args.cov.split(',') if v.strip() != '')
+    except ValueError:
+        raise SystemExit('Error: siteperf: --cov takes integers separated by commas (got %r)' % args.cov)
+    mo = {k: getattr(args, k) for k in ('predFolder', 'Ref', 'motif', 'ModinMotif', 'chr', 'start', 'end', 'outFolder', 'FileID', 'threads')}
+    mo['control'] = [c for c in (args.control or '').split(',') if c]
+    mo['cov'] = cov
+    if not mo['predFolder'] or not mo['control']:
+        raise SystemExit('Error: siteperf: --predFolder and --control are needed')
+    try:
+        siteperf.check_options(mo)
+        from deepmod_amd import _lib
+        if _lib.load().dm_device_count() < 1:
+            raise SystemExit('Error: no gfx950 GPU visible (this build has no CPU path)')
+        siteperf.siteperf(mo)
+    except siteperf.SitePerfError as exc:
+        raise SystemExit('Error: %s' % exc)
 
 
 def mTrainCluster(args):

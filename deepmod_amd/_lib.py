@@ -181,6 +181,18 @@ SIGNATURES = [
     ("dm_cluster_trainer_mask", _c.c_int, [_vp, _c.c_uint64, _i64, _i64, _c.c_float, _vp]),
     ("dm_cluster_trainer_get_state", _c.c_int, [_vp, _vp, _vp, _vp, _c.POINTER(_i64)]),
     ("dm_cluster_trainer_set_state", _c.c_int, [_vp, _vp, _vp, _vp, _i64]),
+    ("dm_siteperf_create", _vp, [_c.c_int, _c.c_int, _vp]),
+    ("dm_siteperf_destroy", None, [_vp]),
+    ("dm_siteperf_set_contig", _c.c_int, [_vp, _vp, _i64, _c.c_char_p, _c.c_int, _c.c_int, _i64, _i64]),
+    ("dm_siteperf_fetch_codes", _c.c_int, [_vp, _vp]),
+    ("dm_siteperf_add_text", _c.c_int, [_vp, _vp, _i64, _c.c_int, _c.c_char_p, _c.POINTER(_i64), _c.POINTER(_c.c_int32), _c.POINTER(_i64)]),
+    ("dm_siteperf_add_records", _c.c_int, [_vp, _c.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("dm_siteperf_fetch_records", _c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("dm_siteperf_finish_contig", _c.c_int, [_vp]),
+    ("dm_siteperf_fetch", _c.c_int, [_vp, _vp, _vp, _c.POINTER(_i64), _c.POINTER(_i64), _c.POINTER(_i64)]),
+    ("dm_siteperf_parse_host", _i64, [_vp, _i64, _c.c_char_p, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _c.POINTER(_c.c_int32), _c.POINTER(_i64)]),
+    ("dm_siteperf_tile_bytes", _c.c_int, []),
+    ("dm_siteperf_times", _c.c_int, [_vp, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
 ]
 
 

@@ -1679,3 +1679,4 @@ int dm_summary_fetch_slice(dm_summary* s, int32_t* touch, int32_t* cov, int32_t*
 #include "xyrows.hip.inc"
 #include "xyparse.hip.inc"
 #include "xygather.hip.inc"
+#include "siteperf.hip.inc"

@@ -1,0 +1,675 @@
+// siteperf.hip.inc — `siteperf`, device part (included by deepmod_hip.hip after xyparse.hip.inc): the BED lines of a run and of its control runs ->
+// the histograms every site-level curve of DeepMod_tools/cal_EcoliDetPerf.py is a function of.
+//   readFA (:31-74)                        sp_code_kernel   one byte per position: bit 0 = '+' site, bit 1 = '-' site, inside start..end only
+//   readmodf (:134-176)                    sp_count_kernel  a run line -> its category (:222), label (1 iff a site) and coverage bucket -> one count
+//   readmodf_dict (:76-104)                sp_scatter_kernel  a control line -> coverage and modified count summed per (position, strand)
+//   add_from_dict (:106-131)               sp_walk_kernel   every (position, strand) a control line named -> one label-0 entry, pct = (100 mod) / cov
+// deepmod_amd/siteperf.py (HostEngine) is the numpy twin of these kernels and the statement of the semantics.
+//
+// The text of a file is split as xyparse.hip.inc splits it (xl_count_kernel, the 64-bit scan, xl_lines_kernel: newline ballots over 16-byte
+// lanes), then sp_parse_kernel reads one line per lane.  Device grammar: at least 12 fields of printable bytes, exactly one ' ' or '\t' between
+// two fields, '\n' after the last (the host appends a missing last one); field 0 is the contig's name byte for byte; fields 1, 9, 10, 11 are
+// 1 - 10 digits with a value <= 2^31 - 1; the position lies on the contig, the percentage is <= 100, the modified count is <= the coverage;
+// field 3 is one byte; field 5 is '+' or '-'.  Any other line ('\r', an empty line, two separators, another contig, a sign ...) is marked: the
+// call reports the first of them and counts nothing, and the caller sends the file through its own parser and dm_siteperf_add_records.
+//
+// Exactness.  Everything counted is an integer: the histogram hist[category 7][label 2][bucket][percentage 101] (bucket = thresholds <=
+// coverage, minus one; below the smallest threshold: no count), the read-level sums tp / fp / tn / fn and the line counters.  A block counts
+// into a private LDS histogram of 32-bit counters (a block sees fewer than 2^32 records) and adds its non-zero bins to the global 64-bit
+// counters once; the sums are reduced per wave and added with one 64-bit atomic per wave.  Integer additions commute and associate, so the
+// result does not depend on the order the atomics land in: two runs give the same bytes, and they are the twin's.
+// The control tables take int32 atomic adds (the caller's contract: the per-file largest coverages of a contig sum to < 2^31, a site at most
+// once per file; the walk refuses a sum that is negative or whose modified count exceeds its coverage).  "The base of the first line seen"
+// (:100) needs an order that atomics do not give: every control line carries the key (file index << 40 | line index) << 8 | base, and a
+// 64-bit atomic min per (position, strand) keeps the smallest: the first line of the first file, whatever the schedule.
+
+namespace spk {
+
+constexpr int THREADS = 256;
+constexpr int MAX_MOTIF = 16;
+constexpr int MAX_THR = 8;
+constexpr int NCAT = 7;                             // M, M_n1B, M_n2B, M_n3B, OtherB, M_nb, Other (:222)
+constexpr int NPCT = 101;
+constexpr int MAX_BLOCKS = 1024;                    // grid of the record kernels: a block loops over its share and flushes once
+constexpr int MAX_NAME = 255;
+constexpr unsigned long long NO_KEY = ~0ull;
+enum { S_TP, S_FP, S_TN, S_FN, S_SKIPPED, S_MISMATCH, S_MAXCOV, S_BADSUM, N_STAT };
+
+struct Motif {
+    unsigned char pat[MAX_MOTIF], rc[MAX_MOTIF];    // the motif in upper case, its reverse complement
+    int m, k;
+    unsigned char B;                                // motif[k] as typed
+};
+struct Name {
+    char s[MAX_NAME + 1];
+    int n;
+};
+struct Thr {
+    int t[MAX_THR];                                 // ascending
+    int n;
+};
+struct Recs {                                       // one BED line each
+    const int *pos, *cov, *pct, *mod;
+    const unsigned char *strand, *base;             // strand 0 '+', 1 '-'
+};
+struct Rec {
+    int pos, cov, pct, mod;
+    unsigned char strand, base;
+};
+
+__host__ __device__ inline unsigned char complement(const unsigned char b) {       // na4com (:29); anything else equals no base
+    return b == 'A' ? 'T' : b == 'T' ? 'A' : b == 'C' ? 'G' : b == 'G' ? 'C' : 0;
+}
+
+// One line p[0 .. n) (without its '\n') -> its record; false: outside the grammar (r is then unspecified).
+__host__ __device__ inline bool parse_line(const char* __restrict__ p, const long long n, const Name& name, const long long contig_len, Rec& r) {
+    long long i = 0;
+    int f = 0;
+    long long num[4] = {0, 0, 0, 0};                // fields 1, 9, 10, 11
+    for (;;) {
+        const long long b = i;
+        for (; i < n; ++i) {
+            const unsigned char c = (unsigned char)p[i];
+            if (c == ' ' || c == '\t') break;
+            if (c < 0x21 || c > 0x7e) return false;
+        }
+        const long long len = i - b;
+        if (len == 0) return false;                 // an empty line, two separators in a row, a separator at either end
+        if (f == 0) {
+            if (len != name.n) return false;
+            for (int j = 0; j < name.n; ++j)
+                if (p[b + j] != name.s[j]) return false;
+        } else if (f == 1 || (f >= 9 && f <= 11)) {
+            if (len > 10) return false;
+            long long v = 0;
+            for (long long j = b; j < i; ++j) {
+                if (p[j] < '0' || p[j] > '9') return false;
+                v = v * 10 + (p[j] - '0');
+            }
+            if (v > 0x7fffffffLL) return false;
+            num[f == 1 ? 0 : f - 8] = v;
+        } else if (f == 3) {
+            if (len != 1) return false;
+            r.base = (unsigned char)p[b];
+        } else if (f == 5) {
+            if (len != 1 || (p[b] != '+' && p[b] != '-')) return false;
+            r.strand = p[b] == '-' ? 1 : 0;
+        }
+        if (f < 12) ++f;
+        if (i == n) break;
+        ++i;
+    }
+    if (f < 12) return false;
+    if (num[0] >= contig_len || num[2] > 100 || num[3] > num[1]) return false;
+    r.pos = int(num[0]);
+    r.cov = int(num[1]);
+    r.pct = int(num[2]);
+    r.mod = int(num[3]);
+    return true;
+}
+
+__device__ inline bool matches(const unsigned char* __restrict__ seq, const long long len, const long long first, const unsigned char* pat, const int m) {
+    if (first < 0 || first + m > len) return false;
+    for (int j = 0; j < m; ++j)
+        if (seq[first + j] != pat[j]) return false;                  // case-sensitive on the FASTA bytes, as the reference
+    return true;
+}
+
+__global__ __launch_bounds__(THREADS) void sp_code_kernel(const unsigned char* __restrict__ seq, const long long len, const Motif mo, const long long lo, const long long hi,
+                                                         unsigned char* __restrict__ code) {
+    const long long i = (long long)blockIdx.x * THREADS + threadIdx.x;
+    if (i >= len) return;
+    unsigned char c = 0;
+    if (i >= lo && i <= hi) {
+        if (matches(seq, len, i - mo.k, mo.pat, mo.m)) c |= 1;
+        if (matches(seq, len, i - (mo.m - 1 - mo.k), mo.rc, mo.m)) c |= 2;
+    }
+    code[i] = c;
+}
+
+__global__ __launch_bounds__(THREADS) void sp_parse_kernel(const char* __restrict__ text, const long long* __restrict__ start, const long long n_rows, const Name name,
+                                                          const long long contig_len, int* __restrict__ pos, int* __restrict__ cov, int* __restrict__ pct,
+                                                          int* __restrict__ mod, unsigned char* __restrict__ strand, unsigned char* __restrict__ base,
+                                                          unsigned char* __restrict__ status) {
+    const long long r = (long long)blockIdx.x * THREADS + threadIdx.x;
+    if (r >= n_rows) return;
+    const long long b = start[r], e = start[r + 1] - 1;              // text[e] is the line's '\n'
+    Rec v = {0, 0, 0, 0, 0, 0};
+    const bool ok = parse_line(text + b, e - b, name, contig_len, v);
+    pos[r] = ok ? v.pos : 0;
+    cov[r] = ok ? v.cov : 0;
+    pct[r] = ok ? v.pct : 0;
+    mod[r] = ok ? v.mod : 0;
+    strand[r] = ok ? v.strand : 0;
+    base[r] = ok ? v.base : 0;
+    status[r] = ok ? 0 : 1;
+}
+
+// the category of (strand s, position pos, line base equal to B or not); code holds len bytes, 0 <= pos < len
+__device__ inline int category(const unsigned char* __restrict__ code, const long long len, const long long pos, const int s, const bool is_b) {
+    const unsigned bit = 1u << s;
+    if (code[pos] & bit) return 0;
+    int near = 0;
+    const int offs[6] = {-3, -2, -1, 1, 2, 3};                       // range(-3, 4) of :119: the first offset with a site decides
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        const long long q = pos + offs[j];
+        if (near == 0 && q >= 0 && q < len && (code[q] & bit)) near = offs[j] < 0 ? -offs[j] : offs[j];
+    }
+    if (is_b) return near ? near : 4;
+    return near ? 5 : 6;
+}
+
+__device__ inline int bucket_of(const Thr& thr, const int cov) {
+    int b = 0;
+#pragma unroll
+    for (int j = 0; j < MAX_THR; ++j) b += (j < thr.n && thr.t[j] <= cov) ? 1 : 0;
+    return b;
+}
+
+// every lane of the wave calls it; one 64-bit atomic per wave with something to add
+__device__ inline void wave_add(unsigned long long* dst, long long v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
+    if ((threadIdx.x & 63) == 0 && v != 0) atomicAdd(dst, (unsigned long long)v);
+}
+
+__device__ inline void zero_bins(unsigned* lh, const int bins) {
+    for (int j = threadIdx.x; j < bins; j += THREADS) lh[j] = 0;
+    __syncthreads();
+}
+
+// lh [NCAT][nt][NPCT] of the block -> hist [NCAT][2][nt][NPCT]; label_m: the label of the entries of category 0 (every other entry has label 0)
+__device__ inline void flush_bins(const unsigned* lh, const int nt, const int label_m, unsigned long long* __restrict__ hist) {
+    __syncthreads();
+    const int per_cat = nt * NPCT;
+    for (int j = threadIdx.x; j < NCAT * per_cat; j += THREADS) {
+        const unsigned v = lh[j];
+        if (!v) continue;
+        const int cat = j / per_cat, rem = j - cat * per_cat;
+        atomicAdd(&hist[(long long)(cat * 2 + (cat == 0 ? label_m : 0)) * per_cat + rem], (unsigned long long)v);
+    }
+}
+
+__global__ __launch_bounds__(THREADS) void sp_count_kernel(const Recs r, const long long n, const unsigned char* __restrict__ code, const unsigned char* __restrict__ seq,
+                                                          const long long len, const long long lo, const long long hi, const unsigned char B, const Thr thr,
+                                                          unsigned long long* __restrict__ hist, unsigned long long* __restrict__ stat) {
+    __shared__ unsigned lh[NCAT * MAX_THR * NPCT];
+    zero_bins(lh, NCAT * thr.n * NPCT);
+    long long tp = 0, fp = 0, tn = 0, fn = 0, skipped = 0, mism = 0;
+    for (long long i = (long long)blockIdx.x * THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * THREADS) {
+        const long long pos = r.pos[i];
+        if (pos < lo || pos > hi) {
+            ++skipped;
+            continue;
+        }
+        const int s = r.strand[i] & 1;
+        const unsigned char base = r.base[i];
+        const unsigned char refb = s ? complement(seq[pos]) : seq[pos];
+        if (base != B || base != refb) ++mism;                       // :153
+        const int cat = category(code, len, pos, s, base == B);
+        const int cv = r.cov[i], md = r.mod[i];
+        if (cat == 0) {
+            tp += md;
+            fn += cv - md;
+        } else {
+            fp += md;
+            tn += cv - md;
+        }
+        const int b = bucket_of(thr, cv);
+        if (b > 0) atomicAdd(&lh[(cat * thr.n + b - 1) * NPCT + r.pct[i]], 1u);
+    }
+    flush_bins(lh, thr.n, 1, hist);
+    wave_add(stat + S_TP, tp);
+    wave_add(stat + S_FP, fp);
+    wave_add(stat + S_TN, tn);
+    wave_add(stat + S_FN, fn);
+    wave_add(stat + S_SKIPPED, skipped);
+    wave_add(stat + S_MISMATCH, mism);
+}
+
+// tab [len][2 strands][cov | mod], key [len][2 strands]
+__global__ __launch_bounds__(THREADS) void sp_scatter_kernel(const Recs r, const long long n, const unsigned char* __restrict__ seq, const long long lo, const long long hi,
+                                                            const unsigned char B, const unsigned long long file_index, int* __restrict__ tab,
+                                                            unsigned long long* __restrict__ key, unsigned long long* __restrict__ stat) {
+    long long skipped = 0, mism = 0;
+    int cmax = 0;
+    for (long long i = (long long)blockIdx.x * THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * THREADS) {
+        const long long pos = r.pos[i];
+        if (pos < lo || pos > hi) {
+            ++skipped;
+            continue;
+        }
+        const int s = r.strand[i] & 1;
+        const unsigned char base = r.base[i];
+        const unsigned char refb = s ? complement(seq[pos]) : seq[pos];
+        if (base != B || base != refb) ++mism;                       // :96
+        const int cv = r.cov[i];
+        const long long e = pos * 2 + s;
+        atomicAdd(&tab[e * 2], cv);
+        atomicAdd(&tab[e * 2 + 1], r.mod[i]);
+        atomicMin(&key[e], (((file_index << 40) | (unsigned long long)i) << 8) | base);
+        cmax = max(cmax, cv);
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) cmax = max(cmax, __shfl_down(cmax, d, 64));
+    if ((threadIdx.x & 63) == 0 && cmax > 0) atomicMax(stat + S_MAXCOV, (unsigned long long)cmax);
+    wave_add(stat + S_SKIPPED, skipped);
+    wave_add(stat + S_MISMATCH, mism);
+}
+
+__global__ __launch_bounds__(THREADS) void sp_walk_kernel(const int* __restrict__ tab, const unsigned long long* __restrict__ key, const unsigned char* __restrict__ code,
+                                                         const long long len, const unsigned char B, const Thr thr, unsigned long long* __restrict__ hist,
+                                                         unsigned long long* __restrict__ stat) {
+    __shared__ unsigned lh[NCAT * MAX_THR * NPCT];
+    zero_bins(lh, NCAT * thr.n * NPCT);
+    long long fp = 0, tn = 0, bad = 0;
+    for (long long e = (long long)blockIdx.x * THREADS + threadIdx.x; e < 2 * len; e += (long long)gridDim.x * THREADS) {
+        const unsigned long long k = key[e];
+        if (k == NO_KEY) continue;
+        const int cv = tab[e * 2], md = tab[e * 2 + 1];
+        if (cv < 0 || md < 0 || md > cv) {
+            ++bad;
+            continue;
+        }
+        const int pct = cv > 0 ? int((100ll * md) / cv) : 0;         // int(mod * 100 / cov) of the sums (:104)
+        const int cat = category(code, len, e >> 1, int(e & 1), (unsigned char)(k & 0xffull) == B);
+        fp += md;
+        tn += cv - md;
+        const int b = bucket_of(thr, cv);
+        if (b > 0) atomicAdd(&lh[(cat * thr.n + b - 1) * NPCT + pct], 1u);
+    }
+    flush_bins(lh, thr.n, 0, hist);
+    wave_add(stat + S_FP, fp);
+    wave_add(stat + S_TN, tn);
+    wave_add(stat + S_BADSUM, bad);
+}
+
+}  // namespace spk
+
+struct dm_siteperf {
+    dm_xyrows* xy = nullptr;                            // stream, the scan and its block sums
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    enum { TEXT, COUNT, START, STATUS, OUT, POS, COV, PCT, MOD, STRAND, BASE, SEQ, CODE, TAB, KEY, HIST, STAT, N_BUF };
+    void* buf[N_BUF] = {};
+    size_t cap[N_BUF] = {};
+    spk::Thr thr = {};
+    spk::Motif motif = {};
+    int64_t len = -1, lo = 0, hi = -1;                  // the open contig (len < 0: none) and its region, clipped to the contig
+    int64_t n_records = 0;                              // records on the device, of the last add_text / add_records
+    int64_t control_files = 0, control_cov = 0;         // of the open contig: control calls so far, the sum of their largest coverages
+    int64_t lines_seen = 0;
+    double parse_ms = 0.0, count_ms = 0.0;
+};
+
+namespace spk {
+
+int ensure(dm_siteperf* h, int which, size_t bytes) {
+    if (h->cap[which] >= bytes && h->buf[which]) return DM_OK;
+    if (h->buf[which]) (void)hipFree(h->buf[which]);
+    h->buf[which] = nullptr;
+    h->cap[which] = 0;
+    const size_t want = bytes + (bytes >> 2) + 256;                  // grow-only, a quarter ahead
+    if (hipMalloc(&h->buf[which], want) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(DM_ENOMEM, "dm_siteperf: hipMalloc(%zu) failed", want);
+    }
+    h->cap[which] = want;
+    return DM_OK;
+}
+
+template <class T>
+T* ptr(dm_siteperf* h, int which) { return static_cast<T*>(h->buf[which]); }
+
+constexpr int64_t MAX_BYTES = int64_t(1) << 40;
+constexpr int64_t MAX_RECORDS = 0x7fffffffLL;
+constexpr int64_t MAX_CONTROL_FILES = int64_t(1) << 16;              // the key holds 16 bits of file index, 40 of line index, 8 of base
+
+int record_buffers(dm_siteperf* h, int64_t n) {
+    using B = dm_siteperf;
+    int rc;
+    for (int which : {int(B::POS), int(B::COV), int(B::PCT), int(B::MOD)})
+        if ((rc = ensure(h, which, size_t(n) * 4)) != DM_OK) return rc;
+    for (int which : {int(B::STRAND), int(B::BASE), int(B::STATUS)})
+        if ((rc = ensure(h, which, size_t(n))) != DM_OK) return rc;
+    return DM_OK;
+}
+
+int add_time(dm_siteperf* h, int first, double& into) {
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, h->ev[first], h->ev[first + 1]));
+    into += double(ms);
+    return DM_OK;
+}
+
+// the n records on the device -> the histograms (run) or the control tables
+int count_records(dm_siteperf* h, int role, int64_t n) {
+    using B = dm_siteperf;
+    h->lines_seen += n;
+    if (n == 0) return DM_OK;
+    hipStream_t s = h->xy->stream;
+    const Recs r = {ptr<const int>(h, B::POS), ptr<const int>(h, B::COV), ptr<const int>(h, B::PCT), ptr<const int>(h, B::MOD),
+                    ptr<const unsigned char>(h, B::STRAND), ptr<const unsigned char>(h, B::BASE)};
+    const dim3 grid{unsigned(std::min<int64_t>((n + THREADS - 1) / THREADS, MAX_BLOCKS))}, block{THREADS};
+    unsigned long long* d_stat = ptr<unsigned long long>(h, B::STAT);
+    if (role == 1) {
+        if (h->control_files >= MAX_CONTROL_FILES) return fail(DM_EINVAL, "dm_siteperf: more than %lld control files of one contig", (long long)MAX_CONTROL_FILES);
+        HIP_TRY(hipMemsetAsync(d_stat + S_MAXCOV, 0, 8, s));
+    }
+    HIP_TRY(hipEventRecord(h->ev[2], s));
+    if (role == 0)
+        hipLaunchKernelGGL(sp_count_kernel, grid, block, 0, s, r, (long long)n, ptr<const unsigned char>(h, B::CODE), ptr<const unsigned char>(h, B::SEQ), (long long)h->len,
+                           (long long)h->lo, (long long)h->hi, h->motif.B, h->thr, ptr<unsigned long long>(h, B::HIST), d_stat);
+    else
+        hipLaunchKernelGGL(sp_scatter_kernel, grid, block, 0, s, r, (long long)n, ptr<const unsigned char>(h, B::SEQ), (long long)h->lo, (long long)h->hi, h->motif.B,
+                           (unsigned long long)h->control_files, ptr<int>(h, B::TAB), ptr<unsigned long long>(h, B::KEY), d_stat);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[3], s));
+    unsigned long long maxcov = 0;
+    if (role == 1) HIP_TRY(hipMemcpyAsync(&maxcov, d_stat + S_MAXCOV, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    int rc = add_time(h, 2, h->count_ms);
+    if (rc) return rc;
+    if (role == 1) {
+        ++h->control_files;
+        h->control_cov += int64_t(maxcov);
+        if (h->control_cov >= (int64_t(1) << 31))
+            return fail(DM_EINVAL, "dm_siteperf: the largest coverages of this contig's control files sum to %lld (2^31 or more): the int32 tables cannot hold them",
+                        (long long)h->control_cov);
+    }
+    return DM_OK;
+}
+
+}  // namespace spk
+
+extern "C" {
+
+int dm_siteperf_tile_bytes(void) { return xlk::TILE; }
+
+void dm_siteperf_destroy(dm_siteperf* h) {
+    if (!h) return;
+    if (h->xy) {
+        (void)hipSetDevice(h->xy->device);
+        (void)hipStreamSynchronize(h->xy->stream);
+    }
+    for (void* b : h->buf)
+        if (b) (void)hipFree(b);
+    for (hipEvent_t e : h->ev)
+        if (e) (void)hipEventDestroy(e);
+    dm_xy_destroy(h->xy);
+    delete h;
+}
+
+dm_siteperf* dm_siteperf_create(int device, int n_thresholds, const int32_t* thresholds) {
+    if (n_thresholds < 1 || n_thresholds > spk::MAX_THR || !thresholds) {
+        fail(DM_EINVAL, "dm_siteperf_create: %d thresholds (1 to %d)", n_thresholds, spk::MAX_THR);
+        return nullptr;
+    }
+    for (int j = 0; j < n_thresholds; ++j)
+        if (thresholds[j] < 0 || (j > 0 && thresholds[j] <= thresholds[j - 1])) {
+            fail(DM_EINVAL, "dm_siteperf_create: the thresholds are non-negative and strictly ascending (threshold %d is %d)", j, thresholds[j]);
+            return nullptr;
+        }
+    dm_xyrows* xy = dm_xy_create(device);
+    if (!xy) return nullptr;
+    dm_siteperf* h = new dm_siteperf;
+    h->xy = xy;
+    h->thr.n = n_thresholds;
+    for (int j = 0; j < n_thresholds; ++j) h->thr.t[j] = thresholds[j];
+    bool ok = true;
+    for (hipEvent_t& e : h->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+    const size_t hist_bytes = size_t(spk::NCAT) * 2 * n_thresholds * spk::NPCT * 8;
+    ok = ok && spk::ensure(h, dm_siteperf::HIST, hist_bytes) == DM_OK && spk::ensure(h, dm_siteperf::STAT, spk::N_STAT * 8) == DM_OK &&
+         spk::ensure(h, dm_siteperf::OUT, 16) == DM_OK;
+    ok = ok && hipMemsetAsync(h->buf[dm_siteperf::HIST], 0, hist_bytes, xy->stream) == hipSuccess &&
+         hipMemsetAsync(h->buf[dm_siteperf::STAT], 0, spk::N_STAT * 8, xy->stream) == hipSuccess && hipStreamSynchronize(xy->stream) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        fail(DM_EDEVICE, "dm_siteperf_create: events or counters on device %d", device);
+        dm_siteperf_destroy(h);
+        return nullptr;
+    }
+    return h;
+}
+
+int dm_siteperf_set_contig(dm_siteperf* h, const uint8_t* seq, int64_t len, const char* motif, int m, int k, int64_t start, int64_t end) {
+    using B = dm_siteperf;
+    if (!h) return fail(DM_EINVAL, "null handle");
+    h->len = -1;
+    if (len < 1 || len > 0x7fffffffLL || !seq) return fail(DM_EINVAL, "dm_siteperf_set_contig: a contig of %lld bases (1 to 2^31 - 1)", (long long)len);
+    if (!motif || m < 1 || m > spk::MAX_MOTIF || k < 0 || k >= m)
+        return fail(DM_EINVAL, "dm_siteperf_set_contig: motif of %d bases (1 to %d), modified offset %d", m, spk::MAX_MOTIF, k);
+    spk::Motif mo = {};
+    mo.m = m;
+    mo.k = k;
+    mo.B = (unsigned char)motif[k];
+    for (int j = 0; j < m; ++j) {
+        const unsigned char c = (unsigned char)motif[j];
+        mo.pat[j] = (c >= 'a' && c <= 'z') ? c - 32 : c;
+    }
+    for (int j = 0; j < m; ++j) {
+        mo.rc[j] = spk::complement(mo.pat[m - 1 - j]);
+        if (!mo.rc[j]) return fail(DM_EINVAL, "dm_siteperf_set_contig: motif base %d is none of A, C, G, T", m - 1 - j);
+    }
+    h->motif = mo;
+    h->lo = start < 0 ? 0 : start;                                    // a negative bound: none (the reference's -1)
+    h->hi = (end < 0 || end > len - 1) ? len - 1 : end;
+    HIP_TRY(hipSetDevice(h->xy->device));
+    int rc;
+    if ((rc = spk::ensure(h, B::SEQ, size_t(len))) || (rc = spk::ensure(h, B::CODE, size_t(len))) || (rc = spk::ensure(h, B::TAB, size_t(len) * 16)) ||
+        (rc = spk::ensure(h, B::KEY, size_t(len) * 16)))
+        return rc;
+    hipStream_t s = h->xy->stream;
+    HIP_TRY(hipMemcpyAsync(h->buf[B::SEQ], seq, size_t(len), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(h->buf[B::TAB], 0, size_t(len) * 16, s));
+    HIP_TRY(hipMemsetAsync(h->buf[B::KEY], 0xff, size_t(len) * 16, s));
+    hipLaunchKernelGGL(spk::sp_code_kernel, dim3(unsigned((len + spk::THREADS - 1) / spk::THREADS)), dim3(spk::THREADS), 0, s, spk::ptr<const unsigned char>(h, B::SEQ),
+                       (long long)len, mo, (long long)h->lo, (long long)h->hi, spk::ptr<unsigned char>(h, B::CODE));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    h->len = len;
+    h->n_records = 0;
+    h->control_files = h->control_cov = 0;
+    return DM_OK;
+}
+
+int dm_siteperf_fetch_codes(dm_siteperf* h, uint8_t* code) {
+    if (!h || !code) return fail(DM_EINVAL, "null argument");
+    if (h->len < 0) return fail(DM_ESTATE, "dm_siteperf_fetch_codes: no contig");
+    HIP_TRY(hipSetDevice(h->xy->device));
+    HIP_TRY(hipMemcpy(code, h->buf[dm_siteperf::CODE], size_t(h->len), hipMemcpyDeviceToHost));
+    return DM_OK;
+}
+
+int64_t dm_siteperf_parse_host(const char* text, int64_t n_bytes, const char* contig_name, int64_t contig_len, int32_t* pos, uint8_t* strand, uint8_t* base, int32_t* cov,
+                               int32_t* pct, int32_t* mod, int64_t cap, int32_t* flag, int64_t* first_bad_line) {
+    if (n_bytes < 0 || (n_bytes > 0 && !text) || !contig_name || cap < 0 || (cap > 0 && (!pos || !strand || !base || !cov || !pct || !mod)))
+        return fail(DM_EINVAL, "dm_siteperf_parse_host: null argument");
+    const size_t name_len = std::strlen(contig_name);
+    if (name_len < 1 || name_len > size_t(spk::MAX_NAME)) return fail(DM_EINVAL, "dm_siteperf_parse_host: a contig name of %zu bytes (1 to %d)", name_len, spk::MAX_NAME);
+    spk::Name name = {};
+    std::memcpy(name.s, contig_name, name_len);
+    name.n = int(name_len);
+    int64_t rows = 0, bad = 0;
+    for (int64_t b = 0; b < n_bytes;) {
+        const void* nl = std::memchr(text + b, '\n', size_t(n_bytes - b));
+        const int64_t e = nl ? static_cast<const char*>(nl) - text : n_bytes;          // a last line without '\n' ends with the text
+        spk::Rec v = {0, 0, 0, 0, 0, 0};
+        const bool ok = spk::parse_line(text + b, e - b, name, contig_len, v);
+        if (!ok && bad == 0) bad = rows + 1;
+        if (rows < cap) {
+            pos[rows] = ok ? v.pos : 0;
+            cov[rows] = ok ? v.cov : 0;
+            pct[rows] = ok ? v.pct : 0;
+            mod[rows] = ok ? v.mod : 0;
+            strand[rows] = ok ? v.strand : 0;
+            base[rows] = ok ? v.base : 0;
+        }
+        ++rows;
+        b = e + 1;
+    }
+    if (flag) *flag = bad != 0;
+    if (first_bad_line) *first_bad_line = bad ? bad : -1;
+    return rows;
+}
+
+int dm_siteperf_add_text(dm_siteperf* h, const char* text, int64_t n_bytes, int role, const char* contig_name, int64_t* n_lines, int32_t* flag, int64_t* first_bad_line) {
+    using B = dm_siteperf;
+    if (!h) return fail(DM_EINVAL, "null handle");
+    if (n_lines) *n_lines = 0;
+    if (flag) *flag = 0;
+    if (first_bad_line) *first_bad_line = -1;
+    if (h->len < 0) return fail(DM_ESTATE, "dm_siteperf_add_text: no contig");
+    if (role != 0 && role != 1) return fail(DM_EINVAL, "dm_siteperf_add_text: role %d (0 run, 1 control)", role);
+    if (n_bytes < 0 || n_bytes >= spk::MAX_BYTES || (n_bytes > 0 && !text)) return fail(DM_EINVAL, "dm_siteperf_add_text: %lld bytes of text", (long long)n_bytes);
+    const size_t name_len = contig_name ? std::strlen(contig_name) : 0;
+    if (name_len < 1 || name_len > size_t(spk::MAX_NAME)) return fail(DM_EINVAL, "dm_siteperf_add_text: a contig name of %zu bytes (1 to %d)", name_len, spk::MAX_NAME);
+    h->n_records = 0;
+    if (n_bytes == 0) return DM_OK;
+    spk::Name name = {};
+    std::memcpy(name.s, contig_name, name_len);
+    name.n = int(name_len);
+    HIP_TRY(hipSetDevice(h->xy->device));
+    const bool add_newline = text[n_bytes - 1] != '\n';
+    const int64_t n = n_bytes + (add_newline ? 1 : 0);
+    const int64_t tiles = (n + xlk::TILE - 1) / xlk::TILE;
+    int rc;
+    if ((rc = spk::ensure(h, B::TEXT, size_t(tiles) * xlk::TILE)) != DM_OK) return rc;     // whole 16-byte groups behind every lane offset below n
+    if ((rc = spk::ensure(h, B::COUNT, size_t(tiles + 1) * 8)) != DM_OK) return rc;
+    hipStream_t s = h->xy->stream;
+    char* d_text = spk::ptr<char>(h, B::TEXT);
+    long long* d_count = spk::ptr<long long>(h, B::COUNT);
+    static const char newline = '\n';
+    HIP_TRY(hipMemcpyAsync(d_text, text, size_t(n_bytes), hipMemcpyHostToDevice, s));
+    if (add_newline) HIP_TRY(hipMemcpyAsync(d_text + n_bytes, &newline, 1, hipMemcpyHostToDevice, s));
+    const dim3 tile_grid{unsigned(tiles)}, block{xlk::THREADS};
+    HIP_TRY(hipEventRecord(h->ev[0], s));
+    hipLaunchKernelGGL(xlk::xl_count_kernel, tile_grid, block, 0, s, d_text, (long long)n, d_count);
+    HIP_TRY(hipGetLastError());
+    if ((rc = xyk::scan_in_place(h->xy, d_count, tiles)) != DM_OK) return rc;
+    long long rows = 0;
+    HIP_TRY(hipMemcpyAsync(&rows, d_count + tiles, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (rows < 1 || rows > n) return fail(DM_ESTATE, "dm_siteperf_add_text: %lld lines in %lld bytes", rows, (long long)n);
+    if (rows > spk::MAX_RECORDS) return fail(DM_EINVAL, "dm_siteperf_add_text: %lld lines (at most %lld)", rows, (long long)spk::MAX_RECORDS);
+    if ((rc = spk::record_buffers(h, rows)) != DM_OK) return rc;
+    if ((rc = spk::ensure(h, B::START, size_t(rows + 1) * 8)) != DM_OK) return rc;
+    long long* d_start = spk::ptr<long long>(h, B::START);
+    unsigned char* d_status = spk::ptr<unsigned char>(h, B::STATUS);
+    long long* d_out = spk::ptr<long long>(h, B::OUT);
+    const dim3 row_grid{unsigned((rows + spk::THREADS - 1) / spk::THREADS)};
+    hipLaunchKernelGGL(xlk::xl_lines_kernel, tile_grid, block, 0, s, d_text, (long long)n, d_count, rows, d_start);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(spk::sp_parse_kernel, row_grid, dim3(spk::THREADS), 0, s, d_text, d_start, rows, name, (long long)h->len, spk::ptr<int>(h, B::POS),
+                       spk::ptr<int>(h, B::COV), spk::ptr<int>(h, B::PCT), spk::ptr<int>(h, B::MOD), spk::ptr<unsigned char>(h, B::STRAND),
+                       spk::ptr<unsigned char>(h, B::BASE), d_status);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(xlk::xl_first_kernel, dim3(1), dim3(xyk::SUM_THREADS), 0, s, d_status, rows, d_out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[1], s));
+    long long first = -1;
+    HIP_TRY(hipMemcpyAsync(&first, d_out, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = spk::add_time(h, 0, h->parse_ms)) != DM_OK) return rc;
+    if (n_lines) *n_lines = rows;
+    if (first >= 0) {                                                // outside the grammar: nothing of this text is counted
+        if (flag) *flag = 1;
+        if (first_bad_line) *first_bad_line = first + 1;
+        return DM_OK;
+    }
+    h->n_records = rows;
+    return spk::count_records(h, role, rows);
+}
+
+int dm_siteperf_add_records(dm_siteperf* h, int role, int64_t n, const int32_t* pos, const uint8_t* strand, const uint8_t* base, const int32_t* cov, const int32_t* pct,
+                            const int32_t* mod) {
+    using B = dm_siteperf;
+    if (!h) return fail(DM_EINVAL, "null handle");
+    if (h->len < 0) return fail(DM_ESTATE, "dm_siteperf_add_records: no contig");
+    if (role != 0 && role != 1) return fail(DM_EINVAL, "dm_siteperf_add_records: role %d (0 run, 1 control)", role);
+    if (n < 0 || n > spk::MAX_RECORDS || (n > 0 && (!pos || !strand || !base || !cov || !pct || !mod))) return fail(DM_EINVAL, "dm_siteperf_add_records: %lld records", (long long)n);
+    for (int64_t i = 0; i < n; ++i)                                  // what the kernels index with, checked before any launch
+        if (pos[i] < 0 || pos[i] >= h->len || strand[i] > 1 || cov[i] < 0 || mod[i] < 0 || mod[i] > cov[i] || pct[i] < 0 || pct[i] > 100)
+            return fail(DM_EINVAL, "dm_siteperf_add_records: record %lld (position %d of %lld, strand %d, coverage %d, percentage %d, modified %d)", (long long)i, pos[i],
+                        (long long)h->len, int(strand[i]), cov[i], pct[i], mod[i]);
+    h->n_records = 0;
+    if (n == 0) return DM_OK;
+    HIP_TRY(hipSetDevice(h->xy->device));
+    int rc = spk::record_buffers(h, n);
+    if (rc) return rc;
+    hipStream_t s = h->xy->stream;
+    HIP_TRY(hipMemcpyAsync(h->buf[B::POS], pos, size_t(n) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->buf[B::COV], cov, size_t(n) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->buf[B::PCT], pct, size_t(n) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->buf[B::MOD], mod, size_t(n) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->buf[B::STRAND], strand, size_t(n), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->buf[B::BASE], base, size_t(n), hipMemcpyHostToDevice, s));
+    h->n_records = n;
+    return spk::count_records(h, role, n);
+}
+
+int dm_siteperf_fetch_records(dm_siteperf* h, int32_t* pos, uint8_t* strand, uint8_t* base, int32_t* cov, int32_t* pct, int32_t* mod) {
+    using B = dm_siteperf;
+    if (!h) return fail(DM_EINVAL, "null handle");
+    const size_t n = size_t(h->n_records);
+    if (n == 0) return DM_OK;
+    HIP_TRY(hipSetDevice(h->xy->device));
+    if (pos) HIP_TRY(hipMemcpy(pos, h->buf[B::POS], n * 4, hipMemcpyDeviceToHost));
+    if (cov) HIP_TRY(hipMemcpy(cov, h->buf[B::COV], n * 4, hipMemcpyDeviceToHost));
+    if (pct) HIP_TRY(hipMemcpy(pct, h->buf[B::PCT], n * 4, hipMemcpyDeviceToHost));
+    if (mod) HIP_TRY(hipMemcpy(mod, h->buf[B::MOD], n * 4, hipMemcpyDeviceToHost));
+    if (strand) HIP_TRY(hipMemcpy(strand, h->buf[B::STRAND], n, hipMemcpyDeviceToHost));
+    if (base) HIP_TRY(hipMemcpy(base, h->buf[B::BASE], n, hipMemcpyDeviceToHost));
+    return DM_OK;
+}
+
+int dm_siteperf_finish_contig(dm_siteperf* h) {
+    using B = dm_siteperf;
+    if (!h) return fail(DM_EINVAL, "null handle");
+    if (h->len < 0) return fail(DM_ESTATE, "dm_siteperf_finish_contig: no contig");
+    const int64_t len = h->len;
+    h->len = -1;
+    h->n_records = 0;
+    if (h->control_files == 0) return DM_OK;                         // no control line: no entry
+    HIP_TRY(hipSetDevice(h->xy->device));
+    hipStream_t s = h->xy->stream;
+    unsigned long long* d_stat = spk::ptr<unsigned long long>(h, B::STAT);
+    const dim3 grid{unsigned(std::min<int64_t>((2 * len + spk::THREADS - 1) / spk::THREADS, spk::MAX_BLOCKS))};
+    HIP_TRY(hipEventRecord(h->ev[2], s));
+    hipLaunchKernelGGL(spk::sp_walk_kernel, grid, dim3(spk::THREADS), 0, s, spk::ptr<const int>(h, B::TAB), spk::ptr<const unsigned long long>(h, B::KEY),
+                       spk::ptr<const unsigned char>(h, B::CODE), (long long)len, h->motif.B, h->thr, spk::ptr<unsigned long long>(h, B::HIST), d_stat);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[3], s));
+    unsigned long long bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, d_stat + spk::S_BADSUM, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    int rc = spk::add_time(h, 2, h->count_ms);
+    if (rc) return rc;
+    if (bad) return fail(DM_EINVAL, "dm_siteperf_finish_contig: %llu control sums left the int32 range", bad);
+    return DM_OK;
+}
+
+int dm_siteperf_fetch(dm_siteperf* h, int64_t* hist, int64_t* counts, int64_t* lines_seen, int64_t* lines_skipped, int64_t* base_mismatch) {
+    using B = dm_siteperf;
+    if (!h) return fail(DM_EINVAL, "null handle");
+    HIP_TRY(hipSetDevice(h->xy->device));
+    HIP_TRY(hipStreamSynchronize(h->xy->stream));
+    long long stat[spk::N_STAT];
+    HIP_TRY(hipMemcpy(stat, h->buf[B::STAT], sizeof stat, hipMemcpyDeviceToHost));
+    if (hist) HIP_TRY(hipMemcpy(hist, h->buf[B::HIST], size_t(spk::NCAT) * 2 * h->thr.n * spk::NPCT * 8, hipMemcpyDeviceToHost));
+    if (counts)
+        for (int j = 0; j < 4; ++j) counts[j] = stat[spk::S_TP + j];
+    if (lines_seen) *lines_seen = h->lines_seen;
+    if (lines_skipped) *lines_skipped = stat[spk::S_SKIPPED];
+    if (base_mismatch) *base_mismatch = stat[spk::S_MISMATCH];
+    return DM_OK;
+}
+
+int dm_siteperf_times(dm_siteperf* h, double* parse_ms, double* count_ms) {
+    if (!h) return fail(DM_EINVAL, "null handle");
+    if (parse_ms) *parse_ms = h->parse_ms;
+    if (count_ms) *count_ms = h->count_ms;
+    return DM_OK;
+}
+
+}  // extern "C"

@@ -710,6 +710,40 @@ int dm_xyset_gather(dm_xyset* s, const int64_t* ids, int64_t n, float* x);
 int dm_trainer_step_set(dm_trainer* t, dm_xyset* s, const int64_t* ids, const float* y, int64_t n, int unbalanced, float* loss);
 int dm_trainer_grad_set(dm_trainer* t, dm_xyset* s, const int64_t* ids, const float* y, int64_t n, int unbalanced, float* loss, float* prob, float* grad);
 
+/* ------------------------------------------------------------------------- siteperf -- */
+/* Site-level ROC / PR of a run against control runs (DeepMod_tools/cal_EcoliDetPerf.py; csrc/siteperf.hip.inc): BED lines ->
+ * hist int64 [category 7][label 2][bucket n_thresholds][percentage 101], the sums tp / fp / tn / fn and line counters.  bucket = (thresholds <=
+ * coverage) - 1; a line below the smallest threshold enters the sums only.  One contig at a time, the counters accumulate; integer atomics only:
+ * the result is exact and the same on every run.  deepmod_amd/siteperf.py (HostEngine) states the semantics.
+ *   create         1 to 8 thresholds, non-negative, strictly ascending.
+ *   set_contig     seq: len FASTA bytes (compared case-sensitively); motif: m <= 16 letters as typed, k the modified offset; start / end inclusive,
+ *                  negative: none.  Writes the site codes (bit 0 '+', bit 1 '-'; fetch_codes: code [len]) and zeroes the control tables.
+ *   add_text       one BED file's bytes, all of contig_name; role 0 run, 1 control.  Device grammar: >= 12 fields of printable bytes, one ' ' or
+ *                  '\t' between them, '\n' at the end; field 0 = contig_name; fields 1, 9, 10, 11 of 1 - 10 digits <= 2^31 - 1; position < len,
+ *                  percentage <= 100, modified <= coverage; field 3 one byte; field 5 '+' or '-'.  A text with a line outside it sets *flag and
+ *                  *first_bad_line (1-based) and is NOT counted: the caller parses it and calls add_records.
+ *   add_records    the same counting from host arrays [n] (pos, cov, pct, mod int32; strand u8 0 '+' 1 '-'; base u8), checked before any launch.
+ *                  fetch_records: the records of the last add_text / add_records as they lie on the device.
+ *   finish_contig  every control (position, strand) -> one label-0 entry, pct = (100 * mod) / cov, base of the first control line (smallest
+ *                  file, then line).  Refused: per-file largest coverages of the contig summing to >= 2^31.
+ *   fetch          hist, counts [4] = tp, fp, tn, fn; lines handed in, lines outside the region, lines with an unexpected base.
+ *   parse_host     the device's line routine compiled for the host (no GPU needed) -> lines.  times: ms of the parse / count kernels (HIP events). */
+typedef struct dm_siteperf dm_siteperf;
+dm_siteperf* dm_siteperf_create(int device, int n_thresholds, const int32_t* thresholds);
+void dm_siteperf_destroy(dm_siteperf* h);
+int dm_siteperf_set_contig(dm_siteperf* h, const uint8_t* seq, int64_t len, const char* motif, int m, int k, int64_t start, int64_t end);
+int dm_siteperf_fetch_codes(dm_siteperf* h, uint8_t* code);
+int dm_siteperf_add_text(dm_siteperf* h, const char* text, int64_t n_bytes, int role, const char* contig_name, int64_t* n_lines, int32_t* flag, int64_t* first_bad_line);
+int dm_siteperf_add_records(dm_siteperf* h, int role, int64_t n, const int32_t* pos, const uint8_t* strand, const uint8_t* base, const int32_t* cov, const int32_t* pct,
+                            const int32_t* mod);
+int dm_siteperf_fetch_records(dm_siteperf* h, int32_t* pos, uint8_t* strand, uint8_t* base, int32_t* cov, int32_t* pct, int32_t* mod);
+int dm_siteperf_finish_contig(dm_siteperf* h);
+int dm_siteperf_fetch(dm_siteperf* h, int64_t* hist, int64_t* counts, int64_t* lines_seen, int64_t* lines_skipped, int64_t* base_mismatch);
+int64_t dm_siteperf_parse_host(const char* text, int64_t n_bytes, const char* contig_name, int64_t contig_len, int32_t* pos, uint8_t* strand, uint8_t* base, int32_t* cov,
+                               int32_t* pct, int32_t* mod, int64_t cap, int32_t* flag, int64_t* first_bad_line);
+int dm_siteperf_tile_bytes(void);
+int dm_siteperf_times(dm_siteperf* h, double* parse_ms, double* count_ms);
+
 #ifdef __cplusplus
 }
 #endif
