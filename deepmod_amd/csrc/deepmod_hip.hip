@@ -442,8 +442,10 @@ int launch_bilstm(dm_model* m, const float* d_x, long long xstride, int64_t n, f
         a.plogit = m->d_plogit;
         dmk::f32_launch(a, grid, m->stream);
     }
+#ifndef DM_ABL_NOHEAD      // timing only (prob / cls stay unwritten): what the finishing kernel and the dependency bubble in front of it cost a step - the most a kernel that finishes its own windows could gain
     hipLaunchKernelGGL(lstmhead::head_finish_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, m->stream, m->d_plogit, (long long)n,
                        npad, m->bout[0], m->bout[1], d_prob, d_cls);
+#endif
     HIP_TRY(hipGetLastError());
     if (m->profile) {
         HIP_TRY(hipEventRecord(e1, m->stream));

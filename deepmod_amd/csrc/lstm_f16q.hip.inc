@@ -24,7 +24,10 @@
 //    (layer 0: 192 x 3 + 64 for 324), N = 100 exactly (super-tile 12 has no row half B: not loaded, not multiplied): 25,600 MFMAs per 32 windows
 //    and direction = 2.94 issued per algorithmic unit (round 4, the mixed step as three products of a 9-slot operand: 28,350 = 3.25).
 //  * weights: [dir][layer][super-tile][own 0..2 | input 0..2 : [row half][hi|lo][lane][8 x f16] | mixed : [row half][lane][8 x f16]] = 26 KB per
-//    super-tile (16 KB layer 0: own 0..2, then the two mixed records), 2 x 26 KB ring.
+//    super-tile (16 KB layer 0: own 0..2, then the two mixed records); the ring has 4 x 26 KB slots in the three-product mode, where the super-tiles
+//    of a stage run in groups of one or two between barriers (ring_slots below; profiles/edges), and 2 x 26 KB in the int8 mode.
+//  * inside an ordinary k32-step the twelve MFMAs run in the snake order: each changes one operand against its predecessor, each accumulator
+//    still takes its three products in the order 0, 1, 2 (profiles/r05/ablate_sched.txt; the only order since profiles/edges).
 //  * everything else as in lstm_f16s.hip.inc: tile-major, the cell update of the super-tile before cut into chunks between the MFMAs, c of
 //    layer 0 in LDS and of layers 1, 2 in registers, the zero-state k32-steps of step 0 skipped, partial logits per direction.
 #ifndef DM16Q_TRANS_COST
@@ -53,11 +56,32 @@ constexpr int REC_BYTES = 4096;                  // one (super-tile, k32-step) r
 constexpr int MIX_BYTES = 2048;                  // one mixed record (its three products side by side along K): row half A 1 KB | row half B 1 KB; layer 0 has two
 constexpr int TILE_BYTES_L0 = (KS_L0 - 1) * REC_BYTES + 2 * MIX_BYTES, TILE_BYTES_L12 = (KS_L12 - 1) * REC_BYTES + MIX_BYTES;      // 16 KB, 26 KB
 constexpr int SLOT_BYTES = TILE_BYTES_L12;
-constexpr int NSLOT = 2;
+// Ring depth per mode.  The int8 mode (MM 1) parks layer 1's cell state in LDS (its registers hold the int32 accumulators) and keeps the two-slot ring:
+// super-tile T + 1 lands in the other slot under super-tile T, one DMA wait and one barrier per super-tile.  The three-product mode (MM 0) has those
+// 52 KB for two more slots and runs TWO super-tiles ahead: super-tile g of the stream (13 per stage, stage after stage) sits in slot g % 4 and issues,
+// before its first MFMA, the DMA of super-tile g + 2 into slot (g + 2) % 4.  The 13 super-tiles of a stage form the groups {0}, {1, 2}, {3, 4}, ...,
+// {11, 12}, and only the LAST super-tile of a group (T even) ends with s_waitcnt vmcnt(0) and s_barrier - 7 per stage instead of 13
+// (profiles/edges/README.md).
+//  * the grouping is a compile-time property of T: every barrier is unconditional, every wave of a workgroup executes the same 7 per stage and
+//    231 per work item whatever its data, so no wave can wait at a barrier another one never reaches; nothing polls or waits on memory.
+//  * the slot written under super-tile g was last read by super-tile g - 2, which lies in an EARLIER group for every T (T odd: the barrier after
+//    T - 1; T even: the one after T - 2; T = 0, 1: the one after super-tile 12 of the stage before), so every wave has left it; it is neither g's
+//    own slot nor that of g's partner in the group (g - 1 or g + 1).
+//  * super-tile g + 2 lies in a LATER group than g (T odd: behind the barrier after T + 1; T even, and T = 11, 12 into the next stage: behind the
+//    one after T or 12), and a wave reaches that barrier only after waiting for all its own pieces: what a group reads is complete.
+// A stage has an odd number of super-tiles, so pairs that ran on across stages would make the position of the barrier a run-time property of the step
+// (or a second copy of the step's code: the kernel's 3,550 static MFMAs are pinned); one single per stage costs one barrier in 39 super-tiles more.
+__host__ __device__ constexpr int ring_slots(int mm) {
+#ifdef DM16Q_ABL_PAIRBAR
+    return 2;
+#else
+    return mm == 0 ? 4 : 2;
+#endif
+}
 constexpr int C2_WAVE_BYTES = NTILE * 1024;      // cell state of layer 0 for one wave: [super-tile][lane][4 fp32]
 constexpr int C2_LAYER_BYTES = WAVES * C2_WAVE_BYTES;
-constexpr size_t LDS_BYTES = size_t(NSLOT) * SLOT_BYTES + C2_LAYER_BYTES;          // 53,248 + 53,248 = 106,496 B
-constexpr size_t LDS_BYTES_I8 = LDS_BYTES + C2_LAYER_BYTES;                        // the int8 mode parks layer 1's cell state in LDS too (its registers hold the int32 accumulators): 159,744 B
+constexpr size_t LDS_BYTES = size_t(ring_slots(0)) * SLOT_BYTES + C2_LAYER_BYTES;          // 106,496 + 53,248 = 159,744 B
+constexpr size_t LDS_BYTES_I8 = size_t(ring_slots(1)) * SLOT_BYTES + 2 * C2_LAYER_BYTES;   // 53,248 + 106,496 = 159,744 B as well
 constexpr size_t WEIGHT_BYTES_DIR = size_t(NTILE) * (TILE_BYTES_L0 + 2 * TILE_BYTES_L12);
 constexpr size_t WEIGHT_BYTES = 2 * WEIGHT_BYTES_DIR;                              // 1,810,432 B
 
@@ -355,7 +379,7 @@ __device__ __forceinline__ void c2_load(WaveState& w, const unsigned c2lds, cons
         for (int q = 0; q < 4; ++q) row[q] = w.c1reg[tile][q];
     } else {
         floatx4 v;
-        // no wait here: LDS returns in order, the wait for the first A fragments (issued after this) covers it
+        // no wait here: LDS returns in order, the next wait for A fragments covers it (it leaves only reads issued after this one outstanding)
         asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(c2lds), "i"(LAYER * C2_LAYER_BYTES));
 #pragma unroll
         for (int q = 0; q < 4; ++q) row[q] = v[q];
@@ -432,6 +456,11 @@ __device__ __forceinline__ void run_stage(const Params& p, WaveState& w, const u
         }
     }
     const bool last_stage = LAYER == 2 && s == LIVE - 1;
+#ifdef DM16Q_AINIT
+    AQuad a[2] = {};
+#else
+    AQuad a[2];                                                         // A fragments, double-buffered over the k32-steps; across the super-tiles of a group: see PF_OUT
+#endif
     static_for<NTILE>([&](auto Tc) {
         constexpr int T = decltype(Tc)::value;
         constexpr int P = T == 0 ? NTILE - 1 : T - 1;                   // the super-tile whose cells are updated under this one's MFMAs
@@ -442,22 +471,23 @@ __device__ __forceinline__ void run_stage(const Params& p, WaveState& w, const u
         if constexpr (T == 0) c2_load<PREV, MM>(w, c2_wave + unsigned(NTILE - 1) * 1024u, NTILE - 1, c2row);
         else c2_load<LAYER, MM>(w, c2_wave + unsigned(P) * 1024u, P, c2row);
         const unsigned a_addr = lds_base + unsigned(w.slot) * SLOT_BYTES + lane16;
-#ifdef DM16Q_AINIT
-        AQuad a[2] = {};
-#else
-        AQuad a[2];
-#endif
-        load_a<K::rec_off(0), WITH_B, K::mixed(0)>(a[0], a_addr);
-        // ---- next tile of the weight stream -> other ring slot ----
-        if (!(last_stage && T == NTILE - 1)) {
-            if constexpr (T + 1 < NTILE) {
-                unsigned toff = unsigned(T + 1) * K::TILE_BYTES;
-                asm volatile("" : "+s"(toff));
-                stage_tile<K::DMA_BYTES>(wdir + (LAYER_OFF[LAYER] + K::DMA_OFF) + toff, lds_base + unsigned(w.slot ^ 1) * SLOT_BYTES + K::DMA_OFF, wave_s, lane16);
-            } else {
-                using KN = StageKind<(LAYER + 1) % 3, FIRST && LAYER < 2>;
-                stage_tile<KN::DMA_BYTES>(wdir + (LAYER_OFF[(LAYER + 1) % 3] + KN::DMA_OFF), lds_base + unsigned(w.slot ^ 1) * SLOT_BYTES + KN::DMA_OFF, wave_s, lane16);
-            }
+        constexpr int NS = ring_slots(MM);
+        constexpr bool EDGE = NS == 2 || (T & 1) == 0;                  // the last super-tile of its group: the DMA wait and the barrier below
+        // no barrier between the two super-tiles of a group: the first one (PF_OUT) reads the second one's first A fragments before its own last k32-step,
+        // into the buffer that step does not use, and the second one (PF_IN) starts on that buffer (AOFS) instead of reading them behind the last MFMA
+        constexpr bool PF_OUT = NS == 4 && (T & 1) == 1, PF_IN = NS == 4 && T >= 2 && (T & 1) == 0;
+        constexpr int AOFS = PF_IN ? (KS & 1) : 0;
+        if constexpr (!PF_IN) load_a<K::rec_off(0), WITH_B, K::mixed(0)>(a[0], a_addr);
+        // ---- super-tile g + AHEAD of the weight stream -> ring slot (g + AHEAD) % NS (see ring_slots); all pieces first (profiles/r05/ablate_dma_spread.txt: later is worse) ----
+        constexpr int AHEAD = NS / 2;
+        if constexpr (T + AHEAD < NTILE) {
+            unsigned toff = unsigned(T + AHEAD) * K::TILE_BYTES;
+            asm volatile("" : "+s"(toff));
+            stage_tile<K::DMA_BYTES>(wdir + (LAYER_OFF[LAYER] + K::DMA_OFF) + toff, lds_base + unsigned((w.slot + AHEAD) & (NS - 1)) * SLOT_BYTES + K::DMA_OFF, wave_s, lane16);
+        } else if (!last_stage) {                                       // (the stream ends with the last stage)
+            using KN = StageKind<(LAYER + 1) % 3, FIRST && LAYER < 2>;
+            constexpr size_t noff = size_t(T + AHEAD - NTILE) * KN::TILE_BYTES;
+            stage_tile<KN::DMA_BYTES>(wdir + (LAYER_OFF[(LAYER + 1) % 3] + KN::DMA_OFF + noff), lds_base + unsigned((w.slot + AHEAD) & (NS - 1)) * SLOT_BYTES + KN::DMA_OFF, wave_s, lane16);
         }
         floatx4 (&d)[4] = w.acc[accT];
         intx4 (&di)[4] = w.acci[accT];
@@ -476,7 +506,8 @@ __device__ __forceinline__ void run_stage(const Params& p, WaveState& w, const u
         static_for<KS>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             constexpr int MIXED = K::mixed(i);
-            if constexpr (i + 1 < KS) load_a<K::rec_off(i + 1), WITH_B, K::mixed(i + 1)>(a[(i + 1) & 1], a_addr);
+            AQuad& ai = a[(i + AOFS) & 1];
+            if constexpr (i + 1 < KS) load_a<K::rec_off(i + 1), WITH_B, K::mixed(i + 1)>(a[(i + 1 + AOFS) & 1], a_addr);
             if constexpr (i == KS - 1) {
                 // the cells of super-tile P are done: their (hi, lo) pairs become operands, their state goes back
                 if constexpr (KS == 1) {                                   // (layer 0 at step 0: one k32-step, nothing to hide under)
@@ -526,7 +557,9 @@ __device__ __forceinline__ void run_stage(const Params& p, WaveState& w, const u
                     if constexpr (L0) mx2[hh] = uintx4{x1a[hh], x1b[hh], 0u, 0u};
                 }
             }
-            wait_a<(i + 1 < KS ? a_reads(WITH_B, K::mixed(i + 1 < KS ? i + 1 : i)) : 0)>(a[i & 1]);
+            constexpr bool WITH_B_NEXT = T + 1 < NTILE - 1;
+            if constexpr (PF_OUT && i == KS - 1) load_a<K::rec_off(0), WITH_B_NEXT, K::mixed(0)>(a[KS & 1], lds_base + unsigned((w.slot + 1) & (NS - 1)) * SLOT_BYTES + lane16);
+            wait_a<(i + 1 < KS ? a_reads(WITH_B, K::mixed(i + 1 < KS ? i + 1 : i)) : (PF_OUT ? a_reads(WITH_B_NEXT, K::mixed(0)) : 0))>(ai);
             // the products: per product the 2 x 2 (row half x window half) tiles of the super-tile, four independent accumulators; each MFMA is
             // followed by its share of super-tile P's cell update (16 cycles hide about two VALU issues)
             constexpr int C0 = DM16Q_PRE + NMF * i;
@@ -541,14 +574,14 @@ __device__ __forceinline__ void run_stage(const Params& p, WaveState& w, const u
                 // all three products of the left-over slots in one MFMA per 16x16 tile (layer 0: a second one for features 4..6); the last
                 // k32-step of a super-tile, no cell chunks under it
                 const halfx8 b0 = as_h8(mx[0]), b1 = as_h8(mx[1]);
-                DM_MF(a[i & 1].hiA, b0, 0, 0)
-                DM_MF(a[i & 1].hiA, b1, 2, 0)
-                if constexpr (WITH_B) { DM_MF(a[i & 1].hiB, b0, 1, 0) DM_MF(a[i & 1].hiB, b1, 3, 0) }
+                DM_MF(ai.hiA, b0, 0, 0)
+                DM_MF(ai.hiA, b1, 2, 0)
+                if constexpr (WITH_B) { DM_MF(ai.hiB, b0, 1, 0) DM_MF(ai.hiB, b1, 3, 0) }
                 if constexpr (MIXED == 2) {
                     const halfx8 e0 = as_h8(mx2[0]), e1 = as_h8(mx2[1]);
-                    DM_MF(a[i & 1].loA, e0, 0, 1)
-                    DM_MF(a[i & 1].loA, e1, 2, 1)
-                    if constexpr (WITH_B) { DM_MF(a[i & 1].loB, e0, 1, 1) DM_MF(a[i & 1].loB, e1, 3, 1) }
+                    DM_MF(ai.loA, e0, 0, 1)
+                    DM_MF(ai.loA, e1, 2, 1)
+                    if constexpr (WITH_B) { DM_MF(ai.loB, e0, 1, 1) DM_MF(ai.loB, e1, 3, 1) }
                 }
             } else {
                 constexpr int t = K::opnd(i);
@@ -560,44 +593,25 @@ __device__ __forceinline__ void run_stage(const Params& p, WaveState& w, const u
                 }
                 if constexpr (I8) {
                     // a_hi w_hi in f16, then both cross terms of the 32 units of this k32-step in one int8 MFMA per tile: A bytes (w_hi8, w_lo8) x B bytes (lo8, hi8)
-                    DM_MF(a[i & 1].hiA, bh[0], 0, 0) DM_CELLQ(0);
-                    DM_MF(a[i & 1].hiA, bh[1], 2, 0) DM_CELLQ(1);
-                    if constexpr (WITH_B) { DM_MF(a[i & 1].hiB, bh[0], 1, 0) DM_CELLQ(2); DM_MF(a[i & 1].hiB, bh[1], 3, 0) DM_CELLQ(3); }
-                    DM_MI(a[i & 1].loA, bl[0], 0) DM_CELLQ(WITH_B ? 4 : 2);
-                    DM_MI(a[i & 1].loA, bl[1], 2) DM_CELLQ(WITH_B ? 5 : 3);
-                    if constexpr (WITH_B) { DM_MI(a[i & 1].loB, bl[0], 1) DM_CELLQ(6); DM_MI(a[i & 1].loB, bl[1], 3) DM_CELLQ(7); }
+                    DM_MF(ai.hiA, bh[0], 0, 0) DM_CELLQ(0);
+                    DM_MF(ai.hiA, bh[1], 2, 0) DM_CELLQ(1);
+                    if constexpr (WITH_B) { DM_MF(ai.hiB, bh[0], 1, 0) DM_CELLQ(2); DM_MF(ai.hiB, bh[1], 3, 0) DM_CELLQ(3); }
+                    DM_MI(ai.loA, bl[0], 0) DM_CELLQ(WITH_B ? 4 : 2);
+                    DM_MI(ai.loA, bl[1], 2) DM_CELLQ(WITH_B ? 5 : 3);
+                    if constexpr (WITH_B) { DM_MI(ai.loB, bl[0], 1) DM_CELLQ(6); DM_MI(ai.loB, bl[1], 3) DM_CELLQ(7); }
                 } else {
-#ifdef DM16Q_SNAKE
-                // every MFMA changes ONE operand against the one before it (row half or window half), also across the products
-                DM_MF(a[i & 1].hiA, bh[0], 0, 0) DM_CELLQ(0);
-                if constexpr (WITH_B) { DM_MF(a[i & 1].hiB, bh[0], 1, 0) DM_CELLQ(1); DM_MF(a[i & 1].hiB, bh[1], 3, 0) DM_CELLQ(2); }
-                DM_MF(a[i & 1].hiA, bh[1], 2, 0) DM_CELLQ(WITH_B ? 3 : 1);
-                DM_MF(a[i & 1].loA, bh[1], 2, 1) DM_CELLQ(WITH_B ? 4 : 2);
-                if constexpr (WITH_B) { DM_MF(a[i & 1].loB, bh[1], 3, 1) DM_CELLQ(5); DM_MF(a[i & 1].loB, bh[0], 1, 1) DM_CELLQ(6); }
-                DM_MF(a[i & 1].loA, bh[0], 0, 1) DM_CELLQ(WITH_B ? 7 : 3);
-                DM_MF(a[i & 1].hiA, bl[0], 0, 2) DM_CELLQ(WITH_B ? 8 : 4);
-                if constexpr (WITH_B) { DM_MF(a[i & 1].hiB, bl[0], 1, 2) DM_CELLQ(9); DM_MF(a[i & 1].hiB, bl[1], 3, 2) DM_CELLQ(10); }
-                DM_MF(a[i & 1].hiA, bl[1], 2, 2) DM_CELLQ(WITH_B ? 11 : 5);
-#else
-                // product 0: a_hi w_hi
-                DM_MF(a[i & 1].hiA, bh[0], 0, 0) DM_CELLQ(0);
-                DM_MF(a[i & 1].hiA, bh[1], 2, 0) DM_CELLQ(1);
-                if constexpr (WITH_B) { DM_MF(a[i & 1].hiB, bh[0], 1, 0) DM_CELLQ(2); DM_MF(a[i & 1].hiB, bh[1], 3, 0) DM_CELLQ(3); }
-#ifdef DM16Q_ABL_I8T      // timing only (results are wrong): both cross terms of a k32-step as ONE v_mfma_i32_16x16x64_i8 per 16x16 tile on the same operand registers
-                DM_MI(a[i & 1].loA, bl[0], 0) DM_CELLQ(WITH_B ? 4 : 2); DM_CELLQ(WITH_B ? 5 : 3);
-                DM_MI(a[i & 1].loA, bl[1], 2) DM_CELLQ(WITH_B ? 6 : 4); DM_CELLQ(WITH_B ? 7 : 5);
-                if constexpr (WITH_B) { DM_MI(a[i & 1].loB, bl[0], 1) DM_CELLQ(8); DM_CELLQ(9); DM_MI(a[i & 1].loB, bl[1], 3) DM_CELLQ(10); DM_CELLQ(11); }
-#else
-                // product 1: a_hi w_lo
-                DM_MF(a[i & 1].loA, bh[0], 0, 1) DM_CELLQ(WITH_B ? 4 : 2);
-                DM_MF(a[i & 1].loA, bh[1], 2, 1) DM_CELLQ(WITH_B ? 5 : 3);
-                if constexpr (WITH_B) { DM_MF(a[i & 1].loB, bh[0], 1, 1) DM_CELLQ(6); DM_MF(a[i & 1].loB, bh[1], 3, 1) DM_CELLQ(7); }
-                // product 2: a_lo w_hi
-                DM_MF(a[i & 1].hiA, bl[0], 0, 2) DM_CELLQ(WITH_B ? 8 : 4);
-                DM_MF(a[i & 1].hiA, bl[1], 2, 2) DM_CELLQ(WITH_B ? 9 : 5);
-                if constexpr (WITH_B) { DM_MF(a[i & 1].hiB, bl[0], 1, 2) DM_CELLQ(10); DM_MF(a[i & 1].hiB, bl[1], 3, 2) DM_CELLQ(11); }
-#endif
-#endif
+                // the snake order (profiles/r05/ablate_sched.txt: 1.328 against 1.337 / 1.339 ms): every MFMA changes ONE operand against the one before it
+                // (row half or window half), also across the products.  Each accumulator Q still receives product 0 (a_hi w_hi), then 1 (a_hi w_lo), then 2
+                // (a_lo w_hi) of the same operands, so the sums are what the product-major order gave, bit for bit
+                DM_MF(ai.hiA, bh[0], 0, 0) DM_CELLQ(0);
+                if constexpr (WITH_B) { DM_MF(ai.hiB, bh[0], 1, 0) DM_CELLQ(1); DM_MF(ai.hiB, bh[1], 3, 0) DM_CELLQ(2); }
+                DM_MF(ai.hiA, bh[1], 2, 0) DM_CELLQ(WITH_B ? 3 : 1);
+                DM_MF(ai.loA, bh[1], 2, 1) DM_CELLQ(WITH_B ? 4 : 2);
+                if constexpr (WITH_B) { DM_MF(ai.loB, bh[1], 3, 1) DM_CELLQ(5); DM_MF(ai.loB, bh[0], 1, 1) DM_CELLQ(6); }
+                DM_MF(ai.loA, bh[0], 0, 1) DM_CELLQ(WITH_B ? 7 : 3);
+                DM_MF(ai.hiA, bl[0], 0, 2) DM_CELLQ(WITH_B ? 8 : 4);
+                if constexpr (WITH_B) { DM_MF(ai.hiB, bl[0], 1, 2) DM_CELLQ(9); DM_MF(ai.hiB, bl[1], 3, 2) DM_CELLQ(10); }
+                DM_MF(ai.hiA, bl[1], 2, 2) DM_CELLQ(WITH_B ? 11 : 5);
                 }
             }
 #undef DM_MF
@@ -605,13 +619,20 @@ __device__ __forceinline__ void run_stage(const Params& p, WaveState& w, const u
 #undef DM_CELLQ
         });
 #undef DM_CHUNK
+#ifdef DM16Q_ABL_PAIRBAR      // timing only, on the TWO-slot ring (the weights of an odd super-tile may not have landed): what one barrier and one DMA wait per two super-tiles
+                              // could save at most - measured before the four-slot ring was built (profiles/edges/README.md)
+        if constexpr ((T & 1) == 0) {
+#else
+        if constexpr (EDGE) {
+#endif
 #ifndef DM16Q_ABL_NOVMWAIT
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // this wave's pieces of the next tile have landed ...
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // this wave's pieces of the next group have landed ...
 #endif
 #ifndef DM16Q_ABL_NOBAR
-        __builtin_amdgcn_s_barrier();                                   // ... everyone's; and everyone is done with this slot
+        __builtin_amdgcn_s_barrier();                                   // ... everyone's; and everyone is done with this group's slots
 #endif
-        w.slot ^= 1;
+        }
+        w.slot = (w.slot + 1) & (NS - 1);
     });
 }
 
@@ -626,7 +647,7 @@ __global__ __launch_bounds__(THREADS, 1) void bilstm_f16q_kernel(const Params p)
     const int grp = lane >> 4, n16 = lane & 15;
     const unsigned lane16 = unsigned(lane) * 16u;
     const unsigned lds_base = (unsigned)(size_t)lds16q;
-    const unsigned c2_wave = lds_base + unsigned(NSLOT) * SLOT_BYTES + unsigned(wave) * C2_WAVE_BYTES + lane16;
+    const unsigned c2_wave = lds_base + unsigned(ring_slots(MM)) * SLOT_BYTES + unsigned(wave) * C2_WAVE_BYTES + lane16;
     const unsigned one2 = grp == 0 ? 0x3C003C00u : 0u;           // f16 (1.0, 1.0): the slots of lane group 0 that meet (bias hi, bias lo) in the mixed k32-step
     const int nwork = 2 * p.ntiles;
     for (int work = blockIdx.x; work < nwork; work += gridDim.x) {
@@ -683,9 +704,10 @@ __global__ __launch_bounds__(THREADS, 1) void bilstm_f16q_kernel(const Params p)
                 if constexpr (MM == 1) asm volatile("ds_write_b128 %0, %1 offset:%2" :: "v"(c2_wave + unsigned(t * 1024)), "v"(z4), "i"(C2_LAYER_BYTES) : "memory");
             }
         }
-        {   // layer 0, super-tile 0 -> slot 0 (step 0: only its mixed record)
+        {   // layer 0, super-tile 0 -> slot 0 (step 0: only its mixed record); the four-slot ring runs two super-tiles ahead: super-tile 1 -> slot 1
             using K0 = StageKind<0, true>;
             stage_tile<K0::DMA_BYTES>(wdir + K0::DMA_OFF, lds_base + K0::DMA_OFF, wave_s, lane16);
+            if constexpr (ring_slots(MM) == 4) stage_tile<K0::DMA_BYTES>(wdir + (K0::TILE_BYTES + K0::DMA_OFF), lds_base + (SLOT_BYTES + K0::DMA_OFF), wave_s, lane16);
         }
         {
             const int row = dir == 0 ? 0 : WIN - 1;
