@@ -1,10 +1,12 @@
-// bedtext.inc — BED text of one contig x strand from the dense counters (host code, included by deepmod_hip.hip).
+// bedtext.inc — BED text of one contig x strand from the dense counters (host code, part of summary.hip).
 //
 // Reference: /root/reference/bin/DeepMod_scripts/myDetect.py:1107-1120 (sum_handler's writer): for every key that was
 // created (touch > 0), in position order,
 //     "<chr> <pos> <pos+1> <Base> <min(cov,1000)> <strand> <pos> <pos+1> 0,0,0 <cov> <pct> <mod> \n"
 // single spaces, a trailing space before the newline, pct = "%d" % (100 * mod / (cov if cov > 0 else 1)) (truncation).
 // A 30x E. coli run has 2.3 M such lines, a human chromosome 1e8: formatted here instead of in a Python loop.
+#pragma once
+#include "host.h"
 
 namespace bedtext {
 // decimal digits of v, two at a time from a 00..99 table

@@ -1,4 +1,4 @@
-// cluster_sites.hip.inc — the CpG-cluster stage from the per-position counters, on the device (included by deepmod_hip.hip).
+// cluster_sites.hip.inc — the CpG-cluster stage from the per-position counters, on the device (part of summary.hip).
 //
 // Replaces, for one contig (or one rank's slice of it), the text round trip of the three tools after `detect`:
 //   DeepMod_tools/sum_chr_mod.py:37-66          rows with mod > 0 of both strands, pct = int(mod * 100 / cov)
@@ -15,6 +15,9 @@
 //   site_feature_kernel  per tile: codes of tile +-26 in LDS, each site reads its 51 + partner codes, writes 14 fp32 features and its record
 // The feature arithmetic is the reference's double arithmetic, operation for operation (divisions stay divisions, no contraction): the
 // fp32 cast of the result is what the MLP is fed, and the file is compared byte for byte with the tools' (tests/test_gpu_cluster_fused.py).
+#pragma once
+#include "host.h"
+#include "blockscan.hip.inc"
 
 namespace csites {
 
@@ -91,29 +94,6 @@ __device__ inline unsigned char site_code(const Args& a, const long long i) {
     if (md <= 0 || cv <= 0) return 0;                        // sum_chr_mod.py:58 drops mod == 0; mod > 0 implies cov > 0 (dm_summary_add)
     const long long pct = (100ll * md) / cv;                  // int(mod * 100 / cov), sum_chr_mod.py:63
     return (unsigned char)((pct > 100 ? 100 : int(pct)) + 1) | (unsigned char)(s << 7);
-}
-
-// exclusive scan of one value per thread over the block; total = the block's sum.  Every thread of the block calls it.
-template <int NT>
-__device__ inline long long block_exclusive_scan(const long long v, long long* wave_total /* LDS [NT / 64] */, long long& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    long long inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-    }
-    if (lane == 63) wave_total[w] = inc;
-    __syncthreads();
-    long long before = 0;
-    total = 0;
-    for (int k = 0; k < NT / 64; ++k) {
-        const long long t = wave_total[k];
-        if (k < w) before += t;
-        total += t;
-    }
-    __syncthreads();                                          // wave_total may be written again
-    return before + inc - v;
 }
 
 __global__ __launch_bounds__(THREADS) void site_code_kernel(const Args a, unsigned char* __restrict__ code /* [count + 2 HALO] */,

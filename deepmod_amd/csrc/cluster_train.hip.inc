@@ -1,4 +1,4 @@
-// cluster_train.hip.inc — training of the CpG-cluster MLP for gfx950 (included by deepmod_hip.hip): forward, backward, Adam.
+// cluster_train.hip.inc — training of the CpG-cluster MLP for gfx950 (part of offline.hip): forward, backward, Adam.
 //
 // The network is the reference's serialized training graph (train_deepmod/na12878_cluster_train_mod-keep_prob0.7-nb25-chr1/Cg.cov5.nb25.meta):
 //   layer_1 = relu(X W_1 + b_1), d_1 = layer_1 / keep_prob * floor(keep_prob + U[0,1));  layer_2 = relu(d_1 W_2 + b_2), d_2 the same;
@@ -21,6 +21,9 @@
 //
 // The dropout mask is this project's own (TensorFlow's random stream cannot be reproduced): a counter-based generator keyed by
 // (seed, step, row in batch, pair of units), units 0..99 = layer 1, 100..119 = layer 2.  Its definition is cluster_train.dropout_keep (numpy).
+#pragma once
+#include "host.h"
+#include "train.hip.inc"
 
 namespace dmct {
 

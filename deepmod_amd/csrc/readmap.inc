@@ -1,4 +1,4 @@
-// readmap.inc — SAM record + reference sequence -> per-base alignment table (host C++, included by deepmod_hip.hip).
+// readmap.inc — SAM record + reference sequence -> per-base alignment table (host C++, part of feed.hip).
 //
 // Replaces the alignment walk of handle_record, /root/reference/bin/DeepMod_scripts/myDetect.py:515-714:
 //   :515-520  POS -> 0-based, strand from FLAG 0x10, CIGAR split into counts and ops
@@ -14,6 +14,8 @@
 //   :684-704  the CpG special case: "C -...- G" against reference "C G...G G" (and its mirror image) swaps the gap
 // This is sequential, branchy byte work on one read (10^3 - 10^5 rows) — it stays on the host, as in the reference,
 // but as compiled code instead of a per-base Python loop.
+#pragma once
+#include "host.h"
 
 namespace readmap {
 
@@ -50,9 +52,10 @@ inline bool is_clip_op(char op) { return op == 'I' || op == 'D' || op == 'N' || 
 //              written and info[DM_MAP_STATUS] = DM_MAP_NEED_ROWS.
 //   readi      may be NULL (the streaming row builder never reads the read-index column)
 //   first_row  the final table is rows [*first_row, *first_row + info[DM_MAP_N_ROWS]) of the columns
-inline int map_read_core(int flag, int64_t pos1, const char* cigar, const char* readseq, int64_t readseq_len, const char* refseq, int64_t refseq_len,
-                         int64_t n_events, char* refb, char* readb, int64_t* refi, uint64_t* readi, int64_t cap, int64_t* info, int64_t* first_row,
-                         int64_t* need_rows, const bool cpg_swap = true) {
+// Declared in host.h (cpg_swap defaults to true there): getfeatures calls it from another translation unit.
+int map_read_core(int flag, int64_t pos1, const char* cigar, const char* readseq, int64_t readseq_len, const char* refseq, int64_t refseq_len,
+                  int64_t n_events, char* refb, char* readb, int64_t* refi, uint64_t* readi, int64_t cap, int64_t* info, int64_t* first_row,
+                  int64_t* need_rows, const bool cpg_swap) {
     for (int i = 0; i < DM_MAP_INFO_LEN; ++i) info[i] = 0;
     *first_row = 0;
     *need_rows = 0;

@@ -1,5 +1,5 @@
-// rowsbatch.inc — one worker batch of reads -> the device-ready arrays of the streaming detect (host C++, included by
-// deepmod_hip.hip after readmap.inc).
+// rowsbatch.inc — one worker batch of reads -> the device-ready arrays of the streaming detect (host C++, part of
+// feed.hip).
 //
 // The streaming worker hands the device, per batch: feature rows [R][7] fp32 (the reads' `tx` matrices back to back, 100 zero
 // rows of padding on both sides of every read), and per row a reference position and a flag byte, plus "extra" (position, flag)
@@ -10,6 +10,9 @@
 //   get_Feature (fnum = 7)                      :839-903   feature rows of a raw read
 //   mPredict1's window / base association       :794-803, :824-833   row k + 100 <-> k-th table row whose readbase is not '-'
 //   sum_handler's per-base flags                :1089-1100 flags: bit0 refbase == Base, bit1 readbase != '-'
+#pragma once
+#include "host.h"
+
 #include <cstdlib>
 #include <memory>
 #include <mutex>

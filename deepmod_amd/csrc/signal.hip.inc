@@ -1,4 +1,4 @@
-// signal.hip.inc — raw-signal normalisation and per-event statistics on the GPU (included by deepmod_hip.hip).
+// signal.hip.inc — raw-signal normalisation and per-event statistics on the GPU (part of feed.hip).
 //
 // Reference: /root/reference/bin/DeepMod_scripts/myDetect.py
 //   :266-282  mnormalized(): over the event-covered slice raw[start_0 : start_last + length_last]
@@ -24,6 +24,8 @@
 //                           left to right, each with the 8-lane / 128-block pairwise scheme), so results are bit-identical
 //                           to the reference's np.mean / np.std, then rint(v * 1000) / 1000 and the cast to float32.
 // Nothing here is GEMM-shaped; the kernels are byte/integer work bounded by HBM and the LDS atomic rate.
+#pragma once
+#include "host.h"
 
 namespace sig {
 

@@ -1,4 +1,4 @@
-// siteperf.hip.inc — `siteperf`, device part (included by deepmod_hip.hip after xyparse.hip.inc): the BED lines of a run and of its control runs ->
+// siteperf.hip.inc — `siteperf`, device part (part of offline.hip): the BED lines of a run and of its control runs ->
 // the histograms every site-level curve of DeepMod_tools/cal_EcoliDetPerf.py is a function of.
 //   readFA (:31-74)                        sp_code_kernel   one byte per position: bit 0 = '+' site, bit 1 = '-' site, inside start..end only
 //   readmodf (:134-176)                    sp_count_kernel  a run line -> its category (:222), label (1 iff a site) and coverage bucket -> one count
@@ -22,6 +22,10 @@
 // once per file; the walk refuses a sum that is negative or whose modified count exceeds its coverage).  "The base of the first line seen"
 // (:100) needs an order that atomics do not give: every control line carries the key (file index << 40 | line index) << 8 | base, and a
 // 64-bit atomic min per (position, strand) keeps the smallest: the first line of the first file, whatever the schedule.
+#pragma once
+#include "host.h"
+#include "xyrows.hip.inc"
+#include "xyparse.hip.inc"
 
 namespace spk {
 

@@ -1,4 +1,4 @@
-// train.hip.inc — BiLSTM training for gfx950 (included by deepmod_hip.hip): forward with a tape, backpropagation through time, Adam.
+// train.hip.inc — BiLSTM training for gfx950 (part of offline.hip): forward with a tape, backpropagation through time, Adam.
 //
 // The network is the reference's training graph (bin/DeepMod_scripts/myMultiBiRNN.py:21-91): two independent stacks of three
 // BasicLSTMCell(100, forget_bias = 1), gates i, j, f, o; the forward stack over rows 0..10 of a 21 x 7 window, the backward stack over rows
@@ -21,6 +21,8 @@
 //
 // Tape: 600 floats per (direction, layer, step, window) = 158,400 B per window: 324 MB at n = 2,048.
 // Algorithmic work of a step: 3 x 8.924 MFLOP per window (forward, dX, dW).
+#pragma once
+#include "host.h"
 
 namespace dmtrain {
 

@@ -1,4 +1,4 @@
-// xygather.hip.inc — train --resident, device part (included by deepmod_hip.hip after xyparse.hip.inc): the windows of a resident set by id.
+// xygather.hip.inc — train --resident, device part (part of offline.hip): the windows of a resident set by id.
 //
 // The training files of a run are segments of one dm_xyset (xyparse.hip.inc).  A window's ID is its index over the concatenated segments:
 // segment s holds the ids [win_off[s], win_off[s + 1]) in the order of its centres, so id -> s is a search over the window prefix sums and
@@ -13,6 +13,10 @@
 // dm_xyset_gather runs it on the set's stream into host or device x.  dm_trainer_step_set / dm_trainer_grad_set run it on the trainer's stream
 // into the trainer's d_x, *bad being the word behind the finite check's flag: trainer_grad_staged reads both back in the one copy it makes
 // anyway, and from there on the step is dm_trainer_step's own code.
+#pragma once
+#include "host.h"
+#include "train.hip.inc"
+#include "xyparse.hip.inc"
 
 namespace xgk {
 

@@ -1,4 +1,4 @@
-// xyparse.hip.inc — predict, device part (included by deepmod_hip.hip after xyrows.hip.inc): the text of one .xy file -> its table, and the rows
+// xyparse.hip.inc — predict, device part (part of offline.hip): the text of one .xy file -> its table, and the rows
 // whose windows are classified.  The inverse of xyrows.hip.inc (which writes this text) and the device statement of train.getDataFromFile_new
 // (np.loadtxt + the selection of myMultiBiRNN.py:306-343).
 //
@@ -24,6 +24,10 @@
 // path only.  dm_xyload_select_host runs the same three rules (row_wanted, the edge, row_label) on a host table.
 // dm_xyload_classify: dm_predict_read_at on the resident table and centres, xl_prob1_kernel gathers column 1 of the probabilities; class,
 // probability and label come back as three plain copies, 6 bytes per window.
+#pragma once
+#include "host.h"
+#include "blockscan.hip.inc"
+#include "xyrows.hip.inc"
 
 namespace xlk {
 

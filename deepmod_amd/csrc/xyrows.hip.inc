@@ -1,4 +1,4 @@
-// xyrows.hip.inc — getfeatures, device part (included by deepmod_hip.hip): which matrix rows of a batch are kept, and their text.
+// xyrows.hip.inc — getfeatures, device part (part of offline.hip): which matrix rows of a batch are kept, and their text.
 //
 // Replaces myGetFeatureBasedPos.py:512-526 (a row is kept if a labelled row of its read lies within +-25 rows; more than 0.9 of the rows kept: all of
 // them; none: the read gives nothing) and np.savetxt(fmt='%.3f') of the kept rows (:123, :343), for all reads of a batch at once and without the
@@ -16,6 +16,10 @@
 // Formatting (checked against Python's '%.3f' on random fp32 patterns below 2^30 and on every k / 2000 with its fp32 neighbours): the sign is the sign
 // bit; q = rint(double(|v|) * 1000.0) - the product of an fp32 and 1000 is exact in double, rint rounds the tie to even as the correctly rounded decimal
 // does; the digits are q / 1000 '.' q % 1000 on three places.
+#pragma once
+#include "host.h"
+#include "blockscan.hip.inc"
+#include "xyrows.inc"
 
 struct dm_xyrows {
     int device = 0;

@@ -1,4 +1,4 @@
-// xyrows.inc — getfeatures, host part (host C++, included by deepmod_hip.hip): alignment table + position lists -> labelled matrix rows, and the
+// xyrows.inc — getfeatures, host part (host C++, part of offline.hip): alignment table + position lists -> labelled matrix rows, and the
 // definition of the .xy.gz text.
 //
 // Replaces, of the reference's bin/DeepMod_scripts/myGetFeatureBasedPos.py:
@@ -11,6 +11,8 @@
 // A matrix row is (pos, lab, code) here: pos = column 0, lab = 0 none | 1 negative (column 1) | 2 positive (column 2), code = the one-hot class
 // dm_rows_assemble takes (0..3 = A C G T, 255 none); columns 7..9 are the (mean, stdv, length) of the event the row shows (rdesc, as dm_rows_assemble).
 // Membership is by (strand, refbasei) VALUE as in the reference: the lists are sorted arrays per contig x strand, cgpos two sorted arrays per read.
+#pragma once
+#include "host.h"
 
 struct dm_xysites {
     int32_t n_contigs = 0;

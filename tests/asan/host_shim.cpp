@@ -1,21 +1,11 @@
 // TEST INFRASTRUCTURE - not part of the product.  The host-only part of the C ABI (readmap.inc, rowsbatch.inc, bedtext.inc: the
 // alignment walk, the row builder of a worker batch, the BED formatter) compiled by gcc with -fsanitize=address,undefined, so that
 // tests/test_asan_host.py can drive it with valid and with corrupted container tables and see every out-of-bounds access.
-// The sources are the product's own files, included where they lie; only the error plumbing of deepmod_hip.hip is restated here.
-#include <algorithm>
-#include <cmath>
-#include <cstdarg>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <string>
-#include <utility>
-#include <thread>
-#include <vector>
+// The sources are the product's own files, included where they lie, and their declarations are the product's (csrc/host.h, its part that
+// needs no HIP); only the definition of the error slot, which the product keeps in deepmod_hip.hip, is restated here.
+#include "../../deepmod_amd/csrc/host.h"
 
-#include "../../include/deepmod_hip.h"
-
-namespace {
+namespace dmhost {
 
 thread_local std::string g_err;
 
@@ -29,7 +19,7 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
-}  // namespace
+}  // namespace dmhost
 
 extern "C" const char* dm_last_error(void) { return g_err.c_str(); }
 

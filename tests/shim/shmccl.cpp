@@ -1,6 +1,6 @@
 // shmccl - TEST INFRASTRUCTURE, not part of the product.
 //
-// A same-node collective library with the entry points libdeepmod_hip binds from librccl (deepmod_amd/csrc/deepmod_hip.hip load_rccl():
+// A same-node collective library with the entry points libdeepmod_hip binds from librccl (deepmod_amd/csrc/summary.hip load_rccl():
 // ncclGetUniqueId, ncclCommInitRank, ncclAllReduce, ncclReduce, ncclReduceScatter, ncclGroupStart / ncclGroupEnd, ncclCommDestroy,
 // ncclGetErrorString, ncclGetVersion), defined against <rccl/rccl.h> itself (round 6) and implemented over one POSIX shared-memory segment and host staging.  RCCL refuses a communicator whose ranks share
 // a device ("Duplicate GPU detected"), so on a one-GPU box the product's N > 1 code - the slice arithmetic of dm_summary_reduce_scatter,

@@ -32,15 +32,18 @@ def test_no_experiment_switch_in_the_shipped_library():
 
 
 def test_a_stray_ablation_macro_is_a_compile_error():
-    """-DDM16Q_ABL_NOCELL (a timing-only kernel) without -DDM_EXPERIMENT must not preprocess."""
+    """-DDM16Q_ABL_NOCELL (a timing-only kernel) without -DDM_EXPERIMENT must not preprocess, in any translation unit of the library."""
     import subprocess
+    import __graft_entry__ as ge
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc")
-    src = os.path.join(ROOT, "deepmod_amd", "csrc", "deepmod_hip.hip")
-    for macro in ("-DDM16Q_ABL_NOCELL", "-DDM16S_ABL_2PROD", "-DDM_ABL_NOEPI", "-DDM16Q_PRE=0", "-DDM_WITH_F16S"):
-        r = subprocess.run([hipcc, "--offload-arch=gfx950", "--cuda-host-only", "-E", macro, src, "-o", os.devnull], capture_output=True, text=True)
-        assert r.returncode != 0 and "DM_EXPERIMENT" in r.stderr, (macro, r.stderr[-300:])
+    runs = [(unit, macro, subprocess.Popen([hipcc, "--offload-arch=gfx950", "--cuda-host-only", "-E", macro, os.path.join(ROOT, "deepmod_amd", "csrc", unit),
+                                            "-o", os.devnull], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True))
+            for unit in ge.UNITS for macro in ("-DDM16Q_ABL_NOCELL", "-DDM16S_ABL_2PROD", "-DDM_ABL_NOEPI", "-DDM16Q_PRE=0", "-DDM_WITH_F16S")]
+    for unit, macro, p in runs:
+        err = p.communicate()[1]
+        assert p.returncode != 0 and "DM_EXPERIMENT" in err, (unit, macro, err[-300:])
 
 
 @pytest.mark.parametrize("kernel", ["f16q", "f16qi8", "f32"])
@@ -104,7 +107,12 @@ def test_profile_staleness_hash_covers_every_source_of_a_kernel(monkeypatch):
         return seen
     for prec, unit in (("f16x3", "kern_f16q0.hip"), ("f16i8", "kern_f16q1.hip"), ("f32", "kern_f32.hip")):
         assert closure(unit, set()) <= set(bench.KERNEL_SOURCES[prec]), (prec, sorted(closure(unit, set()) - set(bench.KERNEL_SOURCES[prec])))
-        assert set(ge.UNIT_DEPS[unit]) | {unit} >= closure(unit, set())            # ... and the build's own dependency list rebuilds the unit for each of them
+    for unit in ge.UNITS:                # ... and the build's own dependency list rebuilds every unit, host or kernel, for each file it is compiled from
+        assert set(ge.UNIT_DEPS[unit]) | {unit} >= closure(unit, set()), (unit, sorted(closure(unit, set()) - set(ge.UNIT_DEPS[unit])))
+    rebuilt = lambda name: sorted(u for u in ge.UNITS if name in ge.UNIT_DEPS[u])          # noqa: E731   the units an edit of csrc/<name> recompiles
+    assert rebuilt("lstm_f16q.hip.inc") == ["kern_f16q0.hip", "kern_f16q1.hip"]
+    assert len(rebuilt("rowsbatch.inc")) == 1
+    assert rebuilt("host.h") == sorted(u for u in ge.UNITS if not u.startswith("kern_"))
     before = bench.kernel_source_sha("f16x3")
     monkeypatch.setattr(ge, "HIPCC_FLAGS", ge.HIPCC_FLAGS + ["-O2"])
     assert bench.kernel_source_sha("f16x3") != before

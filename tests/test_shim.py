@@ -1,5 +1,5 @@
 """CPU: the shared-memory collective stand-in (tests/shim/shmccl.cpp, test infrastructure for tests/test_gpu_multirank.py) builds and exports
-every entry point libdeepmod_hip looks up in its collective library (deepmod_amd/csrc/deepmod_hip.hip load_rccl)."""
+every entry point libdeepmod_hip looks up in its collective library (deepmod_amd/csrc/summary.hip load_rccl)."""
 import ctypes
 import os
 import re
@@ -9,7 +9,7 @@ from shim import build as shim_build
 
 
 def test_shim_exports_what_the_product_binds():
-    src = open(os.path.join(ROOT, "deepmod_amd", "csrc", "deepmod_hip.hip")).read()
+    src = open(os.path.join(ROOT, "deepmod_amd", "csrc", "summary.hip")).read()
     wanted = set(re.findall(r'bind\("(nccl[A-Za-z]+)"', src))
     assert {"ncclGetUniqueId", "ncclCommInitRank", "ncclAllReduce", "ncclReduce", "ncclReduceScatter", "ncclCommDestroy", "ncclGetVersion"} <= wanted
     lib = ctypes.CDLL(shim_build.library())
@@ -26,7 +26,7 @@ def test_collective_library_is_bound_through_its_own_header():
     product is decltype(&ncclX) of the header's prototype, the data types / operations it passes are the header's enumerators, and the stand-in DEFINES
     the header's functions (a drifted signature is a compile error there: build.library() above compiles it).  The constants a CUDA-era copy would have
     hard-coded are checked against the header text itself."""
-    src = open(os.path.join(ROOT, "deepmod_amd", "csrc", "deepmod_hip.hip")).read()
+    src = open(os.path.join(ROOT, "deepmod_amd", "csrc", "summary.hip")).read()
     shim = open(os.path.join(ROOT, "tests", "shim", "shmccl.cpp")).read()
     assert "#include <rccl/rccl.h>" in src and "#include <rccl/rccl.h>" in shim
     assert "struct NcclId" not in src and "NCCL_INT32" not in src and "typedef int (*fn_" not in src
