@@ -656,10 +656,10 @@ def feeder_budget(threads: int, world: int, usable_cpus: int, raw_input: bool):
 def _run_streaming_detect(moptions, ctx, pmanager, items, ngpu):
     """One process per GPU (rank), work items pulled from one shared queue by all ranks, counters merged with RCCL
     (deepmod_amd/stream.py).  -> (error ledger, per-rank stats)"""
-    from . import stream
+    from . import handover, stream
     world = max(1, min(ngpu, len(items)))
-    # (no manager process on this path: the items are known, a shared counter hands them out - stream.WorkList)
-    work_q, result_q = stream.WorkList(items, ctx), ctx.Queue()
+    # (no manager process on this path: the items are known, a shared counter hands them out - handover.WorkList)
+    work_q, result_q = handover.WorkList(items, ctx), ctx.Queue()
     run_opts = dict(moptions, outFolder=moptions['outFolder'] + moptions['FileID'])
     rdv = os.path.join(run_opts['outFolder'], '.rendezvous')
     if os.path.isdir(rdv):
@@ -667,12 +667,12 @@ def _run_streaming_detect(moptions, ctx, pmanager, items, ngpu):
             os.remove(os.path.join(rdv, f))
     from . import rawreads
     raw_input = any(f.endswith(rawreads.RAW_SUFFIX) for it in items for f in it[0])
-    feeders, feeder_procs, warning = feeder_budget(moptions['threads'], world, stream.usable_cpus(), raw_input)
+    feeders, feeder_procs, warning = feeder_budget(moptions['threads'], world, handover.usable_cpus(), raw_input)
     if not moptions.get('feeder_procs', 1):
         feeder_procs = 0
     elif warning:
         print(warning)
-    # raw containers: the signal stage of all feeders runs in the GPU process (stream.signal_server).  Without it every
+    # raw containers: the signal stage of all feeders runs in the GPU process (sigserver.signal_server).  Without it every
     # feeder owns a HIP context, and beyond ~8 such processes per GPU the hardware queues are oversubscribed (8 feeders
     # 9.1e6 base-positions/s, 11 feeders 6.3e6 with the device queue waiting 2.9 of 4.3 s - profiles/r02/README.md)
     if not run_opts.get('signal_server', True) and raw_input:

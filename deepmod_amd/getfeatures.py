@@ -468,13 +468,13 @@ class _Batch:
 
 def _load_event_container(lib, f5f, batch: _Batch, errors) -> None:
     """getEvent's merge (dm_events_merge, rawreads.py) for the reads of one container with event tables"""
-    from . import stream
-    c = stream._open_event_container(f5f)
+    from . import batch as dmbatch
+    c = dmbatch._open_event_container(f5f)
     mev_off = np.empty(c.n + 1, np.int64)
     cap = max(c.n_ev, 1)
     mean, stdv = np.empty(cap, np.float32), np.empty(cap, np.float32)
     start, length, base = np.empty(cap, np.uint64), np.empty(cap, np.uint64), np.empty(cap, 'S1')
-    got = lib.dm_events_merge(*stream._merge_args(c, mev_off), mean.ctypes.data, stdv.ctypes.data, start.ctypes.data, length.ctypes.data, base.ctypes.data)
+    got = lib.dm_events_merge(*dmbatch._merge_args(c, mev_off), mean.ctypes.data, stdv.ctypes.data, start.ctypes.data, length.ctypes.data, base.ctypes.data)
     if got < 0:
         raise ValueError('event offsets of a damaged container')
     for i, m in enumerate(c.meta):
@@ -493,8 +493,8 @@ def _load_event_container(lib, f5f, batch: _Batch, errors) -> None:
 
 
 def _load_move_container(lib, f5f, batch: _Batch, errors) -> None:
-    from . import stream
-    c = stream._open_move_container(f5f)
+    from . import batch as dmbatch
+    c = dmbatch._open_move_container(f5f)
     if c.mv is None:
         errors['No move data'].extend([f5f] * c.n)
         return

@@ -57,7 +57,7 @@ class SignalNormalizer:
 
 
     def event_stats_arrays(self, raw_parts, raw_off, ev_start, ev_length, ev_off):
-        """The batched call on arrays that are already laid out back to back (stream._prepare_batch_c): raw_parts - int16 arrays
+        """The batched call on arrays that are already laid out back to back (batch._prepare_batch_c): raw_parts - int16 arrays
         whose concatenation is the samples of all reads, raw_off / ev_off [n + 1] int64, ev_start / ev_length uint64 (starts relative
         to the read's first sample).  -> (mean f32[E], stdv f32[E], first_empty int64[n])"""
         n = len(raw_off) - 1

@@ -1,5 +1,5 @@
 """Dev tool (GPU box): where the host time of the streaming detect goes.  One worker batch of synthetic reads is prepared
-(deepmod_amd/stream.py:prepare_batch) under cProfile, then submitted to the device, so that host-side hot spots and the
+(deepmod_amd/batch.py:prepare_batch) under cProfile, then submitted to the device, so that host-side hot spots and the
 rows/s of one feeder thread are visible.
     python tools/e2e_rate.py raw|feat|packed [n_reads]"""
 import cProfile, io, os, pstats, sys, tempfile, time
