@@ -37,6 +37,12 @@ epochs, dropout stream and initial draw are this project's own, fixed by --seed 
 runs, for every site category and for motif sites only, at each coverage threshold.  The BED lines are parsed, classified and counted on one
 GPU into integer histograms; the numbers are exact functions of those (deepmod_amd/siteperf.py).  Writes <O>/<id>_siteperf.txt (the
 reference's lines) and <O>/<id>_siteperf.json (the curves); no plots.
+
+`merge --predFolder RUNS --Base C --FileID SUM [--chr chr1,chr2,..] [--Ref genome.fa --clusterCpG [CKPT_PREFIX]] [--threads T]` is
+DeepMod_tools/sum_chr_mod.py for a data set that was split over several detect runs: per contig the *.<chr>+.<Base>.bed / *.<chr>-.<Base>.bed files one to
+three levels below RUNS are parsed, summed and written as RUNS/SUM.<chr>.<Base>.bed on one GPU, byte for byte the tool's file; with --clusterCpG the
+summed counters also go through the CpG-cluster stage (RUNS/SUM_clusterCpG.<chr>.C.bed, the output of generate_motif_pos.py and
+hm_cluster_predict.py on the merged file).  RUNS/SUM_merge.json lists files, lines and kernel times (deepmod_amd/merge.py).
 """
 import argparse
 import os
@@ -183,7 +189,33 @@ def build_parser():
     spf.add_argument('--end', type=int, default=None, help='last position of the region (inclusive; needs --chr)')
     spf.add_argument('--cov', default='1,5', help='coverage thresholds, ascending, at most 8 (default 1,5)')
     spf.set_defaults(func=mSitePerf)
+    mrg = sub.add_parser('merge', parents=[com], help='sum the BED files of several detect runs per contig (sum_chr_mod.py) on the GPU',
+                         description='Per contig: every *.<chr>-.<Base>.bed and *.<chr>+.<Base>.bed one to three levels below --predFolder is parsed on one GPU, '
+                                     'coverage and modified count are summed per (position, strand), and <predFolder>/<FileID>.<chr>.<Base>.bed is written as '
+                                     'DeepMod_tools/sum_chr_mod.py writes it (positions with a modified count of 0 dropped; an empty file for a contig without '
+                                     'input).  Writes <predFolder>/<FileID>_merge.json (files, lines, notes, kernel times).  --threads host threads read ahead.')
+    mrg.add_argument('--predFolder', default=None, help='folder of the runs: the BED files are searched one to three levels below it')
+    mrg.add_argument('--Base', default='C', choices=['A', 'C', 'G', 'T'], help='base of interest: names the files')
+    mrg.add_argument('--chr', default=None, help='contigs to merge, separated by commas (default chr1..22, chrX, chrY, chrM)')
+    mrg.add_argument('--Ref', default=None, help='reference genome FASTA: a line beyond its contig is refused (without it the tables grow with the files)')
+    mrg.add_argument('--clusterCpG', nargs='?', const='', default=None, metavar='CKPT_PREFIX',
+                     help='--Base C with --Ref: also write <predFolder>/<FileID>_clusterCpG.<chr>.C.bed per contig with a site - the output of generate_motif_pos.py '
+                          '(motif CG) and hm_cluster_predict.py on the merged file, computed from the summed counters on the GPU.  CKPT_PREFIX: checkpoint '
+                          'prefix of the cluster model (default: DEEPMOD_CLUSTER_MODEL)')
+    mrg.set_defaults(func=mMerge)
     return parser
+
+
+def mMerge(args):
+    from deepmod_amd import merge
+    mo = {k: getattr(args, k) for k in ('predFolder', 'Base', 'FileID', 'Ref', 'clusterCpG', 'threads')}
+    mo['chr'] = [c for c in (args.chr or '').split(',') if c] or None
+    if not mo['predFolder']:
+        raise SystemExit('Error: merge: --predFolder, the folder of the runs, is needed')
+    try:
+        merge.merge_runs(mo)
+    except merge.MergeError as exc:
+        raise SystemExit('Error: %s' % exc)
 
 
 def mSitePerf(args):

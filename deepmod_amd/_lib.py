@@ -193,6 +193,18 @@ SIGNATURES = [
     ("dm_siteperf_parse_host", _i64, [_vp, _i64, _c.c_char_p, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _c.POINTER(_c.c_int32), _c.POINTER(_i64)]),
     ("dm_siteperf_tile_bytes", _c.c_int, []),
     ("dm_siteperf_times", _c.c_int, [_vp, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
+    ("dm_bedmerge_create", _vp, [_c.c_int]),
+    ("dm_bedmerge_destroy", None, [_vp]),
+    ("dm_bedmerge_open", _c.c_int, [_vp, _vp, _vp, _c.c_char_p, _c.c_int]),
+    ("dm_bedmerge_add_text", _c.c_int, [_vp, _vp, _i64, _c.POINTER(_i64), _c.POINTER(_c.c_int32), _c.POINTER(_i64)]),
+    ("dm_bedmerge_add_records", _c.c_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    ("dm_bedmerge_fetch_records", _c.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    ("dm_bedmerge_format_begin", _c.c_int, [_vp, _c.c_char, _c.POINTER(_i64), _c.POINTER(_i64), _c.POINTER(_i64)]),
+    ("dm_bedmerge_format_next", _c.c_int, [_vp, _vp, _i64, _c.POINTER(_i64)]),
+    ("dm_bedmerge_parse_host", _i64, [_vp, _i64, _c.c_char_p, _i64, _vp, _vp, _vp, _vp, _i64, _c.POINTER(_c.c_int32), _c.POINTER(_i64)]),
+    ("dm_bedmerge_format_host", _i64, [_c.c_char_p, _c.c_char, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _c.POINTER(_i64)]),
+    ("dm_bedmerge_tile_positions", _c.c_int, []),
+    ("dm_bedmerge_times", _c.c_int, [_vp, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
 ]
 
 

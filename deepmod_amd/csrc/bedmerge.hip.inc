@@ -1,0 +1,514 @@
+// bedmerge.hip.inc — `merge`, device part (part of offline.hip): the BED files of several runs of one contig -> their sums in two dm_summary
+// tables -> the merged text of DeepMod_tools/sum_chr_mod.py.
+//   readbed2 (:37-46)    bm_parse_kernel    one line per lane (bmk::parse_line, bedmerge.inc) -> position, strand, coverage, modified, a status byte;
+//                                           the largest position and coverage of the text (one integer atomic max per wave)
+//   mergeMod (:48-54)    bm_add_kernel      a record -> int32 atomic adds into cov and mod of its strand's table, +1 into touch
+//   save_mod (:56-66)    bm_length_kernel   a block per tile of bmk::TILE_POS positions: bytes and lines of the tile (bmk::emit_position, counting sink)
+//                        the 64-bit scan over the tiles
+//                        bm_write_kernel    the same routine with a writing sink at tile offset + block scan of the lanes' bytes
+// The text of a file is split as xyparse.hip.inc splits it (xl_count_kernel, the scan, xl_lines_kernel).  The grammar and the line are stated in
+// bedmerge.inc; a text with a line outside the grammar adds nothing (first line reported), and the caller hands its own parse over through
+// dm_bedmerge_add_records.
+// Exactness and determinism.  Every sum is an int32 integer: additions commute, so the order the atomics land in does not matter.  The guard of
+// siteperf keeps the sums in range: the largest coverages of the texts of a contig sum to < 2^31 (checked BEFORE a text's adds; duplicates of a key
+// inside one file are summed too, as merge.merge_beds sums them - a sum that left 0 <= mod <= cov through them is refused by format_begin).  The
+// format has no atomics: a line's offset is its tile's scanned offset + the block scan of the bytes of the lanes before it, a function of the tables
+// alone, and every output byte has one writer.  Two runs give identical bytes.
+// The tables belong to the caller (dm_summary handles, the ones dm_cluster_sites takes) and have a stream of their own: dm_summary_sync before this
+// handle's stream touches them, a stream synchronisation of this handle before the call returns.
+#pragma once
+#include "host.h"
+#include "blockscan.hip.inc"
+#include "xyrows.hip.inc"
+#include "xyparse.hip.inc"
+#include "bedmerge.inc"
+
+namespace bmk {
+
+constexpr int THREADS = 256;
+constexpr int POS_PER_LANE = TILE_POS / THREADS;
+constexpr int MAX_BLOCKS = 1024;
+enum { S_MAXPOS, S_MAXCOV, S_BADSUM, N_STAT };
+
+__global__ __launch_bounds__(THREADS) void bm_parse_kernel(const char* __restrict__ text, const long long* __restrict__ start, const long long n_rows, const Name name,
+                                                          const long long limit, int* __restrict__ pos, int* __restrict__ cov, int* __restrict__ mod,
+                                                          unsigned char* __restrict__ strand, unsigned char* __restrict__ status, unsigned long long* __restrict__ stat) {
+    const long long r = (long long)blockIdx.x * THREADS + threadIdx.x;
+    long long mp = 0, mc = 0;
+    if (r < n_rows) {
+        const long long b = start[r], e = start[r + 1] - 1;          // text[e] is the line's '\n'
+        Rec v = {0, 0, 0, 0};
+        const bool ok = parse_line(text + b, e - b, name, limit, v);
+        pos[r] = ok ? v.pos : 0;
+        cov[r] = ok ? v.cov : 0;
+        mod[r] = ok ? v.mod : 0;
+        strand[r] = ok ? v.strand : 0;
+        status[r] = ok ? 0 : 1;
+        if (ok) {
+            mp = v.pos;
+            mc = v.cov;
+        }
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        mp = max(mp, __shfl_down(mp, d, 64));
+        mc = max(mc, __shfl_down(mc, d, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (mp > 0) atomicMax(stat + S_MAXPOS, (unsigned long long)mp);
+        if (mc > 0) atomicMax(stat + S_MAXCOV, (unsigned long long)mc);
+    }
+}
+
+// tables: touch | cov | mod of `length` positions each; every pos[i] < length (parse_line's limit / the check of add_records)
+__global__ __launch_bounds__(THREADS) void bm_add_kernel(const int* __restrict__ pos, const int* __restrict__ cov, const int* __restrict__ mod,
+                                                        const unsigned char* __restrict__ strand, const long long n, int* __restrict__ plus, int* __restrict__ minus,
+                                                        const long long length) {
+    for (long long i = (long long)blockIdx.x * THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * THREADS) {
+        const long long q = pos[i];
+        if (q < 0 || q >= length) continue;
+        int* t = (strand[i] & 1) ? minus : plus;
+        atomicAdd(&t[q], 1);
+        atomicAdd(&t[length + q], cov[i]);
+        atomicAdd(&t[2 * length + q], mod[i]);
+    }
+}
+
+// the bytes and lines of the lane's POS_PER_LANE consecutive positions of tile blockIdx.x; bad: a sum outside 0 <= mod <= cov
+__device__ inline void lane_count(const Name& name, const char base, const int* __restrict__ plus, const int* __restrict__ minus, const long long length, long long& bytes,
+                                  int& lines, int& bad) {
+    const long long q0 = (long long)blockIdx.x * TILE_POS + (long long)threadIdx.x * POS_PER_LANE;
+    CountSink s;
+    lines = 0;
+    bad = 0;
+    for (int k = 0; k < POS_PER_LANE; ++k) {
+        const long long q = q0 + k;
+        if (q >= length) break;
+        if (!sum_ok(plus[length + q], plus[2 * length + q]) || !sum_ok(minus[length + q], minus[2 * length + q])) {
+            bad = 1;
+            continue;
+        }
+        lines += emit_position(s, name, base, q, q, plus + length, plus + 2 * length, minus + length, minus + 2 * length);
+    }
+    bytes = s.n;
+}
+
+__global__ __launch_bounds__(THREADS) void bm_length_kernel(const Name name, const char base, const int* __restrict__ plus, const int* __restrict__ minus, const long long length,
+                                                           long long* __restrict__ tile_bytes, long long* __restrict__ tile_lines, unsigned long long* __restrict__ stat) {
+    __shared__ long long wave_total[THREADS / 64];
+    long long bytes, total_bytes, total_lines;
+    int lines, bad;
+    lane_count(name, base, plus, minus, length, bytes, lines, bad);
+    (void)csites::block_exclusive_scan<THREADS>(bytes, wave_total, total_bytes);
+    (void)csites::block_exclusive_scan<THREADS>((long long)lines, wave_total, total_lines);
+    bad = __syncthreads_or(bad);
+    if (threadIdx.x == 0) {
+        tile_bytes[blockIdx.x] = total_bytes;
+        tile_lines[blockIdx.x] = total_lines;
+        if (bad) atomicAdd(stat + S_BADSUM, 1ull);
+    }
+}
+
+// tiles first_tile .. of the grid: their text at out + (tile_off[tile] - tile_off[first_tile])
+__global__ __launch_bounds__(THREADS) void bm_write_kernel(const Name name, const char base, const int* __restrict__ plus, const int* __restrict__ minus, const long long length,
+                                                          const long long* __restrict__ tile_off, const long long first_tile, char* __restrict__ out) {
+    __shared__ long long wave_total[THREADS / 64];
+    const long long tile = first_tile + blockIdx.x;
+    const long long q0 = tile * TILE_POS + (long long)threadIdx.x * POS_PER_LANE;
+    CountSink c;
+    for (int k = 0; k < POS_PER_LANE; ++k)
+        if (q0 + k < length) emit_position(c, name, base, q0 + k, q0 + k, plus + length, plus + 2 * length, minus + length, minus + 2 * length);
+    long long total;
+    const long long ex = csites::block_exclusive_scan<THREADS>(c.n, wave_total, total);
+    if (c.n == 0 || ex + c.n > tile_off[tile + 1] - tile_off[tile]) return;      // (never past the counted length, whatever became of the tables since)
+    WriteSink w{out + (tile_off[tile] - tile_off[first_tile]) + ex};
+    for (int k = 0; k < POS_PER_LANE; ++k)
+        if (q0 + k < length) emit_position(w, name, base, q0 + k, q0 + k, plus + length, plus + 2 * length, minus + length, minus + 2 * length);
+}
+
+}  // namespace bmk
+
+struct dm_bedmerge {
+    dm_xyrows* xy = nullptr;                            // stream, the scan and its block sums
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // parse, add, format: begin / end
+    enum { TEXT, COUNT, START, STATUS, OUT, POS, COV, MOD, STRAND, STAT, TBYTES, TLINES, FTEXT, N_BUF };
+    void* buf[N_BUF] = {};
+    size_t cap[N_BUF] = {};
+    dm_summary *plus = nullptr, *minus = nullptr;       // the open contig's tables (null: none), the caller's
+    bool fixed = false;                                 // the table length is the contig's: a line beyond it is outside the grammar
+    bmk::Name name = {};
+    int64_t n_records = 0;                              // records on the device, of the last add_text / add_records
+    int64_t cov_bound = 0;                              // of the open contig: the sum of the largest coverages of its texts
+    int64_t lines_seen = 0;
+    // the format in progress
+    std::vector<long long> tile_off;                    // [tiles + 1]: the first text byte of every tile (empty: no format begun)
+    int64_t next_tile = 0, format_length = 0;
+    char format_base = 0;
+    double parse_ms = 0.0, add_ms = 0.0, format_ms = 0.0;
+};
+
+namespace bmk {
+
+int ensure(dm_bedmerge* h, int which, size_t bytes) {
+    if (h->cap[which] >= bytes && h->buf[which]) return DM_OK;
+    if (h->buf[which]) (void)hipFree(h->buf[which]);
+    h->buf[which] = nullptr;
+    h->cap[which] = 0;
+    const size_t want = bytes + (bytes >> 2) + 256;                  // grow-only, a quarter ahead
+    if (hipMalloc(&h->buf[which], want) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(DM_ENOMEM, "dm_bedmerge: hipMalloc(%zu) failed", want);
+    }
+    h->cap[which] = want;
+    return DM_OK;
+}
+
+template <class T>
+T* ptr(dm_bedmerge* h, int which) { return static_cast<T*>(h->buf[which]); }
+
+constexpr int64_t MAX_BYTES = int64_t(1) << 40;
+constexpr int64_t MAX_RECORDS = 0x7fffffffLL;
+
+int record_buffers(dm_bedmerge* h, int64_t n) {
+    using B = dm_bedmerge;
+    int rc;
+    for (int which : {int(B::POS), int(B::COV), int(B::MOD)})
+        if ((rc = ensure(h, which, size_t(n) * 4)) != DM_OK) return rc;
+    for (int which : {int(B::STRAND), int(B::STATUS)})
+        if ((rc = ensure(h, which, size_t(n))) != DM_OK) return rc;
+    return DM_OK;
+}
+
+int add_time(dm_bedmerge* h, int first, double& into) {
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, h->ev[first], h->ev[first + 1]));
+    into += double(ms);
+    return DM_OK;
+}
+
+// the n records on the device, whose largest position and coverage are max_pos and max_cov -> the tables
+int add_device_records(dm_bedmerge* h, int64_t n, int64_t max_pos, int64_t max_cov) {
+    using B = dm_bedmerge;
+    if (n == 0) return DM_OK;
+    if (h->cov_bound + max_cov >= (int64_t(1) << 31))
+        return fail(DM_EINVAL, "dm_bedmerge: the largest coverages of this contig's files sum to %lld (2^31 or more): the int32 tables cannot hold them",
+                    (long long)(h->cov_bound + max_cov));
+    int rc;
+    if ((rc = dm_summary_sync(h->plus)) != DM_OK || (rc = dm_summary_sync(h->minus)) != DM_OK) return rc;
+    if (!h->fixed && max_pos + 1 > dm_summary_length(h->plus)) {     // the table grows to the largest position + 1 of the file
+        if ((rc = dm_summary_grow(h->plus, max_pos + 1)) != DM_OK || (rc = dm_summary_grow(h->minus, max_pos + 1)) != DM_OK) return rc;
+    }
+    const int64_t length = dm_summary_length(h->plus);
+    if (dm_summary_length(h->minus) != length || max_pos >= length)
+        return fail(DM_ESTATE, "dm_bedmerge: tables of %lld and %lld positions, largest position %lld", (long long)length, (long long)dm_summary_length(h->minus), (long long)max_pos);
+    hipStream_t s = h->xy->stream;
+    const dim3 grid{unsigned(std::min<int64_t>((n + THREADS - 1) / THREADS, MAX_BLOCKS))};
+    HIP_TRY(hipEventRecord(h->ev[2], s));
+    hipLaunchKernelGGL(bm_add_kernel, grid, dim3(THREADS), 0, s, ptr<const int>(h, B::POS), ptr<const int>(h, B::COV), ptr<const int>(h, B::MOD),
+                       ptr<const unsigned char>(h, B::STRAND), (long long)n, static_cast<int*>(dm_summary_device_ptr(h->plus)),
+                       static_cast<int*>(dm_summary_device_ptr(h->minus)), (long long)length);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[3], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = add_time(h, 2, h->add_ms)) != DM_OK) return rc;
+    h->cov_bound += max_cov;
+    h->lines_seen += n;
+    h->tile_off.clear();                                              // a format begun before this add is over
+    return DM_OK;
+}
+
+}  // namespace bmk
+
+extern "C" {
+
+int dm_bedmerge_tile_positions(void) { return bmk::TILE_POS; }
+
+void dm_bedmerge_destroy(dm_bedmerge* h) {
+    if (!h) return;
+    if (h->xy) {
+        (void)hipSetDevice(h->xy->device);
+        (void)hipStreamSynchronize(h->xy->stream);
+    }
+    for (void* b : h->buf)
+        if (b) (void)hipFree(b);
+    for (hipEvent_t e : h->ev)
+        if (e) (void)hipEventDestroy(e);
+    dm_xy_destroy(h->xy);
+    delete h;
+}
+
+dm_bedmerge* dm_bedmerge_create(int device) {
+    dm_xyrows* xy = dm_xy_create(device);
+    if (!xy) return nullptr;
+    dm_bedmerge* h = new dm_bedmerge;
+    h->xy = xy;
+    bool ok = true;
+    for (hipEvent_t& e : h->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+    ok = ok && bmk::ensure(h, dm_bedmerge::STAT, bmk::N_STAT * 8) == DM_OK && bmk::ensure(h, dm_bedmerge::OUT, 16) == DM_OK;
+    if (!ok) {
+        (void)hipGetLastError();
+        fail(DM_EDEVICE, "dm_bedmerge_create: events or counters on device %d", device);
+        dm_bedmerge_destroy(h);
+        return nullptr;
+    }
+    return h;
+}
+
+int dm_bedmerge_open(dm_bedmerge* h, dm_summary* plus, dm_summary* minus, const char* contig_name, int fixed_length) {
+    if (!h) return fail(DM_EINVAL, "null handle");
+    h->plus = h->minus = nullptr;
+    h->tile_off.clear();
+    h->n_records = 0;
+    if (!plus || !minus || plus == minus) return fail(DM_EINVAL, "dm_bedmerge_open: two tables, one per strand");
+    if (plus->device != h->xy->device || minus->device != h->xy->device) return fail(DM_EINVAL, "dm_bedmerge_open: the tables are on another device than the handle (%d)", h->xy->device);
+    const int64_t length = dm_summary_length(plus);
+    if (length != dm_summary_length(minus) || length < 1 || length > bmk::MAX_LENGTH)
+        return fail(DM_EINVAL, "dm_bedmerge_open: tables of %lld and %lld positions (equal, 1 to 2^31 - 1)", (long long)length, (long long)dm_summary_length(minus));
+    if (!bmk::set_name(h->name, contig_name)) return fail(DM_EINVAL, "dm_bedmerge_open: a contig name of 1 to %d printable bytes", bmk::MAX_NAME);
+    h->plus = plus;
+    h->minus = minus;
+    h->fixed = fixed_length != 0;
+    h->cov_bound = 0;
+    h->lines_seen = 0;
+    return DM_OK;
+}
+
+int64_t dm_bedmerge_parse_host(const char* text, int64_t n_bytes, const char* contig_name, int64_t table_length, int32_t* pos, uint8_t* strand, int32_t* cov, int32_t* mod,
+                               int64_t cap, int32_t* flag, int64_t* first_bad_line) {
+    if (n_bytes < 0 || (n_bytes > 0 && !text) || cap < 0 || (cap > 0 && (!pos || !strand || !cov || !mod))) return fail(DM_EINVAL, "dm_bedmerge_parse_host: null argument");
+    bmk::Name name = {};
+    if (!bmk::set_name(name, contig_name)) return fail(DM_EINVAL, "dm_bedmerge_parse_host: a contig name of 1 to %d printable bytes", bmk::MAX_NAME);
+    const long long limit = (table_length < 0 || table_length > bmk::MAX_LENGTH) ? bmk::MAX_LENGTH : table_length;
+    int64_t bad = 0;
+    const int64_t rows = bmk::parse_text(text, n_bytes, name, limit, pos, strand, cov, mod, cap, &bad);
+    if (flag) *flag = bad != 0;
+    if (first_bad_line) *first_bad_line = bad ? bad : -1;
+    return rows;
+}
+
+int64_t dm_bedmerge_format_host(const char* contig_name, char base, int64_t first_pos, int64_t length, const int32_t* cov_plus, const int32_t* mod_plus,
+                                const int32_t* cov_minus, const int32_t* mod_minus, char* out, int64_t cap, int64_t* n_lines) {
+    bmk::Name name = {};
+    if (!bmk::set_name(name, contig_name)) return fail(DM_EINVAL, "dm_bedmerge_format_host: a contig name of 1 to %d printable bytes", bmk::MAX_NAME);
+    if (first_pos < 0 || length < 0 || first_pos + length > bmk::MAX_LENGTH || cap < 0)
+        return fail(DM_EINVAL, "dm_bedmerge_format_host: positions %lld .. +%lld (inside 0 .. 2^31 - 2)", (long long)first_pos, (long long)length);
+    if ((cov_plus == nullptr) != (mod_plus == nullptr) || (cov_minus == nullptr) != (mod_minus == nullptr))
+        return fail(DM_EINVAL, "dm_bedmerge_format_host: a strand is given by both of its tables or by neither");
+    int64_t bad = -1;
+    const int64_t bytes = bmk::format_tables(name, base, first_pos, length, cov_plus, mod_plus, cov_minus, mod_minus, out, cap, n_lines, &bad);
+    if (bytes < 0) return fail(DM_EINVAL, "dm_bedmerge_format_host: the sums of position %lld are outside 0 <= modified <= coverage", (long long)(first_pos + bad));
+    return bytes;
+}
+
+int dm_bedmerge_add_text(dm_bedmerge* h, const char* text, int64_t n_bytes, int64_t* n_lines, int32_t* flag, int64_t* first_bad_line) {
+    using B = dm_bedmerge;
+    if (!h) return fail(DM_EINVAL, "null handle");
+    if (n_lines) *n_lines = 0;
+    if (flag) *flag = 0;
+    if (first_bad_line) *first_bad_line = -1;
+    if (!h->plus) return fail(DM_ESTATE, "dm_bedmerge_add_text: no contig");
+    if (n_bytes < 0 || n_bytes >= bmk::MAX_BYTES || (n_bytes > 0 && !text)) return fail(DM_EINVAL, "dm_bedmerge_add_text: %lld bytes of text", (long long)n_bytes);
+    h->n_records = 0;
+    if (n_bytes == 0) return DM_OK;
+    HIP_TRY(hipSetDevice(h->xy->device));
+    const bool add_newline = text[n_bytes - 1] != '\n';
+    const int64_t n = n_bytes + (add_newline ? 1 : 0);
+    const int64_t tiles = (n + xlk::TILE - 1) / xlk::TILE;
+    int rc;
+    if ((rc = bmk::ensure(h, B::TEXT, size_t(tiles) * xlk::TILE)) != DM_OK) return rc;     // whole 16-byte groups behind every lane offset below n
+    if ((rc = bmk::ensure(h, B::COUNT, size_t(tiles + 1) * 8)) != DM_OK) return rc;
+    hipStream_t s = h->xy->stream;
+    char* d_text = bmk::ptr<char>(h, B::TEXT);
+    long long* d_count = bmk::ptr<long long>(h, B::COUNT);
+    unsigned long long* d_stat = bmk::ptr<unsigned long long>(h, B::STAT);
+    static const char newline = '\n';
+    HIP_TRY(hipMemcpyAsync(d_text, text, size_t(n_bytes), hipMemcpyHostToDevice, s));
+    if (add_newline) HIP_TRY(hipMemcpyAsync(d_text + n_bytes, &newline, 1, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_stat, 0, bmk::N_STAT * 8, s));
+    const dim3 tile_grid{unsigned(tiles)}, block{xlk::THREADS};
+    HIP_TRY(hipEventRecord(h->ev[0], s));
+    hipLaunchKernelGGL(xlk::xl_count_kernel, tile_grid, block, 0, s, d_text, (long long)n, d_count);
+    HIP_TRY(hipGetLastError());
+    if ((rc = xyk::scan_in_place(h->xy, d_count, tiles)) != DM_OK) return rc;
+    long long rows = 0;
+    HIP_TRY(hipMemcpyAsync(&rows, d_count + tiles, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (rows < 1 || rows > n) return fail(DM_ESTATE, "dm_bedmerge_add_text: %lld lines in %lld bytes", rows, (long long)n);
+    if (rows > bmk::MAX_RECORDS) return fail(DM_EINVAL, "dm_bedmerge_add_text: %lld lines (at most %lld)", rows, (long long)bmk::MAX_RECORDS);
+    if ((rc = bmk::record_buffers(h, rows)) != DM_OK) return rc;
+    if ((rc = bmk::ensure(h, B::START, size_t(rows + 1) * 8)) != DM_OK) return rc;
+    long long* d_start = bmk::ptr<long long>(h, B::START);
+    unsigned char* d_status = bmk::ptr<unsigned char>(h, B::STATUS);
+    long long* d_out = bmk::ptr<long long>(h, B::OUT);
+    const long long limit = h->fixed ? (long long)dm_summary_length(h->plus) : bmk::MAX_LENGTH;
+    const dim3 row_grid{unsigned((rows + bmk::THREADS - 1) / bmk::THREADS)};
+    hipLaunchKernelGGL(xlk::xl_lines_kernel, tile_grid, block, 0, s, d_text, (long long)n, d_count, rows, d_start);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(bmk::bm_parse_kernel, row_grid, dim3(bmk::THREADS), 0, s, d_text, d_start, rows, h->name, limit, bmk::ptr<int>(h, B::POS), bmk::ptr<int>(h, B::COV),
+                       bmk::ptr<int>(h, B::MOD), bmk::ptr<unsigned char>(h, B::STRAND), d_status, d_stat);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(xlk::xl_first_kernel, dim3(1), dim3(xyk::SUM_THREADS), 0, s, d_status, rows, d_out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[1], s));
+    long long first = -1;
+    unsigned long long stat[bmk::N_STAT] = {};
+    HIP_TRY(hipMemcpyAsync(&first, d_out, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(stat, d_stat, sizeof stat, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = bmk::add_time(h, 0, h->parse_ms)) != DM_OK) return rc;
+    if (n_lines) *n_lines = rows;
+    if (first >= 0) {                                                // outside the grammar: nothing of this text is added
+        if (flag) *flag = 1;
+        if (first_bad_line) *first_bad_line = first + 1;
+        return DM_OK;
+    }
+    h->n_records = rows;
+    return bmk::add_device_records(h, rows, int64_t(stat[bmk::S_MAXPOS]), int64_t(stat[bmk::S_MAXCOV]));
+}
+
+int dm_bedmerge_add_records(dm_bedmerge* h, int64_t n, const int32_t* pos, const uint8_t* strand, const int32_t* cov, const int32_t* mod) {
+    using B = dm_bedmerge;
+    if (!h) return fail(DM_EINVAL, "null handle");
+    if (!h->plus) return fail(DM_ESTATE, "dm_bedmerge_add_records: no contig");
+    if (n < 0 || n > bmk::MAX_RECORDS || (n > 0 && (!pos || !strand || !cov || !mod))) return fail(DM_EINVAL, "dm_bedmerge_add_records: %lld records", (long long)n);
+    const int64_t limit = h->fixed ? dm_summary_length(h->plus) : int64_t(bmk::MAX_LENGTH);
+    int64_t max_pos = 0, max_cov = 0;
+    for (int64_t i = 0; i < n; ++i) {                                // what the kernel indexes with, checked before any launch
+        if (pos[i] < 0 || pos[i] >= limit || strand[i] > 1 || cov[i] < 0 || mod[i] < 0 || mod[i] > cov[i])
+            return fail(DM_EINVAL, "dm_bedmerge_add_records: record %lld (position %d of %lld, strand %d, coverage %d, modified %d)", (long long)i, pos[i], (long long)limit,
+                        int(strand[i]), cov[i], mod[i]);
+        max_pos = std::max<int64_t>(max_pos, pos[i]);
+        max_cov = std::max<int64_t>(max_cov, cov[i]);
+    }
+    h->n_records = 0;
+    if (n == 0) return DM_OK;
+    HIP_TRY(hipSetDevice(h->xy->device));
+    int rc = bmk::record_buffers(h, n);
+    if (rc) return rc;
+    hipStream_t s = h->xy->stream;
+    HIP_TRY(hipMemcpyAsync(h->buf[B::POS], pos, size_t(n) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->buf[B::COV], cov, size_t(n) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->buf[B::MOD], mod, size_t(n) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->buf[B::STRAND], strand, size_t(n), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    h->n_records = n;
+    return bmk::add_device_records(h, n, max_pos, max_cov);
+}
+
+int dm_bedmerge_fetch_records(dm_bedmerge* h, int32_t* pos, uint8_t* strand, int32_t* cov, int32_t* mod) {
+    using B = dm_bedmerge;
+    if (!h) return fail(DM_EINVAL, "null handle");
+    const size_t n = size_t(h->n_records);
+    if (n == 0) return DM_OK;
+    HIP_TRY(hipSetDevice(h->xy->device));
+    if (pos) HIP_TRY(hipMemcpy(pos, h->buf[B::POS], n * 4, hipMemcpyDeviceToHost));
+    if (cov) HIP_TRY(hipMemcpy(cov, h->buf[B::COV], n * 4, hipMemcpyDeviceToHost));
+    if (mod) HIP_TRY(hipMemcpy(mod, h->buf[B::MOD], n * 4, hipMemcpyDeviceToHost));
+    if (strand) HIP_TRY(hipMemcpy(strand, h->buf[B::STRAND], n, hipMemcpyDeviceToHost));
+    return DM_OK;
+}
+
+int dm_bedmerge_format_begin(dm_bedmerge* h, char base, int64_t* n_lines, int64_t* n_bytes, int64_t* largest_tile_bytes) {
+    using B = dm_bedmerge;
+    if (!h) return fail(DM_EINVAL, "null handle");
+    h->tile_off.clear();
+    if (n_lines) *n_lines = 0;
+    if (n_bytes) *n_bytes = 0;
+    if (largest_tile_bytes) *largest_tile_bytes = 0;
+    if (!h->plus) return fail(DM_ESTATE, "dm_bedmerge_format_begin: no contig");
+    if ((unsigned char)base < 0x21 || (unsigned char)base > 0x7e) return fail(DM_EINVAL, "dm_bedmerge_format_begin: base byte %d", int(base));
+    HIP_TRY(hipSetDevice(h->xy->device));
+    int rc;
+    if ((rc = dm_summary_sync(h->plus)) != DM_OK || (rc = dm_summary_sync(h->minus)) != DM_OK) return rc;
+    const int64_t length = dm_summary_length(h->plus);
+    if (length != dm_summary_length(h->minus) || length < 1 || length > bmk::MAX_LENGTH)
+        return fail(DM_ESTATE, "dm_bedmerge_format_begin: tables of %lld and %lld positions", (long long)length, (long long)dm_summary_length(h->minus));
+    const int64_t tiles = (length + bmk::TILE_POS - 1) / bmk::TILE_POS;
+    if ((rc = bmk::ensure(h, B::TBYTES, size_t(tiles + 1) * 8)) != DM_OK || (rc = bmk::ensure(h, B::TLINES, size_t(tiles + 1) * 8)) != DM_OK) return rc;
+    hipStream_t s = h->xy->stream;
+    long long* d_bytes = bmk::ptr<long long>(h, B::TBYTES);
+    long long* d_lines = bmk::ptr<long long>(h, B::TLINES);
+    unsigned long long* d_stat = bmk::ptr<unsigned long long>(h, B::STAT);
+    HIP_TRY(hipMemsetAsync(d_stat + bmk::S_BADSUM, 0, 8, s));
+    HIP_TRY(hipEventRecord(h->ev[4], s));
+    hipLaunchKernelGGL(bmk::bm_length_kernel, dim3(unsigned(tiles)), dim3(bmk::THREADS), 0, s, h->name, base, static_cast<const int*>(dm_summary_device_ptr(h->plus)),
+                       static_cast<const int*>(dm_summary_device_ptr(h->minus)), (long long)length, d_bytes, d_lines, d_stat);
+    HIP_TRY(hipGetLastError());
+    if ((rc = xyk::scan_in_place(h->xy, d_bytes, tiles)) != DM_OK || (rc = xyk::scan_in_place(h->xy, d_lines, tiles)) != DM_OK) return rc;
+    HIP_TRY(hipEventRecord(h->ev[5], s));
+    std::vector<long long> off(size_t(tiles) + 1);
+    long long lines = 0;
+    unsigned long long bad = 0;
+    HIP_TRY(hipMemcpyAsync(off.data(), d_bytes, off.size() * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&lines, d_lines + tiles, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&bad, d_stat + bmk::S_BADSUM, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = bmk::add_time(h, 4, h->format_ms)) != DM_OK) return rc;
+    if (bad) return fail(DM_EINVAL, "dm_bedmerge_format_begin: the sums of %llu tiles left 0 <= modified <= coverage (int32 overflow through repeated keys)", bad);
+    long long largest = 0;
+    for (int64_t t = 0; t < tiles; ++t) {
+        if (off[t + 1] < off[t]) return fail(DM_ESTATE, "dm_bedmerge_format_begin: descending tile offsets");
+        largest = std::max(largest, off[t + 1] - off[t]);
+    }
+    h->tile_off.swap(off);
+    h->next_tile = 0;
+    h->format_length = length;
+    h->format_base = base;
+    if (n_lines) *n_lines = lines;
+    if (n_bytes) *n_bytes = h->tile_off[size_t(tiles)];
+    if (largest_tile_bytes) *largest_tile_bytes = largest;
+    return DM_OK;
+}
+
+// -> 1: text was returned and more follows, 0: this was the last run (or there is no text), < 0: an error
+int dm_bedmerge_format_next(dm_bedmerge* h, char* out, int64_t cap, int64_t* got) {
+    using B = dm_bedmerge;
+    if (!h) return fail(DM_EINVAL, "null handle");
+    if (got) *got = 0;
+    if (h->tile_off.empty() || !h->plus) return fail(DM_ESTATE, "dm_bedmerge_format_next: no format begun (or the tables changed since)");
+    if (cap < 0 || (cap > 0 && !out) || !got) return fail(DM_EINVAL, "dm_bedmerge_format_next: null argument");
+    const int64_t tiles = int64_t(h->tile_off.size()) - 1;
+    const std::vector<long long>& off = h->tile_off;
+    int64_t t0 = h->next_tile;
+    while (t0 < tiles && off[size_t(t0) + 1] == off[size_t(t0)]) ++t0;                     // tiles without text
+    if (t0 >= tiles) {
+        h->next_tile = tiles;
+        return 0;
+    }
+    if (off[size_t(t0) + 1] - off[size_t(t0)] > cap)
+        return fail(DM_EINVAL, "dm_bedmerge_format_next: a buffer of %lld bytes does not hold the tile at position %lld: %lld bytes are needed", (long long)cap,
+                    (long long)(t0 * bmk::TILE_POS), (long long)(off[size_t(t0) + 1] - off[size_t(t0)]));
+    // the last tile whose end still fits: off is ascending
+    const int64_t t1 = int64_t(std::upper_bound(off.begin() + t0 + 1, off.end(), off[size_t(t0)] + cap) - off.begin()) - 1;
+    const int64_t bytes = off[size_t(t1)] - off[size_t(t0)];
+    if (t1 <= t0 || bytes <= 0 || bytes > cap) return fail(DM_ESTATE, "dm_bedmerge_format_next: tiles %lld .. %lld of %lld bytes", (long long)t0, (long long)t1, (long long)bytes);
+    if (dm_summary_length(h->plus) != h->format_length || dm_summary_length(h->minus) != h->format_length)
+        return fail(DM_ESTATE, "dm_bedmerge_format_next: the tables changed since format_begin");
+    HIP_TRY(hipSetDevice(h->xy->device));
+    int rc;
+    if ((rc = bmk::ensure(h, B::FTEXT, size_t(bytes))) != DM_OK) return rc;
+    hipStream_t s = h->xy->stream;
+    HIP_TRY(hipEventRecord(h->ev[4], s));
+    hipLaunchKernelGGL(bmk::bm_write_kernel, dim3(unsigned(t1 - t0)), dim3(bmk::THREADS), 0, s, h->name, h->format_base, static_cast<const int*>(dm_summary_device_ptr(h->plus)),
+                       static_cast<const int*>(dm_summary_device_ptr(h->minus)), (long long)h->format_length, bmk::ptr<const long long>(h, B::TBYTES), (long long)t0,
+                       bmk::ptr<char>(h, B::FTEXT));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[5], s));
+    HIP_TRY(hipMemcpyAsync(out, h->buf[B::FTEXT], size_t(bytes), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = bmk::add_time(h, 4, h->format_ms)) != DM_OK) return rc;
+    *got = bytes;
+    h->next_tile = t1;
+    while (h->next_tile < tiles && off[size_t(h->next_tile) + 1] == off[size_t(h->next_tile)]) ++h->next_tile;
+    return h->next_tile < tiles ? 1 : 0;
+}
+
+int dm_bedmerge_times(dm_bedmerge* h, double* parse_ms, double* add_ms, double* format_ms) {
+    if (!h) return fail(DM_EINVAL, "null handle");
+    if (parse_ms) *parse_ms = h->parse_ms;
+    if (add_ms) *add_ms = h->add_ms;
+    if (format_ms) *format_ms = h->format_ms;
+    return DM_OK;
+}
+
+}  // extern "C"

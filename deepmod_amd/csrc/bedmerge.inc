@@ -1,0 +1,216 @@
+// bedmerge.inc — `merge`, the line routines (plain C++: part of offline.hip through bedmerge.hip.inc, and compiled by g++ as it stands:
+// tests/merge_asan_driver.cpp).  One BED line -> its (position, strand, coverage, modified) record, and one (position, strand) of the summed
+// tables -> its line in the dialect of DeepMod_tools/sum_chr_mod.py:63.  The kernels of bedmerge.hip.inc and the host entry points below run
+// the same two routines, so the device and the host cannot disagree on a line.
+//
+// Grammar of a line (parse_line; the '\n' is not part of it): fields of printable bytes (0x21 - 0x7e) separated by runs of one or more ' ' /
+// '\t', leading and trailing runs allowed; at least 12 fields; field 0 is the contig's name byte for byte; fields 1, 9, 11 (position,
+// coverage, modified) are 1 - 10 digits with a value <= 2^31 - 1; field 5 is '+' or '-'; modified <= coverage; position < limit (the table
+// length, at most 2^31 - 1 so that position + 1 is an int32).  Fields 3 and 10 are not looked at: sum_chr_mod.py never reads them.  Inside
+// are what detect writes (single spaces, one before the newline), what sum_chr_mod.py writes (two spaces after the strand) and what
+// hm_cluster_predict.py writes (13 fields); outside are '\r', a blank line, another contig, a sign, 11 fields, 11 digits.
+//
+// A line of the output (emit_line): '%s %d %d %s %d %s  %d %d 0,0,0 %d %d %d\n' % (chr, pos, pos + 1, Base, min(cov, 1000), strand, pos,
+// pos + 1, cov, pct, mod), written for mod > 0 only, '+' before '-' at one position.  pct = (100 * mod) / cov in 64-bit integers: with
+// 0 < mod <= cov < 2^31 the product is below 2^38, exact as a double, and the double quotient truncates to the integer quotient (a quotient
+// that is an integer is exact; any other lies at least 1 / cov > 2^-31 from one, far more than an ulp of a number below 101), so it is
+// Python's int(mod * 100 / cov).
+#pragma once
+#include <cstdint>
+#include <cstring>
+
+#if defined(__HIPCC__)
+#define BM_HD __host__ __device__
+#else
+#define BM_HD
+#endif
+
+namespace bmk {
+
+constexpr int MAX_NAME = 255;
+constexpr long long MAX_LENGTH = 0x7fffffffLL;      // positions 0 .. 2^31 - 2
+constexpr int TILE_POS = 1024;                      // positions of one format tile (dm_bedmerge_tile_positions)
+
+struct Name {
+    char s[MAX_NAME + 1];
+    int n;
+};
+struct Rec {
+    int pos, cov, mod;
+    unsigned char strand;                           // 0 '+', 1 '-'
+};
+
+// One line p[0 .. n) (without its '\n') -> its record; false: outside the grammar (r is then unspecified).  Reads p[0 .. n) only.
+BM_HD inline bool parse_line(const char* p, const long long n, const Name& name, const long long limit, Rec& r) {
+    long long i = 0;
+    int f = 0;
+    long long num[3] = {0, 0, 0};                   // fields 1, 9, 11
+    r.strand = 0;
+    for (;;) {
+        while (i < n && (p[i] == ' ' || p[i] == '\t')) ++i;
+        if (i >= n) break;
+        const long long b = i;
+        for (; i < n; ++i) {
+            const unsigned char c = (unsigned char)p[i];
+            if (c == ' ' || c == '\t') break;
+            if (c < 0x21 || c > 0x7e) return false;
+        }
+        const long long len = i - b;
+        if (f == 0) {
+            if (len != name.n) return false;
+            for (int j = 0; j < name.n; ++j)
+                if (p[b + j] != name.s[j]) return false;
+        } else if (f == 1 || f == 9 || f == 11) {
+            if (len > 10) return false;
+            long long v = 0;
+            for (long long j = b; j < i; ++j) {
+                if (p[j] < '0' || p[j] > '9') return false;
+                v = v * 10 + (p[j] - '0');
+            }
+            if (v > 0x7fffffffLL) return false;
+            num[f == 1 ? 0 : (f == 9 ? 1 : 2)] = v;
+        } else if (f == 5) {
+            if (len != 1 || (p[b] != '+' && p[b] != '-')) return false;
+            r.strand = p[b] == '-' ? 1 : 0;
+        }
+        if (f < 12) ++f;
+    }
+    if (f < 12) return false;
+    if (num[2] > num[1] || num[0] >= limit) return false;
+    r.pos = int(num[0]);
+    r.cov = int(num[1]);
+    r.mod = int(num[2]);
+    return true;
+}
+
+struct CountSink {
+    long long n = 0;
+    BM_HD void put(char) { ++n; }
+};
+struct WriteSink {
+    char* p;
+    BM_HD void put(const char c) { *p++ = c; }
+};
+
+template <class Sink>
+BM_HD inline void put_uint(Sink& s, unsigned long long v) {        // the decimal digits of v, most significant first
+    unsigned long long p = 1;
+    while (p <= v / 10) p *= 10;
+    while (p) {
+        const unsigned long long d = v / p;
+        s.put(char('0' + int(d)));
+        v -= d * p;
+        p /= 10;
+    }
+}
+
+// The line of (pos, strand) with the sums cov, mod (0 < mod <= cov).  The same routine counts and writes: the two cannot disagree on a length.
+template <class Sink>
+BM_HD inline void emit_line(Sink& s, const Name& name, const char base, const long long pos, const int strand, const long long cov, const long long mod) {
+    for (int j = 0; j < name.n; ++j) s.put(name.s[j]);
+    s.put(' ');
+    put_uint(s, (unsigned long long)pos);
+    s.put(' ');
+    put_uint(s, (unsigned long long)(pos + 1));
+    s.put(' ');
+    s.put(base);
+    s.put(' ');
+    put_uint(s, (unsigned long long)(cov < 1000 ? cov : 1000));
+    s.put(' ');
+    s.put(strand ? '-' : '+');
+    s.put(' ');
+    s.put(' ');
+    put_uint(s, (unsigned long long)pos);
+    s.put(' ');
+    put_uint(s, (unsigned long long)(pos + 1));
+    s.put(' ');
+    s.put('0');
+    s.put(',');
+    s.put('0');
+    s.put(',');
+    s.put('0');
+    s.put(' ');
+    put_uint(s, (unsigned long long)cov);
+    s.put(' ');
+    put_uint(s, (unsigned long long)(cov > 0 ? (100 * mod) / cov : 0));
+    s.put(' ');
+    put_uint(s, (unsigned long long)mod);
+    s.put('\n');
+}
+
+// what a sum has to be for the formatter (and for an exact percentage); the overflow guard of the adds keeps the sums here
+BM_HD inline bool sum_ok(const long long cov, const long long mod) { return cov >= 0 && mod >= 0 && mod <= cov; }
+
+// The lines of table position q (index i of the arrays; a null strand holds nothing): '+' first.  -> lines emitted
+template <class Sink>
+BM_HD inline int emit_position(Sink& s, const Name& name, const char base, const long long q, const long long i, const int32_t* cov_p, const int32_t* mod_p,
+                               const int32_t* cov_m, const int32_t* mod_m) {
+    int lines = 0;
+    if (mod_p && mod_p[i] > 0) {
+        emit_line(s, name, base, q, 0, cov_p[i], mod_p[i]);
+        ++lines;
+    }
+    if (mod_m && mod_m[i] > 0) {
+        emit_line(s, name, base, q, 1, cov_m[i], mod_m[i]);
+        ++lines;
+    }
+    return lines;
+}
+
+inline bool set_name(Name& name, const char* contig_name) {
+    const size_t n = contig_name ? std::strlen(contig_name) : 0;
+    if (n < 1 || n > size_t(MAX_NAME)) return false;
+    for (size_t j = 0; j < n; ++j)
+        if ((unsigned char)contig_name[j] < 0x21 || (unsigned char)contig_name[j] > 0x7e) return false;
+    std::memset(name.s, 0, sizeof name.s);
+    std::memcpy(name.s, contig_name, n);
+    name.n = int(n);
+    return true;
+}
+
+// The text [0, n_bytes) line by line (a last line without '\n' ends with the text) -> its records, as many as fit `cap`; -> lines.
+// *bad: the first line outside the grammar (1-based), 0: none.
+inline int64_t parse_text(const char* text, const int64_t n_bytes, const Name& name, const long long limit, int32_t* pos, uint8_t* strand, int32_t* cov, int32_t* mod,
+                          const int64_t cap, int64_t* bad) {
+    int64_t rows = 0;
+    *bad = 0;
+    for (int64_t b = 0; b < n_bytes;) {
+        const void* nl = std::memchr(text + b, '\n', size_t(n_bytes - b));
+        const int64_t e = nl ? static_cast<const char*>(nl) - text : n_bytes;
+        Rec v = {0, 0, 0, 0};
+        const bool ok = parse_line(text + b, e - b, name, limit, v);
+        if (!ok && *bad == 0) *bad = rows + 1;
+        if (rows < cap) {
+            pos[rows] = ok ? v.pos : 0;
+            cov[rows] = ok ? v.cov : 0;
+            mod[rows] = ok ? v.mod : 0;
+            strand[rows] = ok ? v.strand : 0;
+        }
+        ++rows;
+        b = e + 1;
+    }
+    return rows;
+}
+
+// The text of positions first_pos .. first_pos + length - 1 from the four tables: counted first; written only if it fits `cap`.
+// -> bytes of the text, -1: a sum outside 0 <= mod <= cov (*bad_index: its index).
+inline int64_t format_tables(const Name& name, const char base, const int64_t first_pos, const int64_t length, const int32_t* cov_p, const int32_t* mod_p,
+                             const int32_t* cov_m, const int32_t* mod_m, char* out, const int64_t cap, int64_t* lines, int64_t* bad_index) {
+    CountSink count;
+    int64_t n_lines = 0;
+    for (int64_t i = 0; i < length; ++i) {
+        if ((mod_p && !sum_ok(cov_p[i], mod_p[i])) || (mod_m && !sum_ok(cov_m[i], mod_m[i]))) {
+            *bad_index = i;
+            return -1;
+        }
+        n_lines += emit_position(count, name, base, first_pos + i, i, cov_p, mod_p, cov_m, mod_m);
+    }
+    if (lines) *lines = n_lines;
+    if (out && cap >= count.n) {
+        WriteSink w{out};
+        for (int64_t i = 0; i < length; ++i) emit_position(w, name, base, first_pos + i, i, cov_p, mod_p, cov_m, mod_m);
+    }
+    return count.n;
+}
+
+}  // namespace bmk

@@ -744,6 +744,50 @@ int64_t dm_siteperf_parse_host(const char* text, int64_t n_bytes, const char* co
 int dm_siteperf_tile_bytes(void);
 int dm_siteperf_times(dm_siteperf* h, double* parse_ms, double* count_ms);
 
+/* ---------------------------------------------------------------------------- merge -- */
+/* Sum the BED files of several runs of one contig and write the merged file (DeepMod_tools/sum_chr_mod.py; csrc/bedmerge.hip.inc, bedmerge.inc,
+ * DESIGN.md 17): lines -> (position, strand, coverage, modified) -> int32 sums in two dm_summary tables (the caller's: '+' and '-', of equal
+ * length, at most 2^31 - 1 positions; the handles dm_cluster_sites takes) -> the text, in runs of whole tiles.  Integer atomics for the sums, no
+ * atomics in the text: two runs give identical bytes.  merge.merge_beds / merge.save_mod of deepmod_amd/merge.py state the semantics.
+ *   open           the tables and the contig's name (1 - 255 printable bytes).  fixed_length != 0: the tables have the contig's length, a line beyond
+ *                  it is outside the grammar; 0: the tables are grown (dm_summary_grow) to the largest position + 1 of a text before its adds.
+ *   add_text       one BED file's bytes.  Device grammar of a line: fields of printable bytes (0x21 - 0x7e) separated by runs of one or more ' ' /
+ *                  '\t', leading and trailing runs allowed, '\n' at the end (a missing last one is supplied); at least 12 fields; field 0 = the
+ *                  contig's name byte for byte; fields 1, 9, 11 (position, coverage, modified) of 1 - 10 digits, <= 2^31 - 1; field 5 '+' or '-';
+ *                  modified <= coverage; position < the table length when it is fixed, <= 2^31 - 2 otherwise; fields 3 and 10 are not looked at.
+ *                  Inside: what detect writes (a space before the newline), what sum_chr_mod.py writes (two spaces after the strand), what
+ *                  hm_cluster_predict.py writes (13 fields).  Outside: '\r', a blank line, another contig, a sign, 11 fields, 11 digits.  A text with
+ *                  a line outside it sets *flag and *first_bad_line (1-based) and adds NOTHING: the caller parses it and calls add_records.
+ *                  Per record: touch += 1, cov += coverage, mod += modified at (strand, position); two records of one text on one key both count.
+ *   add_records    the same adds from host arrays [n] (pos, cov, mod int32; strand u8 0 '+' 1 '-'), checked before any launch.
+ *                  Both refuse (DM_EINVAL, nothing added) a text or array with which the largest coverages of the contig's texts would sum to
+ *                  >= 2^31.  fetch_records: the records of the last add_text / add_records as they lie on the device.
+ *   format_begin   lines and bytes of the merged text, and the bytes of its largest tile (dm_bedmerge_tile_positions() positions each).  A line
+ *                  '%s %d %d %s %d %s  %d %d 0,0,0 %d %d %d\n' (name, pos, pos + 1, base, min(cov, 1000), strand, pos, pos + 1, cov,
+ *                  (100 * mod) / cov, mod) for every (position, strand) with mod > 0, '+' before '-' at one position.
+ *   format_next    the next run of whole tiles that fits `cap` bytes -> out, *got bytes; returns 1 while more follows, 0 after the last run,
+ *                  < 0 on error: a cap below the next tile's bytes is DM_EINVAL, and dm_last_error names the size needed.  The tables must not
+ *                  change between format_begin and the last format_next.
+ *   parse_host / format_host   the two line routines compiled for the host (no GPU needed).  parse_host -> lines, records as far as cap reaches
+ *                  (table_length < 0: none given).  format_host: tables of positions first_pos .. first_pos + length - 1 (a strand may be NULL) ->
+ *                  the bytes of the text; written only if out is given and cap holds them all.
+ *   times          ms of the parse / add / format kernels so far (HIP events). */
+typedef struct dm_bedmerge dm_bedmerge;
+dm_bedmerge* dm_bedmerge_create(int device);
+void dm_bedmerge_destroy(dm_bedmerge* h);
+int dm_bedmerge_open(dm_bedmerge* h, dm_summary* plus, dm_summary* minus, const char* contig_name, int fixed_length);
+int dm_bedmerge_add_text(dm_bedmerge* h, const char* text, int64_t n_bytes, int64_t* n_lines, int32_t* flag, int64_t* first_bad_line);
+int dm_bedmerge_add_records(dm_bedmerge* h, int64_t n, const int32_t* pos, const uint8_t* strand, const int32_t* cov, const int32_t* mod);
+int dm_bedmerge_fetch_records(dm_bedmerge* h, int32_t* pos, uint8_t* strand, int32_t* cov, int32_t* mod);
+int dm_bedmerge_format_begin(dm_bedmerge* h, char base, int64_t* n_lines, int64_t* n_bytes, int64_t* largest_tile_bytes);
+int dm_bedmerge_format_next(dm_bedmerge* h, char* out, int64_t cap, int64_t* got);
+int64_t dm_bedmerge_parse_host(const char* text, int64_t n_bytes, const char* contig_name, int64_t table_length, int32_t* pos, uint8_t* strand, int32_t* cov, int32_t* mod,
+                               int64_t cap, int32_t* flag, int64_t* first_bad_line);
+int64_t dm_bedmerge_format_host(const char* contig_name, char base, int64_t first_pos, int64_t length, const int32_t* cov_plus, const int32_t* mod_plus,
+                                const int32_t* cov_minus, const int32_t* mod_minus, char* out, int64_t cap, int64_t* n_lines);
+int dm_bedmerge_tile_positions(void);
+int dm_bedmerge_times(dm_bedmerge* h, double* parse_ms, double* add_ms, double* format_ms);
+
 #ifdef __cplusplus
 }
 #endif
