@@ -43,6 +43,16 @@ DeepMod_tools/sum_chr_mod.py for a data set that was split over several detect r
 three levels below RUNS are parsed, summed and written as RUNS/SUM.<chr>.<Base>.bed on one GPU, byte for byte the tool's file; with --clusterCpG the
 summed counters also go through the CpG-cluster stage (RUNS/SUM_clusterCpG.<chr>.C.bed, the output of generate_motif_pos.py and
 hm_cluster_predict.py on the merged file).  RUNS/SUM_merge.json lists files, lines and kernel times (deepmod_amd/merge.py).
+
+`bsperf --predFolder RUNS --truth rep1.bed,rep2.bed[,..] --Base C --outFolder O --FileID id [--chr chr1,chr2,..] [--cov 1,5,10] [--predCov 1]
+[--methylated 90] [--unmethylated 0] [--Ref genome.fa] [--clusterCpG [CKPT_PREFIX]] [--threads T]` is Step 5 of Example 3 of the reference's
+docs/Reproducibility.md, for which it ships no script: the predicted percentages of the runs below RUNS (summed as `merge` sums them) against 1 to 4
+whole-genome bisulfite bedMethyl replicates.  A site is completely methylated if its percentage is >= --methylated in every replicate,
+completely un-methylated if it is <= --unmethylated in every replicate, at a bisulfite coverage >= each --cov threshold in every replicate.  The
+truth text is parsed, joined with the counters and counted on one GPU; O/id_bsperf.txt has ROC AUC, average precision, Pearson r and RMSE per
+threshold, raw and (with --clusterCpG) after the CpG-cluster stage on the same sites; O/id_bsperf.json has every counter and curve
+(deepmod_amd/bsperf.py).  Hand in the mod_pos.* files of `detect` runs: the files `merge` and sum_chr_mod.py write drop every position whose
+modified count is 0, which are exactly the unmethylated sites.
 """
 import argparse
 import os
@@ -203,7 +213,48 @@ def build_parser():
                           '(motif CG) and hm_cluster_predict.py on the merged file, computed from the summed counters on the GPU.  CKPT_PREFIX: checkpoint '
                           'prefix of the cluster model (default: DEEPMOD_CLUSTER_MODEL)')
     mrg.set_defaults(func=mMerge)
+    bsp = sub.add_parser('bsperf', parents=[com], help='score a run against whole-genome bisulfite replicates (Reproducibility.md, Example 3, Step 5) on the GPU',
+                         description='Per contig: every *.<chr>-.<Base>.bed and *.<chr>+.<Base>.bed one to three levels below --predFolder is summed as merge sums '
+                                     'them, joined with the bedMethyl replicates of --truth and counted on one GPU.  Hand in the mod_pos.* files of detect runs: '
+                                     'the files merge and sum_chr_mod.py write drop every position whose modified count is 0, and that removes exactly the '
+                                     'unmethylated sites.  Writes <outFolder>/<FileID>_bsperf.txt (per threshold: sites scored and without a prediction, ROC AUC, '
+                                     'average precision, Pearson r, RMSE) and <outFolder>/<FileID>_bsperf.json (inputs, lines, every counter, the curves, kernel times).')
+    bsp.add_argument('--predFolder', default=None, help='folder of the runs: the BED files are searched one to three levels below it')
+    bsp.add_argument('--truth', default=None, help='1 to 4 whole-genome bisulfite bedMethyl replicates, separated by commas (11 columns; the first line is skipped)')
+    bsp.add_argument('--Base', default='C', choices=['A', 'C', 'G', 'T'], help='base of interest: names the files')
+    bsp.add_argument('--chr', default=None, help='contigs to score, separated by commas, at most 64 (default chr1..22, chrX, chrY, chrM)')
+    bsp.add_argument('--cov', default='1,5,10', help='thresholds on the bisulfite coverage of every replicate, ascending, at most 8 (default 1,5,10)')
+    bsp.add_argument('--predCov', type=int, default=1, help='least summed coverage of a predicted site (default 1)')
+    bsp.add_argument('--methylated', type=int, default=90, help='a site is completely methylated at this percentage or more in every replicate (default 90)')
+    bsp.add_argument('--unmethylated', type=int, default=0, help='a site is completely un-methylated at this percentage or less in every replicate (default 0)')
+    bsp.add_argument('--Ref', default=None, help='reference genome FASTA: fixes the contig lengths (without it a contig is as long as the largest position seen + 1)')
+    bsp.add_argument('--clusterCpG', nargs='?', const='', default=None, metavar='CKPT_PREFIX',
+                     help='--Base C with --Ref: also score the percentages of the CpG-cluster stage on the same sites, side by side with the raw ones.  '
+                          'CKPT_PREFIX: checkpoint prefix of the cluster model (default: DEEPMOD_CLUSTER_MODEL)')
+    bsp.set_defaults(func=mBsPerf)
     return parser
+
+
+def mBsPerf(args):
+    from deepmod_amd import bsperf
+    try:
+        cov = tuple(int(v) for v in args.cov.split(',') if v.strip() != '')
+    except ValueError:
+        raise SystemExit('Error: bsperf: --cov takes integers separated by commas (got %r)' % args.cov)
+    mo = {k: getattr(args, k) for k in ('predFolder', 'Base', 'outFolder', 'FileID', 'predCov', 'methylated', 'unmethylated', 'Ref', 'clusterCpG', 'threads')}
+    mo['chr'] = [c for c in (args.chr or '').split(',') if c] or None
+    mo['truth'] = [p for p in (args.truth or '').split(',') if p]
+    mo['cov'] = cov
+    if not mo['predFolder']:
+        raise SystemExit('Error: bsperf: --predFolder, the folder of the runs, is needed')
+    try:
+        bsperf.check_options(mo)
+        from deepmod_amd import _lib
+        if _lib.load().dm_device_count() < 1:
+            raise SystemExit('Error: no gfx950 GPU visible (this build has no CPU path)')
+        bsperf.bsperf(mo)
+    except bsperf.BsPerfError as exc:
+        raise SystemExit('Error: %s' % exc)
 
 
 def mMerge(args):

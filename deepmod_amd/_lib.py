@@ -205,6 +205,20 @@ SIGNATURES = [
     ("dm_bedmerge_format_host", _i64, [_c.c_char_p, _c.c_char, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _c.POINTER(_i64)]),
     ("dm_bedmerge_tile_positions", _c.c_int, []),
     ("dm_bedmerge_times", _c.c_int, [_vp, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
+    ("dm_bsperf_create", _vp, [_c.c_int, _c.c_int, _vp, _vp, _c.c_int, _vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    ("dm_bsperf_destroy", None, [_vp]),
+    ("dm_bsperf_add_truth_text", _c.c_int, [_vp, _c.c_int, _vp, _i64, _c.c_int, _vp, _c.POINTER(_i64), _c.POINTER(_c.c_int32), _c.POINTER(_i64)]),
+    ("dm_bsperf_add_truth_records", _c.c_int, [_vp, _c.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("dm_bsperf_fetch_records", _c.c_int, [_vp, _vp, _vp]),
+    ("dm_bsperf_open", _c.c_int, [_vp, _c.c_int, _vp, _vp]),
+    ("dm_bsperf_close_contig", _c.c_int, [_vp]),
+    ("dm_bsperf_fill", _c.c_int, [_vp, _c.c_int, _i64, _vp, _vp, _c.POINTER(_i64), _c.POINTER(_c.c_int32)]),
+    ("dm_bsperf_count", _c.c_int, [_vp]),
+    ("dm_bsperf_add_scores", _c.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    ("dm_bsperf_fetch", _c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("dm_bsperf_parse_host", _i64, [_vp, _i64, _c.c_int, _vp, _vp, _c.c_int, _vp, _vp, _i64, _vp, _c.POINTER(_c.c_int32), _c.POINTER(_i64)]),
+    ("dm_bsperf_tile_bytes", _c.c_int, []),
+    ("dm_bsperf_times", _c.c_int, [_vp, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
 ]
 
 

@@ -1,0 +1,650 @@
+// bsperf.hip.inc — `bsperf`, device part (part of offline.hip): the predicted percentages of a run against the bisulfite replicates of
+// docs/Reproducibility.md, Example 3, Step 5 -> the integer counters every reported score is a function of.
+//   readBed (hm_cluster_predict.py:20-41)  bs_parse_kernel    one line per lane (bsk::parse_line, bsperf.inc) -> its class and record; the classes counted per wave
+//                                          the 64-bit scan of the kept lines, bs_compact_kernel: the records in line order (position, meta: 8 B each)
+//   the replicates' dicts                  bs_fill_kernel     a record -> atomicExch into the 32-bit slot of (replicate, strand, position) of the open contig;
+//                                                             a non-zero previous value is a key that occurs twice in the replicate
+//   the join and the classes               bs_count_kernel    one sweep over (strand, position): the R truth slots, and the prediction - kind 0: coverage and
+//                                                             modified count of the two dm_summary tables, kind 1: the clustered percentage of bs_score_kernel
+// deepmod_amd/bsperf.py (HostEngine) is the numpy twin of these kernels and the statement of the semantics.
+// The text of a chunk is split as xyparse.hip.inc splits it (xl_count_kernel, the 64-bit scan, xl_lines_kernel: newline ballots over 16-byte
+// lanes).  A chunk with a line outside the grammar of bsperf.inc reports the first such line and adds nothing.
+//
+// Exactness.  Everything counted is an integer.  A block counts into a private LDS histogram of 32-bit counters (a block sees fewer than 2^32
+// sites) and adds its non-zero bins to the global 64-bit counters once; the moments and the plain counters are summed per lane, reduced per wave
+// and added with one 64-bit atomic per wave.  Integer additions commute and associate: the result does not depend on the order the atomics land
+// in, two runs give the same bytes, and they are the twin's.  x = (100 * mod) / cov in 64-bit integers is merge's percentage (bedmerge.inc).
+// A duplicate key is reported as the smallest (position, strand) that was written twice (a 64-bit atomic min): the same on every run.
+// The tables belong to the caller (dm_summary handles) and have a stream of their own: dm_summary_sync before this handle's stream touches them,
+// a stream synchronisation of this handle before a call returns.
+#pragma once
+#include "host.h"
+#include "xyrows.hip.inc"
+#include "xyparse.hip.inc"
+#include "bsperf.inc"
+
+namespace bsk {
+
+constexpr int THREADS = 256;
+constexpr int MAX_BLOCKS = 1024;                    // grid of the record and sweep kernels: a block loops over its share and flushes once
+constexpr int NMOM = 6;                             // n, sum x, sum y, sum xy, sum x^2, sum y^2
+constexpr unsigned PRESENT = 0x80000000u;           // a truth slot: PRESENT | percentage << 16 | coverage
+enum { S_UNTRUTHED, S_BELOW = 2, S_BADSUM = 4, S_DUP, N_STAT };       // untruthed and below_threshold per kind
+
+struct Params {
+    int thr[MAX_THR];                               // ascending
+    int n_thr, n_rep, methylated, unmethylated, pred_cov;
+};
+
+__host__ __device__ inline int kind_bins(const int n_thr) { return 3 * n_thr * NPCT + 3 * n_thr; }       // hist [3][T][101] | unpredicted [3][T]
+
+// every lane of the wave calls it; one 64-bit atomic per wave with something to add
+__device__ inline void wave_add(unsigned long long* dst, long long v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
+    if ((threadIdx.x & 63) == 0 && v != 0) atomicAdd(dst, (unsigned long long)v);
+}
+
+__global__ __launch_bounds__(THREADS) void bs_parse_kernel(const char* __restrict__ text, const long long* __restrict__ start, const long long n_rows,
+                                                          const Names* __restrict__ names, const int first_chunk, int* __restrict__ rpos, unsigned* __restrict__ rmeta,
+                                                          long long* __restrict__ want, unsigned char* __restrict__ status, unsigned long long* __restrict__ lstat) {
+    const long long r = (long long)blockIdx.x * THREADS + threadIdx.x;
+    int cls = N_LINE;                                                // a lane without a line
+    if (r < n_rows) {
+        const long long b = start[r], e = start[r + 1] - 1;          // text[e] is the line's '\n'
+        Rec v = {0, 0};
+        cls = (first_chunk && r == 0) ? int(L_HEADER) : parse_line(text + b, e - b, *names, v);
+        rpos[r] = cls == L_RECORD ? v.pos : 0;
+        rmeta[r] = cls == L_RECORD ? v.meta : 0u;
+        want[r] = cls == L_RECORD ? 1 : 0;
+        status[r] = cls == L_BAD ? 1 : 0;
+    }
+#pragma unroll
+    for (int k = 0; k < N_LINE; ++k) wave_add(lstat + k, cls == k ? 1 : 0);
+}
+
+__global__ __launch_bounds__(THREADS) void bs_compact_kernel(const int* __restrict__ rpos, const unsigned* __restrict__ rmeta, const long long* __restrict__ scan,
+                                                            const long long n_rows, int* __restrict__ pos, unsigned* __restrict__ meta) {
+    const long long r = (long long)blockIdx.x * THREADS + threadIdx.x;
+    if (r >= n_rows) return;
+    const long long at = scan[r];
+    if (scan[r + 1] == at) return;
+    pos[at] = rpos[r];
+    meta[at] = rmeta[r];
+}
+
+// table: the replicate's slots [2 strands][length]; every pos[i] < length (checked on the host before the launch)
+__global__ __launch_bounds__(THREADS) void bs_fill_kernel(const int* __restrict__ pos, const unsigned* __restrict__ meta, const long long n, unsigned* __restrict__ table,
+                                                         const long long length, unsigned long long* __restrict__ stat) {
+    for (long long i = (long long)blockIdx.x * THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * THREADS) {
+        const long long q = pos[i];
+        if (q < 0 || q >= length) continue;
+        const unsigned m = meta[i];
+        const int s = meta_strand(m);
+        const unsigned old = atomicExch(&table[(long long)s * length + q], PRESENT | (m & 0x7fffffu));
+        if (old) atomicMin(stat + S_DUP, (unsigned long long)(q * 2 + s));
+    }
+}
+
+// score [2 strands][length]: 0 no site, 1 + percentage; the keys are distinct (checked on the host): one writer per byte
+__global__ __launch_bounds__(THREADS) void bs_score_kernel(const int* __restrict__ pos, const unsigned char* __restrict__ strand, const unsigned char* __restrict__ pct,
+                                                          const long long n, unsigned char* __restrict__ score, const long long length) {
+    for (long long i = (long long)blockIdx.x * THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * THREADS) {
+        const long long q = pos[i];
+        if (q < 0 || q >= length) continue;
+        score[(long long)(strand[i] & 1) * length + q] = (unsigned char)(pct[i] + 1);
+    }
+}
+
+// KIND 0: plus / minus are the dm_summary tables (touch | cov | mod of `length` positions each); KIND 1: score.
+// hist: this kind's kind_bins() counters, mom: this kind's [T][NMOM], stat: S_UNTRUTHED + KIND, S_BELOW + KIND, S_BADSUM
+template <int KIND>
+__global__ __launch_bounds__(THREADS) void bs_count_kernel(const unsigned* __restrict__ truth, const int* __restrict__ plus, const int* __restrict__ minus,
+                                                          const unsigned char* __restrict__ score, const long long length, const Params p,
+                                                          unsigned long long* __restrict__ hist, unsigned long long* __restrict__ mom, unsigned long long* __restrict__ stat) {
+    __shared__ unsigned lh[3 * MAX_THR * NPCT + 3 * MAX_THR];
+    const int T = p.n_thr, bins = kind_bins(T);
+    for (int j = threadIdx.x; j < bins; j += THREADS) lh[j] = 0;
+    __syncthreads();
+    long long acc[MAX_THR][NMOM];
+#pragma unroll
+    for (int j = 0; j < MAX_THR; ++j)
+#pragma unroll
+        for (int k = 0; k < NMOM; ++k) acc[j][k] = 0;
+    long long untruthed = 0, below = 0, badsum = 0;
+    for (long long e = (long long)blockIdx.x * THREADS + threadIdx.x; e < 2 * length; e += (long long)gridDim.x * THREADS) {
+        const int s = e >= length ? 1 : 0;
+        const long long q = e - (long long)s * length;
+        bool predicted;
+        int x = 0;
+        if constexpr (KIND == 0) {
+            const int* t = s ? minus : plus;
+            const int cv = t[length + q], md = t[2 * length + q];
+            if (cv < 0 || md < 0 || md > cv) {
+                ++badsum;
+                continue;
+            }
+            predicted = cv >= p.pred_cov;                            // pred_cov >= 1: a predicted site has coverage
+            if (predicted) x = int((100ll * md) / cv);
+        } else {
+            const int sc = score[e];
+            predicted = sc != 0;
+            x = sc - 1;
+        }
+        bool has = true, all_high = true, all_low = true;
+        int m = MAX_COV, y = 0;
+        for (int r = 0; r < p.n_rep; ++r) {
+            const unsigned slot = truth[((long long)(r * 2 + s)) * length + q];
+            has = has && slot != 0;
+            const int pct = int((slot >> 16) & 0x7fu);
+            m = min(m, int(slot & 0xffffu));
+            y += pct;
+            all_high = all_high && pct >= p.methylated;
+            all_low = all_low && pct <= p.unmethylated;
+        }
+        if (!has) {
+            if (predicted) ++untruthed;
+            continue;
+        }
+        int b = 0;
+#pragma unroll
+        for (int j = 0; j < MAX_THR; ++j) b += (j < T && p.thr[j] <= m) ? 1 : 0;
+        if (b == 0) {
+            ++below;
+            continue;
+        }
+        --b;
+        const int label = all_high ? 1 : (all_low ? 0 : 2);
+        if (!predicted) {
+            atomicAdd(&lh[3 * T * NPCT + label * T + b], 1u);
+            continue;
+        }
+        atomicAdd(&lh[(label * T + b) * NPCT + x], 1u);
+#pragma unroll
+        for (int j = 0; j < MAX_THR; ++j)
+            if (j == b) {
+                acc[j][0] += 1;
+                acc[j][1] += x;
+                acc[j][2] += y;
+                acc[j][3] += x * y;
+                acc[j][4] += x * x;
+                acc[j][5] += y * y;
+            }
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < bins; j += THREADS) {
+        const unsigned v = lh[j];
+        if (v) atomicAdd(&hist[j], (unsigned long long)v);
+    }
+#pragma unroll
+    for (int j = 0; j < MAX_THR; ++j)
+        if (j < T) {
+#pragma unroll
+            for (int k = 0; k < NMOM; ++k) wave_add(mom + j * NMOM + k, acc[j][k]);
+        }
+    wave_add(stat + S_UNTRUTHED + KIND, untruthed);
+    wave_add(stat + S_BELOW + KIND, below);
+    wave_add(stat + S_BADSUM, badsum);
+}
+
+}  // namespace bsk
+
+struct dm_bsperf {
+    dm_xyrows* xy = nullptr;                            // stream, the scan and its block sums
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // parse, fill, count: begin / end
+    enum { TEXT, COUNT, START, STATUS, OUT, WANT, RPOS, RMETA, POS, META, NAMES, LSTAT, TRUTH, SCORE, SPOS, SSTRAND, SPCT, HIST, MOM, STAT, N_BUF };
+    void* buf[N_BUF] = {};
+    size_t cap[N_BUF] = {};
+    bsk::Names names = {};
+    bsk::Params par = {};
+    int64_t lines[bsk::N_LINE] = {};                    // of every chunk taken so far
+    int64_t n_records = 0;                              // records on the device, of the last add_truth_text / add_truth_records
+    dm_summary *plus = nullptr, *minus = nullptr;       // the open contig's tables (null: none), the caller's
+    int contig = -1;
+    int64_t length = 0;
+    bool refused = false, counted = false, scored = false;
+    double parse_ms = 0.0, fill_ms = 0.0, count_ms = 0.0;
+};
+
+namespace bsk {
+
+int ensure(dm_bsperf* h, int which, size_t bytes) {
+    if (h->cap[which] >= bytes && h->buf[which]) return DM_OK;
+    if (h->buf[which]) (void)hipFree(h->buf[which]);
+    h->buf[which] = nullptr;
+    h->cap[which] = 0;
+    const size_t want = bytes + (bytes >> 2) + 256;                  // grow-only, a quarter ahead
+    if (hipMalloc(&h->buf[which], want) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(DM_ENOMEM, "dm_bsperf: hipMalloc(%zu) failed", want);
+    }
+    h->cap[which] = want;
+    return DM_OK;
+}
+
+template <class T>
+T* ptr(dm_bsperf* h, int which) { return static_cast<T*>(h->buf[which]); }
+
+constexpr int64_t MAX_BYTES = int64_t(1) << 40;
+constexpr int64_t MAX_RECORDS = 0x7fffffffLL;
+
+int add_time(dm_bsperf* h, int first, double& into) {
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, h->ev[first], h->ev[first + 1]));
+    into += double(ms);
+    return DM_OK;
+}
+
+size_t hist_counters(const dm_bsperf* h) { return size_t(2) * kind_bins(h->par.n_thr); }
+size_t mom_counters(const dm_bsperf* h) { return size_t(2) * h->par.n_thr * NMOM; }
+
+// the sweep of one kind over the open contig
+int count_kind(dm_bsperf* h, int kind) {
+    using B = dm_bsperf;
+    int rc;
+    if ((rc = dm_summary_sync(h->plus)) != DM_OK || (rc = dm_summary_sync(h->minus)) != DM_OK) return rc;
+    if (dm_summary_length(h->plus) != h->length || dm_summary_length(h->minus) != h->length)
+        return fail(DM_ESTATE, "dm_bsperf: the tables changed since the contig was opened (%lld positions then)", (long long)h->length);
+    hipStream_t s = h->xy->stream;
+    unsigned long long* d_stat = ptr<unsigned long long>(h, B::STAT);
+    unsigned long long* d_hist = ptr<unsigned long long>(h, B::HIST) + size_t(kind) * kind_bins(h->par.n_thr);
+    unsigned long long* d_mom = ptr<unsigned long long>(h, B::MOM) + size_t(kind) * h->par.n_thr * NMOM;
+    const int* plus = static_cast<const int*>(dm_summary_device_ptr(h->plus));
+    const int* minus = static_cast<const int*>(dm_summary_device_ptr(h->minus));
+    const dim3 grid{unsigned(std::min<int64_t>((2 * h->length + THREADS - 1) / THREADS, MAX_BLOCKS))};
+    HIP_TRY(hipMemsetAsync(d_stat + S_BADSUM, 0, 8, s));
+    HIP_TRY(hipEventRecord(h->ev[4], s));
+    if (kind == 0)
+        hipLaunchKernelGGL(bs_count_kernel<0>, grid, dim3(THREADS), 0, s, ptr<const unsigned>(h, B::TRUTH), plus, minus, (const unsigned char*)nullptr, (long long)h->length,
+                           h->par, d_hist, d_mom, d_stat);
+    else
+        hipLaunchKernelGGL(bs_count_kernel<1>, grid, dim3(THREADS), 0, s, ptr<const unsigned>(h, B::TRUTH), plus, minus, ptr<const unsigned char>(h, B::SCORE),
+                           (long long)h->length, h->par, d_hist, d_mom, d_stat);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[5], s));
+    unsigned long long bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, d_stat + S_BADSUM, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = add_time(h, 4, h->count_ms)) != DM_OK) return rc;
+    if (bad) return fail(DM_EINVAL, "dm_bsperf_count: the sums of %llu positions are outside 0 <= modified <= coverage", bad);
+    return DM_OK;
+}
+
+}  // namespace bsk
+
+extern "C" {
+
+int dm_bsperf_tile_bytes(void) { return xlk::TILE; }
+
+void dm_bsperf_destroy(dm_bsperf* h) {
+    if (!h) return;
+    if (h->xy) {
+        (void)hipSetDevice(h->xy->device);
+        (void)hipStreamSynchronize(h->xy->stream);
+    }
+    for (void* b : h->buf)
+        if (b) (void)hipFree(b);
+    for (hipEvent_t e : h->ev)
+        if (e) (void)hipEventDestroy(e);
+    dm_xy_destroy(h->xy);
+    delete h;
+}
+
+static int bs_options(bsk::Params& par, int n_thresholds, const int32_t* thresholds, int n_replicates, int methylated, int unmethylated, int pred_cov, const char* who) {
+    if (n_thresholds < 1 || n_thresholds > bsk::MAX_THR || !thresholds) return fail(DM_EINVAL, "%s: %d thresholds (1 to %d)", who, n_thresholds, bsk::MAX_THR);
+    for (int j = 0; j < n_thresholds; ++j)
+        if (thresholds[j] < 1 || (j > 0 && thresholds[j] <= thresholds[j - 1]))
+            return fail(DM_EINVAL, "%s: the thresholds are positive and strictly ascending (threshold %d is %d)", who, j, thresholds[j]);
+    if (n_replicates < 1 || n_replicates > bsk::MAX_REP) return fail(DM_EINVAL, "%s: %d replicates (1 to %d)", who, n_replicates, bsk::MAX_REP);
+    if (unmethylated < 0 || methylated > 100 || unmethylated >= methylated)
+        return fail(DM_EINVAL, "%s: 0 <= unmethylated < methylated <= 100 (got %d, %d)", who, unmethylated, methylated);
+    if (pred_cov < 1) return fail(DM_EINVAL, "%s: a least prediction coverage of %d (1 or more)", who, pred_cov);
+    par = {};
+    par.n_thr = n_thresholds;
+    for (int j = 0; j < n_thresholds; ++j) par.thr[j] = thresholds[j];
+    par.n_rep = n_replicates;
+    par.methylated = methylated;
+    par.unmethylated = unmethylated;
+    par.pred_cov = pred_cov;
+    return DM_OK;
+}
+
+dm_bsperf* dm_bsperf_create(int device, int n_contigs, const char* const* names, const int64_t* lengths, int n_thresholds, const int32_t* thresholds, int n_replicates,
+                            int methylated, int unmethylated, int pred_cov) {
+    using B = dm_bsperf;
+    bsk::Params par;
+    if (bs_options(par, n_thresholds, thresholds, n_replicates, methylated, unmethylated, pred_cov, "dm_bsperf_create") != DM_OK) return nullptr;
+    bsk::Names nm;
+    const int which = bsk::set_names(nm, n_contigs, names, lengths);
+    if (which) {
+        fail(DM_EINVAL, "dm_bsperf_create: 1 to %d distinct contig names of 1 to %d printable bytes, lengths of 1 to 2^31 - 1 (contig %d of %d)", bsk::MAX_CONTIGS,
+             bsk::MAX_NAME, which - 1, n_contigs);
+        return nullptr;
+    }
+    dm_xyrows* xy = dm_xy_create(device);
+    if (!xy) return nullptr;
+    dm_bsperf* h = new dm_bsperf;
+    h->xy = xy;
+    h->par = par;
+    h->names = nm;
+    bool ok = true;
+    for (hipEvent_t& e : h->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+    const size_t hist_bytes = bsk::hist_counters(h) * 8, mom_bytes = bsk::mom_counters(h) * 8;
+    ok = ok && bsk::ensure(h, B::HIST, hist_bytes) == DM_OK && bsk::ensure(h, B::MOM, mom_bytes) == DM_OK && bsk::ensure(h, B::STAT, bsk::N_STAT * 8) == DM_OK &&
+         bsk::ensure(h, B::LSTAT, bsk::N_LINE * 8) == DM_OK && bsk::ensure(h, B::OUT, 16) == DM_OK && bsk::ensure(h, B::NAMES, sizeof(bsk::Names)) == DM_OK;
+    hipStream_t s = xy->stream;
+    ok = ok && hipMemsetAsync(h->buf[B::HIST], 0, hist_bytes, s) == hipSuccess && hipMemsetAsync(h->buf[B::MOM], 0, mom_bytes, s) == hipSuccess &&
+         hipMemsetAsync(h->buf[B::STAT], 0, bsk::N_STAT * 8, s) == hipSuccess &&
+         hipMemcpyAsync(h->buf[B::NAMES], &h->names, sizeof(bsk::Names), hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        fail(DM_EDEVICE, "dm_bsperf_create: events or counters on device %d", device);
+        dm_bsperf_destroy(h);
+        return nullptr;
+    }
+    return h;
+}
+
+int64_t dm_bsperf_parse_host(const char* text, int64_t n_bytes, int n_contigs, const char* const* names, const int64_t* lengths, int is_first_chunk, int32_t* pos,
+                             uint32_t* meta, int64_t cap, int64_t* lines, int32_t* flag, int64_t* first_bad_line) {
+    if (n_bytes < 0 || (n_bytes > 0 && !text) || cap < 0 || (cap > 0 && (!pos || !meta))) return fail(DM_EINVAL, "dm_bsperf_parse_host: null argument");
+    bsk::Names nm;
+    const int which = bsk::set_names(nm, n_contigs, names, lengths);
+    if (which)
+        return fail(DM_EINVAL, "dm_bsperf_parse_host: 1 to %d distinct contig names of 1 to %d printable bytes, lengths of 1 to 2^31 - 1 (contig %d of %d)", bsk::MAX_CONTIGS,
+                    bsk::MAX_NAME, which - 1, n_contigs);
+    int64_t counted[bsk::N_LINE], bad = 0;
+    const int64_t recs = bsk::parse_text(text, n_bytes, nm, is_first_chunk != 0, pos, meta, cap, counted, &bad);
+    if (lines)
+        for (int k = 0; k < bsk::N_LINE; ++k) lines[k] = counted[k];
+    if (flag) *flag = bad != 0;
+    if (first_bad_line) *first_bad_line = bad ? bad : -1;
+    return recs;
+}
+
+int dm_bsperf_add_truth_text(dm_bsperf* h, int replicate, const char* text, int64_t n_bytes, int is_first_chunk, int64_t* lines, int64_t* n_records, int32_t* flag,
+                             int64_t* first_bad_line) {
+    using B = dm_bsperf;
+    if (!h) return fail(DM_EINVAL, "null handle");
+    if (lines)
+        for (int k = 0; k < bsk::N_LINE; ++k) lines[k] = 0;
+    if (n_records) *n_records = 0;
+    if (flag) *flag = 0;
+    if (first_bad_line) *first_bad_line = -1;
+    if (replicate < 0 || replicate >= h->par.n_rep) return fail(DM_EINVAL, "dm_bsperf_add_truth_text: replicate %d of %d", replicate, h->par.n_rep);
+    if (n_bytes < 0 || n_bytes >= bsk::MAX_BYTES || (n_bytes > 0 && !text)) return fail(DM_EINVAL, "dm_bsperf_add_truth_text: %lld bytes of text", (long long)n_bytes);
+    h->n_records = 0;
+    if (n_bytes == 0) return DM_OK;
+    HIP_TRY(hipSetDevice(h->xy->device));
+    const bool add_newline = text[n_bytes - 1] != '\n';
+    const int64_t n = n_bytes + (add_newline ? 1 : 0);
+    const int64_t tiles = (n + xlk::TILE - 1) / xlk::TILE;
+    int rc;
+    if ((rc = bsk::ensure(h, B::TEXT, size_t(tiles) * xlk::TILE)) != DM_OK) return rc;      // whole 16-byte groups behind every lane offset below n
+    if ((rc = bsk::ensure(h, B::COUNT, size_t(tiles + 1) * 8)) != DM_OK) return rc;
+    hipStream_t s = h->xy->stream;
+    char* d_text = bsk::ptr<char>(h, B::TEXT);
+    long long* d_count = bsk::ptr<long long>(h, B::COUNT);
+    unsigned long long* d_lstat = bsk::ptr<unsigned long long>(h, B::LSTAT);
+    static const char newline = '\n';
+    HIP_TRY(hipMemcpyAsync(d_text, text, size_t(n_bytes), hipMemcpyHostToDevice, s));
+    if (add_newline) HIP_TRY(hipMemcpyAsync(d_text + n_bytes, &newline, 1, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_lstat, 0, bsk::N_LINE * 8, s));
+    const dim3 tile_grid{unsigned(tiles)}, block{xlk::THREADS};
+    HIP_TRY(hipEventRecord(h->ev[0], s));
+    hipLaunchKernelGGL(xlk::xl_count_kernel, tile_grid, block, 0, s, d_text, (long long)n, d_count);
+    HIP_TRY(hipGetLastError());
+    if ((rc = xyk::scan_in_place(h->xy, d_count, tiles)) != DM_OK) return rc;
+    long long rows = 0;
+    HIP_TRY(hipMemcpyAsync(&rows, d_count + tiles, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (rows < 1 || rows > n) return fail(DM_ESTATE, "dm_bsperf_add_truth_text: %lld lines in %lld bytes", rows, (long long)n);
+    if (rows > bsk::MAX_RECORDS) return fail(DM_EINVAL, "dm_bsperf_add_truth_text: %lld lines in one chunk (at most %lld)", rows, (long long)bsk::MAX_RECORDS);
+    for (int which : {int(B::RPOS), int(B::RMETA), int(B::POS), int(B::META)})
+        if ((rc = bsk::ensure(h, which, size_t(rows) * 4)) != DM_OK) return rc;
+    if ((rc = bsk::ensure(h, B::STATUS, size_t(rows))) != DM_OK || (rc = bsk::ensure(h, B::START, size_t(rows + 1) * 8)) != DM_OK ||
+        (rc = bsk::ensure(h, B::WANT, size_t(rows + 1) * 8)) != DM_OK)
+        return rc;
+    long long* d_start = bsk::ptr<long long>(h, B::START);
+    long long* d_want = bsk::ptr<long long>(h, B::WANT);
+    unsigned char* d_status = bsk::ptr<unsigned char>(h, B::STATUS);
+    long long* d_out = bsk::ptr<long long>(h, B::OUT);
+    const dim3 row_grid{unsigned((rows + bsk::THREADS - 1) / bsk::THREADS)};
+    hipLaunchKernelGGL(xlk::xl_lines_kernel, tile_grid, block, 0, s, d_text, (long long)n, d_count, rows, d_start);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(bsk::bs_parse_kernel, row_grid, dim3(bsk::THREADS), 0, s, d_text, d_start, rows, bsk::ptr<const bsk::Names>(h, B::NAMES), is_first_chunk != 0 ? 1 : 0,
+                       bsk::ptr<int>(h, B::RPOS), bsk::ptr<unsigned>(h, B::RMETA), d_want, d_status, d_lstat);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(xlk::xl_first_kernel, dim3(1), dim3(xyk::SUM_THREADS), 0, s, d_status, rows, d_out);
+    HIP_TRY(hipGetLastError());
+    if ((rc = xyk::scan_in_place(h->xy, d_want, rows)) != DM_OK) return rc;
+    hipLaunchKernelGGL(bsk::bs_compact_kernel, row_grid, dim3(bsk::THREADS), 0, s, bsk::ptr<const int>(h, B::RPOS), bsk::ptr<const unsigned>(h, B::RMETA), d_want, rows,
+                       bsk::ptr<int>(h, B::POS), bsk::ptr<unsigned>(h, B::META));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[1], s));
+    long long first = -1, recs = 0;
+    unsigned long long counted[bsk::N_LINE] = {};
+    HIP_TRY(hipMemcpyAsync(&first, d_out, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&recs, d_want + rows, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(counted, d_lstat, sizeof counted, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = bsk::add_time(h, 0, h->parse_ms)) != DM_OK) return rc;
+    if (first >= 0) {                                                // outside the grammar: nothing of this chunk is taken
+        if (flag) *flag = 1;
+        if (first_bad_line) *first_bad_line = first + 1;
+        return DM_OK;
+    }
+    if (recs < 0 || recs > rows || recs != (long long)counted[bsk::L_RECORD])
+        return fail(DM_ESTATE, "dm_bsperf_add_truth_text: %lld records of %lld lines (%llu counted)", recs, rows, counted[bsk::L_RECORD]);
+    for (int k = 0; k < bsk::N_LINE; ++k) {
+        h->lines[k] += int64_t(counted[k]);
+        if (lines) lines[k] = int64_t(counted[k]);
+    }
+    h->n_records = recs;
+    if (n_records) *n_records = recs;
+    return DM_OK;
+}
+
+int dm_bsperf_add_truth_records(dm_bsperf* h, int replicate, int64_t n, const uint8_t* contig, const uint8_t* strand, const int32_t* pos, const int32_t* cov,
+                                const int32_t* pct, const int64_t* lines) {
+    using B = dm_bsperf;
+    if (!h) return fail(DM_EINVAL, "null handle");
+    if (replicate < 0 || replicate >= h->par.n_rep) return fail(DM_EINVAL, "dm_bsperf_add_truth_records: replicate %d of %d", replicate, h->par.n_rep);
+    if (n < 0 || n > bsk::MAX_RECORDS || (n > 0 && (!contig || !strand || !pos || !cov || !pct)) || !lines)
+        return fail(DM_EINVAL, "dm_bsperf_add_truth_records: %lld records", (long long)n);
+    if (lines[bsk::L_RECORD] != n) return fail(DM_EINVAL, "dm_bsperf_add_truth_records: %lld records, %lld record lines", (long long)n, (long long)lines[bsk::L_RECORD]);
+    for (int k = 0; k < bsk::N_LINE; ++k)
+        if (lines[k] < 0) return fail(DM_EINVAL, "dm_bsperf_add_truth_records: line counter %d is %lld", k, (long long)lines[k]);
+    for (int64_t i = 0; i < n; ++i)                                  // what the kernels index with, checked before any launch
+        if (contig[i] >= h->names.n || strand[i] > 1 || pos[i] < 0 || pos[i] >= h->names.limit[contig[i]] || cov[i] < 1 || pct[i] < 0 || pct[i] > 100)
+            return fail(DM_EINVAL, "dm_bsperf_add_truth_records: record %lld (contig %d of %d, strand %d, position %d, coverage %d, percentage %d)", (long long)i,
+                        int(contig[i]), h->names.n, int(strand[i]), pos[i], cov[i], pct[i]);
+    h->n_records = 0;
+    if (n > 0) {
+        std::vector<uint32_t> meta(size_t(n), 0u);
+        for (int64_t i = 0; i < n; ++i) meta[size_t(i)] = bsk::pack_meta(contig[i], strand[i], cov[i], pct[i]);
+        HIP_TRY(hipSetDevice(h->xy->device));
+        int rc;
+        if ((rc = bsk::ensure(h, B::POS, size_t(n) * 4)) != DM_OK || (rc = bsk::ensure(h, B::META, size_t(n) * 4)) != DM_OK) return rc;
+        hipStream_t s = h->xy->stream;
+        HIP_TRY(hipMemcpyAsync(h->buf[B::POS], pos, size_t(n) * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(h->buf[B::META], meta.data(), size_t(n) * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    for (int k = 0; k < bsk::N_LINE; ++k) h->lines[k] += lines[k];
+    h->n_records = n;
+    return DM_OK;
+}
+
+int dm_bsperf_fetch_records(dm_bsperf* h, int32_t* pos, uint32_t* meta) {
+    using B = dm_bsperf;
+    if (!h) return fail(DM_EINVAL, "null handle");
+    const size_t n = size_t(h->n_records);
+    if (n == 0) return DM_OK;
+    HIP_TRY(hipSetDevice(h->xy->device));
+    if (pos) HIP_TRY(hipMemcpy(pos, h->buf[B::POS], n * 4, hipMemcpyDeviceToHost));
+    if (meta) HIP_TRY(hipMemcpy(meta, h->buf[B::META], n * 4, hipMemcpyDeviceToHost));
+    return DM_OK;
+}
+
+int dm_bsperf_close_contig(dm_bsperf* h) {
+    if (!h) return fail(DM_EINVAL, "null handle");
+    h->plus = h->minus = nullptr;
+    h->contig = -1;
+    h->length = 0;
+    h->refused = h->counted = h->scored = false;
+    return DM_OK;
+}
+
+int dm_bsperf_open(dm_bsperf* h, int contig_index, dm_summary* plus, dm_summary* minus) {
+    using B = dm_bsperf;
+    if (!h) return fail(DM_EINVAL, "null handle");
+    (void)dm_bsperf_close_contig(h);
+    if (contig_index < 0 || contig_index >= h->names.n) return fail(DM_EINVAL, "dm_bsperf_open: contig %d of %d", contig_index, h->names.n);
+    if (!plus || !minus || plus == minus) return fail(DM_EINVAL, "dm_bsperf_open: two tables, one per strand");
+    if (plus->device != h->xy->device || minus->device != h->xy->device) return fail(DM_EINVAL, "dm_bsperf_open: the tables are on another device than the handle (%d)", h->xy->device);
+    const int64_t length = dm_summary_length(plus);
+    if (length != dm_summary_length(minus) || length < 1 || length > bsk::MAX_LENGTH)
+        return fail(DM_EINVAL, "dm_bsperf_open: tables of %lld and %lld positions (equal, 1 to 2^31 - 1)", (long long)length, (long long)dm_summary_length(minus));
+    if (length > h->names.limit[contig_index])
+        return fail(DM_EINVAL, "dm_bsperf_open: tables of %lld positions for a contig of %lld", (long long)length, (long long)h->names.limit[contig_index]);
+    HIP_TRY(hipSetDevice(h->xy->device));
+    const size_t slots = size_t(h->par.n_rep) * 2 * size_t(length);
+    int rc;
+    if ((rc = bsk::ensure(h, B::TRUTH, slots * 4)) != DM_OK) return rc;
+    hipStream_t s = h->xy->stream;
+    HIP_TRY(hipMemsetAsync(h->buf[B::TRUTH], 0, slots * 4, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    h->plus = plus;
+    h->minus = minus;
+    h->contig = contig_index;
+    h->length = length;
+    return DM_OK;
+}
+
+int dm_bsperf_fill(dm_bsperf* h, int replicate, int64_t n, const int32_t* pos, const uint32_t* meta, int64_t* dup_pos, int32_t* dup_strand) {
+    using B = dm_bsperf;
+    if (!h) return fail(DM_EINVAL, "null handle");
+    if (dup_pos) *dup_pos = -1;
+    if (dup_strand) *dup_strand = -1;
+    if (!h->plus) return fail(DM_ESTATE, "dm_bsperf_fill: no contig");
+    if (h->counted) return fail(DM_ESTATE, "dm_bsperf_fill: the contig has been counted");
+    if (replicate < 0 || replicate >= h->par.n_rep) return fail(DM_EINVAL, "dm_bsperf_fill: replicate %d of %d", replicate, h->par.n_rep);
+    if (n < 0 || n > bsk::MAX_RECORDS || (n > 0 && (!pos || !meta))) return fail(DM_EINVAL, "dm_bsperf_fill: %lld records", (long long)n);
+    for (int64_t i = 0; i < n; ++i)                                  // what the kernel indexes with, checked before any launch
+        if (pos[i] < 0 || pos[i] >= h->length || bsk::meta_contig(meta[i]) != h->contig || bsk::meta_cov(meta[i]) < 1 || bsk::meta_pct(meta[i]) > 100)
+            return fail(DM_EINVAL, "dm_bsperf_fill: record %lld (contig %d, the open one is %d; position %d of %lld; coverage %d, percentage %d)", (long long)i,
+                        bsk::meta_contig(meta[i]), h->contig, pos[i], (long long)h->length, bsk::meta_cov(meta[i]), bsk::meta_pct(meta[i]));
+    if (n == 0) return DM_OK;
+    HIP_TRY(hipSetDevice(h->xy->device));
+    int rc;
+    if ((rc = bsk::ensure(h, B::POS, size_t(n) * 4)) != DM_OK || (rc = bsk::ensure(h, B::META, size_t(n) * 4)) != DM_OK) return rc;
+    h->n_records = 0;                                                // the record buffers now hold this fill
+    hipStream_t s = h->xy->stream;
+    unsigned long long* d_stat = bsk::ptr<unsigned long long>(h, B::STAT);
+    HIP_TRY(hipMemcpyAsync(h->buf[B::POS], pos, size_t(n) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->buf[B::META], meta, size_t(n) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_stat + bsk::S_DUP, 0xff, 8, s));
+    const dim3 grid{unsigned(std::min<int64_t>((n + bsk::THREADS - 1) / bsk::THREADS, bsk::MAX_BLOCKS))};
+    HIP_TRY(hipEventRecord(h->ev[2], s));
+    hipLaunchKernelGGL(bsk::bs_fill_kernel, grid, dim3(bsk::THREADS), 0, s, bsk::ptr<const int>(h, B::POS), bsk::ptr<const unsigned>(h, B::META), (long long)n,
+                       bsk::ptr<unsigned>(h, B::TRUTH) + size_t(replicate) * 2 * size_t(h->length), (long long)h->length, d_stat);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[3], s));
+    unsigned long long dup = ~0ull;
+    HIP_TRY(hipMemcpyAsync(&dup, d_stat + bsk::S_DUP, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = bsk::add_time(h, 2, h->fill_ms)) != DM_OK) return rc;
+    if (dup != ~0ull) {
+        h->refused = true;
+        if (dup_pos) *dup_pos = int64_t(dup >> 1);
+        if (dup_strand) *dup_strand = int32_t(dup & 1);
+        return fail(DM_EINVAL, "dm_bsperf_fill: replicate %d holds position %llu of strand %c twice: the contig is refused", replicate, dup >> 1, (dup & 1) ? '-' : '+');
+    }
+    return DM_OK;
+}
+
+int dm_bsperf_count(dm_bsperf* h) {
+    if (!h) return fail(DM_EINVAL, "null handle");
+    if (!h->plus) return fail(DM_ESTATE, "dm_bsperf_count: no contig");
+    if (h->refused) return fail(DM_ESTATE, "dm_bsperf_count: the contig was refused for a key that occurs twice in a replicate");
+    if (h->counted) return fail(DM_ESTATE, "dm_bsperf_count: the contig has been counted");
+    HIP_TRY(hipSetDevice(h->xy->device));
+    const int rc = bsk::count_kind(h, 0);
+    if (rc == DM_OK) h->counted = true;
+    return rc;
+}
+
+int dm_bsperf_add_scores(dm_bsperf* h, int64_t n, const int32_t* pos, const uint8_t* strand, const int32_t* pct) {
+    using B = dm_bsperf;
+    if (!h) return fail(DM_EINVAL, "null handle");
+    if (!h->plus) return fail(DM_ESTATE, "dm_bsperf_add_scores: no contig");
+    if (!h->counted || h->scored) return fail(DM_ESTATE, "dm_bsperf_add_scores: once per contig, after dm_bsperf_count");
+    if (n < 0 || n > bsk::MAX_RECORDS || (n > 0 && (!pos || !strand || !pct))) return fail(DM_EINVAL, "dm_bsperf_add_scores: %lld sites", (long long)n);
+    std::vector<int64_t> key(size_t(n), 0);
+    std::vector<uint8_t> value(size_t(n), 0);
+    for (int64_t i = 0; i < n; ++i) {                                // what the kernel indexes with, checked before any launch
+        if (pos[i] < 0 || pos[i] >= h->length || strand[i] > 1 || pct[i] < 0 || pct[i] > 100)
+            return fail(DM_EINVAL, "dm_bsperf_add_scores: site %lld (position %d of %lld, strand %d, percentage %d)", (long long)i, pos[i], (long long)h->length, int(strand[i]),
+                        pct[i]);
+        key[size_t(i)] = int64_t(pos[i]) * 2 + strand[i];
+        value[size_t(i)] = uint8_t(pct[i]);
+    }
+    std::sort(key.begin(), key.end());
+    const auto twice = std::adjacent_find(key.begin(), key.end());
+    if (twice != key.end()) return fail(DM_EINVAL, "dm_bsperf_add_scores: position %lld of strand %c occurs twice", (long long)(*twice >> 1), (*twice & 1) ? '-' : '+');
+    HIP_TRY(hipSetDevice(h->xy->device));
+    int rc;
+    if ((rc = bsk::ensure(h, B::SCORE, size_t(h->length) * 2)) != DM_OK || (rc = bsk::ensure(h, B::SPOS, size_t(n) * 4 + 4)) != DM_OK ||
+        (rc = bsk::ensure(h, B::SSTRAND, size_t(n) + 1)) != DM_OK || (rc = bsk::ensure(h, B::SPCT, size_t(n) + 1)) != DM_OK)
+        return rc;
+    hipStream_t s = h->xy->stream;
+    HIP_TRY(hipMemsetAsync(h->buf[B::SCORE], 0, size_t(h->length) * 2, s));
+    if (n > 0) {
+        HIP_TRY(hipMemcpyAsync(h->buf[B::SPOS], pos, size_t(n) * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(h->buf[B::SSTRAND], strand, size_t(n), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(h->buf[B::SPCT], value.data(), size_t(n), hipMemcpyHostToDevice, s));
+        const dim3 grid{unsigned(std::min<int64_t>((n + bsk::THREADS - 1) / bsk::THREADS, bsk::MAX_BLOCKS))};
+        hipLaunchKernelGGL(bsk::bs_score_kernel, grid, dim3(bsk::THREADS), 0, s, bsk::ptr<const int>(h, B::SPOS), bsk::ptr<const unsigned char>(h, B::SSTRAND),
+                           bsk::ptr<const unsigned char>(h, B::SPCT), (long long)n, bsk::ptr<unsigned char>(h, B::SCORE), (long long)h->length);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(s));                                // the host arrays of this call are read by now
+    rc = bsk::count_kind(h, 1);
+    if (rc == DM_OK) h->scored = true;
+    return rc;
+}
+
+int dm_bsperf_fetch(dm_bsperf* h, int64_t* hist, int64_t* unpredicted, int64_t* moments, int64_t* untruthed, int64_t* below_threshold, int64_t* lines) {
+    using B = dm_bsperf;
+    if (!h) return fail(DM_EINVAL, "null handle");
+    HIP_TRY(hipSetDevice(h->xy->device));
+    HIP_TRY(hipStreamSynchronize(h->xy->stream));
+    const int T = h->par.n_thr, per_kind = bsk::kind_bins(T), hist_part = 3 * T * bsk::NPCT;
+    std::vector<long long> all(bsk::hist_counters(h));
+    long long stat[bsk::N_STAT];
+    HIP_TRY(hipMemcpy(all.data(), h->buf[B::HIST], all.size() * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(stat, h->buf[B::STAT], sizeof stat, hipMemcpyDeviceToHost));
+    if (moments) HIP_TRY(hipMemcpy(moments, h->buf[B::MOM], bsk::mom_counters(h) * 8, hipMemcpyDeviceToHost));
+    for (int kind = 0; kind < 2; ++kind) {
+        if (hist)
+            for (int j = 0; j < hist_part; ++j) hist[kind * hist_part + j] = all[size_t(kind) * per_kind + j];
+        if (unpredicted)
+            for (int j = 0; j < 3 * T; ++j) unpredicted[kind * 3 * T + j] = all[size_t(kind) * per_kind + hist_part + j];
+        if (untruthed) untruthed[kind] = stat[bsk::S_UNTRUTHED + kind];
+        if (below_threshold) below_threshold[kind] = stat[bsk::S_BELOW + kind];
+    }
+    if (lines)
+        for (int k = 0; k < bsk::N_LINE; ++k) lines[k] = h->lines[k];
+    return DM_OK;
+}
+
+int dm_bsperf_times(dm_bsperf* h, double* parse_ms, double* fill_ms, double* count_ms) {
+    if (!h) return fail(DM_EINVAL, "null handle");
+    if (parse_ms) *parse_ms = h->parse_ms;
+    if (fill_ms) *fill_ms = h->fill_ms;
+    if (count_ms) *count_ms = h->count_ms;
+    return DM_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // offline.hip — libdeepmod_hip.so, training and the offline commands: the BiLSTM trainer, the cluster trainer, getfeatures (the .xy writer), predict
-// (the .xy parser), the resident gather of train --resident, siteperf, merge.  Interface to the other units: host.h.
+// (the .xy parser), the resident gather of train --resident, siteperf, merge, bsperf.  Interface to the other units: host.h.
 #include "train.hip.inc"
 #include "cluster_train.hip.inc"
 #include "xyrows.inc"
@@ -8,3 +8,4 @@
 #include "xygather.hip.inc"
 #include "siteperf.hip.inc"
 #include "bedmerge.hip.inc"
+#include "bsperf.hip.inc"

@@ -788,6 +788,63 @@ int64_t dm_bedmerge_format_host(const char* contig_name, char base, int64_t firs
 int dm_bedmerge_tile_positions(void);
 int dm_bedmerge_times(dm_bedmerge* h, double* parse_ms, double* add_ms, double* format_ms);
 
+/* --------------------------------------------------------------------------- bsperf -- */
+/* Score the predicted percentages of a run against whole-genome bisulfite replicates (docs/Reproducibility.md, Example 3, Step 5;
+ * csrc/bsperf.hip.inc, bsperf.inc).  The prediction side of a contig are two dm_summary tables (the caller's: the ones dm_bedmerge
+ * fills); the truth side are 1 - 4 bedMethyl replicates, parsed in chunks into records that the caller buckets by contig.  Counters, all int64 and
+ * accumulating over contigs: hist [kind 2][label 3][bucket T][percentage 101] (sites with truth and a prediction; kind 0 raw, 1 clustered),
+ * unpredicted [kind][label][bucket], moments [kind][bucket][6] = n, sum x, sum y, sum xy, sum x^2, sum y^2 over all labels, untruthed [kind],
+ * below_threshold [kind].  Per (strand, position): the site has truth if every replicate has a record; m = min coverage, bucket = (thresholds
+ * <= m) - 1 (none: below_threshold only); label 1 if every percentage >= methylated, else 0 if every percentage <= unmethylated, else 2;
+ * y = the sum of the percentages; predicted if the summed coverage >= pred_cov, x = (100 * mod) / cov in integers (kind 1: a site of add_scores,
+ * x its percentage).  Integer atomics only: exact, and the same on every run.  deepmod_amd/bsperf.py (HostEngine) states the semantics.
+ *   create         1 - 64 distinct contig names of 1 - 63 printable bytes; lengths: NULL or per contig its positions (< 0: not known, at most
+ *                  2^31 - 1 positions); 1 - 8 thresholds >= 1, strictly ascending; 1 - 4 replicates; 0 <= unmethylated < methylated <= 100;
+ *                  pred_cov >= 1.
+ *   add_truth_text one chunk of a replicate's text, cut at a line end (a missing last '\n' is supplied); is_first_chunk != 0: line 1 is the
+ *                  file's first line and is skipped unread.  Rules of a line, in this order: its length without leading and trailing ' ' / '\t'
+ *                  is <= 20: skipped.  Grammar: fields of printable bytes (0x21 - 0x7e) separated by runs of one or more ' ' / '\t', leading
+ *                  and trailing runs allowed; exactly 11 fields; fields 1, 9, 10 (position, coverage, percentage) of 1 - 10 digits, <= 2^31 - 1;
+ *                  percentage <= 100.  Field 5 neither '+' nor '-': skipped.  Field 0 none of the names, byte for byte: skipped.  Position at or
+ *                  beyond the contig's length (2^31 - 1 if not known): outside the grammar.  Coverage 0: dropped.  Else a record: position, and
+ *                  meta = min(coverage, 65535) | percentage << 16 | strand << 23 | contig index << 24.  Outside the grammar: 10 or 12 fields,
+ *                  '\r', a sign, 11 digits, percentage 101.  A chunk with such a line sets *flag and *first_bad_line (1-based) and adds NOTHING:
+ *                  the caller parses it and calls add_truth_records.  lines [6]: records, first lines, short lines, other strands, other
+ *                  contigs, coverage 0, of this chunk; the handle sums them (fetch).  The records stay on the device, in line order.
+ *   add_truth_records  the records (contig index u8, strand u8 0 '+' 1 '-', pos, cov >= 1, pct int32) and the line counters of a chunk the caller
+ *                  parsed, checked before any copy; they take the place of the device parser's.
+ *   fetch_records  the records of the last add_truth_text / add_truth_records as they lie on the device: pos int32 [n], meta uint32 [n].
+ *   open           the open contig: its index and its two tables, of equal length, at most the contig's.  One zeroed 32-bit slot per (replicate,
+ *                  strand, position).  close_contig lets go of the tables.
+ *   fill           records of the open contig (as fetch_records gave them) into the slots of `replicate`, checked before any launch: another
+ *                  contig, a position outside the tables, coverage 0 are DM_EINVAL.  A key that occurs twice in the replicate (in one call or
+ *                  in two): DM_EINVAL, *dup_pos / *dup_strand the smallest such key, and the contig cannot be counted any more.
+ *   count          kind 0: one sweep over (strand, position) of the open contig, once.  DM_EINVAL: a sum outside 0 <= modified <= coverage.
+ *   add_scores     kind 1, once, after count: n distinct sites (pos int32, strand u8, percentage 0 - 100 int32), checked before any launch; every
+ *                  other position is unpredicted in kind 1.
+ *   fetch          the counters as laid out above, and lines [6] summed over the chunks.
+ *   parse_host     the line routine compiled for the host (no GPU needed) -> records, written as far as cap reaches.
+ *   times          ms of the parse / fill / count kernels so far (HIP events).  tile_bytes: bytes of one tile of the line splitter. */
+typedef struct dm_bsperf dm_bsperf;
+dm_bsperf* dm_bsperf_create(int device, int n_contigs, const char* const* names, const int64_t* lengths, int n_thresholds, const int32_t* thresholds, int n_replicates,
+                            int methylated, int unmethylated, int pred_cov);
+void dm_bsperf_destroy(dm_bsperf* h);
+int dm_bsperf_add_truth_text(dm_bsperf* h, int replicate, const char* text, int64_t n_bytes, int is_first_chunk, int64_t* lines, int64_t* n_records, int32_t* flag,
+                             int64_t* first_bad_line);
+int dm_bsperf_add_truth_records(dm_bsperf* h, int replicate, int64_t n, const uint8_t* contig, const uint8_t* strand, const int32_t* pos, const int32_t* cov,
+                                const int32_t* pct, const int64_t* lines);
+int dm_bsperf_fetch_records(dm_bsperf* h, int32_t* pos, uint32_t* meta);
+int dm_bsperf_open(dm_bsperf* h, int contig_index, dm_summary* plus, dm_summary* minus);
+int dm_bsperf_close_contig(dm_bsperf* h);
+int dm_bsperf_fill(dm_bsperf* h, int replicate, int64_t n, const int32_t* pos, const uint32_t* meta, int64_t* dup_pos, int32_t* dup_strand);
+int dm_bsperf_count(dm_bsperf* h);
+int dm_bsperf_add_scores(dm_bsperf* h, int64_t n, const int32_t* pos, const uint8_t* strand, const int32_t* pct);
+int dm_bsperf_fetch(dm_bsperf* h, int64_t* hist, int64_t* unpredicted, int64_t* moments, int64_t* untruthed, int64_t* below_threshold, int64_t* lines);
+int64_t dm_bsperf_parse_host(const char* text, int64_t n_bytes, int n_contigs, const char* const* names, const int64_t* lengths, int is_first_chunk, int32_t* pos,
+                             uint32_t* meta, int64_t cap, int64_t* lines, int32_t* flag, int64_t* first_bad_line);
+int dm_bsperf_tile_bytes(void);
+int dm_bsperf_times(dm_bsperf* h, double* parse_ms, double* fill_ms, double* count_ms);
+
 #ifdef __cplusplus
 }
 #endif
