@@ -6,8 +6,7 @@
 //   save_mod (:56-66)    bm_length_kernel   a block per tile of bmk::TILE_POS positions: bytes and lines of the tile (bmk::emit_position, counting sink)
 //                        the 64-bit scan over the tiles
 //                        bm_write_kernel    the same routine with a writing sink at tile offset + block scan of the lanes' bytes
-// The text of a file is split as xyparse.hip.inc splits it (xl_count_kernel, the scan, xl_lines_kernel).  The grammar and the line are stated in
-// bedmerge.inc; a text with a line outside the grammar adds nothing (first line reported), and the caller hands its own parse over through
+// The text of a file is split into lines by textlines.hip.inc (xlk::split).  The grammar and the line are stated in bedmerge.inc; a text with a line outside the grammar adds nothing (first line reported), and the caller hands its own parse over through
 // dm_bedmerge_add_records.
 // Exactness and determinism.  Every sum is an int32 integer: additions commute, so the order the atomics land in does not matter.  The guard of
 // siteperf keeps the sums in range: the largest coverages of the texts of a contig sum to < 2^31 (checked BEFORE a text's adds; duplicates of a key
@@ -20,7 +19,7 @@
 #include "host.h"
 #include "blockscan.hip.inc"
 #include "xyrows.hip.inc"
-#include "xyparse.hip.inc"
+#include "textlines.hip.inc"
 #include "bedmerge.inc"
 
 namespace bmk {
@@ -131,9 +130,8 @@ __global__ __launch_bounds__(THREADS) void bm_write_kernel(const Name name, cons
 struct dm_bedmerge {
     dm_xyrows* xy = nullptr;                            // stream, the scan and its block sums
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // parse, add, format: begin / end
-    enum { TEXT, COUNT, START, STATUS, OUT, POS, COV, MOD, STRAND, STAT, TBYTES, TLINES, FTEXT, N_BUF };
-    void* buf[N_BUF] = {};
-    size_t cap[N_BUF] = {};
+    enum { POS = xlk::N_SPLIT, COV, MOD, STRAND, STAT, TBYTES, TLINES, FTEXT, N_BUF };
+    DevBufs<N_BUF> b{"dm_bedmerge"};
     dm_summary *plus = nullptr, *minus = nullptr;       // the open contig's tables (null: none), the caller's
     bool fixed = false;                                 // the table length is the contig's: a line beyond it is outside the grammar
     bmk::Name name = {};
@@ -149,40 +147,15 @@ struct dm_bedmerge {
 
 namespace bmk {
 
-int ensure(dm_bedmerge* h, int which, size_t bytes) {
-    if (h->cap[which] >= bytes && h->buf[which]) return DM_OK;
-    if (h->buf[which]) (void)hipFree(h->buf[which]);
-    h->buf[which] = nullptr;
-    h->cap[which] = 0;
-    const size_t want = bytes + (bytes >> 2) + 256;                  // grow-only, a quarter ahead
-    if (hipMalloc(&h->buf[which], want) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(DM_ENOMEM, "dm_bedmerge: hipMalloc(%zu) failed", want);
-    }
-    h->cap[which] = want;
-    return DM_OK;
-}
-
-template <class T>
-T* ptr(dm_bedmerge* h, int which) { return static_cast<T*>(h->buf[which]); }
-
-constexpr int64_t MAX_BYTES = int64_t(1) << 40;
 constexpr int64_t MAX_RECORDS = 0x7fffffffLL;
 
 int record_buffers(dm_bedmerge* h, int64_t n) {
     using B = dm_bedmerge;
     int rc;
     for (int which : {int(B::POS), int(B::COV), int(B::MOD)})
-        if ((rc = ensure(h, which, size_t(n) * 4)) != DM_OK) return rc;
-    for (int which : {int(B::STRAND), int(B::STATUS)})
-        if ((rc = ensure(h, which, size_t(n))) != DM_OK) return rc;
-    return DM_OK;
-}
-
-int add_time(dm_bedmerge* h, int first, double& into) {
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, h->ev[first], h->ev[first + 1]));
-    into += double(ms);
+        if ((rc = h->b.ensure(which, size_t(n) * 4)) != DM_OK) return rc;
+    for (int which : {int(B::STRAND), int(xlk::STATUS)})
+        if ((rc = h->b.ensure(which, size_t(n))) != DM_OK) return rc;
     return DM_OK;
 }
 
@@ -204,13 +177,13 @@ int add_device_records(dm_bedmerge* h, int64_t n, int64_t max_pos, int64_t max_c
     hipStream_t s = h->xy->stream;
     const dim3 grid{unsigned(std::min<int64_t>((n + THREADS - 1) / THREADS, MAX_BLOCKS))};
     HIP_TRY(hipEventRecord(h->ev[2], s));
-    hipLaunchKernelGGL(bm_add_kernel, grid, dim3(THREADS), 0, s, ptr<const int>(h, B::POS), ptr<const int>(h, B::COV), ptr<const int>(h, B::MOD),
-                       ptr<const unsigned char>(h, B::STRAND), (long long)n, static_cast<int*>(dm_summary_device_ptr(h->plus)),
+    hipLaunchKernelGGL(bm_add_kernel, grid, dim3(THREADS), 0, s, h->b.ptr<const int>(B::POS), h->b.ptr<const int>(B::COV), h->b.ptr<const int>(B::MOD),
+                       h->b.ptr<const unsigned char>(B::STRAND), (long long)n, static_cast<int*>(dm_summary_device_ptr(h->plus)),
                        static_cast<int*>(dm_summary_device_ptr(h->minus)), (long long)length);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(h->ev[3], s));
     HIP_TRY(hipStreamSynchronize(s));
-    if ((rc = add_time(h, 2, h->add_ms)) != DM_OK) return rc;
+    if ((rc = add_time(h->ev[2], h->ev[3], h->add_ms)) != DM_OK) return rc;
     h->cov_bound += max_cov;
     h->lines_seen += n;
     h->tile_off.clear();                                              // a format begun before this add is over
@@ -229,8 +202,7 @@ void dm_bedmerge_destroy(dm_bedmerge* h) {
         (void)hipSetDevice(h->xy->device);
         (void)hipStreamSynchronize(h->xy->stream);
     }
-    for (void* b : h->buf)
-        if (b) (void)hipFree(b);
+    h->b.release();
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
     dm_xy_destroy(h->xy);
@@ -244,7 +216,7 @@ dm_bedmerge* dm_bedmerge_create(int device) {
     h->xy = xy;
     bool ok = true;
     for (hipEvent_t& e : h->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-    ok = ok && bmk::ensure(h, dm_bedmerge::STAT, bmk::N_STAT * 8) == DM_OK && bmk::ensure(h, dm_bedmerge::OUT, 16) == DM_OK;
+    ok = ok && h->b.ensure(dm_bedmerge::STAT, bmk::N_STAT * 8) == DM_OK;
     if (!ok) {
         (void)hipGetLastError();
         fail(DM_EDEVICE, "dm_bedmerge_create: events or counters on device %d", device);
@@ -264,7 +236,7 @@ int dm_bedmerge_open(dm_bedmerge* h, dm_summary* plus, dm_summary* minus, const 
     const int64_t length = dm_summary_length(plus);
     if (length != dm_summary_length(minus) || length < 1 || length > bmk::MAX_LENGTH)
         return fail(DM_EINVAL, "dm_bedmerge_open: tables of %lld and %lld positions (equal, 1 to 2^31 - 1)", (long long)length, (long long)dm_summary_length(minus));
-    if (!bmk::set_name(h->name, contig_name)) return fail(DM_EINVAL, "dm_bedmerge_open: a contig name of 1 to %d printable bytes", bmk::MAX_NAME);
+    if (!bmk::set_name(h->name, contig_name)) return fail(DM_EINVAL, "dm_bedmerge_open: a contig name of 1 to %d printable bytes", bed::MAX_NAME);
     h->plus = plus;
     h->minus = minus;
     h->fixed = fixed_length != 0;
@@ -277,7 +249,7 @@ int64_t dm_bedmerge_parse_host(const char* text, int64_t n_bytes, const char* co
                                int64_t cap, int32_t* flag, int64_t* first_bad_line) {
     if (n_bytes < 0 || (n_bytes > 0 && !text) || cap < 0 || (cap > 0 && (!pos || !strand || !cov || !mod))) return fail(DM_EINVAL, "dm_bedmerge_parse_host: null argument");
     bmk::Name name = {};
-    if (!bmk::set_name(name, contig_name)) return fail(DM_EINVAL, "dm_bedmerge_parse_host: a contig name of 1 to %d printable bytes", bmk::MAX_NAME);
+    if (!bmk::set_name(name, contig_name)) return fail(DM_EINVAL, "dm_bedmerge_parse_host: a contig name of 1 to %d printable bytes", bed::MAX_NAME);
     const long long limit = (table_length < 0 || table_length > bmk::MAX_LENGTH) ? bmk::MAX_LENGTH : table_length;
     int64_t bad = 0;
     const int64_t rows = bmk::parse_text(text, n_bytes, name, limit, pos, strand, cov, mod, cap, &bad);
@@ -289,7 +261,7 @@ int64_t dm_bedmerge_parse_host(const char* text, int64_t n_bytes, const char* co
 int64_t dm_bedmerge_format_host(const char* contig_name, char base, int64_t first_pos, int64_t length, const int32_t* cov_plus, const int32_t* mod_plus,
                                 const int32_t* cov_minus, const int32_t* mod_minus, char* out, int64_t cap, int64_t* n_lines) {
     bmk::Name name = {};
-    if (!bmk::set_name(name, contig_name)) return fail(DM_EINVAL, "dm_bedmerge_format_host: a contig name of 1 to %d printable bytes", bmk::MAX_NAME);
+    if (!bmk::set_name(name, contig_name)) return fail(DM_EINVAL, "dm_bedmerge_format_host: a contig name of 1 to %d printable bytes", bed::MAX_NAME);
     if (first_pos < 0 || length < 0 || first_pos + length > bmk::MAX_LENGTH || cap < 0)
         return fail(DM_EINVAL, "dm_bedmerge_format_host: positions %lld .. +%lld (inside 0 .. 2^31 - 2)", (long long)first_pos, (long long)length);
     if ((cov_plus == nullptr) != (mod_plus == nullptr) || (cov_minus == nullptr) != (mod_minus == nullptr))
@@ -307,55 +279,28 @@ int dm_bedmerge_add_text(dm_bedmerge* h, const char* text, int64_t n_bytes, int6
     if (flag) *flag = 0;
     if (first_bad_line) *first_bad_line = -1;
     if (!h->plus) return fail(DM_ESTATE, "dm_bedmerge_add_text: no contig");
-    if (n_bytes < 0 || n_bytes >= bmk::MAX_BYTES || (n_bytes > 0 && !text)) return fail(DM_EINVAL, "dm_bedmerge_add_text: %lld bytes of text", (long long)n_bytes);
     h->n_records = 0;
-    if (n_bytes == 0) return DM_OK;
     HIP_TRY(hipSetDevice(h->xy->device));
-    const bool add_newline = text[n_bytes - 1] != '\n';
-    const int64_t n = n_bytes + (add_newline ? 1 : 0);
-    const int64_t tiles = (n + xlk::TILE - 1) / xlk::TILE;
-    int rc;
-    if ((rc = bmk::ensure(h, B::TEXT, size_t(tiles) * xlk::TILE)) != DM_OK) return rc;     // whole 16-byte groups behind every lane offset below n
-    if ((rc = bmk::ensure(h, B::COUNT, size_t(tiles + 1) * 8)) != DM_OK) return rc;
     hipStream_t s = h->xy->stream;
-    char* d_text = bmk::ptr<char>(h, B::TEXT);
-    long long* d_count = bmk::ptr<long long>(h, B::COUNT);
-    unsigned long long* d_stat = bmk::ptr<unsigned long long>(h, B::STAT);
-    static const char newline = '\n';
-    HIP_TRY(hipMemcpyAsync(d_text, text, size_t(n_bytes), hipMemcpyHostToDevice, s));
-    if (add_newline) HIP_TRY(hipMemcpyAsync(d_text + n_bytes, &newline, 1, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(d_stat, 0, bmk::N_STAT * 8, s));
-    const dim3 tile_grid{unsigned(tiles)}, block{xlk::THREADS};
-    HIP_TRY(hipEventRecord(h->ev[0], s));
-    hipLaunchKernelGGL(xlk::xl_count_kernel, tile_grid, block, 0, s, d_text, (long long)n, d_count);
-    HIP_TRY(hipGetLastError());
-    if ((rc = xyk::scan_in_place(h->xy, d_count, tiles)) != DM_OK) return rc;
+    unsigned long long* d_stat = h->b.ptr<unsigned long long>(B::STAT);
+    if (n_bytes > 0) HIP_TRY(hipMemsetAsync(d_stat, 0, bmk::N_STAT * 8, s));
+    int rc;
     long long rows = 0;
-    HIP_TRY(hipMemcpyAsync(&rows, d_count + tiles, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (rows < 1 || rows > n) return fail(DM_ESTATE, "dm_bedmerge_add_text: %lld lines in %lld bytes", rows, (long long)n);
-    if (rows > bmk::MAX_RECORDS) return fail(DM_EINVAL, "dm_bedmerge_add_text: %lld lines (at most %lld)", rows, (long long)bmk::MAX_RECORDS);
+    if ((rc = xlk::split(h->xy, h->b, text, n_bytes, bmk::MAX_RECORDS, "dm_bedmerge_add_text", "lines", h->ev[0], &rows)) != DM_OK || rows == 0) return rc;
     if ((rc = bmk::record_buffers(h, rows)) != DM_OK) return rc;
-    if ((rc = bmk::ensure(h, B::START, size_t(rows + 1) * 8)) != DM_OK) return rc;
-    long long* d_start = bmk::ptr<long long>(h, B::START);
-    unsigned char* d_status = bmk::ptr<unsigned char>(h, B::STATUS);
-    long long* d_out = bmk::ptr<long long>(h, B::OUT);
     const long long limit = h->fixed ? (long long)dm_summary_length(h->plus) : bmk::MAX_LENGTH;
-    const dim3 row_grid{unsigned((rows + bmk::THREADS - 1) / bmk::THREADS)};
-    hipLaunchKernelGGL(xlk::xl_lines_kernel, tile_grid, block, 0, s, d_text, (long long)n, d_count, rows, d_start);
+    hipLaunchKernelGGL(bmk::bm_parse_kernel, dim3(unsigned((rows + bmk::THREADS - 1) / bmk::THREADS)), dim3(bmk::THREADS), 0, s, h->b.ptr<const char>(xlk::TEXT),
+                       h->b.ptr<const long long>(xlk::START), rows, h->name, limit, h->b.ptr<int>(B::POS), h->b.ptr<int>(B::COV), h->b.ptr<int>(B::MOD),
+                       h->b.ptr<unsigned char>(B::STRAND), h->b.ptr<unsigned char>(xlk::STATUS), d_stat);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(bmk::bm_parse_kernel, row_grid, dim3(bmk::THREADS), 0, s, d_text, d_start, rows, h->name, limit, bmk::ptr<int>(h, B::POS), bmk::ptr<int>(h, B::COV),
-                       bmk::ptr<int>(h, B::MOD), bmk::ptr<unsigned char>(h, B::STRAND), d_status, d_stat);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(xlk::xl_first_kernel, dim3(1), dim3(xyk::SUM_THREADS), 0, s, d_status, rows, d_out);
-    HIP_TRY(hipGetLastError());
+    if ((rc = xlk::first_bad(h->xy, h->b, rows)) != DM_OK) return rc;
     HIP_TRY(hipEventRecord(h->ev[1], s));
     long long first = -1;
     unsigned long long stat[bmk::N_STAT] = {};
-    HIP_TRY(hipMemcpyAsync(&first, d_out, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&first, h->b.buf[xlk::OUT], 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(stat, d_stat, sizeof stat, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if ((rc = bmk::add_time(h, 0, h->parse_ms)) != DM_OK) return rc;
+    if ((rc = add_time(h->ev[0], h->ev[1], h->parse_ms)) != DM_OK) return rc;
     if (n_lines) *n_lines = rows;
     if (first >= 0) {                                                // outside the grammar: nothing of this text is added
         if (flag) *flag = 1;
@@ -386,10 +331,10 @@ int dm_bedmerge_add_records(dm_bedmerge* h, int64_t n, const int32_t* pos, const
     int rc = bmk::record_buffers(h, n);
     if (rc) return rc;
     hipStream_t s = h->xy->stream;
-    HIP_TRY(hipMemcpyAsync(h->buf[B::POS], pos, size_t(n) * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->buf[B::COV], cov, size_t(n) * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->buf[B::MOD], mod, size_t(n) * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->buf[B::STRAND], strand, size_t(n), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->b.buf[B::POS], pos, size_t(n) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->b.buf[B::COV], cov, size_t(n) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->b.buf[B::MOD], mod, size_t(n) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->b.buf[B::STRAND], strand, size_t(n), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));
     h->n_records = n;
     return bmk::add_device_records(h, n, max_pos, max_cov);
@@ -401,10 +346,10 @@ int dm_bedmerge_fetch_records(dm_bedmerge* h, int32_t* pos, uint8_t* strand, int
     const size_t n = size_t(h->n_records);
     if (n == 0) return DM_OK;
     HIP_TRY(hipSetDevice(h->xy->device));
-    if (pos) HIP_TRY(hipMemcpy(pos, h->buf[B::POS], n * 4, hipMemcpyDeviceToHost));
-    if (cov) HIP_TRY(hipMemcpy(cov, h->buf[B::COV], n * 4, hipMemcpyDeviceToHost));
-    if (mod) HIP_TRY(hipMemcpy(mod, h->buf[B::MOD], n * 4, hipMemcpyDeviceToHost));
-    if (strand) HIP_TRY(hipMemcpy(strand, h->buf[B::STRAND], n, hipMemcpyDeviceToHost));
+    if (pos) HIP_TRY(hipMemcpy(pos, h->b.buf[B::POS], n * 4, hipMemcpyDeviceToHost));
+    if (cov) HIP_TRY(hipMemcpy(cov, h->b.buf[B::COV], n * 4, hipMemcpyDeviceToHost));
+    if (mod) HIP_TRY(hipMemcpy(mod, h->b.buf[B::MOD], n * 4, hipMemcpyDeviceToHost));
+    if (strand) HIP_TRY(hipMemcpy(strand, h->b.buf[B::STRAND], n, hipMemcpyDeviceToHost));
     return DM_OK;
 }
 
@@ -424,11 +369,11 @@ int dm_bedmerge_format_begin(dm_bedmerge* h, char base, int64_t* n_lines, int64_
     if (length != dm_summary_length(h->minus) || length < 1 || length > bmk::MAX_LENGTH)
         return fail(DM_ESTATE, "dm_bedmerge_format_begin: tables of %lld and %lld positions", (long long)length, (long long)dm_summary_length(h->minus));
     const int64_t tiles = (length + bmk::TILE_POS - 1) / bmk::TILE_POS;
-    if ((rc = bmk::ensure(h, B::TBYTES, size_t(tiles + 1) * 8)) != DM_OK || (rc = bmk::ensure(h, B::TLINES, size_t(tiles + 1) * 8)) != DM_OK) return rc;
+    if ((rc = h->b.ensure(B::TBYTES, size_t(tiles + 1) * 8)) != DM_OK || (rc = h->b.ensure(B::TLINES, size_t(tiles + 1) * 8)) != DM_OK) return rc;
     hipStream_t s = h->xy->stream;
-    long long* d_bytes = bmk::ptr<long long>(h, B::TBYTES);
-    long long* d_lines = bmk::ptr<long long>(h, B::TLINES);
-    unsigned long long* d_stat = bmk::ptr<unsigned long long>(h, B::STAT);
+    long long* d_bytes = h->b.ptr<long long>(B::TBYTES);
+    long long* d_lines = h->b.ptr<long long>(B::TLINES);
+    unsigned long long* d_stat = h->b.ptr<unsigned long long>(B::STAT);
     HIP_TRY(hipMemsetAsync(d_stat + bmk::S_BADSUM, 0, 8, s));
     HIP_TRY(hipEventRecord(h->ev[4], s));
     hipLaunchKernelGGL(bmk::bm_length_kernel, dim3(unsigned(tiles)), dim3(bmk::THREADS), 0, s, h->name, base, static_cast<const int*>(dm_summary_device_ptr(h->plus)),
@@ -443,7 +388,7 @@ int dm_bedmerge_format_begin(dm_bedmerge* h, char base, int64_t* n_lines, int64_
     HIP_TRY(hipMemcpyAsync(&lines, d_lines + tiles, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(&bad, d_stat + bmk::S_BADSUM, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if ((rc = bmk::add_time(h, 4, h->format_ms)) != DM_OK) return rc;
+    if ((rc = add_time(h->ev[4], h->ev[5], h->format_ms)) != DM_OK) return rc;
     if (bad) return fail(DM_EINVAL, "dm_bedmerge_format_begin: the sums of %llu tiles left 0 <= modified <= coverage (int32 overflow through repeated keys)", bad);
     long long largest = 0;
     for (int64_t t = 0; t < tiles; ++t) {
@@ -486,17 +431,17 @@ int dm_bedmerge_format_next(dm_bedmerge* h, char* out, int64_t cap, int64_t* got
         return fail(DM_ESTATE, "dm_bedmerge_format_next: the tables changed since format_begin");
     HIP_TRY(hipSetDevice(h->xy->device));
     int rc;
-    if ((rc = bmk::ensure(h, B::FTEXT, size_t(bytes))) != DM_OK) return rc;
+    if ((rc = h->b.ensure(B::FTEXT, size_t(bytes))) != DM_OK) return rc;
     hipStream_t s = h->xy->stream;
     HIP_TRY(hipEventRecord(h->ev[4], s));
     hipLaunchKernelGGL(bmk::bm_write_kernel, dim3(unsigned(t1 - t0)), dim3(bmk::THREADS), 0, s, h->name, h->format_base, static_cast<const int*>(dm_summary_device_ptr(h->plus)),
-                       static_cast<const int*>(dm_summary_device_ptr(h->minus)), (long long)h->format_length, bmk::ptr<const long long>(h, B::TBYTES), (long long)t0,
-                       bmk::ptr<char>(h, B::FTEXT));
+                       static_cast<const int*>(dm_summary_device_ptr(h->minus)), (long long)h->format_length, h->b.ptr<const long long>(B::TBYTES), (long long)t0,
+                       h->b.ptr<char>(B::FTEXT));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(h->ev[5], s));
-    HIP_TRY(hipMemcpyAsync(out, h->buf[B::FTEXT], size_t(bytes), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out, h->b.buf[B::FTEXT], size_t(bytes), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if ((rc = bmk::add_time(h, 4, h->format_ms)) != DM_OK) return rc;
+    if ((rc = add_time(h->ev[4], h->ev[5], h->format_ms)) != DM_OK) return rc;
     *got = bytes;
     h->next_tile = t1;
     while (h->next_tile < tiles && off[size_t(h->next_tile) + 1] == off[size_t(h->next_tile)]) ++h->next_tile;

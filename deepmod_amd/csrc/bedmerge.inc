@@ -3,7 +3,7 @@
 // tables -> its line in the dialect of DeepMod_tools/sum_chr_mod.py:63.  The kernels of bedmerge.hip.inc and the host entry points below run
 // the same two routines, so the device and the host cannot disagree on a line.
 //
-// Grammar of a line (parse_line; the '\n' is not part of it): fields of printable bytes (0x21 - 0x7e) separated by runs of one or more ' ' /
+// Grammar of a line (parse_line, on the routines of bedline.inc; the '\n' is not part of it): fields of printable bytes (0x21 - 0x7e) separated by runs of one or more ' ' /
 // '\t', leading and trailing runs allowed; at least 12 fields; field 0 is the contig's name byte for byte; fields 1, 9, 11 (position,
 // coverage, modified) are 1 - 10 digits with a value <= 2^31 - 1; field 5 is '+' or '-'; modified <= coverage; position < limit (the table
 // length, at most 2^31 - 1 so that position + 1 is an int32).  Fields 3 and 10 are not looked at: sum_chr_mod.py never reads them.  Inside
@@ -16,25 +16,16 @@
 // that is an integer is exact; any other lies at least 1 / cov > 2^-31 from one, far more than an ulp of a number below 101), so it is
 // Python's int(mod * 100 / cov).
 #pragma once
-#include <cstdint>
-#include <cstring>
+#include "bedline.inc"
 
-#if defined(__HIPCC__)
-#define BM_HD __host__ __device__
-#else
-#define BM_HD
-#endif
+#define BM_HD BED_HD
 
 namespace bmk {
 
-constexpr int MAX_NAME = 255;
+using bed::Name;
 constexpr long long MAX_LENGTH = 0x7fffffffLL;      // positions 0 .. 2^31 - 2
 constexpr int TILE_POS = 1024;                      // positions of one format tile (dm_bedmerge_tile_positions)
 
-struct Name {
-    char s[MAX_NAME + 1];
-    int n;
-};
 struct Rec {
     int pos, cov, mod;
     unsigned char strand;                           // 0 '+', 1 '-'
@@ -42,36 +33,20 @@ struct Rec {
 
 // One line p[0 .. n) (without its '\n') -> its record; false: outside the grammar (r is then unspecified).  Reads p[0 .. n) only.
 BM_HD inline bool parse_line(const char* p, const long long n, const Name& name, const long long limit, Rec& r) {
-    long long i = 0;
-    int f = 0;
+    long long i = 0, b, len;
     long long num[3] = {0, 0, 0};                   // fields 1, 9, 11
+    int f = 0;
     r.strand = 0;
     for (;;) {
-        while (i < n && (p[i] == ' ' || p[i] == '\t')) ++i;
+        bed::skip_seps(p, n, i);
         if (i >= n) break;
-        const long long b = i;
-        for (; i < n; ++i) {
-            const unsigned char c = (unsigned char)p[i];
-            if (c == ' ' || c == '\t') break;
-            if (c < 0x21 || c > 0x7e) return false;
-        }
-        const long long len = i - b;
+        if (bed::next_field(p, n, i, b, len) != bed::F_FIELD) return false;
         if (f == 0) {
-            if (len != name.n) return false;
-            for (int j = 0; j < name.n; ++j)
-                if (p[b + j] != name.s[j]) return false;
+            if (!bed::same_bytes(p, b, len, name.s, name.n)) return false;
         } else if (f == 1 || f == 9 || f == 11) {
-            if (len > 10) return false;
-            long long v = 0;
-            for (long long j = b; j < i; ++j) {
-                if (p[j] < '0' || p[j] > '9') return false;
-                v = v * 10 + (p[j] - '0');
-            }
-            if (v > 0x7fffffffLL) return false;
-            num[f == 1 ? 0 : (f == 9 ? 1 : 2)] = v;
+            if (!bed::parse_u31(p, b, i, num[f == 1 ? 0 : (f == 9 ? 1 : 2)])) return false;
         } else if (f == 5) {
-            if (len != 1 || (p[b] != '+' && p[b] != '-')) return false;
-            r.strand = p[b] == '-' ? 1 : 0;
+            if (!bed::strand_of(p, b, len, r.strand)) return false;
         }
         if (f < 12) ++f;
     }
@@ -157,39 +132,24 @@ BM_HD inline int emit_position(Sink& s, const Name& name, const char base, const
     return lines;
 }
 
-inline bool set_name(Name& name, const char* contig_name) {
-    const size_t n = contig_name ? std::strlen(contig_name) : 0;
-    if (n < 1 || n > size_t(MAX_NAME)) return false;
-    for (size_t j = 0; j < n; ++j)
-        if ((unsigned char)contig_name[j] < 0x21 || (unsigned char)contig_name[j] > 0x7e) return false;
-    std::memset(name.s, 0, sizeof name.s);
-    std::memcpy(name.s, contig_name, n);
-    name.n = int(n);
-    return true;
-}
+// a contig name for `merge`: 1 to bed::MAX_NAME bytes, all of them printable (the name is written into every line of the output)
+inline bool set_name(Name& name, const char* contig_name) { return bed::set_name(name, contig_name) && bed::printable(name.s, name.n); }
 
-// The text [0, n_bytes) line by line (a last line without '\n' ends with the text) -> its records, as many as fit `cap`; -> lines.
+// The text [0, n_bytes) line by line -> its records, as many as fit `cap` (a line outside the grammar: zeros); -> lines.
 // *bad: the first line outside the grammar (1-based), 0: none.
 inline int64_t parse_text(const char* text, const int64_t n_bytes, const Name& name, const long long limit, int32_t* pos, uint8_t* strand, int32_t* cov, int32_t* mod,
                           const int64_t cap, int64_t* bad) {
-    int64_t rows = 0;
-    *bad = 0;
-    for (int64_t b = 0; b < n_bytes;) {
-        const void* nl = std::memchr(text + b, '\n', size_t(n_bytes - b));
-        const int64_t e = nl ? static_cast<const char*>(nl) - text : n_bytes;
+    return bed::for_each_line(text, n_bytes, bad, [&](const char* line, const int64_t len, const int64_t row) {
         Rec v = {0, 0, 0, 0};
-        const bool ok = parse_line(text + b, e - b, name, limit, v);
-        if (!ok && *bad == 0) *bad = rows + 1;
-        if (rows < cap) {
-            pos[rows] = ok ? v.pos : 0;
-            cov[rows] = ok ? v.cov : 0;
-            mod[rows] = ok ? v.mod : 0;
-            strand[rows] = ok ? v.strand : 0;
+        const bool ok = parse_line(line, len, name, limit, v);
+        if (row < cap) {
+            pos[row] = ok ? v.pos : 0;
+            cov[row] = ok ? v.cov : 0;
+            mod[row] = ok ? v.mod : 0;
+            strand[row] = ok ? v.strand : 0;
         }
-        ++rows;
-        b = e + 1;
-    }
-    return rows;
+        return ok;
+    });
 }
 
 // The text of positions first_pos .. first_pos + length - 1 from the four tables: counted first; written only if it fits `cap`.

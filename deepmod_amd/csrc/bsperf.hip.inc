@@ -7,8 +7,7 @@
 //   the join and the classes               bs_count_kernel    one sweep over (strand, position): the R truth slots, and the prediction - kind 0: coverage and
 //                                                             modified count of the two dm_summary tables, kind 1: the clustered percentage of bs_score_kernel
 // deepmod_amd/bsperf.py (HostEngine) is the numpy twin of these kernels and the statement of the semantics.
-// The text of a chunk is split as xyparse.hip.inc splits it (xl_count_kernel, the 64-bit scan, xl_lines_kernel: newline ballots over 16-byte
-// lanes).  A chunk with a line outside the grammar of bsperf.inc reports the first such line and adds nothing.
+// The text of a chunk is split into lines by textlines.hip.inc (xlk::split).  A chunk with a line outside the grammar of bsperf.inc reports the first such line and adds nothing.
 //
 // Exactness.  Everything counted is an integer.  A block counts into a private LDS histogram of 32-bit counters (a block sees fewer than 2^32
 // sites) and adds its non-zero bins to the global 64-bit counters once; the moments and the plain counters are summed per lane, reduced per wave
@@ -20,7 +19,7 @@
 #pragma once
 #include "host.h"
 #include "xyrows.hip.inc"
-#include "xyparse.hip.inc"
+#include "textlines.hip.inc"
 #include "bsperf.inc"
 
 namespace bsk {
@@ -192,9 +191,8 @@ __global__ __launch_bounds__(THREADS) void bs_count_kernel(const unsigned* __res
 struct dm_bsperf {
     dm_xyrows* xy = nullptr;                            // stream, the scan and its block sums
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // parse, fill, count: begin / end
-    enum { TEXT, COUNT, START, STATUS, OUT, WANT, RPOS, RMETA, POS, META, NAMES, LSTAT, TRUTH, SCORE, SPOS, SSTRAND, SPCT, HIST, MOM, STAT, N_BUF };
-    void* buf[N_BUF] = {};
-    size_t cap[N_BUF] = {};
+    enum { WANT = xlk::N_SPLIT, RPOS, RMETA, POS, META, NAMES, LSTAT, TRUTH, SCORE, SPOS, SSTRAND, SPCT, HIST, MOM, STAT, N_BUF };
+    DevBufs<N_BUF> b{"dm_bsperf"};
     bsk::Names names = {};
     bsk::Params par = {};
     int64_t lines[bsk::N_LINE] = {};                    // of every chunk taken so far
@@ -208,32 +206,7 @@ struct dm_bsperf {
 
 namespace bsk {
 
-int ensure(dm_bsperf* h, int which, size_t bytes) {
-    if (h->cap[which] >= bytes && h->buf[which]) return DM_OK;
-    if (h->buf[which]) (void)hipFree(h->buf[which]);
-    h->buf[which] = nullptr;
-    h->cap[which] = 0;
-    const size_t want = bytes + (bytes >> 2) + 256;                  // grow-only, a quarter ahead
-    if (hipMalloc(&h->buf[which], want) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(DM_ENOMEM, "dm_bsperf: hipMalloc(%zu) failed", want);
-    }
-    h->cap[which] = want;
-    return DM_OK;
-}
-
-template <class T>
-T* ptr(dm_bsperf* h, int which) { return static_cast<T*>(h->buf[which]); }
-
-constexpr int64_t MAX_BYTES = int64_t(1) << 40;
 constexpr int64_t MAX_RECORDS = 0x7fffffffLL;
-
-int add_time(dm_bsperf* h, int first, double& into) {
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, h->ev[first], h->ev[first + 1]));
-    into += double(ms);
-    return DM_OK;
-}
 
 size_t hist_counters(const dm_bsperf* h) { return size_t(2) * kind_bins(h->par.n_thr); }
 size_t mom_counters(const dm_bsperf* h) { return size_t(2) * h->par.n_thr * NMOM; }
@@ -246,26 +219,26 @@ int count_kind(dm_bsperf* h, int kind) {
     if (dm_summary_length(h->plus) != h->length || dm_summary_length(h->minus) != h->length)
         return fail(DM_ESTATE, "dm_bsperf: the tables changed since the contig was opened (%lld positions then)", (long long)h->length);
     hipStream_t s = h->xy->stream;
-    unsigned long long* d_stat = ptr<unsigned long long>(h, B::STAT);
-    unsigned long long* d_hist = ptr<unsigned long long>(h, B::HIST) + size_t(kind) * kind_bins(h->par.n_thr);
-    unsigned long long* d_mom = ptr<unsigned long long>(h, B::MOM) + size_t(kind) * h->par.n_thr * NMOM;
+    unsigned long long* d_stat = h->b.ptr<unsigned long long>(B::STAT);
+    unsigned long long* d_hist = h->b.ptr<unsigned long long>(B::HIST) + size_t(kind) * kind_bins(h->par.n_thr);
+    unsigned long long* d_mom = h->b.ptr<unsigned long long>(B::MOM) + size_t(kind) * h->par.n_thr * NMOM;
     const int* plus = static_cast<const int*>(dm_summary_device_ptr(h->plus));
     const int* minus = static_cast<const int*>(dm_summary_device_ptr(h->minus));
     const dim3 grid{unsigned(std::min<int64_t>((2 * h->length + THREADS - 1) / THREADS, MAX_BLOCKS))};
     HIP_TRY(hipMemsetAsync(d_stat + S_BADSUM, 0, 8, s));
     HIP_TRY(hipEventRecord(h->ev[4], s));
     if (kind == 0)
-        hipLaunchKernelGGL(bs_count_kernel<0>, grid, dim3(THREADS), 0, s, ptr<const unsigned>(h, B::TRUTH), plus, minus, (const unsigned char*)nullptr, (long long)h->length,
+        hipLaunchKernelGGL(bs_count_kernel<0>, grid, dim3(THREADS), 0, s, h->b.ptr<const unsigned>(B::TRUTH), plus, minus, (const unsigned char*)nullptr, (long long)h->length,
                            h->par, d_hist, d_mom, d_stat);
     else
-        hipLaunchKernelGGL(bs_count_kernel<1>, grid, dim3(THREADS), 0, s, ptr<const unsigned>(h, B::TRUTH), plus, minus, ptr<const unsigned char>(h, B::SCORE),
+        hipLaunchKernelGGL(bs_count_kernel<1>, grid, dim3(THREADS), 0, s, h->b.ptr<const unsigned>(B::TRUTH), plus, minus, h->b.ptr<const unsigned char>(B::SCORE),
                            (long long)h->length, h->par, d_hist, d_mom, d_stat);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(h->ev[5], s));
     unsigned long long bad = 0;
     HIP_TRY(hipMemcpyAsync(&bad, d_stat + S_BADSUM, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if ((rc = add_time(h, 4, h->count_ms)) != DM_OK) return rc;
+    if ((rc = add_time(h->ev[4], h->ev[5], h->count_ms)) != DM_OK) return rc;
     if (bad) return fail(DM_EINVAL, "dm_bsperf_count: the sums of %llu positions are outside 0 <= modified <= coverage", bad);
     return DM_OK;
 }
@@ -282,8 +255,7 @@ void dm_bsperf_destroy(dm_bsperf* h) {
         (void)hipSetDevice(h->xy->device);
         (void)hipStreamSynchronize(h->xy->stream);
     }
-    for (void* b : h->buf)
-        if (b) (void)hipFree(b);
+    h->b.release();
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
     dm_xy_destroy(h->xy);
@@ -330,12 +302,12 @@ dm_bsperf* dm_bsperf_create(int device, int n_contigs, const char* const* names,
     bool ok = true;
     for (hipEvent_t& e : h->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
     const size_t hist_bytes = bsk::hist_counters(h) * 8, mom_bytes = bsk::mom_counters(h) * 8;
-    ok = ok && bsk::ensure(h, B::HIST, hist_bytes) == DM_OK && bsk::ensure(h, B::MOM, mom_bytes) == DM_OK && bsk::ensure(h, B::STAT, bsk::N_STAT * 8) == DM_OK &&
-         bsk::ensure(h, B::LSTAT, bsk::N_LINE * 8) == DM_OK && bsk::ensure(h, B::OUT, 16) == DM_OK && bsk::ensure(h, B::NAMES, sizeof(bsk::Names)) == DM_OK;
+    ok = ok && h->b.ensure(B::HIST, hist_bytes) == DM_OK && h->b.ensure(B::MOM, mom_bytes) == DM_OK && h->b.ensure(B::STAT, bsk::N_STAT * 8) == DM_OK &&
+         h->b.ensure(B::LSTAT, bsk::N_LINE * 8) == DM_OK && h->b.ensure(B::NAMES, sizeof(bsk::Names)) == DM_OK;
     hipStream_t s = xy->stream;
-    ok = ok && hipMemsetAsync(h->buf[B::HIST], 0, hist_bytes, s) == hipSuccess && hipMemsetAsync(h->buf[B::MOM], 0, mom_bytes, s) == hipSuccess &&
-         hipMemsetAsync(h->buf[B::STAT], 0, bsk::N_STAT * 8, s) == hipSuccess &&
-         hipMemcpyAsync(h->buf[B::NAMES], &h->names, sizeof(bsk::Names), hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+    ok = ok && hipMemsetAsync(h->b.buf[B::HIST], 0, hist_bytes, s) == hipSuccess && hipMemsetAsync(h->b.buf[B::MOM], 0, mom_bytes, s) == hipSuccess &&
+         hipMemsetAsync(h->b.buf[B::STAT], 0, bsk::N_STAT * 8, s) == hipSuccess &&
+         hipMemcpyAsync(h->b.buf[B::NAMES], &h->names, sizeof(bsk::Names), hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         fail(DM_EDEVICE, "dm_bsperf_create: events or counters on device %d", device);
@@ -372,63 +344,36 @@ int dm_bsperf_add_truth_text(dm_bsperf* h, int replicate, const char* text, int6
     if (flag) *flag = 0;
     if (first_bad_line) *first_bad_line = -1;
     if (replicate < 0 || replicate >= h->par.n_rep) return fail(DM_EINVAL, "dm_bsperf_add_truth_text: replicate %d of %d", replicate, h->par.n_rep);
-    if (n_bytes < 0 || n_bytes >= bsk::MAX_BYTES || (n_bytes > 0 && !text)) return fail(DM_EINVAL, "dm_bsperf_add_truth_text: %lld bytes of text", (long long)n_bytes);
     h->n_records = 0;
-    if (n_bytes == 0) return DM_OK;
     HIP_TRY(hipSetDevice(h->xy->device));
-    const bool add_newline = text[n_bytes - 1] != '\n';
-    const int64_t n = n_bytes + (add_newline ? 1 : 0);
-    const int64_t tiles = (n + xlk::TILE - 1) / xlk::TILE;
-    int rc;
-    if ((rc = bsk::ensure(h, B::TEXT, size_t(tiles) * xlk::TILE)) != DM_OK) return rc;      // whole 16-byte groups behind every lane offset below n
-    if ((rc = bsk::ensure(h, B::COUNT, size_t(tiles + 1) * 8)) != DM_OK) return rc;
     hipStream_t s = h->xy->stream;
-    char* d_text = bsk::ptr<char>(h, B::TEXT);
-    long long* d_count = bsk::ptr<long long>(h, B::COUNT);
-    unsigned long long* d_lstat = bsk::ptr<unsigned long long>(h, B::LSTAT);
-    static const char newline = '\n';
-    HIP_TRY(hipMemcpyAsync(d_text, text, size_t(n_bytes), hipMemcpyHostToDevice, s));
-    if (add_newline) HIP_TRY(hipMemcpyAsync(d_text + n_bytes, &newline, 1, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(d_lstat, 0, bsk::N_LINE * 8, s));
-    const dim3 tile_grid{unsigned(tiles)}, block{xlk::THREADS};
-    HIP_TRY(hipEventRecord(h->ev[0], s));
-    hipLaunchKernelGGL(xlk::xl_count_kernel, tile_grid, block, 0, s, d_text, (long long)n, d_count);
-    HIP_TRY(hipGetLastError());
-    if ((rc = xyk::scan_in_place(h->xy, d_count, tiles)) != DM_OK) return rc;
+    unsigned long long* d_lstat = h->b.ptr<unsigned long long>(B::LSTAT);
+    if (n_bytes > 0) HIP_TRY(hipMemsetAsync(d_lstat, 0, bsk::N_LINE * 8, s));
+    int rc;
     long long rows = 0;
-    HIP_TRY(hipMemcpyAsync(&rows, d_count + tiles, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (rows < 1 || rows > n) return fail(DM_ESTATE, "dm_bsperf_add_truth_text: %lld lines in %lld bytes", rows, (long long)n);
-    if (rows > bsk::MAX_RECORDS) return fail(DM_EINVAL, "dm_bsperf_add_truth_text: %lld lines in one chunk (at most %lld)", rows, (long long)bsk::MAX_RECORDS);
+    if ((rc = xlk::split(h->xy, h->b, text, n_bytes, bsk::MAX_RECORDS, "dm_bsperf_add_truth_text", "lines in one chunk", h->ev[0], &rows)) != DM_OK || rows == 0) return rc;
     for (int which : {int(B::RPOS), int(B::RMETA), int(B::POS), int(B::META)})
-        if ((rc = bsk::ensure(h, which, size_t(rows) * 4)) != DM_OK) return rc;
-    if ((rc = bsk::ensure(h, B::STATUS, size_t(rows))) != DM_OK || (rc = bsk::ensure(h, B::START, size_t(rows + 1) * 8)) != DM_OK ||
-        (rc = bsk::ensure(h, B::WANT, size_t(rows + 1) * 8)) != DM_OK)
-        return rc;
-    long long* d_start = bsk::ptr<long long>(h, B::START);
-    long long* d_want = bsk::ptr<long long>(h, B::WANT);
-    unsigned char* d_status = bsk::ptr<unsigned char>(h, B::STATUS);
-    long long* d_out = bsk::ptr<long long>(h, B::OUT);
+        if ((rc = h->b.ensure(which, size_t(rows) * 4)) != DM_OK) return rc;
+    if ((rc = h->b.ensure(xlk::STATUS, size_t(rows))) != DM_OK || (rc = h->b.ensure(B::WANT, size_t(rows + 1) * 8)) != DM_OK) return rc;
+    long long* d_want = h->b.ptr<long long>(B::WANT);
     const dim3 row_grid{unsigned((rows + bsk::THREADS - 1) / bsk::THREADS)};
-    hipLaunchKernelGGL(xlk::xl_lines_kernel, tile_grid, block, 0, s, d_text, (long long)n, d_count, rows, d_start);
+    hipLaunchKernelGGL(bsk::bs_parse_kernel, row_grid, dim3(bsk::THREADS), 0, s, h->b.ptr<const char>(xlk::TEXT), h->b.ptr<const long long>(xlk::START), rows,
+                       h->b.ptr<const bsk::Names>(B::NAMES), is_first_chunk != 0 ? 1 : 0, h->b.ptr<int>(B::RPOS), h->b.ptr<unsigned>(B::RMETA), d_want,
+                       h->b.ptr<unsigned char>(xlk::STATUS), d_lstat);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(bsk::bs_parse_kernel, row_grid, dim3(bsk::THREADS), 0, s, d_text, d_start, rows, bsk::ptr<const bsk::Names>(h, B::NAMES), is_first_chunk != 0 ? 1 : 0,
-                       bsk::ptr<int>(h, B::RPOS), bsk::ptr<unsigned>(h, B::RMETA), d_want, d_status, d_lstat);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(xlk::xl_first_kernel, dim3(1), dim3(xyk::SUM_THREADS), 0, s, d_status, rows, d_out);
-    HIP_TRY(hipGetLastError());
+    if ((rc = xlk::first_bad(h->xy, h->b, rows)) != DM_OK) return rc;
     if ((rc = xyk::scan_in_place(h->xy, d_want, rows)) != DM_OK) return rc;
-    hipLaunchKernelGGL(bsk::bs_compact_kernel, row_grid, dim3(bsk::THREADS), 0, s, bsk::ptr<const int>(h, B::RPOS), bsk::ptr<const unsigned>(h, B::RMETA), d_want, rows,
-                       bsk::ptr<int>(h, B::POS), bsk::ptr<unsigned>(h, B::META));
+    hipLaunchKernelGGL(bsk::bs_compact_kernel, row_grid, dim3(bsk::THREADS), 0, s, h->b.ptr<const int>(B::RPOS), h->b.ptr<const unsigned>(B::RMETA), d_want, rows,
+                       h->b.ptr<int>(B::POS), h->b.ptr<unsigned>(B::META));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(h->ev[1], s));
     long long first = -1, recs = 0;
     unsigned long long counted[bsk::N_LINE] = {};
-    HIP_TRY(hipMemcpyAsync(&first, d_out, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&first, h->b.buf[xlk::OUT], 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(&recs, d_want + rows, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(counted, d_lstat, sizeof counted, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if ((rc = bsk::add_time(h, 0, h->parse_ms)) != DM_OK) return rc;
+    if ((rc = add_time(h->ev[0], h->ev[1], h->parse_ms)) != DM_OK) return rc;
     if (first >= 0) {                                                // outside the grammar: nothing of this chunk is taken
         if (flag) *flag = 1;
         if (first_bad_line) *first_bad_line = first + 1;
@@ -465,10 +410,10 @@ int dm_bsperf_add_truth_records(dm_bsperf* h, int replicate, int64_t n, const ui
         for (int64_t i = 0; i < n; ++i) meta[size_t(i)] = bsk::pack_meta(contig[i], strand[i], cov[i], pct[i]);
         HIP_TRY(hipSetDevice(h->xy->device));
         int rc;
-        if ((rc = bsk::ensure(h, B::POS, size_t(n) * 4)) != DM_OK || (rc = bsk::ensure(h, B::META, size_t(n) * 4)) != DM_OK) return rc;
+        if ((rc = h->b.ensure(B::POS, size_t(n) * 4)) != DM_OK || (rc = h->b.ensure(B::META, size_t(n) * 4)) != DM_OK) return rc;
         hipStream_t s = h->xy->stream;
-        HIP_TRY(hipMemcpyAsync(h->buf[B::POS], pos, size_t(n) * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(h->buf[B::META], meta.data(), size_t(n) * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(h->b.buf[B::POS], pos, size_t(n) * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(h->b.buf[B::META], meta.data(), size_t(n) * 4, hipMemcpyHostToDevice, s));
         HIP_TRY(hipStreamSynchronize(s));
     }
     for (int k = 0; k < bsk::N_LINE; ++k) h->lines[k] += lines[k];
@@ -482,8 +427,8 @@ int dm_bsperf_fetch_records(dm_bsperf* h, int32_t* pos, uint32_t* meta) {
     const size_t n = size_t(h->n_records);
     if (n == 0) return DM_OK;
     HIP_TRY(hipSetDevice(h->xy->device));
-    if (pos) HIP_TRY(hipMemcpy(pos, h->buf[B::POS], n * 4, hipMemcpyDeviceToHost));
-    if (meta) HIP_TRY(hipMemcpy(meta, h->buf[B::META], n * 4, hipMemcpyDeviceToHost));
+    if (pos) HIP_TRY(hipMemcpy(pos, h->b.buf[B::POS], n * 4, hipMemcpyDeviceToHost));
+    if (meta) HIP_TRY(hipMemcpy(meta, h->b.buf[B::META], n * 4, hipMemcpyDeviceToHost));
     return DM_OK;
 }
 
@@ -511,9 +456,9 @@ int dm_bsperf_open(dm_bsperf* h, int contig_index, dm_summary* plus, dm_summary*
     HIP_TRY(hipSetDevice(h->xy->device));
     const size_t slots = size_t(h->par.n_rep) * 2 * size_t(length);
     int rc;
-    if ((rc = bsk::ensure(h, B::TRUTH, slots * 4)) != DM_OK) return rc;
+    if ((rc = h->b.ensure(B::TRUTH, slots * 4)) != DM_OK) return rc;
     hipStream_t s = h->xy->stream;
-    HIP_TRY(hipMemsetAsync(h->buf[B::TRUTH], 0, slots * 4, s));
+    HIP_TRY(hipMemsetAsync(h->b.buf[B::TRUTH], 0, slots * 4, s));
     HIP_TRY(hipStreamSynchronize(s));
     h->plus = plus;
     h->minus = minus;
@@ -538,23 +483,23 @@ int dm_bsperf_fill(dm_bsperf* h, int replicate, int64_t n, const int32_t* pos, c
     if (n == 0) return DM_OK;
     HIP_TRY(hipSetDevice(h->xy->device));
     int rc;
-    if ((rc = bsk::ensure(h, B::POS, size_t(n) * 4)) != DM_OK || (rc = bsk::ensure(h, B::META, size_t(n) * 4)) != DM_OK) return rc;
+    if ((rc = h->b.ensure(B::POS, size_t(n) * 4)) != DM_OK || (rc = h->b.ensure(B::META, size_t(n) * 4)) != DM_OK) return rc;
     h->n_records = 0;                                                // the record buffers now hold this fill
     hipStream_t s = h->xy->stream;
-    unsigned long long* d_stat = bsk::ptr<unsigned long long>(h, B::STAT);
-    HIP_TRY(hipMemcpyAsync(h->buf[B::POS], pos, size_t(n) * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->buf[B::META], meta, size_t(n) * 4, hipMemcpyHostToDevice, s));
+    unsigned long long* d_stat = h->b.ptr<unsigned long long>(B::STAT);
+    HIP_TRY(hipMemcpyAsync(h->b.buf[B::POS], pos, size_t(n) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->b.buf[B::META], meta, size_t(n) * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(d_stat + bsk::S_DUP, 0xff, 8, s));
     const dim3 grid{unsigned(std::min<int64_t>((n + bsk::THREADS - 1) / bsk::THREADS, bsk::MAX_BLOCKS))};
     HIP_TRY(hipEventRecord(h->ev[2], s));
-    hipLaunchKernelGGL(bsk::bs_fill_kernel, grid, dim3(bsk::THREADS), 0, s, bsk::ptr<const int>(h, B::POS), bsk::ptr<const unsigned>(h, B::META), (long long)n,
-                       bsk::ptr<unsigned>(h, B::TRUTH) + size_t(replicate) * 2 * size_t(h->length), (long long)h->length, d_stat);
+    hipLaunchKernelGGL(bsk::bs_fill_kernel, grid, dim3(bsk::THREADS), 0, s, h->b.ptr<const int>(B::POS), h->b.ptr<const unsigned>(B::META), (long long)n,
+                       h->b.ptr<unsigned>(B::TRUTH) + size_t(replicate) * 2 * size_t(h->length), (long long)h->length, d_stat);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(h->ev[3], s));
     unsigned long long dup = ~0ull;
     HIP_TRY(hipMemcpyAsync(&dup, d_stat + bsk::S_DUP, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if ((rc = bsk::add_time(h, 2, h->fill_ms)) != DM_OK) return rc;
+    if ((rc = add_time(h->ev[2], h->ev[3], h->fill_ms)) != DM_OK) return rc;
     if (dup != ~0ull) {
         h->refused = true;
         if (dup_pos) *dup_pos = int64_t(dup >> 1);
@@ -595,18 +540,18 @@ int dm_bsperf_add_scores(dm_bsperf* h, int64_t n, const int32_t* pos, const uint
     if (twice != key.end()) return fail(DM_EINVAL, "dm_bsperf_add_scores: position %lld of strand %c occurs twice", (long long)(*twice >> 1), (*twice & 1) ? '-' : '+');
     HIP_TRY(hipSetDevice(h->xy->device));
     int rc;
-    if ((rc = bsk::ensure(h, B::SCORE, size_t(h->length) * 2)) != DM_OK || (rc = bsk::ensure(h, B::SPOS, size_t(n) * 4 + 4)) != DM_OK ||
-        (rc = bsk::ensure(h, B::SSTRAND, size_t(n) + 1)) != DM_OK || (rc = bsk::ensure(h, B::SPCT, size_t(n) + 1)) != DM_OK)
+    if ((rc = h->b.ensure(B::SCORE, size_t(h->length) * 2)) != DM_OK || (rc = h->b.ensure(B::SPOS, size_t(n) * 4 + 4)) != DM_OK ||
+        (rc = h->b.ensure(B::SSTRAND, size_t(n) + 1)) != DM_OK || (rc = h->b.ensure(B::SPCT, size_t(n) + 1)) != DM_OK)
         return rc;
     hipStream_t s = h->xy->stream;
-    HIP_TRY(hipMemsetAsync(h->buf[B::SCORE], 0, size_t(h->length) * 2, s));
+    HIP_TRY(hipMemsetAsync(h->b.buf[B::SCORE], 0, size_t(h->length) * 2, s));
     if (n > 0) {
-        HIP_TRY(hipMemcpyAsync(h->buf[B::SPOS], pos, size_t(n) * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(h->buf[B::SSTRAND], strand, size_t(n), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(h->buf[B::SPCT], value.data(), size_t(n), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(h->b.buf[B::SPOS], pos, size_t(n) * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(h->b.buf[B::SSTRAND], strand, size_t(n), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(h->b.buf[B::SPCT], value.data(), size_t(n), hipMemcpyHostToDevice, s));
         const dim3 grid{unsigned(std::min<int64_t>((n + bsk::THREADS - 1) / bsk::THREADS, bsk::MAX_BLOCKS))};
-        hipLaunchKernelGGL(bsk::bs_score_kernel, grid, dim3(bsk::THREADS), 0, s, bsk::ptr<const int>(h, B::SPOS), bsk::ptr<const unsigned char>(h, B::SSTRAND),
-                           bsk::ptr<const unsigned char>(h, B::SPCT), (long long)n, bsk::ptr<unsigned char>(h, B::SCORE), (long long)h->length);
+        hipLaunchKernelGGL(bsk::bs_score_kernel, grid, dim3(bsk::THREADS), 0, s, h->b.ptr<const int>(B::SPOS), h->b.ptr<const unsigned char>(B::SSTRAND),
+                           h->b.ptr<const unsigned char>(B::SPCT), (long long)n, h->b.ptr<unsigned char>(B::SCORE), (long long)h->length);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipStreamSynchronize(s));                                // the host arrays of this call are read by now
@@ -623,9 +568,9 @@ int dm_bsperf_fetch(dm_bsperf* h, int64_t* hist, int64_t* unpredicted, int64_t* 
     const int T = h->par.n_thr, per_kind = bsk::kind_bins(T), hist_part = 3 * T * bsk::NPCT;
     std::vector<long long> all(bsk::hist_counters(h));
     long long stat[bsk::N_STAT];
-    HIP_TRY(hipMemcpy(all.data(), h->buf[B::HIST], all.size() * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(stat, h->buf[B::STAT], sizeof stat, hipMemcpyDeviceToHost));
-    if (moments) HIP_TRY(hipMemcpy(moments, h->buf[B::MOM], bsk::mom_counters(h) * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(all.data(), h->b.buf[B::HIST], all.size() * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(stat, h->b.buf[B::STAT], sizeof stat, hipMemcpyDeviceToHost));
+    if (moments) HIP_TRY(hipMemcpy(moments, h->b.buf[B::MOM], bsk::mom_counters(h) * 8, hipMemcpyDeviceToHost));
     for (int kind = 0; kind < 2; ++kind) {
         if (hist)
             for (int j = 0; j < hist_part; ++j) hist[kind * hist_part + j] = all[size_t(kind) * per_kind + j];

@@ -5,21 +5,16 @@
 // The reading rules are readBed's (hm_cluster_predict.py:20-41; cluster_train.read_truth): the first line of a FILE is skipped unread (the
 // caller says which chunk starts a file); a line whose length without leading and trailing ' ' / '\t' is <= 20 is skipped; a kept line has
 // exactly 11 fields, of which 0 (contig), 1 (position), 5 (strand), 9 (coverage) and 10 (percentage) are used; a line with coverage 0 is dropped.
-// Grammar of a kept line (parse_line; the '\n' is not part of it): fields of printable bytes (0x21 - 0x7e) separated by runs of one or more
+// Grammar of a kept line (parse_line, on the routines of bedline.inc; the '\n' is not part of it): fields of printable bytes (0x21 - 0x7e) separated by runs of one or more
 // ' ' / '\t', leading and trailing runs allowed; exactly 11 fields; fields 1, 9, 10 are 1 - 10 digits with a value <= 2^31 - 1; field 10 is
 // <= 100; the position of a line of a requested contig is below that contig's limit (its length, or 2^31 - 1).  Outside are 10 or 12 fields,
 // '\r', a sign, 11 digits, a percentage of 101, a position beyond the contig.
 // Classes, decided in this order on a line inside the grammar: strand neither '+' nor '-' (skipped and counted), contig not among the requested
 // names (compared byte for byte: chr1 is neither chr10 nor chr), coverage 0 (dropped), record.
 #pragma once
-#include <cstdint>
-#include <cstring>
+#include "bedline.inc"
 
-#if defined(__HIPCC__)
-#define BS_HD __host__ __device__
-#else
-#define BS_HD
-#endif
+#define BS_HD BED_HD
 
 namespace bsk {
 
@@ -58,34 +53,20 @@ BS_HD inline int meta_contig(const unsigned m) { return int(m >> 24); }
 
 // One line p[0 .. n) (without its '\n') -> its class (L_RECORD: r is its record; L_BAD: outside the grammar).  Reads p[0 .. n) only.
 BS_HD inline int parse_line(const char* p, const long long n, const Names& names, Rec& r) {
-    long long lo = 0, hi = n;
-    while (lo < hi && (p[lo] == ' ' || p[lo] == '\t')) ++lo;
-    while (hi > lo && (p[hi - 1] == ' ' || p[hi - 1] == '\t')) --hi;
-    if (hi - lo <= SHORT_LINE) return L_SHORT;
-    long long i = lo, name_b = 0, name_len = 0, strand_b = 0, strand_len = 0;
-    int f = 0;
+    long long i = 0, hi = n;
+    bed::skip_seps(p, n, i);
+    while (hi > i && bed::is_sep(p[hi - 1])) --hi;
+    if (hi - i <= SHORT_LINE) return L_SHORT;
+    long long b, len, name_b = 0, name_len = 0, strand_b = 0, strand_len = 0;
     long long num[3] = {0, 0, 0};                   // fields 1, 9, 10
-    while (i < hi) {
-        while (i < hi && (p[i] == ' ' || p[i] == '\t')) ++i;
-        const long long b = i;
-        for (; i < hi; ++i) {
-            const unsigned char c = (unsigned char)p[i];
-            if (c == ' ' || c == '\t') break;
-            if (c < 0x21 || c > 0x7e) return L_BAD;
-        }
-        const long long len = i - b;
+    int f = 0;
+    for (; i < hi; bed::skip_seps(p, hi, i)) {
+        if (bed::next_field(p, hi, i, b, len) != bed::F_FIELD) return L_BAD;
         if (f == 0) {
             name_b = b;
             name_len = len;
         } else if (f == 1 || f == 9 || f == 10) {
-            if (len > 10) return L_BAD;
-            long long v = 0;
-            for (long long j = b; j < i; ++j) {
-                if (p[j] < '0' || p[j] > '9') return L_BAD;
-                v = v * 10 + (p[j] - '0');
-            }
-            if (v > 0x7fffffffLL) return L_BAD;
-            num[f == 1 ? 0 : f - 8] = v;
+            if (!bed::parse_u31(p, b, i, num[f == 1 ? 0 : f - 8])) return L_BAD;
         } else if (f == 5) {
             strand_b = b;
             strand_len = len;
@@ -93,19 +74,16 @@ BS_HD inline int parse_line(const char* p, const long long n, const Names& names
         if (++f > 11) return L_BAD;
     }
     if (f != 11 || num[2] > 100) return L_BAD;
-    if (strand_len != 1 || (p[strand_b] != '+' && p[strand_b] != '-')) return L_STRAND;
+    unsigned char strand;
+    if (!bed::strand_of(p, strand_b, strand_len, strand)) return L_STRAND;
     int c = -1;
-    for (int k = 0; k < names.n && c < 0; ++k) {
-        if (names.len[k] != name_len) continue;
-        bool same = true;
-        for (int j = 0; j < names.len[k]; ++j) same = same && p[name_b + j] == names.s[k][j];
-        if (same) c = k;
-    }
+    for (int k = 0; k < names.n && c < 0; ++k)
+        if (bed::same_bytes(p, name_b, name_len, names.s[k], names.len[k])) c = k;
     if (c < 0) return L_CONTIG;
     if (num[0] >= names.limit[c]) return L_BAD;
     if (num[1] == 0) return L_ZERO;
     r.pos = int(num[0]);
-    r.meta = pack_meta(c, p[strand_b] == '-' ? 1 : 0, num[1], int(num[2]));
+    r.meta = pack_meta(c, strand, num[1], int(num[2]));
     return L_RECORD;
 }
 
@@ -115,9 +93,7 @@ inline int set_names(Names& names, const int n, const char* const* list, const i
     if (n < 1 || n > MAX_CONTIGS || !list) return 1;
     for (int k = 0; k < n; ++k) {
         const size_t len = list[k] ? std::strlen(list[k]) : 0;
-        if (len < 1 || len > size_t(MAX_NAME)) return k + 1;
-        for (size_t j = 0; j < len; ++j)
-            if ((unsigned char)list[k][j] < 0x21 || (unsigned char)list[k][j] > 0x7e) return k + 1;
+        if (len < 1 || len > size_t(MAX_NAME) || !bed::printable(list[k], (long long)len)) return k + 1;
         for (int q = 0; q < k; ++q)
             if (size_t(names.len[q]) == len && std::memcmp(names.s[q], list[k], len) == 0) return k + 1;
         std::memcpy(names.s[k], list[k], len);
@@ -134,29 +110,22 @@ inline int set_names(Names& names, const int n, const char* const* list, const i
 // -> records.  lines [N_LINE]: the lines of every class; *bad: the first line outside the grammar (1-based), 0: none.
 inline int64_t parse_text(const char* text, const int64_t n_bytes, const Names& names, const bool first_chunk, int32_t* pos, uint32_t* meta, const int64_t cap,
                           int64_t* lines, int64_t* bad) {
-    int64_t rows = 0, recs = 0;
-    *bad = 0;
+    int64_t recs = 0;
     for (int k = 0; k < N_LINE; ++k) lines[k] = 0;
-    for (int64_t b = 0; b < n_bytes;) {
-        const void* nl = std::memchr(text + b, '\n', size_t(n_bytes - b));
-        const int64_t e = nl ? static_cast<const char*>(nl) - text : n_bytes;
+    bed::for_each_line(text, n_bytes, bad, [&](const char* line, const int64_t len, const int64_t row) {
         Rec v = {0, 0};
-        const int cls = (first_chunk && rows == 0) ? int(L_HEADER) : parse_line(text + b, e - b, names, v);
-        ++rows;
-        if (cls == L_BAD) {
-            if (*bad == 0) *bad = rows;
-        } else {
-            ++lines[cls];
-            if (cls == L_RECORD) {
-                if (recs < cap) {
-                    pos[recs] = v.pos;
-                    meta[recs] = v.meta;
-                }
-                ++recs;
+        const int cls = (first_chunk && row == 0) ? int(L_HEADER) : parse_line(line, len, names, v);
+        if (cls == L_BAD) return false;
+        ++lines[cls];
+        if (cls == L_RECORD) {
+            if (recs < cap) {
+                pos[recs] = v.pos;
+                meta[recs] = v.meta;
             }
+            ++recs;
         }
-        b = e + 1;
-    }
+        return true;
+    });
     return recs;
 }
 

@@ -1,6 +1,7 @@
 // host.h - what the host-side translation units of libdeepmod_hip.so share (deepmod_hip.hip, summary.hip, feed.hip, offline.hip; DESIGN.md
 // "Translation units").  Internal, not installed.  Declarations only: every object named here is defined exactly once, in deepmod_hip.hip
-// (map_read_core: in readmap.inc) - a variable defined in this header would silently become one copy per unit.
+// (map_read_core: in readmap.inc) - a variable defined in this header would silently become one copy per unit.  The two pieces of code it
+// holds are inline and own no object: DevBufs, the grow-only device blocks of a handle, and add_time.
 // Without HIP (g++ on the host-only files: tests/asan/host_shim.cpp) the header is its first part alone: the C ABI and the error slot.
 #pragma once
 
@@ -52,6 +53,45 @@ namespace dmhost {
 DM_HIDDEN_SYM bool is_device_ptr(const void* p);
 }  // namespace dmhost
 using dmhost::is_device_ptr;
+
+// The device buffers of a handle, N blocks that only grow: a block that is large enough is kept, a larger one is allocated with room to spare.
+// `who` is the handle's name in the message of a failed allocation.
+template <int N>
+struct DevBufs {
+    const char* who;
+    void* buf[N] = {};
+    size_t cap[N] = {};
+    int ensure(int which, size_t bytes) {
+        if (cap[which] >= bytes && buf[which]) return DM_OK;
+        if (buf[which]) (void)hipFree(buf[which]);
+        buf[which] = nullptr;
+        cap[which] = 0;
+        const size_t want = bytes + (bytes >> 2) + 256;                  // grow-only, a quarter ahead
+        if (hipMalloc(&buf[which], want) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(DM_ENOMEM, "%s: hipMalloc(%zu) failed", who, want);
+        }
+        cap[which] = want;
+        return DM_OK;
+    }
+    template <class T>
+    T* ptr(int which) const { return static_cast<T*>(buf[which]); }
+    void release() {
+        for (int i = 0; i < N; ++i) {
+            if (buf[i]) (void)hipFree(buf[i]);
+            buf[i] = nullptr;
+            cap[i] = 0;
+        }
+    }
+};
+
+// into += the milliseconds between two recorded events that have completed
+DM_HIDDEN_SYM inline int add_time(hipEvent_t begin, hipEvent_t end, double& into) {
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, begin, end));
+    into += double(ms);
+    return DM_OK;
+}
 
 // ---------------------------------------------------------------------------------------------
 // handles that more than one file needs: dm_model crosses units (summary.hip follows its stream, offline.hip reads its device), dm_summary and

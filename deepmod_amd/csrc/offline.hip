@@ -1,9 +1,11 @@
-// offline.hip — libdeepmod_hip.so, training and the offline commands: the BiLSTM trainer, the cluster trainer, getfeatures (the .xy writer), predict
-// (the .xy parser), the resident gather of train --resident, siteperf, merge, bsperf.  Interface to the other units: host.h.
+// offline.hip — libdeepmod_hip.so, training and the offline commands: the BiLSTM trainer, the cluster trainer, getfeatures (the .xy writer), the
+// line splitter of every text parsed on the device (textlines.hip.inc), predict (the .xy parser), the resident gather of train --resident,
+// siteperf, merge, bsperf (their line grammars: siteperf.inc, bedmerge.inc, bsperf.inc on bedline.inc).  Interface to the other units: host.h.
 #include "train.hip.inc"
 #include "cluster_train.hip.inc"
 #include "xyrows.inc"
 #include "xyrows.hip.inc"
+#include "textlines.hip.inc"
 #include "xyparse.hip.inc"
 #include "xygather.hip.inc"
 #include "siteperf.hip.inc"

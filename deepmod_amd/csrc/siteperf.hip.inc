@@ -6,12 +6,10 @@
 //   add_from_dict (:106-131)               sp_walk_kernel   every (position, strand) a control line named -> one label-0 entry, pct = (100 mod) / cov
 // deepmod_amd/siteperf.py (HostEngine) is the numpy twin of these kernels and the statement of the semantics.
 //
-// The text of a file is split as xyparse.hip.inc splits it (xl_count_kernel, the 64-bit scan, xl_lines_kernel: newline ballots over 16-byte
-// lanes), then sp_parse_kernel reads one line per lane.  Device grammar: at least 12 fields of printable bytes, exactly one ' ' or '\t' between
-// two fields, '\n' after the last (the host appends a missing last one); field 0 is the contig's name byte for byte; fields 1, 9, 10, 11 are
-// 1 - 10 digits with a value <= 2^31 - 1; the position lies on the contig, the percentage is <= 100, the modified count is <= the coverage;
-// field 3 is one byte; field 5 is '+' or '-'.  Any other line ('\r', an empty line, two separators, another contig, a sign ...) is marked: the
-// call reports the first of them and counts nothing, and the caller sends the file through its own parser and dm_siteperf_add_records.
+// The text of a file is split into lines by textlines.hip.inc (xlk::split), then sp_parse_kernel reads one line per lane with spk::parse_line
+// (siteperf.inc, where the device grammar is stated).  A line outside it ('\r', an empty line, two separators, another contig, a sign ...) is
+// marked: the call reports the first of them and counts nothing, and the caller sends the file through its own parser and
+// dm_siteperf_add_records.
 //
 // Exactness.  Everything counted is an integer: the histogram hist[category 7][label 2][bucket][percentage 101] (bucket = thresholds <=
 // coverage, minus one; below the smallest threshold: no count), the read-level sums tp / fp / tn / fn and the line counters.  A block counts
@@ -25,7 +23,8 @@
 #pragma once
 #include "host.h"
 #include "xyrows.hip.inc"
-#include "xyparse.hip.inc"
+#include "textlines.hip.inc"
+#include "siteperf.inc"
 
 namespace spk {
 
@@ -35,7 +34,6 @@ constexpr int MAX_THR = 8;
 constexpr int NCAT = 7;                             // M, M_n1B, M_n2B, M_n3B, OtherB, M_nb, Other (:222)
 constexpr int NPCT = 101;
 constexpr int MAX_BLOCKS = 1024;                    // grid of the record kernels: a block loops over its share and flushes once
-constexpr int MAX_NAME = 255;
 constexpr unsigned long long NO_KEY = ~0ull;
 enum { S_TP, S_FP, S_TN, S_FN, S_SKIPPED, S_MISMATCH, S_MAXCOV, S_BADSUM, N_STAT };
 
@@ -43,10 +41,6 @@ struct Motif {
     unsigned char pat[MAX_MOTIF], rc[MAX_MOTIF];    // the motif in upper case, its reverse complement
     int m, k;
     unsigned char B;                                // motif[k] as typed
-};
-struct Name {
-    char s[MAX_NAME + 1];
-    int n;
 };
 struct Thr {
     int t[MAX_THR];                                 // ascending
@@ -56,60 +50,9 @@ struct Recs {                                       // one BED line each
     const int *pos, *cov, *pct, *mod;
     const unsigned char *strand, *base;             // strand 0 '+', 1 '-'
 };
-struct Rec {
-    int pos, cov, pct, mod;
-    unsigned char strand, base;
-};
 
 __host__ __device__ inline unsigned char complement(const unsigned char b) {       // na4com (:29); anything else equals no base
     return b == 'A' ? 'T' : b == 'T' ? 'A' : b == 'C' ? 'G' : b == 'G' ? 'C' : 0;
-}
-
-// One line p[0 .. n) (without its '\n') -> its record; false: outside the grammar (r is then unspecified).
-__host__ __device__ inline bool parse_line(const char* __restrict__ p, const long long n, const Name& name, const long long contig_len, Rec& r) {
-    long long i = 0;
-    int f = 0;
-    long long num[4] = {0, 0, 0, 0};                // fields 1, 9, 10, 11
-    for (;;) {
-        const long long b = i;
-        for (; i < n; ++i) {
-            const unsigned char c = (unsigned char)p[i];
-            if (c == ' ' || c == '\t') break;
-            if (c < 0x21 || c > 0x7e) return false;
-        }
-        const long long len = i - b;
-        if (len == 0) return false;                 // an empty line, two separators in a row, a separator at either end
-        if (f == 0) {
-            if (len != name.n) return false;
-            for (int j = 0; j < name.n; ++j)
-                if (p[b + j] != name.s[j]) return false;
-        } else if (f == 1 || (f >= 9 && f <= 11)) {
-            if (len > 10) return false;
-            long long v = 0;
-            for (long long j = b; j < i; ++j) {
-                if (p[j] < '0' || p[j] > '9') return false;
-                v = v * 10 + (p[j] - '0');
-            }
-            if (v > 0x7fffffffLL) return false;
-            num[f == 1 ? 0 : f - 8] = v;
-        } else if (f == 3) {
-            if (len != 1) return false;
-            r.base = (unsigned char)p[b];
-        } else if (f == 5) {
-            if (len != 1 || (p[b] != '+' && p[b] != '-')) return false;
-            r.strand = p[b] == '-' ? 1 : 0;
-        }
-        if (f < 12) ++f;
-        if (i == n) break;
-        ++i;
-    }
-    if (f < 12) return false;
-    if (num[0] >= contig_len || num[2] > 100 || num[3] > num[1]) return false;
-    r.pos = int(num[0]);
-    r.cov = int(num[1]);
-    r.pct = int(num[2]);
-    r.mod = int(num[3]);
-    return true;
 }
 
 __device__ inline bool matches(const unsigned char* __restrict__ seq, const long long len, const long long first, const unsigned char* pat, const int m) {
@@ -131,7 +74,7 @@ __global__ __launch_bounds__(THREADS) void sp_code_kernel(const unsigned char* _
     code[i] = c;
 }
 
-__global__ __launch_bounds__(THREADS) void sp_parse_kernel(const char* __restrict__ text, const long long* __restrict__ start, const long long n_rows, const Name name,
+__global__ __launch_bounds__(THREADS) void sp_parse_kernel(const char* __restrict__ text, const long long* __restrict__ start, const long long n_rows, const bed::Name name,
                                                           const long long contig_len, int* __restrict__ pos, int* __restrict__ cov, int* __restrict__ pct,
                                                           int* __restrict__ mod, unsigned char* __restrict__ strand, unsigned char* __restrict__ base,
                                                           unsigned char* __restrict__ status) {
@@ -294,9 +237,8 @@ __global__ __launch_bounds__(THREADS) void sp_walk_kernel(const int* __restrict_
 struct dm_siteperf {
     dm_xyrows* xy = nullptr;                            // stream, the scan and its block sums
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    enum { TEXT, COUNT, START, STATUS, OUT, POS, COV, PCT, MOD, STRAND, BASE, SEQ, CODE, TAB, KEY, HIST, STAT, N_BUF };
-    void* buf[N_BUF] = {};
-    size_t cap[N_BUF] = {};
+    enum { POS = xlk::N_SPLIT, COV, PCT, MOD, STRAND, BASE, SEQ, CODE, TAB, KEY, HIST, STAT, N_BUF };
+    DevBufs<N_BUF> b{"dm_siteperf"};
     spk::Thr thr = {};
     spk::Motif motif = {};
     int64_t len = -1, lo = 0, hi = -1;                  // the open contig (len < 0: none) and its region, clipped to the contig
@@ -308,24 +250,6 @@ struct dm_siteperf {
 
 namespace spk {
 
-int ensure(dm_siteperf* h, int which, size_t bytes) {
-    if (h->cap[which] >= bytes && h->buf[which]) return DM_OK;
-    if (h->buf[which]) (void)hipFree(h->buf[which]);
-    h->buf[which] = nullptr;
-    h->cap[which] = 0;
-    const size_t want = bytes + (bytes >> 2) + 256;                  // grow-only, a quarter ahead
-    if (hipMalloc(&h->buf[which], want) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(DM_ENOMEM, "dm_siteperf: hipMalloc(%zu) failed", want);
-    }
-    h->cap[which] = want;
-    return DM_OK;
-}
-
-template <class T>
-T* ptr(dm_siteperf* h, int which) { return static_cast<T*>(h->buf[which]); }
-
-constexpr int64_t MAX_BYTES = int64_t(1) << 40;
 constexpr int64_t MAX_RECORDS = 0x7fffffffLL;
 constexpr int64_t MAX_CONTROL_FILES = int64_t(1) << 16;              // the key holds 16 bits of file index, 40 of line index, 8 of base
 
@@ -333,16 +257,9 @@ int record_buffers(dm_siteperf* h, int64_t n) {
     using B = dm_siteperf;
     int rc;
     for (int which : {int(B::POS), int(B::COV), int(B::PCT), int(B::MOD)})
-        if ((rc = ensure(h, which, size_t(n) * 4)) != DM_OK) return rc;
-    for (int which : {int(B::STRAND), int(B::BASE), int(B::STATUS)})
-        if ((rc = ensure(h, which, size_t(n))) != DM_OK) return rc;
-    return DM_OK;
-}
-
-int add_time(dm_siteperf* h, int first, double& into) {
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, h->ev[first], h->ev[first + 1]));
-    into += double(ms);
+        if ((rc = h->b.ensure(which, size_t(n) * 4)) != DM_OK) return rc;
+    for (int which : {int(B::STRAND), int(B::BASE), int(xlk::STATUS)})
+        if ((rc = h->b.ensure(which, size_t(n))) != DM_OK) return rc;
     return DM_OK;
 }
 
@@ -352,27 +269,27 @@ int count_records(dm_siteperf* h, int role, int64_t n) {
     h->lines_seen += n;
     if (n == 0) return DM_OK;
     hipStream_t s = h->xy->stream;
-    const Recs r = {ptr<const int>(h, B::POS), ptr<const int>(h, B::COV), ptr<const int>(h, B::PCT), ptr<const int>(h, B::MOD),
-                    ptr<const unsigned char>(h, B::STRAND), ptr<const unsigned char>(h, B::BASE)};
+    const Recs r = {h->b.ptr<const int>(B::POS), h->b.ptr<const int>(B::COV), h->b.ptr<const int>(B::PCT), h->b.ptr<const int>(B::MOD),
+                    h->b.ptr<const unsigned char>(B::STRAND), h->b.ptr<const unsigned char>(B::BASE)};
     const dim3 grid{unsigned(std::min<int64_t>((n + THREADS - 1) / THREADS, MAX_BLOCKS))}, block{THREADS};
-    unsigned long long* d_stat = ptr<unsigned long long>(h, B::STAT);
+    unsigned long long* d_stat = h->b.ptr<unsigned long long>(B::STAT);
     if (role == 1) {
         if (h->control_files >= MAX_CONTROL_FILES) return fail(DM_EINVAL, "dm_siteperf: more than %lld control files of one contig", (long long)MAX_CONTROL_FILES);
         HIP_TRY(hipMemsetAsync(d_stat + S_MAXCOV, 0, 8, s));
     }
     HIP_TRY(hipEventRecord(h->ev[2], s));
     if (role == 0)
-        hipLaunchKernelGGL(sp_count_kernel, grid, block, 0, s, r, (long long)n, ptr<const unsigned char>(h, B::CODE), ptr<const unsigned char>(h, B::SEQ), (long long)h->len,
-                           (long long)h->lo, (long long)h->hi, h->motif.B, h->thr, ptr<unsigned long long>(h, B::HIST), d_stat);
+        hipLaunchKernelGGL(sp_count_kernel, grid, block, 0, s, r, (long long)n, h->b.ptr<const unsigned char>(B::CODE), h->b.ptr<const unsigned char>(B::SEQ), (long long)h->len,
+                           (long long)h->lo, (long long)h->hi, h->motif.B, h->thr, h->b.ptr<unsigned long long>(B::HIST), d_stat);
     else
-        hipLaunchKernelGGL(sp_scatter_kernel, grid, block, 0, s, r, (long long)n, ptr<const unsigned char>(h, B::SEQ), (long long)h->lo, (long long)h->hi, h->motif.B,
-                           (unsigned long long)h->control_files, ptr<int>(h, B::TAB), ptr<unsigned long long>(h, B::KEY), d_stat);
+        hipLaunchKernelGGL(sp_scatter_kernel, grid, block, 0, s, r, (long long)n, h->b.ptr<const unsigned char>(B::SEQ), (long long)h->lo, (long long)h->hi, h->motif.B,
+                           (unsigned long long)h->control_files, h->b.ptr<int>(B::TAB), h->b.ptr<unsigned long long>(B::KEY), d_stat);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(h->ev[3], s));
     unsigned long long maxcov = 0;
     if (role == 1) HIP_TRY(hipMemcpyAsync(&maxcov, d_stat + S_MAXCOV, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    int rc = add_time(h, 2, h->count_ms);
+    int rc = add_time(h->ev[2], h->ev[3], h->count_ms);
     if (rc) return rc;
     if (role == 1) {
         ++h->control_files;
@@ -396,8 +313,7 @@ void dm_siteperf_destroy(dm_siteperf* h) {
         (void)hipSetDevice(h->xy->device);
         (void)hipStreamSynchronize(h->xy->stream);
     }
-    for (void* b : h->buf)
-        if (b) (void)hipFree(b);
+    h->b.release();
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
     dm_xy_destroy(h->xy);
@@ -423,10 +339,9 @@ dm_siteperf* dm_siteperf_create(int device, int n_thresholds, const int32_t* thr
     bool ok = true;
     for (hipEvent_t& e : h->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
     const size_t hist_bytes = size_t(spk::NCAT) * 2 * n_thresholds * spk::NPCT * 8;
-    ok = ok && spk::ensure(h, dm_siteperf::HIST, hist_bytes) == DM_OK && spk::ensure(h, dm_siteperf::STAT, spk::N_STAT * 8) == DM_OK &&
-         spk::ensure(h, dm_siteperf::OUT, 16) == DM_OK;
-    ok = ok && hipMemsetAsync(h->buf[dm_siteperf::HIST], 0, hist_bytes, xy->stream) == hipSuccess &&
-         hipMemsetAsync(h->buf[dm_siteperf::STAT], 0, spk::N_STAT * 8, xy->stream) == hipSuccess && hipStreamSynchronize(xy->stream) == hipSuccess;
+    ok = ok && h->b.ensure(dm_siteperf::HIST, hist_bytes) == DM_OK && h->b.ensure(dm_siteperf::STAT, spk::N_STAT * 8) == DM_OK;
+    ok = ok && hipMemsetAsync(h->b.buf[dm_siteperf::HIST], 0, hist_bytes, xy->stream) == hipSuccess &&
+         hipMemsetAsync(h->b.buf[dm_siteperf::STAT], 0, spk::N_STAT * 8, xy->stream) == hipSuccess && hipStreamSynchronize(xy->stream) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         fail(DM_EDEVICE, "dm_siteperf_create: events or counters on device %d", device);
@@ -460,15 +375,15 @@ int dm_siteperf_set_contig(dm_siteperf* h, const uint8_t* seq, int64_t len, cons
     h->hi = (end < 0 || end > len - 1) ? len - 1 : end;
     HIP_TRY(hipSetDevice(h->xy->device));
     int rc;
-    if ((rc = spk::ensure(h, B::SEQ, size_t(len))) || (rc = spk::ensure(h, B::CODE, size_t(len))) || (rc = spk::ensure(h, B::TAB, size_t(len) * 16)) ||
-        (rc = spk::ensure(h, B::KEY, size_t(len) * 16)))
+    if ((rc = h->b.ensure(B::SEQ, size_t(len))) || (rc = h->b.ensure(B::CODE, size_t(len))) || (rc = h->b.ensure(B::TAB, size_t(len) * 16)) ||
+        (rc = h->b.ensure(B::KEY, size_t(len) * 16)))
         return rc;
     hipStream_t s = h->xy->stream;
-    HIP_TRY(hipMemcpyAsync(h->buf[B::SEQ], seq, size_t(len), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(h->buf[B::TAB], 0, size_t(len) * 16, s));
-    HIP_TRY(hipMemsetAsync(h->buf[B::KEY], 0xff, size_t(len) * 16, s));
-    hipLaunchKernelGGL(spk::sp_code_kernel, dim3(unsigned((len + spk::THREADS - 1) / spk::THREADS)), dim3(spk::THREADS), 0, s, spk::ptr<const unsigned char>(h, B::SEQ),
-                       (long long)len, mo, (long long)h->lo, (long long)h->hi, spk::ptr<unsigned char>(h, B::CODE));
+    HIP_TRY(hipMemcpyAsync(h->b.buf[B::SEQ], seq, size_t(len), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(h->b.buf[B::TAB], 0, size_t(len) * 16, s));
+    HIP_TRY(hipMemsetAsync(h->b.buf[B::KEY], 0xff, size_t(len) * 16, s));
+    hipLaunchKernelGGL(spk::sp_code_kernel, dim3(unsigned((len + spk::THREADS - 1) / spk::THREADS)), dim3(spk::THREADS), 0, s, h->b.ptr<const unsigned char>(B::SEQ),
+                       (long long)len, mo, (long long)h->lo, (long long)h->hi, h->b.ptr<unsigned char>(B::CODE));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
     h->len = len;
@@ -481,7 +396,7 @@ int dm_siteperf_fetch_codes(dm_siteperf* h, uint8_t* code) {
     if (!h || !code) return fail(DM_EINVAL, "null argument");
     if (h->len < 0) return fail(DM_ESTATE, "dm_siteperf_fetch_codes: no contig");
     HIP_TRY(hipSetDevice(h->xy->device));
-    HIP_TRY(hipMemcpy(code, h->buf[dm_siteperf::CODE], size_t(h->len), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(code, h->b.buf[dm_siteperf::CODE], size_t(h->len), hipMemcpyDeviceToHost));
     return DM_OK;
 }
 
@@ -489,29 +404,10 @@ int64_t dm_siteperf_parse_host(const char* text, int64_t n_bytes, const char* co
                                int32_t* pct, int32_t* mod, int64_t cap, int32_t* flag, int64_t* first_bad_line) {
     if (n_bytes < 0 || (n_bytes > 0 && !text) || !contig_name || cap < 0 || (cap > 0 && (!pos || !strand || !base || !cov || !pct || !mod)))
         return fail(DM_EINVAL, "dm_siteperf_parse_host: null argument");
-    const size_t name_len = std::strlen(contig_name);
-    if (name_len < 1 || name_len > size_t(spk::MAX_NAME)) return fail(DM_EINVAL, "dm_siteperf_parse_host: a contig name of %zu bytes (1 to %d)", name_len, spk::MAX_NAME);
-    spk::Name name = {};
-    std::memcpy(name.s, contig_name, name_len);
-    name.n = int(name_len);
-    int64_t rows = 0, bad = 0;
-    for (int64_t b = 0; b < n_bytes;) {
-        const void* nl = std::memchr(text + b, '\n', size_t(n_bytes - b));
-        const int64_t e = nl ? static_cast<const char*>(nl) - text : n_bytes;          // a last line without '\n' ends with the text
-        spk::Rec v = {0, 0, 0, 0, 0, 0};
-        const bool ok = spk::parse_line(text + b, e - b, name, contig_len, v);
-        if (!ok && bad == 0) bad = rows + 1;
-        if (rows < cap) {
-            pos[rows] = ok ? v.pos : 0;
-            cov[rows] = ok ? v.cov : 0;
-            pct[rows] = ok ? v.pct : 0;
-            mod[rows] = ok ? v.mod : 0;
-            strand[rows] = ok ? v.strand : 0;
-            base[rows] = ok ? v.base : 0;
-        }
-        ++rows;
-        b = e + 1;
-    }
+    bed::Name name = {};
+    if (!bed::set_name(name, contig_name)) return fail(DM_EINVAL, "dm_siteperf_parse_host: a contig name of %zu bytes (1 to %d)", std::strlen(contig_name), bed::MAX_NAME);
+    int64_t bad = 0;
+    const int64_t rows = spk::parse_text(text, n_bytes, name, contig_len, pos, strand, base, cov, pct, mod, cap, &bad);
     if (flag) *flag = bad != 0;
     if (first_bad_line) *first_bad_line = bad ? bad : -1;
     return rows;
@@ -525,56 +421,26 @@ int dm_siteperf_add_text(dm_siteperf* h, const char* text, int64_t n_bytes, int 
     if (first_bad_line) *first_bad_line = -1;
     if (h->len < 0) return fail(DM_ESTATE, "dm_siteperf_add_text: no contig");
     if (role != 0 && role != 1) return fail(DM_EINVAL, "dm_siteperf_add_text: role %d (0 run, 1 control)", role);
-    if (n_bytes < 0 || n_bytes >= spk::MAX_BYTES || (n_bytes > 0 && !text)) return fail(DM_EINVAL, "dm_siteperf_add_text: %lld bytes of text", (long long)n_bytes);
-    const size_t name_len = contig_name ? std::strlen(contig_name) : 0;
-    if (name_len < 1 || name_len > size_t(spk::MAX_NAME)) return fail(DM_EINVAL, "dm_siteperf_add_text: a contig name of %zu bytes (1 to %d)", name_len, spk::MAX_NAME);
+    bed::Name name = {};
+    if (!bed::set_name(name, contig_name))
+        return fail(DM_EINVAL, "dm_siteperf_add_text: a contig name of %zu bytes (1 to %d)", contig_name ? std::strlen(contig_name) : size_t(0), bed::MAX_NAME);
     h->n_records = 0;
-    if (n_bytes == 0) return DM_OK;
-    spk::Name name = {};
-    std::memcpy(name.s, contig_name, name_len);
-    name.n = int(name_len);
     HIP_TRY(hipSetDevice(h->xy->device));
-    const bool add_newline = text[n_bytes - 1] != '\n';
-    const int64_t n = n_bytes + (add_newline ? 1 : 0);
-    const int64_t tiles = (n + xlk::TILE - 1) / xlk::TILE;
     int rc;
-    if ((rc = spk::ensure(h, B::TEXT, size_t(tiles) * xlk::TILE)) != DM_OK) return rc;     // whole 16-byte groups behind every lane offset below n
-    if ((rc = spk::ensure(h, B::COUNT, size_t(tiles + 1) * 8)) != DM_OK) return rc;
-    hipStream_t s = h->xy->stream;
-    char* d_text = spk::ptr<char>(h, B::TEXT);
-    long long* d_count = spk::ptr<long long>(h, B::COUNT);
-    static const char newline = '\n';
-    HIP_TRY(hipMemcpyAsync(d_text, text, size_t(n_bytes), hipMemcpyHostToDevice, s));
-    if (add_newline) HIP_TRY(hipMemcpyAsync(d_text + n_bytes, &newline, 1, hipMemcpyHostToDevice, s));
-    const dim3 tile_grid{unsigned(tiles)}, block{xlk::THREADS};
-    HIP_TRY(hipEventRecord(h->ev[0], s));
-    hipLaunchKernelGGL(xlk::xl_count_kernel, tile_grid, block, 0, s, d_text, (long long)n, d_count);
-    HIP_TRY(hipGetLastError());
-    if ((rc = xyk::scan_in_place(h->xy, d_count, tiles)) != DM_OK) return rc;
     long long rows = 0;
-    HIP_TRY(hipMemcpyAsync(&rows, d_count + tiles, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (rows < 1 || rows > n) return fail(DM_ESTATE, "dm_siteperf_add_text: %lld lines in %lld bytes", rows, (long long)n);
-    if (rows > spk::MAX_RECORDS) return fail(DM_EINVAL, "dm_siteperf_add_text: %lld lines (at most %lld)", rows, (long long)spk::MAX_RECORDS);
+    if ((rc = xlk::split(h->xy, h->b, text, n_bytes, spk::MAX_RECORDS, "dm_siteperf_add_text", "lines", h->ev[0], &rows)) != DM_OK || rows == 0) return rc;
     if ((rc = spk::record_buffers(h, rows)) != DM_OK) return rc;
-    if ((rc = spk::ensure(h, B::START, size_t(rows + 1) * 8)) != DM_OK) return rc;
-    long long* d_start = spk::ptr<long long>(h, B::START);
-    unsigned char* d_status = spk::ptr<unsigned char>(h, B::STATUS);
-    long long* d_out = spk::ptr<long long>(h, B::OUT);
-    const dim3 row_grid{unsigned((rows + spk::THREADS - 1) / spk::THREADS)};
-    hipLaunchKernelGGL(xlk::xl_lines_kernel, tile_grid, block, 0, s, d_text, (long long)n, d_count, rows, d_start);
+    hipStream_t s = h->xy->stream;
+    hipLaunchKernelGGL(spk::sp_parse_kernel, dim3(unsigned((rows + spk::THREADS - 1) / spk::THREADS)), dim3(spk::THREADS), 0, s, h->b.ptr<const char>(xlk::TEXT),
+                       h->b.ptr<const long long>(xlk::START), rows, name, (long long)h->len, h->b.ptr<int>(B::POS), h->b.ptr<int>(B::COV), h->b.ptr<int>(B::PCT),
+                       h->b.ptr<int>(B::MOD), h->b.ptr<unsigned char>(B::STRAND), h->b.ptr<unsigned char>(B::BASE), h->b.ptr<unsigned char>(xlk::STATUS));
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(spk::sp_parse_kernel, row_grid, dim3(spk::THREADS), 0, s, d_text, d_start, rows, name, (long long)h->len, spk::ptr<int>(h, B::POS),
-                       spk::ptr<int>(h, B::COV), spk::ptr<int>(h, B::PCT), spk::ptr<int>(h, B::MOD), spk::ptr<unsigned char>(h, B::STRAND),
-                       spk::ptr<unsigned char>(h, B::BASE), d_status);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(xlk::xl_first_kernel, dim3(1), dim3(xyk::SUM_THREADS), 0, s, d_status, rows, d_out);
-    HIP_TRY(hipGetLastError());
+    if ((rc = xlk::first_bad(h->xy, h->b, rows)) != DM_OK) return rc;
     HIP_TRY(hipEventRecord(h->ev[1], s));
     long long first = -1;
-    HIP_TRY(hipMemcpyAsync(&first, d_out, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&first, h->b.buf[xlk::OUT], 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if ((rc = spk::add_time(h, 0, h->parse_ms)) != DM_OK) return rc;
+    if ((rc = add_time(h->ev[0], h->ev[1], h->parse_ms)) != DM_OK) return rc;
     if (n_lines) *n_lines = rows;
     if (first >= 0) {                                                // outside the grammar: nothing of this text is counted
         if (flag) *flag = 1;
@@ -602,12 +468,12 @@ int dm_siteperf_add_records(dm_siteperf* h, int role, int64_t n, const int32_t* 
     int rc = spk::record_buffers(h, n);
     if (rc) return rc;
     hipStream_t s = h->xy->stream;
-    HIP_TRY(hipMemcpyAsync(h->buf[B::POS], pos, size_t(n) * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->buf[B::COV], cov, size_t(n) * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->buf[B::PCT], pct, size_t(n) * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->buf[B::MOD], mod, size_t(n) * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->buf[B::STRAND], strand, size_t(n), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->buf[B::BASE], base, size_t(n), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->b.buf[B::POS], pos, size_t(n) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->b.buf[B::COV], cov, size_t(n) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->b.buf[B::PCT], pct, size_t(n) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->b.buf[B::MOD], mod, size_t(n) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->b.buf[B::STRAND], strand, size_t(n), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->b.buf[B::BASE], base, size_t(n), hipMemcpyHostToDevice, s));
     h->n_records = n;
     return spk::count_records(h, role, n);
 }
@@ -618,12 +484,12 @@ int dm_siteperf_fetch_records(dm_siteperf* h, int32_t* pos, uint8_t* strand, uin
     const size_t n = size_t(h->n_records);
     if (n == 0) return DM_OK;
     HIP_TRY(hipSetDevice(h->xy->device));
-    if (pos) HIP_TRY(hipMemcpy(pos, h->buf[B::POS], n * 4, hipMemcpyDeviceToHost));
-    if (cov) HIP_TRY(hipMemcpy(cov, h->buf[B::COV], n * 4, hipMemcpyDeviceToHost));
-    if (pct) HIP_TRY(hipMemcpy(pct, h->buf[B::PCT], n * 4, hipMemcpyDeviceToHost));
-    if (mod) HIP_TRY(hipMemcpy(mod, h->buf[B::MOD], n * 4, hipMemcpyDeviceToHost));
-    if (strand) HIP_TRY(hipMemcpy(strand, h->buf[B::STRAND], n, hipMemcpyDeviceToHost));
-    if (base) HIP_TRY(hipMemcpy(base, h->buf[B::BASE], n, hipMemcpyDeviceToHost));
+    if (pos) HIP_TRY(hipMemcpy(pos, h->b.buf[B::POS], n * 4, hipMemcpyDeviceToHost));
+    if (cov) HIP_TRY(hipMemcpy(cov, h->b.buf[B::COV], n * 4, hipMemcpyDeviceToHost));
+    if (pct) HIP_TRY(hipMemcpy(pct, h->b.buf[B::PCT], n * 4, hipMemcpyDeviceToHost));
+    if (mod) HIP_TRY(hipMemcpy(mod, h->b.buf[B::MOD], n * 4, hipMemcpyDeviceToHost));
+    if (strand) HIP_TRY(hipMemcpy(strand, h->b.buf[B::STRAND], n, hipMemcpyDeviceToHost));
+    if (base) HIP_TRY(hipMemcpy(base, h->b.buf[B::BASE], n, hipMemcpyDeviceToHost));
     return DM_OK;
 }
 
@@ -637,17 +503,17 @@ int dm_siteperf_finish_contig(dm_siteperf* h) {
     if (h->control_files == 0) return DM_OK;                         // no control line: no entry
     HIP_TRY(hipSetDevice(h->xy->device));
     hipStream_t s = h->xy->stream;
-    unsigned long long* d_stat = spk::ptr<unsigned long long>(h, B::STAT);
+    unsigned long long* d_stat = h->b.ptr<unsigned long long>(B::STAT);
     const dim3 grid{unsigned(std::min<int64_t>((2 * len + spk::THREADS - 1) / spk::THREADS, spk::MAX_BLOCKS))};
     HIP_TRY(hipEventRecord(h->ev[2], s));
-    hipLaunchKernelGGL(spk::sp_walk_kernel, grid, dim3(spk::THREADS), 0, s, spk::ptr<const int>(h, B::TAB), spk::ptr<const unsigned long long>(h, B::KEY),
-                       spk::ptr<const unsigned char>(h, B::CODE), (long long)len, h->motif.B, h->thr, spk::ptr<unsigned long long>(h, B::HIST), d_stat);
+    hipLaunchKernelGGL(spk::sp_walk_kernel, grid, dim3(spk::THREADS), 0, s, h->b.ptr<const int>(B::TAB), h->b.ptr<const unsigned long long>(B::KEY),
+                       h->b.ptr<const unsigned char>(B::CODE), (long long)len, h->motif.B, h->thr, h->b.ptr<unsigned long long>(B::HIST), d_stat);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(h->ev[3], s));
     unsigned long long bad = 0;
     HIP_TRY(hipMemcpyAsync(&bad, d_stat + spk::S_BADSUM, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    int rc = spk::add_time(h, 2, h->count_ms);
+    int rc = add_time(h->ev[2], h->ev[3], h->count_ms);
     if (rc) return rc;
     if (bad) return fail(DM_EINVAL, "dm_siteperf_finish_contig: %llu control sums left the int32 range", bad);
     return DM_OK;
@@ -659,8 +525,8 @@ int dm_siteperf_fetch(dm_siteperf* h, int64_t* hist, int64_t* counts, int64_t* l
     HIP_TRY(hipSetDevice(h->xy->device));
     HIP_TRY(hipStreamSynchronize(h->xy->stream));
     long long stat[spk::N_STAT];
-    HIP_TRY(hipMemcpy(stat, h->buf[B::STAT], sizeof stat, hipMemcpyDeviceToHost));
-    if (hist) HIP_TRY(hipMemcpy(hist, h->buf[B::HIST], size_t(spk::NCAT) * 2 * h->thr.n * spk::NPCT * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(stat, h->b.buf[B::STAT], sizeof stat, hipMemcpyDeviceToHost));
+    if (hist) HIP_TRY(hipMemcpy(hist, h->b.buf[B::HIST], size_t(spk::NCAT) * 2 * h->thr.n * spk::NPCT * 8, hipMemcpyDeviceToHost));
     if (counts)
         for (int j = 0; j < 4; ++j) counts[j] = stat[spk::S_TP + j];
     if (lines_seen) *lines_seen = h->lines_seen;

@@ -85,21 +85,6 @@ int set_offsets(dm_xyset* s) {
     return DM_OK;
 }
 
-// a scratch block of dm_xyset_gather (ids or x of a host caller): grow-only, a quarter ahead
-int set_scratch(void*& block, size_t& cap, size_t bytes) {
-    if (block && cap >= bytes) return DM_OK;
-    if (block) (void)hipFree(block);
-    block = nullptr;
-    cap = 0;
-    const size_t want = bytes + (bytes >> 2) + 256;
-    if (hipMalloc(&block, want) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(DM_ENOMEM, "dm_xyset_gather: hipMalloc(%zu) failed", want);
-    }
-    cap = want;
-    return DM_OK;
-}
-
 void launch_gather(dm_xyset* s, const long long* d_ids, int64_t n, float* d_x, unsigned long long* d_bad, hipStream_t stream) {
     hipLaunchKernelGGL(xg_gather_kernel, dim3(unsigned((n + WPB - 1) / WPB)), dim3(THREADS), 0, stream, s->feats, s->centre, s->d_off, int(s->d_off_segs),
                        d_ids, (long long)n, d_x, d_bad);
@@ -164,14 +149,14 @@ int dm_xyset_gather(dm_xyset* s, const int64_t* ids, int64_t n, float* x) {
         (void)hipGetLastError();
         return fail(DM_ENOMEM, "dm_xyset_gather: hipMalloc(8) failed");
     }
-    if (!id_dev && (rc = xgk::set_scratch(s->g_ids, s->cap_g_ids, size_t(n) * 8)) != DM_OK) return rc;
-    if (!x_dev && (rc = xgk::set_scratch(s->g_x, s->cap_g_x, floats * 4)) != DM_OK) return rc;
+    if (!id_dev && (rc = s->gather.ensure(dm_xyset::G_IDS, size_t(n) * 8)) != DM_OK) return rc;
+    if (!x_dev && (rc = s->gather.ensure(dm_xyset::G_X, floats * 4)) != DM_OK) return rc;
     const long long* d_ids = reinterpret_cast<const long long*>(ids);
     if (!id_dev) {
-        HIP_TRY(hipMemcpyAsync(s->g_ids, ids, size_t(n) * 8, hipMemcpyHostToDevice, s->stream));
-        d_ids = static_cast<const long long*>(s->g_ids);
+        HIP_TRY(hipMemcpyAsync(s->gather.buf[dm_xyset::G_IDS], ids, size_t(n) * 8, hipMemcpyHostToDevice, s->stream));
+        d_ids = s->gather.ptr<const long long>(dm_xyset::G_IDS);
     }
-    float* d_x = x_dev ? x : static_cast<float*>(s->g_x);
+    float* d_x = x_dev ? x : s->gather.ptr<float>(dm_xyset::G_X);
     HIP_TRY(hipMemsetAsync(s->g_bad, 0, 8, s->stream));
     xgk::launch_gather(s, d_ids, n, d_x, static_cast<unsigned long long*>(s->g_bad), s->stream);
     HIP_TRY(hipGetLastError());

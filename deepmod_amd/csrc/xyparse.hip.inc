@@ -10,13 +10,9 @@
 // power 10^k of its k decimals as an integer <= 10^15 - both exact as doubles - ONE IEEE division, the sign last (-0.000 is -0.0), the cast to
 // float.  m / 10^k with exact operands is the correctly rounded double of the decimal (Clinger's exact case), i.e. what strtod and np.loadtxt
 // produce before their cast; contraction is off so that the division stays a division.
-// Plain launches on the stream of the handle's scan, no atomics, one writer per output element: two calls on the same bytes give the same bytes.
-//   xl_count_kernel   a tile of TILE bytes, 16 per lane (one dwordx4 load): newlines counted with one ballot per byte column -> count per tile
-//   xyk::scan_in_place  exclusive 64-bit scan of the tile counts: the first line of every tile, the row count R behind them
-//   xl_lines_kernel   the same loads again: a newline's rank = the tile's first line + the block scan of the lane counts -> the first byte of
-//                     every line
+// The text is split into lines by textlines.hip.inc (xlk::split: the newline kernels and the 64-bit scan), then
 //   xl_parse_kernel   one row per lane: parse_row -> head [R][3] (position, two labels), feats [R][7], a status byte
-//   xl_first_kernel   one block: the smallest row with a status byte set (-1: none)
+//   xlk::first_bad    the smallest row with a status byte set (-1: none)
 // Selection (xl_want_kernel, the scan, xl_compact_kernel): a row is wanted unless both labels are below 0.01f; under kind '-' not if
 // lo < int(position) < hi, under '+' only then (the float32 position truncated, as the reference's astype(int)); the wanted rows in ascending
 // order -> centre int32 [n] and label u8 [n] (1: int(column 2) == 1, myMultiBiRNN.py:407); a wanted row with fewer than 10 rows to an edge of the
@@ -26,14 +22,12 @@
 // probability and label come back as three plain copies, 6 bytes per window.
 #pragma once
 #include "host.h"
-#include "blockscan.hip.inc"
 #include "xyrows.hip.inc"
+#include "textlines.hip.inc"
+#include "bedline.inc"                                  // for_each_line
 
 namespace xlk {
 
-constexpr int THREADS = 256;
-constexpr int LANE_BYTES = 16;
-constexpr int TILE = THREADS * LANE_BYTES;          // dm_xyload_tile_bytes()
 constexpr int MAX_DIGITS = 15;
 constexpr int HALF = DM_WINDOW / 2;
 
@@ -73,53 +67,6 @@ __host__ __device__ inline bool parse_row(const char* __restrict__ p, const long
     return true;
 }
 
-__device__ inline uint4 load_lane(const char* __restrict__ text, const long long off, const long long n_bytes) {
-    // the buffer holds whole 16-byte groups (dm_xyload_parse sizes it so); what lies behind n_bytes is masked by newline_mask
-    return off < n_bytes ? *reinterpret_cast<const uint4*>(text + off) : uint4{0u, 0u, 0u, 0u};
-}
-
-// bit j: byte j of the lane's 16 is a '\n' of the text
-__device__ inline unsigned newline_mask(const uint4 v, const long long off, const long long n_bytes) {
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-    unsigned mask = 0;
-#pragma unroll
-    for (int j = 0; j < LANE_BYTES; ++j)
-        if (((w[j >> 2] >> (8 * (j & 3))) & 0xffu) == 0x0au && off + j < n_bytes) mask |= 1u << j;
-    return mask;
-}
-
-__global__ __launch_bounds__(THREADS) void xl_count_kernel(const char* __restrict__ text, const long long n_bytes, long long* __restrict__ count) {
-    __shared__ int wave_count[THREADS / 64];
-    const long long off = (long long)blockIdx.x * TILE + (long long)threadIdx.x * LANE_BYTES;
-    const unsigned mask = newline_mask(load_lane(text, off, n_bytes), off, n_bytes);
-    int c = 0;
-#pragma unroll
-    for (int j = 0; j < LANE_BYTES; ++j) c += __popcll(__ballot((mask >> j) & 1u));
-    if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        long long t = 0;
-        for (int k = 0; k < THREADS / 64; ++k) t += wave_count[k];
-        count[blockIdx.x] = t;
-    }
-}
-
-// start [R + 1]: start[r] = the first byte of line r, start[R] = the byte behind the last newline
-__global__ __launch_bounds__(THREADS) void xl_lines_kernel(const char* __restrict__ text, const long long n_bytes, const long long* __restrict__ tile_row,
-                                                          const long long n_rows, long long* __restrict__ start) {
-    __shared__ long long wave_total[THREADS / 64];
-    const long long off = (long long)blockIdx.x * TILE + (long long)threadIdx.x * LANE_BYTES;
-    const unsigned mask = newline_mask(load_lane(text, off, n_bytes), off, n_bytes);
-    long long total;
-    long long r = tile_row[blockIdx.x] + csites::block_exclusive_scan<THREADS>((long long)__popc(mask), wave_total, total);
-    if (blockIdx.x == 0 && threadIdx.x == 0) start[0] = 0;
-    for (int j = 0; j < LANE_BYTES; ++j)
-        if ((mask >> j) & 1u) {
-            ++r;                                                     // this newline ends line r - 1
-            if (r <= n_rows) start[r] = off + j + 1;
-        }
-}
-
 __global__ __launch_bounds__(THREADS) void xl_parse_kernel(const char* __restrict__ text, const long long* __restrict__ start, const long long n_rows,
                                                           float* __restrict__ head, float* __restrict__ feats, unsigned char* __restrict__ status) {
     const long long r = (long long)blockIdx.x * THREADS + threadIdx.x;
@@ -132,23 +79,6 @@ __global__ __launch_bounds__(THREADS) void xl_parse_kernel(const char* __restric
 #pragma unroll
     for (int c = 0; c < DM_NFEAT; ++c) feats[DM_NFEAT * r + c] = ok ? v[3 + c] : 0.0f;
     status[r] = ok ? 0 : 1;
-}
-
-// out[0] = the smallest i with status[i] != 0, -1 if there is none
-__global__ __launch_bounds__(xyk::SUM_THREADS) void xl_first_kernel(const unsigned char* __restrict__ status, const long long n, long long* __restrict__ out) {
-    __shared__ long long wave_min[xyk::SUM_THREADS / 64];
-    const long long none = 0x7fffffffffffffffLL;
-    long long best = none;
-    for (long long i = threadIdx.x; i < n; i += xyk::SUM_THREADS)
-        if (status[i] && i < best) best = i;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) best = min(best, __shfl_xor(best, d, 64));
-    if ((threadIdx.x & 63) == 0) wave_min[threadIdx.x >> 6] = best;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < xyk::SUM_THREADS / 64; ++k) best = min(best, wave_min[k]);
-        out[0] = best == none ? -1 : best;
-    }
 }
 
 __host__ __device__ inline bool row_wanted(const float* __restrict__ h /* position, label 0, label 1 */, const int kind, const long long lo, const long long hi) {
@@ -194,9 +124,8 @@ __global__ __launch_bounds__(THREADS) void xl_prob1_kernel(const float* __restri
 struct dm_xyload {
     dm_xyrows* xy = nullptr;                            // stream, the scan and its block sums
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    enum { TEXT, COUNT, START, HEAD, FEATS, STATUS, WANT, CENTRE, LABEL, OUT, PROB, PROB1, CLS, N_BUF };
-    void* buf[N_BUF] = {};
-    size_t cap[N_BUF] = {};
+    enum { HEAD = xlk::N_SPLIT, FEATS, WANT, CENTRE, LABEL, PROB, PROB1, CLS, N_BUF };
+    DevBufs<N_BUF> b{"dm_xyload"};
     int64_t n_rows = -1, n = -1;                        // of the table on the device (-1: none) and of its selection (-1: none)
     bool flagged = false;                               // the last text held a line outside the grammar: its table is not to be used
     bool parse_timed = false, select_timed = false;
@@ -204,32 +133,13 @@ struct dm_xyload {
 
 namespace xlk {
 
-int ensure(dm_xyload* h, int which, size_t bytes) {
-    if (h->cap[which] >= bytes && h->buf[which]) return DM_OK;
-    if (h->buf[which]) (void)hipFree(h->buf[which]);
-    h->buf[which] = nullptr;
-    h->cap[which] = 0;
-    const size_t want = bytes + (bytes >> 2) + 256;                  // grow-only, a quarter ahead
-    if (hipMalloc(&h->buf[which], want) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(DM_ENOMEM, "dm_xyload: hipMalloc(%zu) failed", want);
-    }
-    h->cap[which] = want;
-    return DM_OK;
-}
-
-template <class T>
-T* ptr(dm_xyload* h, int which) { return static_cast<T*>(h->buf[which]); }
-
-constexpr int64_t MAX_BYTES = int64_t(1) << 40;
 constexpr int64_t MAX_ROWS = 0x7fffffffLL - HALF;                     // centre is int32
 
 int table_buffers(dm_xyload* h, int64_t n_rows) {
     int rc;
-    if ((rc = ensure(h, dm_xyload::HEAD, size_t(n_rows) * 12)) != DM_OK) return rc;
-    if ((rc = ensure(h, dm_xyload::FEATS, size_t(n_rows) * 4 * DM_NFEAT)) != DM_OK) return rc;
-    if ((rc = ensure(h, dm_xyload::STATUS, size_t(n_rows))) != DM_OK) return rc;
-    return ensure(h, dm_xyload::OUT, 16);
+    if ((rc = h->b.ensure(dm_xyload::HEAD, size_t(n_rows) * 12)) != DM_OK) return rc;
+    if ((rc = h->b.ensure(dm_xyload::FEATS, size_t(n_rows) * 4 * DM_NFEAT)) != DM_OK) return rc;
+    return h->b.ensure(STATUS, size_t(n_rows));
 }
 
 }  // namespace xlk
@@ -242,8 +152,7 @@ int dm_xyload_scan_block(void) { return xyk::SCAN_TILE; }
 void dm_xyload_destroy(dm_xyload* h) {
     if (!h) return;
     if (h->xy) (void)hipSetDevice(h->xy->device);
-    for (void* b : h->buf)
-        if (b) (void)hipFree(b);
+    h->b.release();
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
     dm_xy_destroy(h->xy);
@@ -266,18 +175,14 @@ dm_xyload* dm_xyload_create(int device) {
 
 int64_t dm_xyload_parse_host(const char* text, int64_t n_bytes, float* table, int64_t cap_rows, int32_t* flag, int64_t* first_bad_line) {
     if (n_bytes < 0 || (n_bytes > 0 && !text) || cap_rows < 0 || (cap_rows > 0 && !table)) return fail(DM_EINVAL, "dm_xyload_parse_host: null argument");
-    int64_t rows = 0, bad = 0;
-    float v[10];
-    for (int64_t b = 0; b < n_bytes;) {
-        const void* nl = std::memchr(text + b, '\n', size_t(n_bytes - b));
-        const int64_t e = nl ? static_cast<const char*>(nl) - text : n_bytes;          // a last line without '\n' ends with the text
-        const bool ok = xlk::parse_row(text + b, e - b, v);
-        if (!ok && bad == 0) bad = rows + 1;
-        if (rows < cap_rows)
-            for (int c = 0; c < 10; ++c) table[10 * rows + c] = ok ? v[c] : 0.0f;
-        ++rows;
-        b = e + 1;
-    }
+    int64_t bad = 0;
+    const int64_t rows = bed::for_each_line(text, n_bytes, &bad, [&](const char* line, const int64_t len, const int64_t row) {
+        float v[10];
+        const bool ok = xlk::parse_row(line, len, v);
+        if (row < cap_rows)
+            for (int c = 0; c < 10; ++c) table[10 * row + c] = ok ? v[c] : 0.0f;
+        return ok;
+    });
     if (flag) *flag = bad != 0;
     if (first_bad_line) *first_bad_line = bad ? bad : -1;
     return rows;
@@ -314,50 +219,24 @@ int dm_xyload_parse(dm_xyload* h, const char* text, int64_t n_bytes, int64_t* n_
     if (n_rows) *n_rows = 0;
     if (flag) *flag = 0;
     if (first_bad_line) *first_bad_line = -1;
-    if (n_bytes < 0 || n_bytes >= xlk::MAX_BYTES || (n_bytes > 0 && !text)) return fail(DM_EINVAL, "dm_xyload_parse: %lld bytes of text", (long long)n_bytes);
     HIP_TRY(hipSetDevice(h->xy->device));
     using B = dm_xyload;
     int rc;
-    if (n_bytes == 0) {                                              // an empty file: a table of no rows
-        if ((rc = xlk::table_buffers(h, 0)) != DM_OK) return rc;
+    long long rows = 0;
+    if ((rc = xlk::split(h->xy, h->b, text, n_bytes, xlk::MAX_ROWS, "dm_xyload_parse", "rows", h->ev[0], &rows)) != DM_OK) return rc;
+    if ((rc = xlk::table_buffers(h, rows)) != DM_OK) return rc;
+    if (rows == 0) {                                                 // an empty file: a table of no rows
         h->n_rows = 0;
         return DM_OK;
     }
-    const bool add_newline = text[n_bytes - 1] != '\n';
-    const int64_t n = n_bytes + (add_newline ? 1 : 0);
-    const int64_t tiles = (n + xlk::TILE - 1) / xlk::TILE;
-    if ((rc = xlk::ensure(h, B::TEXT, size_t(tiles) * xlk::TILE)) != DM_OK) return rc;    // whole 16-byte groups behind every lane offset below n
-    if ((rc = xlk::ensure(h, B::COUNT, size_t(tiles + 1) * 8)) != DM_OK) return rc;
-    if ((rc = xlk::ensure(h, B::OUT, 16)) != DM_OK) return rc;
     hipStream_t s = h->xy->stream;
-    char* d_text = xlk::ptr<char>(h, B::TEXT);
-    long long* d_count = xlk::ptr<long long>(h, B::COUNT);
-    static const char newline = '\n';
-    HIP_TRY(hipMemcpyAsync(d_text, text, size_t(n_bytes), hipMemcpyHostToDevice, s));
-    if (add_newline) HIP_TRY(hipMemcpyAsync(d_text + n_bytes, &newline, 1, hipMemcpyHostToDevice, s));
-    const dim3 tile_grid{unsigned(tiles)}, block{xlk::THREADS};
-    HIP_TRY(hipEventRecord(h->ev[0], s));
-    hipLaunchKernelGGL(xlk::xl_count_kernel, tile_grid, block, 0, s, d_text, (long long)n, d_count);
+    hipLaunchKernelGGL(xlk::xl_parse_kernel, dim3(unsigned((rows + xlk::THREADS - 1) / xlk::THREADS)), dim3(xlk::THREADS), 0, s, h->b.ptr<const char>(xlk::TEXT),
+                       h->b.ptr<const long long>(xlk::START), rows, h->b.ptr<float>(B::HEAD), h->b.ptr<float>(B::FEATS), h->b.ptr<unsigned char>(xlk::STATUS));
     HIP_TRY(hipGetLastError());
-    if ((rc = xyk::scan_in_place(h->xy, d_count, tiles)) != DM_OK) return rc;
-    long long rows = 0;
-    HIP_TRY(hipMemcpyAsync(&rows, d_count + tiles, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (rows < 1 || rows > n) return fail(DM_ESTATE, "dm_xyload_parse: %lld lines in %lld bytes", rows, (long long)n);
-    if (rows > xlk::MAX_ROWS) return fail(DM_EINVAL, "dm_xyload_parse: %lld rows (at most %lld)", rows, (long long)xlk::MAX_ROWS);
-    if ((rc = xlk::table_buffers(h, rows)) != DM_OK) return rc;
-    if ((rc = xlk::ensure(h, B::START, size_t(rows + 1) * 8)) != DM_OK) return rc;
-    long long* d_start = xlk::ptr<long long>(h, B::START);
-    unsigned char* d_status = xlk::ptr<unsigned char>(h, B::STATUS);
-    long long* d_out = xlk::ptr<long long>(h, B::OUT);
-    const dim3 row_grid{unsigned((rows + xlk::THREADS - 1) / xlk::THREADS)};
-    hipLaunchKernelGGL(xlk::xl_lines_kernel, tile_grid, block, 0, s, d_text, (long long)n, d_count, rows, d_start);
-    hipLaunchKernelGGL(xlk::xl_parse_kernel, row_grid, block, 0, s, d_text, d_start, rows, xlk::ptr<float>(h, B::HEAD), xlk::ptr<float>(h, B::FEATS), d_status);
-    hipLaunchKernelGGL(xlk::xl_first_kernel, dim3(1), dim3(xyk::SUM_THREADS), 0, s, d_status, rows, d_out);
-    HIP_TRY(hipGetLastError());
+    if ((rc = xlk::first_bad(h->xy, h->b, rows)) != DM_OK) return rc;
     HIP_TRY(hipEventRecord(h->ev[1], s));
     long long first = -1;
-    HIP_TRY(hipMemcpyAsync(&first, d_out, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&first, h->b.buf[xlk::OUT], 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     h->n_rows = rows;
     h->flagged = first >= 0;
@@ -382,8 +261,8 @@ int dm_xyload_set_table(dm_xyload* h, const float* table, int64_t n_rows) {
         std::memcpy(&feats[size_t(r) * DM_NFEAT], table + 10 * r + 3, 4 * DM_NFEAT);
     }
     if (n_rows > 0) {
-        HIP_TRY(hipMemcpyAsync(h->buf[dm_xyload::HEAD], head.data(), head.size() * 4, hipMemcpyHostToDevice, h->xy->stream));
-        HIP_TRY(hipMemcpyAsync(h->buf[dm_xyload::FEATS], feats.data(), feats.size() * 4, hipMemcpyHostToDevice, h->xy->stream));
+        HIP_TRY(hipMemcpyAsync(h->b.buf[dm_xyload::HEAD], head.data(), head.size() * 4, hipMemcpyHostToDevice, h->xy->stream));
+        HIP_TRY(hipMemcpyAsync(h->b.buf[dm_xyload::FEATS], feats.data(), feats.size() * 4, hipMemcpyHostToDevice, h->xy->stream));
         HIP_TRY(hipStreamSynchronize(h->xy->stream));
     }
     h->n_rows = n_rows;
@@ -406,21 +285,19 @@ int64_t dm_xyload_select(dm_xyload* h, int kind, int64_t lo, int64_t hi, int64_t
     HIP_TRY(hipSetDevice(h->xy->device));
     using B = dm_xyload;
     int rc;
-    if ((rc = xlk::ensure(h, B::WANT, size_t(rows + 1) * 8)) != DM_OK) return rc;
+    if ((rc = h->b.ensure(B::WANT, size_t(rows + 1) * 8)) != DM_OK) return rc;
     hipStream_t s = h->xy->stream;
-    const float* d_head = xlk::ptr<float>(h, B::HEAD);
-    long long* d_want = xlk::ptr<long long>(h, B::WANT);
-    unsigned char* d_status = xlk::ptr<unsigned char>(h, B::STATUS);
-    long long* d_out = xlk::ptr<long long>(h, B::OUT);
+    const float* d_head = h->b.ptr<float>(B::HEAD);
+    long long* d_want = h->b.ptr<long long>(B::WANT);
     const dim3 row_grid{unsigned((rows + xlk::THREADS - 1) / xlk::THREADS)}, block{xlk::THREADS};
     HIP_TRY(hipEventRecord(h->ev[2], s));
     hipLaunchKernelGGL(xlk::xl_want_kernel, row_grid, block, 0, s, d_head, (long long)rows, kind == 0 ? 0 : (kind == '-' ? -1 : 1), (long long)lo, (long long)hi, d_want,
-                       d_status);
-    hipLaunchKernelGGL(xlk::xl_first_kernel, dim3(1), dim3(xyk::SUM_THREADS), 0, s, d_status, (long long)rows, d_out);
+                       h->b.ptr<unsigned char>(xlk::STATUS));
     HIP_TRY(hipGetLastError());
+    if ((rc = xlk::first_bad(h->xy, h->b, rows)) != DM_OK) return rc;
     if ((rc = xyk::scan_in_place(h->xy, d_want, rows)) != DM_OK) return rc;
     long long out[2] = {-1, 0};
-    HIP_TRY(hipMemcpyAsync(&out[0], d_out, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&out[0], h->b.buf[xlk::OUT], 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(&out[1], d_want + rows, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (out[0] >= 0) {
@@ -431,9 +308,9 @@ int64_t dm_xyload_select(dm_xyload* h, int kind, int64_t lo, int64_t hi, int64_t
     const int64_t n = out[1];
     if (n < 0 || n > rows) return fail(DM_ESTATE, "dm_xyload_select: %lld of %lld rows", (long long)n, (long long)rows);
     if (n > 0) {
-        if ((rc = xlk::ensure(h, B::CENTRE, size_t(n) * 4)) != DM_OK) return rc;
-        if ((rc = xlk::ensure(h, B::LABEL, size_t(n))) != DM_OK) return rc;
-        hipLaunchKernelGGL(xlk::xl_compact_kernel, row_grid, block, 0, s, d_head, d_want, (long long)rows, xlk::ptr<int>(h, B::CENTRE), xlk::ptr<unsigned char>(h, B::LABEL));
+        if ((rc = h->b.ensure(B::CENTRE, size_t(n) * 4)) != DM_OK) return rc;
+        if ((rc = h->b.ensure(B::LABEL, size_t(n))) != DM_OK) return rc;
+        hipLaunchKernelGGL(xlk::xl_compact_kernel, row_grid, block, 0, s, d_head, d_want, (long long)rows, h->b.ptr<int>(B::CENTRE), h->b.ptr<unsigned char>(B::LABEL));
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(h->ev[3], s));
@@ -455,10 +332,10 @@ int dm_xyload_set_selection(dm_xyload* h, const int32_t* centre, const uint8_t* 
     HIP_TRY(hipSetDevice(h->xy->device));
     if (n > 0) {
         int rc;
-        if ((rc = xlk::ensure(h, dm_xyload::CENTRE, size_t(n) * 4)) != DM_OK) return rc;
-        if ((rc = xlk::ensure(h, dm_xyload::LABEL, size_t(n))) != DM_OK) return rc;
-        HIP_TRY(hipMemcpyAsync(h->buf[dm_xyload::CENTRE], centre, size_t(n) * 4, hipMemcpyHostToDevice, h->xy->stream));
-        HIP_TRY(hipMemcpyAsync(h->buf[dm_xyload::LABEL], label, size_t(n), hipMemcpyHostToDevice, h->xy->stream));
+        if ((rc = h->b.ensure(dm_xyload::CENTRE, size_t(n) * 4)) != DM_OK) return rc;
+        if ((rc = h->b.ensure(dm_xyload::LABEL, size_t(n))) != DM_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(h->b.buf[dm_xyload::CENTRE], centre, size_t(n) * 4, hipMemcpyHostToDevice, h->xy->stream));
+        HIP_TRY(hipMemcpyAsync(h->b.buf[dm_xyload::LABEL], label, size_t(n), hipMemcpyHostToDevice, h->xy->stream));
         HIP_TRY(hipStreamSynchronize(h->xy->stream));
     }
     h->n = n;
@@ -468,8 +345,8 @@ int dm_xyload_set_selection(dm_xyload* h, const int32_t* centre, const uint8_t* 
 int dm_xyload_device(dm_xyload* h, const float** d_feats, const int32_t** d_centre, int64_t* n_rows, int64_t* n) {
     if (!h) return fail(DM_EINVAL, "null handle");
     if (h->n_rows < 0) return fail(DM_ESTATE, "dm_xyload_device: no table");
-    if (d_feats) *d_feats = xlk::ptr<const float>(h, dm_xyload::FEATS);
-    if (d_centre) *d_centre = h->n > 0 ? xlk::ptr<const int32_t>(h, dm_xyload::CENTRE) : nullptr;
+    if (d_feats) *d_feats = h->b.ptr<const float>(dm_xyload::FEATS);
+    if (d_centre) *d_centre = h->n > 0 ? h->b.ptr<const int32_t>(dm_xyload::CENTRE) : nullptr;
     if (n_rows) *n_rows = h->n_rows;
     if (n) *n = h->n;
     return DM_OK;
@@ -482,10 +359,10 @@ int dm_xyload_fetch(dm_xyload* h, float* feats, float* head, int32_t* centre, ui
     HIP_TRY(hipSetDevice(h->xy->device));
     hipStream_t s = h->xy->stream;
     using B = dm_xyload;
-    if (feats && h->n_rows > 0) HIP_TRY(hipMemcpyAsync(feats, h->buf[B::FEATS], size_t(h->n_rows) * 4 * DM_NFEAT, hipMemcpyDeviceToHost, s));
-    if (head && h->n_rows > 0) HIP_TRY(hipMemcpyAsync(head, h->buf[B::HEAD], size_t(h->n_rows) * 12, hipMemcpyDeviceToHost, s));
-    if (centre && h->n > 0) HIP_TRY(hipMemcpyAsync(centre, h->buf[B::CENTRE], size_t(h->n) * 4, hipMemcpyDeviceToHost, s));
-    if (label && h->n > 0) HIP_TRY(hipMemcpyAsync(label, h->buf[B::LABEL], size_t(h->n), hipMemcpyDeviceToHost, s));
+    if (feats && h->n_rows > 0) HIP_TRY(hipMemcpyAsync(feats, h->b.buf[B::FEATS], size_t(h->n_rows) * 4 * DM_NFEAT, hipMemcpyDeviceToHost, s));
+    if (head && h->n_rows > 0) HIP_TRY(hipMemcpyAsync(head, h->b.buf[B::HEAD], size_t(h->n_rows) * 12, hipMemcpyDeviceToHost, s));
+    if (centre && h->n > 0) HIP_TRY(hipMemcpyAsync(centre, h->b.buf[B::CENTRE], size_t(h->n) * 4, hipMemcpyDeviceToHost, s));
+    if (label && h->n > 0) HIP_TRY(hipMemcpyAsync(label, h->b.buf[B::LABEL], size_t(h->n), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return DM_OK;
 }
@@ -499,19 +376,19 @@ int dm_xyload_classify(dm_xyload* h, dm_model* m, float* prob1, uint8_t* cls, ui
     const int64_t n = h->n;
     using B = dm_xyload;
     int rc;
-    if ((rc = xlk::ensure(h, B::PROB, size_t(n) * 8)) != DM_OK) return rc;
-    if ((rc = xlk::ensure(h, B::PROB1, size_t(n) * 4)) != DM_OK) return rc;
-    if ((rc = xlk::ensure(h, B::CLS, size_t(n))) != DM_OK) return rc;
-    float* d_prob = xlk::ptr<float>(h, B::PROB);
-    if ((rc = dm_predict_read_at(m, xlk::ptr<const float>(h, B::FEATS), h->n_rows, xlk::ptr<const int32_t>(h, B::CENTRE), n, d_prob, xlk::ptr<uint8_t>(h, B::CLS))) != DM_OK)
+    if ((rc = h->b.ensure(B::PROB, size_t(n) * 8)) != DM_OK) return rc;
+    if ((rc = h->b.ensure(B::PROB1, size_t(n) * 4)) != DM_OK) return rc;
+    if ((rc = h->b.ensure(B::CLS, size_t(n))) != DM_OK) return rc;
+    float* d_prob = h->b.ptr<float>(B::PROB);
+    if ((rc = dm_predict_read_at(m, h->b.ptr<const float>(B::FEATS), h->n_rows, h->b.ptr<const int32_t>(B::CENTRE), n, d_prob, h->b.ptr<uint8_t>(B::CLS))) != DM_OK)
         return rc;
     if ((rc = dm_model_sync(m)) != DM_OK) return rc;                 // a model in asynchronous mode has only queued the launch
     hipStream_t s = h->xy->stream;
-    hipLaunchKernelGGL(xlk::xl_prob1_kernel, dim3(unsigned((n + xlk::THREADS - 1) / xlk::THREADS)), dim3(xlk::THREADS), 0, s, d_prob, (long long)n, xlk::ptr<float>(h, B::PROB1));
+    hipLaunchKernelGGL(xlk::xl_prob1_kernel, dim3(unsigned((n + xlk::THREADS - 1) / xlk::THREADS)), dim3(xlk::THREADS), 0, s, d_prob, (long long)n, h->b.ptr<float>(B::PROB1));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(prob1, h->buf[B::PROB1], size_t(n) * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(cls, h->buf[B::CLS], size_t(n), hipMemcpyDeviceToHost, s));
-    if (label) HIP_TRY(hipMemcpyAsync(label, h->buf[B::LABEL], size_t(n), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(prob1, h->b.buf[B::PROB1], size_t(n) * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(cls, h->b.buf[B::CLS], size_t(n), hipMemcpyDeviceToHost, s));
+    if (label) HIP_TRY(hipMemcpyAsync(label, h->b.buf[B::LABEL], size_t(n), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return DM_OK;
 }
@@ -556,8 +433,9 @@ struct dm_xyset {
     size_t cap_off = 0;
     int64_t d_off_segs = -1;
     std::vector<long long> off_host;
-    void *g_ids = nullptr, *g_x = nullptr, *g_bad = nullptr;
-    size_t cap_g_ids = 0, cap_g_x = 0;
+    enum { G_IDS, G_X, N_GATHER };
+    DevBufs<N_GATHER> gather{"dm_xyset_gather"};            // ids or x of a host caller
+    void* g_bad = nullptr;
 };
 
 namespace xlk {
@@ -592,8 +470,9 @@ void dm_xyset_destroy(dm_xyset* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
-    for (void* b : {(void*)s->feats, (void*)s->centre, (void*)s->label, (void*)s->prob, (void*)s->prob1, (void*)s->cls, (void*)s->d_off, s->g_ids, s->g_x, s->g_bad})
+    for (void* b : {(void*)s->feats, (void*)s->centre, (void*)s->label, (void*)s->prob, (void*)s->prob1, (void*)s->cls, (void*)s->d_off, s->g_bad})
         if (b) (void)hipFree(b);
+    s->gather.release();
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
 }
@@ -643,9 +522,9 @@ int dm_xyset_append(dm_xyset* s, dm_xyload* h) {
     if ((rc = xlk::set_grow(s, s->centre, s->cap_centre, wins, wins + n, sizeof(int32_t))) != DM_OK) return rc;
     if ((rc = xlk::set_grow(s, s->label, s->cap_label, wins, wins + n, 1)) != DM_OK) return rc;
     using B = dm_xyload;
-    HIP_TRY(hipMemcpyAsync(s->feats + rows * DM_NFEAT, h->buf[B::FEATS], size_t(R) * 4 * DM_NFEAT, hipMemcpyDeviceToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(s->centre + wins, h->buf[B::CENTRE], size_t(n) * 4, hipMemcpyDeviceToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(s->label + wins, h->buf[B::LABEL], size_t(n), hipMemcpyDeviceToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->feats + rows * DM_NFEAT, h->b.buf[B::FEATS], size_t(R) * 4 * DM_NFEAT, hipMemcpyDeviceToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->centre + wins, h->b.buf[B::CENTRE], size_t(n) * 4, hipMemcpyDeviceToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->label + wins, h->b.buf[B::LABEL], size_t(n), hipMemcpyDeviceToDevice, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));                        // the loader may take its next file, or be destroyed
     s->row_off.push_back(rows + R);
     s->win_off.push_back(wins + n);

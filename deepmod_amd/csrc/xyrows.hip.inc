@@ -26,8 +26,7 @@ struct dm_xyrows {
     hipStream_t stream = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     enum { POS, LAB, CODE, RDESC, SCAN, LEN, KEEP, BSUM, RCOUNT, RMODE, RBYTE, BFLAG, OUT, TEXT, N_BUF };
-    void* buf[N_BUF] = {};
-    size_t cap[N_BUF] = {};
+    DevBufs<N_BUF> b{"dm_xy_rows"};
     int64_t n_reads = 0, n_rows = 0, n_bytes = -1;      // of the last call (n_bytes < 0: none)
     bool host_result = false, timed = false;            // the last call went through dm_xy_rows_host: its results are the vectors below
     std::vector<char> h_text;
@@ -267,26 +266,12 @@ __global__ __launch_bounds__(THREADS) void xy_write_kernel(const long long* __re
     emit_row(s, pos[q], lab[q], code[q], v.mean, v.stdv, v.len);
 }
 
-int ensure(dm_xyrows* h, int which, size_t bytes) {
-    if (h->cap[which] >= bytes && h->buf[which]) return DM_OK;
-    if (h->buf[which]) (void)hipFree(h->buf[which]);
-    h->buf[which] = nullptr;
-    h->cap[which] = 0;
-    const size_t want = bytes + (bytes >> 2) + 256;                  // grow-only, a quarter ahead
-    if (hipMalloc(&h->buf[which], want) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(DM_ENOMEM, "dm_xy_rows: hipMalloc(%zu) failed", want);
-    }
-    h->cap[which] = want;
-    return DM_OK;
-}
-
 // exclusive scan of n values in place (a holds n + 1), on the handle's stream
 int scan_in_place(dm_xyrows* h, long long* a, int64_t n) {
     const int64_t tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
-    int rc = ensure(h, dm_xyrows::BSUM, size_t(tiles + 1) * 8);
+    int rc = h->b.ensure(dm_xyrows::BSUM, size_t(tiles + 1) * 8);
     if (rc) return rc;
-    long long* bsum = static_cast<long long*>(h->buf[dm_xyrows::BSUM]);
+    long long* bsum = static_cast<long long*>(h->b.buf[dm_xyrows::BSUM]);
     hipLaunchKernelGGL(scan_tile_kernel, dim3(unsigned(tiles)), dim3(THREADS), 0, h->stream, a, (long long)n, bsum);
     hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(SUM_THREADS), 0, h->stream, bsum, (long long)tiles);
     hipLaunchKernelGGL(scan_add_kernel, dim3(unsigned(tiles)), dim3(THREADS), 0, h->stream, a, (long long)n, bsum, (long long)tiles);
@@ -320,8 +305,7 @@ dm_xyrows* dm_xy_create(int device) {
 void dm_xy_destroy(dm_xyrows* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    for (void* b : h->buf)
-        if (b) (void)hipFree(b);
+    h->b.release();
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -346,19 +330,19 @@ int64_t dm_xy_rows(dm_xyrows* h, const int64_t* pos, const uint8_t* lab, const u
     const size_t need[B::N_BUF] = {size_t(n_rows) * 8, size_t(n_rows), size_t(n_rows), size_t(n_reads) * 32, size_t(n_rows + 1) * 8, size_t(n_rows + 1) * 8,
                                    size_t(n_rows), 0, size_t(n_reads + 1) * 8, size_t(n_reads), size_t(n_reads + 1) * 8, size_t(blocks) * 4, 16, 0};
     for (int i = 0; i < B::N_BUF; ++i)
-        if (need[i] && (rc = xyk::ensure(h, i, need[i])) != DM_OK) return rc;
-    long long* d_pos = static_cast<long long*>(h->buf[B::POS]);
-    unsigned char* d_lab = static_cast<unsigned char*>(h->buf[B::LAB]);
-    unsigned char* d_code = static_cast<unsigned char*>(h->buf[B::CODE]);
-    long long* d_rdesc = static_cast<long long*>(h->buf[B::RDESC]);
-    long long* d_scan = static_cast<long long*>(h->buf[B::SCAN]);
-    long long* d_len = static_cast<long long*>(h->buf[B::LEN]);
-    unsigned char* d_keep = static_cast<unsigned char*>(h->buf[B::KEEP]);
-    long long* d_rcount = static_cast<long long*>(h->buf[B::RCOUNT]);
-    unsigned char* d_rmode = static_cast<unsigned char*>(h->buf[B::RMODE]);
-    long long* d_rbyte = static_cast<long long*>(h->buf[B::RBYTE]);
-    unsigned* d_bflag = static_cast<unsigned*>(h->buf[B::BFLAG]);
-    long long* d_out = static_cast<long long*>(h->buf[B::OUT]);
+        if (need[i] && (rc = h->b.ensure(i, need[i])) != DM_OK) return rc;
+    long long* d_pos = static_cast<long long*>(h->b.buf[B::POS]);
+    unsigned char* d_lab = static_cast<unsigned char*>(h->b.buf[B::LAB]);
+    unsigned char* d_code = static_cast<unsigned char*>(h->b.buf[B::CODE]);
+    long long* d_rdesc = static_cast<long long*>(h->b.buf[B::RDESC]);
+    long long* d_scan = static_cast<long long*>(h->b.buf[B::SCAN]);
+    long long* d_len = static_cast<long long*>(h->b.buf[B::LEN]);
+    unsigned char* d_keep = static_cast<unsigned char*>(h->b.buf[B::KEEP]);
+    long long* d_rcount = static_cast<long long*>(h->b.buf[B::RCOUNT]);
+    unsigned char* d_rmode = static_cast<unsigned char*>(h->b.buf[B::RMODE]);
+    long long* d_rbyte = static_cast<long long*>(h->b.buf[B::RBYTE]);
+    unsigned* d_bflag = static_cast<unsigned*>(h->b.buf[B::BFLAG]);
+    long long* d_out = static_cast<long long*>(h->b.buf[B::OUT]);
     HIP_TRY(hipMemcpyAsync(d_pos, pos, size_t(n_rows) * 8, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(d_lab, lab, size_t(n_rows), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(d_code, code, size_t(n_rows), hipMemcpyHostToDevice, h->stream));
@@ -402,9 +386,9 @@ int64_t dm_xy_rows(dm_xyrows* h, const int64_t* pos, const uint8_t* lab, const u
     }
     const int64_t total = out[1];
     if (total > 0) {
-        if ((rc = xyk::ensure(h, B::TEXT, size_t(total))) != DM_OK) return rc;
+        if ((rc = h->b.ensure(B::TEXT, size_t(total))) != DM_OK) return rc;
         hipLaunchKernelGGL(xyk::xy_write_kernel, row_grid, block, 0, h->stream, d_pos, d_lab, d_code, d_ev3, d_rdesc, int(n_reads), (long long)n_rows, d_keep, d_len,
-                           static_cast<char*>(h->buf[B::TEXT]));
+                           static_cast<char*>(h->b.buf[B::TEXT]));
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(h->ev[2], h->stream));
@@ -426,10 +410,10 @@ int dm_xy_rows_fetch(dm_xyrows* h, char* text, uint8_t* keep, int64_t* read_row_
     }
     using B = dm_xyrows;
     HIP_TRY(hipSetDevice(h->device));
-    if (text && h->n_bytes > 0) HIP_TRY(hipMemcpyAsync(text, h->buf[B::TEXT], size_t(h->n_bytes), hipMemcpyDeviceToHost, h->stream));
-    if (keep) HIP_TRY(hipMemcpyAsync(keep, h->buf[B::KEEP], size_t(h->n_rows), hipMemcpyDeviceToHost, h->stream));
-    if (read_row_off) HIP_TRY(hipMemcpyAsync(read_row_off, h->buf[B::RCOUNT], size_t(h->n_reads + 1) * 8, hipMemcpyDeviceToHost, h->stream));
-    if (read_byte_off) HIP_TRY(hipMemcpyAsync(read_byte_off, h->buf[B::RBYTE], size_t(h->n_reads + 1) * 8, hipMemcpyDeviceToHost, h->stream));
+    if (text && h->n_bytes > 0) HIP_TRY(hipMemcpyAsync(text, h->b.buf[B::TEXT], size_t(h->n_bytes), hipMemcpyDeviceToHost, h->stream));
+    if (keep) HIP_TRY(hipMemcpyAsync(keep, h->b.buf[B::KEEP], size_t(h->n_rows), hipMemcpyDeviceToHost, h->stream));
+    if (read_row_off) HIP_TRY(hipMemcpyAsync(read_row_off, h->b.buf[B::RCOUNT], size_t(h->n_reads + 1) * 8, hipMemcpyDeviceToHost, h->stream));
+    if (read_byte_off) HIP_TRY(hipMemcpyAsync(read_byte_off, h->b.buf[B::RBYTE], size_t(h->n_reads + 1) * 8, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return DM_OK;
 }
@@ -438,9 +422,9 @@ int dm_xy_rows_fetch(dm_xyrows* h, char* text, uint8_t* keep, int64_t* read_row_
 int dm_xy_scan(dm_xyrows* h, int64_t* values, int64_t n) {
     if (!h || !values || n <= 0 || n > (int64_t(1) << 40)) return fail(DM_EINVAL, "dm_xy_scan: null argument or no value");
     HIP_TRY(hipSetDevice(h->device));
-    int rc = xyk::ensure(h, dm_xyrows::LEN, size_t(n + 1) * 8);
+    int rc = h->b.ensure(dm_xyrows::LEN, size_t(n + 1) * 8);
     if (rc) return rc;
-    long long* d = static_cast<long long*>(h->buf[dm_xyrows::LEN]);
+    long long* d = static_cast<long long*>(h->b.buf[dm_xyrows::LEN]);
     HIP_TRY(hipMemcpyAsync(d, values, size_t(n) * 8, hipMemcpyHostToDevice, h->stream));
     if ((rc = xyk::scan_in_place(h, d, n)) != DM_OK) return rc;
     HIP_TRY(hipMemcpyAsync(values, d, size_t(n + 1) * 8, hipMemcpyDeviceToHost, h->stream));

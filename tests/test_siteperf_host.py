@@ -1,8 +1,9 @@
 """CPU: the numpy statement of `siteperf` (deepmod_amd/siteperf.py, HostEngine) against the lines the reference's own cal_EcoliDetPerf.py printed
-(tests/golden/siteperf_cases.json, made by tests/golden/make_golden_siteperf.py), the category rule at its edges, the command's refusals and the
-shim's argument mapping."""
+(tests/golden/siteperf_cases.json, made by tests/golden/make_golden_siteperf.py), the category rule at its edges, the command's refusals, the
+shim's argument mapping, and the line routine under the address sanitizer (tests/siteperf_asan_driver.cpp)."""
 import json
 import os
+import shutil
 import subprocess
 import sys
 
@@ -261,3 +262,21 @@ def test_measures_without_entries_and_without_a_class():
     m = sp.measures(h, (1, 5))
     assert m["motif_mp"][1]["auc"] == 1.0 and m["motif_mp"][1]["ap"] == 1.0
     assert m["motif_mp"][5]["positives"] == 2 and m["motif_mp"][5]["negatives"] == 0 and m["motif_mp"][5]["ap"] == 1.0
+
+
+def test_line_routine_under_address_sanitizer(tmp_path):
+    """tests/siteperf_asan_driver.cpp: csrc/siteperf.inc (on csrc/bedline.inc) built as a PROGRAM with -fsanitize=address,undefined and the sanitizer
+    runtime linked in statically - every text and record array in a heap block of exactly its size; the good and bad lines above, texts cut at every
+    byte, random byte mutations; every accepted record inside the contig, percentage <= 100, modified <= coverage."""
+    gxx = shutil.which('g++')
+    runtime = subprocess.run([gxx, '-print-file-name=libasan.a'], capture_output=True, text=True).stdout.strip() if gxx else ''
+    if not gxx or not os.path.isabs(runtime) or not os.path.exists(runtime):
+        pytest.skip('g++ / static libasan not available')
+    exe = str(tmp_path / 'siteperf_asan_driver')
+    build = subprocess.run([gxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-static-libasan', '-fno-sanitize-recover=undefined',
+                            '-fno-omit-frame-pointer', '-pthread', '-o', exe, os.path.join(ROOT, 'tests', 'siteperf_asan_driver.cpp')],
+                           capture_output=True, text=True, timeout=600)
+    assert build.returncode == 0, build.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0:abort_on_error=1:verify_asan_link_order=0', UBSAN_OPTIONS='halt_on_error=1:print_stacktrace=1')
+    res = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0 and 'SITEPERF-ASAN-OK' in res.stdout, res.stdout[-1500:] + res.stderr[-4000:]
