@@ -53,6 +53,14 @@ truth text is parsed, joined with the counters and counted on one GPU; O/id_bspe
 threshold, raw and (with --clusterCpG) after the CpG-cluster stage on the same sites; O/id_bsperf.json has every counter and curve
 (deepmod_amd/bsperf.py).  Hand in the mod_pos.* files of `detect` runs: the files `merge` and sum_chr_mod.py write drop every position whose
 modified count is 0, which are exactly the unmethylated sites.
+
+`bslabels --truth rep1.bed,rep2.bed[,..] --Ref genome.fa --Base C --outFolder O --FileID id [--chr chr1,chr2,..] [--motif CG --ModinMotif 0] [--cov 5]
+[--methylated 90] [--unmethylated 0]` writes the three position lists `getfeatures --motifORPos 2 --fulmod F --anymod A --nomod N` reads, from 1 to 4
+whole-genome bisulfite bedMethyl replicates read by `bsperf`'s rules: per contig O/id.fulmod.<chr>.txt (sites of the motif at >= --methylated in every
+replicate, every replicate at coverage >= --cov), O/id.nomod.<chr>.txt (<= --unmethylated in every replicate, at that coverage) and O/id.anymod.<chr>.txt
+(every other site of the motif that has a record in a replicate: getfeatures --posneg 1 labels a position of anymod not at all, so every site one
+cannot be sure of belongs there).  Lines are `chr strand pos` with the 0-based position, classified and formatted on one GPU; O/id_bslabels.json has the
+line and class counters (deepmod_amd/bslabels.py).  The workflow closes: bslabels -> getfeatures -> train -> detect -> bsperf.
 """
 import argparse
 import os
@@ -232,7 +240,33 @@ def build_parser():
                      help='--Base C with --Ref: also score the percentages of the CpG-cluster stage on the same sites, side by side with the raw ones.  '
                           'CKPT_PREFIX: checkpoint prefix of the cluster model (default: DEEPMOD_CLUSTER_MODEL)')
     bsp.set_defaults(func=mBsPerf)
+    bsl = sub.add_parser('bslabels', parents=[com], help='training position lists (getfeatures --fulmod / --anymod / --nomod) from bisulfite replicates on the GPU',
+                         description='Per contig: the bedMethyl replicates of --truth, read by the rules of bsperf, are joined per (strand, position) with the sites '
+                                     'of the motif in --Ref and classified on one GPU.  Writes <outFolder>/<FileID>.fulmod.<chr>.txt, .anymod.<chr>.txt and '
+                                     '.nomod.<chr>.txt (lines `chr strand pos`, 0-based, as getfeatures --motifORPos 2 reads them) and '
+                                     '<outFolder>/<FileID>_bslabels.json (inputs, line and class counters, notes, kernel times).')
+    bsl.add_argument('--truth', default=None, help='1 to 4 whole-genome bisulfite bedMethyl replicates, separated by commas (11 columns; the first line is skipped)')
+    bsl.add_argument('--Ref', default=None, help='reference genome FASTA (needed: getfeatures refuses a position that is not in the reference)')
+    bsl.add_argument('--Base', default='C', choices=['A', 'C', 'G', 'T'], help='base of interest')
+    bsl.add_argument('--chr', default=None, help='contigs to write lists for, separated by commas, at most 64 (default: those of chr1..22, chrX, chrY, chrM in --Ref)')
+    bsl.add_argument('--motif', default=None, help='motif a site lies in, 1 to 8 letters of A, C, G, T (default: --Base alone)')
+    bsl.add_argument('--ModinMotif', type=int, default=0, help='offset of the modified base in the motif; the letter there is --Base (default 0)')
+    bsl.add_argument('--cov', type=int, default=5, help='least bisulfite coverage in every replicate of a fulmod / nomod site, 1 to 65535 (default 5)')
+    bsl.add_argument('--methylated', type=int, default=90, help='fulmod: this percentage or more in every replicate (default 90)')
+    bsl.add_argument('--unmethylated', type=int, default=0, help='nomod: this percentage or less in every replicate (default 0)')
+    bsl.set_defaults(func=mBsLabels)
     return parser
+
+
+def mBsLabels(args):
+    from deepmod_amd import bslabels
+    mo = {k: getattr(args, k) for k in ('Ref', 'Base', 'outFolder', 'FileID', 'motif', 'ModinMotif', 'cov', 'methylated', 'unmethylated', 'threads')}
+    mo['chr'] = [c for c in (args.chr or '').split(',') if c] or None
+    mo['truth'] = [p for p in (args.truth or '').split(',') if p]
+    try:
+        bslabels.bslabels(mo)                            # checks the options (the FASTA is read once), then refuses without a gfx950 GPU
+    except bslabels.BsLabelsError as exc:
+        raise SystemExit('Error: %s' % exc)
 
 
 def mBsPerf(args):

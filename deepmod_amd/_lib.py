@@ -219,6 +219,21 @@ SIGNATURES = [
     ("dm_bsperf_parse_host", _i64, [_vp, _i64, _c.c_int, _vp, _vp, _c.c_int, _vp, _vp, _i64, _vp, _c.POINTER(_c.c_int32), _c.POINTER(_i64)]),
     ("dm_bsperf_tile_bytes", _c.c_int, []),
     ("dm_bsperf_times", _c.c_int, [_vp, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
+    ("dm_bslabels_create", _vp, [_c.c_int, _c.c_int, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    ("dm_bslabels_destroy", None, [_vp]),
+    ("dm_bslabels_add_truth_text", _c.c_int, [_vp, _c.c_int, _vp, _i64, _c.c_int, _vp, _c.POINTER(_i64), _c.POINTER(_c.c_int32), _c.POINTER(_i64)]),
+    ("dm_bslabels_add_truth_records", _c.c_int, [_vp, _c.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("dm_bslabels_fetch_records", _c.c_int, [_vp, _vp, _vp]),
+    ("dm_bslabels_open", _c.c_int, [_vp, _c.c_int, _vp, _i64, _c.c_char_p, _c.c_int, _c.c_int]),
+    ("dm_bslabels_fill", _c.c_int, [_vp, _c.c_int, _i64, _vp, _vp, _c.POINTER(_i64), _c.POINTER(_c.c_int32)]),
+    ("dm_bslabels_classify", _c.c_int, [_vp, _vp]),
+    ("dm_bslabels_fetch_classes", _c.c_int, [_vp, _vp]),
+    ("dm_bslabels_format_begin", _c.c_int, [_vp, _c.c_int, _c.POINTER(_i64), _c.POINTER(_i64), _c.POINTER(_i64)]),
+    ("dm_bslabels_format_next", _c.c_int, [_vp, _vp, _i64, _c.POINTER(_i64)]),
+    ("dm_bslabels_close_contig", _c.c_int, [_vp]),
+    ("dm_bslabels_format_host", _i64, [_c.c_char_p, _c.c_int, _vp, _vp, _i64, _i64, _vp, _i64]),
+    ("dm_bslabels_tile_positions", _c.c_int, []),
+    ("dm_bslabels_times", _c.c_int, [_vp, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
 ]
 
 

@@ -16,6 +16,7 @@
 // A duplicate key is reported as the smallest (position, strand) that was written twice (a 64-bit atomic min): the same on every run.
 // The tables belong to the caller (dm_summary handles) and have a stream of their own: dm_summary_sync before this handle's stream touches them,
 // a stream synchronisation of this handle before a call returns.
+// The truth side - text to records to slots - is bsk::Truth, which dm_bslabels (bslabels.hip.inc) is built on as well.
 #pragma once
 #include "host.h"
 #include "xyrows.hip.inc"
@@ -28,7 +29,7 @@ constexpr int THREADS = 256;
 constexpr int MAX_BLOCKS = 1024;                    // grid of the record and sweep kernels: a block loops over its share and flushes once
 constexpr int NMOM = 6;                             // n, sum x, sum y, sum xy, sum x^2, sum y^2
 constexpr unsigned PRESENT = 0x80000000u;           // a truth slot: PRESENT | percentage << 16 | coverage
-enum { S_UNTRUTHED, S_BELOW = 2, S_BADSUM = 4, S_DUP, N_STAT };       // untruthed and below_threshold per kind
+enum { S_UNTRUTHED, S_BELOW = 2, S_BADSUM = 4, N_STAT };              // untruthed and below_threshold per kind
 
 struct Params {
     int thr[MAX_THR];                               // ascending
@@ -72,16 +73,16 @@ __global__ __launch_bounds__(THREADS) void bs_compact_kernel(const int* __restri
     meta[at] = rmeta[r];
 }
 
-// table: the replicate's slots [2 strands][length]; every pos[i] < length (checked on the host before the launch)
+// table: the replicate's slots [2 strands][length]; every pos[i] < length (checked on the host before the launch); dup: the smallest key written twice
 __global__ __launch_bounds__(THREADS) void bs_fill_kernel(const int* __restrict__ pos, const unsigned* __restrict__ meta, const long long n, unsigned* __restrict__ table,
-                                                         const long long length, unsigned long long* __restrict__ stat) {
+                                                         const long long length, unsigned long long* __restrict__ dup) {
     for (long long i = (long long)blockIdx.x * THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * THREADS) {
         const long long q = pos[i];
         if (q < 0 || q >= length) continue;
         const unsigned m = meta[i];
         const int s = meta_strand(m);
         const unsigned old = atomicExch(&table[(long long)s * length + q], PRESENT | (m & 0x7fffffu));
-        if (old) atomicMin(stat + S_DUP, (unsigned long long)(q * 2 + s));
+        if (old) atomicMin(dup, (unsigned long long)(q * 2 + s));
     }
 }
 
@@ -188,25 +189,227 @@ __global__ __launch_bounds__(THREADS) void bs_count_kernel(const unsigned* __res
 
 }  // namespace bsk
 
-struct dm_bsperf {
-    dm_xyrows* xy = nullptr;                            // stream, the scan and its block sums
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // parse, fill, count: begin / end
-    enum { WANT = xlk::N_SPLIT, RPOS, RMETA, POS, META, NAMES, LSTAT, TRUTH, SCORE, SPOS, SSTRAND, SPCT, HIST, MOM, STAT, N_BUF };
-    DevBufs<N_BUF> b{"dm_bsperf"};
-    bsk::Names names = {};
-    bsk::Params par = {};
-    int64_t lines[bsk::N_LINE] = {};                    // of every chunk taken so far
-    int64_t n_records = 0;                              // records on the device, of the last add_truth_text / add_truth_records
-    dm_summary *plus = nullptr, *minus = nullptr;       // the open contig's tables (null: none), the caller's
-    int contig = -1;
-    int64_t length = 0;
-    bool refused = false, counted = false, scored = false;
-    double parse_ms = 0.0, fill_ms = 0.0, count_ms = 0.0;
-};
-
 namespace bsk {
 
 constexpr int64_t MAX_RECORDS = 0x7fffffffLL;
+
+// The truth side of a handle: the replicates' text -> records -> one 32-bit slot per (replicate, strand, position) of the open contig.  dm_bsperf
+// and dm_bslabels (bslabels.hip.inc) are built on it, so both read, check and join the replicates with this one copy; `who` is the entry
+// point named in a message.
+struct Truth {
+    dm_xyrows* xy = nullptr;                            // stream, the scan and its block sums
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};                        // parse, fill: begin / end
+    enum { WANT = xlk::N_SPLIT, RPOS, RMETA, POS, META, NAMES, LSTAT, TRUTH, DUP, N_BUF };
+    DevBufs<N_BUF> b{"dm_bsperf"};
+    Names names = {};
+    int n_rep = 0;
+    int64_t lines[N_LINE] = {};                         // of every chunk taken so far
+    int64_t n_records = 0;                              // records on the device, of the last add_truth_text / add_truth_records
+    int contig = -1;                                    // the open contig (-1: none) and the positions of its slot table
+    int64_t length = 0;
+    bool refused = false;                               // a key occurred twice in a replicate
+    double parse_ms = 0.0, fill_ms = 0.0;
+};
+
+// the stream, the events, the names on the device; false (with the message set): the caller destroys what it built
+bool truth_init(Truth* t, int device, const Names& nm, int n_rep, const char* handle, const char* who) {
+    using B = Truth;
+    t->b.who = handle;
+    t->xy = dm_xy_create(device);
+    if (!t->xy) return false;
+    t->names = nm;
+    t->n_rep = n_rep;
+    bool ok = true;
+    for (hipEvent_t& e : t->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+    ok = ok && t->b.ensure(B::LSTAT, N_LINE * 8) == DM_OK && t->b.ensure(B::NAMES, sizeof(Names)) == DM_OK && t->b.ensure(B::DUP, 8) == DM_OK;
+    hipStream_t s = t->xy->stream;
+    ok = ok && hipMemcpyAsync(t->b.buf[B::NAMES], &t->names, sizeof(Names), hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        fail(DM_EDEVICE, "%s: events or counters on device %d", who, device);
+    }
+    return ok;
+}
+
+void truth_release(Truth* t) {
+    if (t->xy) {
+        (void)hipSetDevice(t->xy->device);
+        (void)hipStreamSynchronize(t->xy->stream);
+    }
+    t->b.release();
+    for (hipEvent_t e : t->ev)
+        if (e) (void)hipEventDestroy(e);
+    dm_xy_destroy(t->xy);
+    t->xy = nullptr;
+}
+
+int truth_add_text(Truth* h, const char* who, int replicate, const char* text, int64_t n_bytes, int is_first_chunk, int64_t* lines, int64_t* n_records, int32_t* flag,
+                   int64_t* first_bad_line) {
+    using B = Truth;
+    if (lines)
+        for (int k = 0; k < N_LINE; ++k) lines[k] = 0;
+    if (n_records) *n_records = 0;
+    if (flag) *flag = 0;
+    if (first_bad_line) *first_bad_line = -1;
+    if (replicate < 0 || replicate >= h->n_rep) return fail(DM_EINVAL, "%s: replicate %d of %d", who, replicate, h->n_rep);
+    h->n_records = 0;
+    HIP_TRY(hipSetDevice(h->xy->device));
+    hipStream_t s = h->xy->stream;
+    unsigned long long* d_lstat = h->b.ptr<unsigned long long>(B::LSTAT);
+    if (n_bytes > 0) HIP_TRY(hipMemsetAsync(d_lstat, 0, N_LINE * 8, s));
+    int rc;
+    long long rows = 0;
+    if ((rc = xlk::split(h->xy, h->b, text, n_bytes, MAX_RECORDS, who, "lines in one chunk", h->ev[0], &rows)) != DM_OK || rows == 0) return rc;
+    for (int which : {int(B::RPOS), int(B::RMETA), int(B::POS), int(B::META)})
+        if ((rc = h->b.ensure(which, size_t(rows) * 4)) != DM_OK) return rc;
+    if ((rc = h->b.ensure(xlk::STATUS, size_t(rows))) != DM_OK || (rc = h->b.ensure(B::WANT, size_t(rows + 1) * 8)) != DM_OK) return rc;
+    long long* d_want = h->b.ptr<long long>(B::WANT);
+    const dim3 row_grid{unsigned((rows + THREADS - 1) / THREADS)};
+    hipLaunchKernelGGL(bs_parse_kernel, row_grid, dim3(THREADS), 0, s, h->b.ptr<const char>(xlk::TEXT), h->b.ptr<const long long>(xlk::START), rows,
+                       h->b.ptr<const Names>(B::NAMES), is_first_chunk != 0 ? 1 : 0, h->b.ptr<int>(B::RPOS), h->b.ptr<unsigned>(B::RMETA), d_want,
+                       h->b.ptr<unsigned char>(xlk::STATUS), d_lstat);
+    HIP_TRY(hipGetLastError());
+    if ((rc = xlk::first_bad(h->xy, h->b, rows)) != DM_OK) return rc;
+    if ((rc = xyk::scan_in_place(h->xy, d_want, rows)) != DM_OK) return rc;
+    hipLaunchKernelGGL(bs_compact_kernel, row_grid, dim3(THREADS), 0, s, h->b.ptr<const int>(B::RPOS), h->b.ptr<const unsigned>(B::RMETA), d_want, rows,
+                       h->b.ptr<int>(B::POS), h->b.ptr<unsigned>(B::META));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[1], s));
+    long long first = -1, recs = 0;
+    unsigned long long counted[N_LINE] = {};
+    HIP_TRY(hipMemcpyAsync(&first, h->b.buf[xlk::OUT], 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&recs, d_want + rows, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(counted, d_lstat, sizeof counted, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = add_time(h->ev[0], h->ev[1], h->parse_ms)) != DM_OK) return rc;
+    if (first >= 0) {                                                // outside the grammar: nothing of this chunk is taken
+        if (flag) *flag = 1;
+        if (first_bad_line) *first_bad_line = first + 1;
+        return DM_OK;
+    }
+    if (recs < 0 || recs > rows || recs != (long long)counted[L_RECORD])
+        return fail(DM_ESTATE, "%s: %lld records of %lld lines (%llu counted)", who, recs, rows, counted[L_RECORD]);
+    for (int k = 0; k < N_LINE; ++k) {
+        h->lines[k] += int64_t(counted[k]);
+        if (lines) lines[k] = int64_t(counted[k]);
+    }
+    h->n_records = recs;
+    if (n_records) *n_records = recs;
+    return DM_OK;
+}
+
+int truth_add_records(Truth* h, const char* who, int replicate, int64_t n, const uint8_t* contig, const uint8_t* strand, const int32_t* pos, const int32_t* cov,
+                      const int32_t* pct, const int64_t* lines) {
+    using B = Truth;
+    if (replicate < 0 || replicate >= h->n_rep) return fail(DM_EINVAL, "%s: replicate %d of %d", who, replicate, h->n_rep);
+    if (n < 0 || n > MAX_RECORDS || (n > 0 && (!contig || !strand || !pos || !cov || !pct)) || !lines) return fail(DM_EINVAL, "%s: %lld records", who, (long long)n);
+    if (lines[L_RECORD] != n) return fail(DM_EINVAL, "%s: %lld records, %lld record lines", who, (long long)n, (long long)lines[L_RECORD]);
+    for (int k = 0; k < N_LINE; ++k)
+        if (lines[k] < 0) return fail(DM_EINVAL, "%s: line counter %d is %lld", who, k, (long long)lines[k]);
+    for (int64_t i = 0; i < n; ++i)                                  // what the kernels index with, checked before any launch
+        if (contig[i] >= h->names.n || strand[i] > 1 || pos[i] < 0 || pos[i] >= h->names.limit[contig[i]] || cov[i] < 1 || pct[i] < 0 || pct[i] > 100)
+            return fail(DM_EINVAL, "%s: record %lld (contig %d of %d, strand %d, position %d, coverage %d, percentage %d)", who, (long long)i, int(contig[i]), h->names.n,
+                        int(strand[i]), pos[i], cov[i], pct[i]);
+    h->n_records = 0;
+    if (n > 0) {
+        std::vector<uint32_t> meta(size_t(n), 0u);
+        for (int64_t i = 0; i < n; ++i) meta[size_t(i)] = pack_meta(contig[i], strand[i], cov[i], pct[i]);
+        HIP_TRY(hipSetDevice(h->xy->device));
+        int rc;
+        if ((rc = h->b.ensure(B::POS, size_t(n) * 4)) != DM_OK || (rc = h->b.ensure(B::META, size_t(n) * 4)) != DM_OK) return rc;
+        hipStream_t s = h->xy->stream;
+        HIP_TRY(hipMemcpyAsync(h->b.buf[B::POS], pos, size_t(n) * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(h->b.buf[B::META], meta.data(), size_t(n) * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    for (int k = 0; k < N_LINE; ++k) h->lines[k] += lines[k];
+    h->n_records = n;
+    return DM_OK;
+}
+
+int truth_fetch_records(Truth* h, int32_t* pos, uint32_t* meta) {
+    using B = Truth;
+    const size_t n = size_t(h->n_records);
+    if (n == 0) return DM_OK;
+    HIP_TRY(hipSetDevice(h->xy->device));
+    if (pos) HIP_TRY(hipMemcpy(pos, h->b.buf[B::POS], n * 4, hipMemcpyDeviceToHost));
+    if (meta) HIP_TRY(hipMemcpy(meta, h->b.buf[B::META], n * 4, hipMemcpyDeviceToHost));
+    return DM_OK;
+}
+
+void truth_close(Truth* h) {
+    h->contig = -1;
+    h->length = 0;
+    h->refused = false;
+}
+
+// the zeroed slots of contig `contig_index`, `length` positions per strand (both checked by the caller)
+int truth_open(Truth* h, int contig_index, int64_t length) {
+    using B = Truth;
+    HIP_TRY(hipSetDevice(h->xy->device));
+    const size_t slots = size_t(h->n_rep) * 2 * size_t(length);
+    int rc;
+    if ((rc = h->b.ensure(B::TRUTH, slots * 4)) != DM_OK) return rc;
+    hipStream_t s = h->xy->stream;
+    HIP_TRY(hipMemsetAsync(h->b.buf[B::TRUTH], 0, slots * 4, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    h->contig = contig_index;
+    h->length = length;
+    h->refused = false;
+    return DM_OK;
+}
+
+// the caller has checked that a contig is open and may still be filled
+int truth_fill(Truth* h, const char* who, int replicate, int64_t n, const int32_t* pos, const uint32_t* meta, int64_t* dup_pos, int32_t* dup_strand) {
+    using B = Truth;
+    if (replicate < 0 || replicate >= h->n_rep) return fail(DM_EINVAL, "%s: replicate %d of %d", who, replicate, h->n_rep);
+    if (n < 0 || n > MAX_RECORDS || (n > 0 && (!pos || !meta))) return fail(DM_EINVAL, "%s: %lld records", who, (long long)n);
+    for (int64_t i = 0; i < n; ++i)                                  // what the kernel indexes with, checked before any launch
+        if (pos[i] < 0 || pos[i] >= h->length || meta_contig(meta[i]) != h->contig || meta_cov(meta[i]) < 1 || meta_pct(meta[i]) > 100)
+            return fail(DM_EINVAL, "%s: record %lld (contig %d, the open one is %d; position %d of %lld; coverage %d, percentage %d)", who, (long long)i,
+                        meta_contig(meta[i]), h->contig, pos[i], (long long)h->length, meta_cov(meta[i]), meta_pct(meta[i]));
+    if (n == 0) return DM_OK;
+    HIP_TRY(hipSetDevice(h->xy->device));
+    int rc;
+    if ((rc = h->b.ensure(B::POS, size_t(n) * 4)) != DM_OK || (rc = h->b.ensure(B::META, size_t(n) * 4)) != DM_OK) return rc;
+    h->n_records = 0;                                                // the record buffers now hold this fill
+    hipStream_t s = h->xy->stream;
+    unsigned long long* d_dup = h->b.ptr<unsigned long long>(B::DUP);
+    HIP_TRY(hipMemcpyAsync(h->b.buf[B::POS], pos, size_t(n) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->b.buf[B::META], meta, size_t(n) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_dup, 0xff, 8, s));
+    const dim3 grid{unsigned(std::min<int64_t>((n + THREADS - 1) / THREADS, MAX_BLOCKS))};
+    HIP_TRY(hipEventRecord(h->ev[2], s));
+    hipLaunchKernelGGL(bs_fill_kernel, grid, dim3(THREADS), 0, s, h->b.ptr<const int>(B::POS), h->b.ptr<const unsigned>(B::META), (long long)n,
+                       h->b.ptr<unsigned>(B::TRUTH) + size_t(replicate) * 2 * size_t(h->length), (long long)h->length, d_dup);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[3], s));
+    unsigned long long dup = ~0ull;
+    HIP_TRY(hipMemcpyAsync(&dup, d_dup, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = add_time(h->ev[2], h->ev[3], h->fill_ms)) != DM_OK) return rc;
+    if (dup != ~0ull) {
+        h->refused = true;
+        if (dup_pos) *dup_pos = int64_t(dup >> 1);
+        if (dup_strand) *dup_strand = int32_t(dup & 1);
+        return fail(DM_EINVAL, "%s: replicate %d holds position %llu of strand %c twice: the contig is refused", who, replicate, dup >> 1, (dup & 1) ? '-' : '+');
+    }
+    return DM_OK;
+}
+
+}  // namespace bsk
+
+struct dm_bsperf : bsk::Truth {
+    hipEvent_t cev[2] = {nullptr, nullptr};             // count: begin / end
+    enum { SCORE, SPOS, SSTRAND, SPCT, HIST, MOM, STAT, N_OWN };
+    DevBufs<N_OWN> c{"dm_bsperf"};                      // what the count needs on top of the truth side
+    bsk::Params par = {};
+    dm_summary *plus = nullptr, *minus = nullptr;       // the open contig's tables (null: none), the caller's
+    bool counted = false, scored = false;
+    double count_ms = 0.0;
+};
+
+namespace bsk {
 
 size_t hist_counters(const dm_bsperf* h) { return size_t(2) * kind_bins(h->par.n_thr); }
 size_t mom_counters(const dm_bsperf* h) { return size_t(2) * h->par.n_thr * NMOM; }
@@ -219,26 +422,26 @@ int count_kind(dm_bsperf* h, int kind) {
     if (dm_summary_length(h->plus) != h->length || dm_summary_length(h->minus) != h->length)
         return fail(DM_ESTATE, "dm_bsperf: the tables changed since the contig was opened (%lld positions then)", (long long)h->length);
     hipStream_t s = h->xy->stream;
-    unsigned long long* d_stat = h->b.ptr<unsigned long long>(B::STAT);
-    unsigned long long* d_hist = h->b.ptr<unsigned long long>(B::HIST) + size_t(kind) * kind_bins(h->par.n_thr);
-    unsigned long long* d_mom = h->b.ptr<unsigned long long>(B::MOM) + size_t(kind) * h->par.n_thr * NMOM;
+    unsigned long long* d_stat = h->c.ptr<unsigned long long>(B::STAT);
+    unsigned long long* d_hist = h->c.ptr<unsigned long long>(B::HIST) + size_t(kind) * kind_bins(h->par.n_thr);
+    unsigned long long* d_mom = h->c.ptr<unsigned long long>(B::MOM) + size_t(kind) * h->par.n_thr * NMOM;
     const int* plus = static_cast<const int*>(dm_summary_device_ptr(h->plus));
     const int* minus = static_cast<const int*>(dm_summary_device_ptr(h->minus));
     const dim3 grid{unsigned(std::min<int64_t>((2 * h->length + THREADS - 1) / THREADS, MAX_BLOCKS))};
     HIP_TRY(hipMemsetAsync(d_stat + S_BADSUM, 0, 8, s));
-    HIP_TRY(hipEventRecord(h->ev[4], s));
+    HIP_TRY(hipEventRecord(h->cev[0], s));
     if (kind == 0)
-        hipLaunchKernelGGL(bs_count_kernel<0>, grid, dim3(THREADS), 0, s, h->b.ptr<const unsigned>(B::TRUTH), plus, minus, (const unsigned char*)nullptr, (long long)h->length,
+        hipLaunchKernelGGL(bs_count_kernel<0>, grid, dim3(THREADS), 0, s, h->b.ptr<const unsigned>(Truth::TRUTH), plus, minus, (const unsigned char*)nullptr, (long long)h->length,
                            h->par, d_hist, d_mom, d_stat);
     else
-        hipLaunchKernelGGL(bs_count_kernel<1>, grid, dim3(THREADS), 0, s, h->b.ptr<const unsigned>(B::TRUTH), plus, minus, h->b.ptr<const unsigned char>(B::SCORE),
+        hipLaunchKernelGGL(bs_count_kernel<1>, grid, dim3(THREADS), 0, s, h->b.ptr<const unsigned>(Truth::TRUTH), plus, minus, h->c.ptr<const unsigned char>(B::SCORE),
                            (long long)h->length, h->par, d_hist, d_mom, d_stat);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->ev[5], s));
+    HIP_TRY(hipEventRecord(h->cev[1], s));
     unsigned long long bad = 0;
     HIP_TRY(hipMemcpyAsync(&bad, d_stat + S_BADSUM, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if ((rc = add_time(h->ev[4], h->ev[5], h->count_ms)) != DM_OK) return rc;
+    if ((rc = add_time(h->cev[0], h->cev[1], h->count_ms)) != DM_OK) return rc;
     if (bad) return fail(DM_EINVAL, "dm_bsperf_count: the sums of %llu positions are outside 0 <= modified <= coverage", bad);
     return DM_OK;
 }
@@ -251,14 +454,10 @@ int dm_bsperf_tile_bytes(void) { return xlk::TILE; }
 
 void dm_bsperf_destroy(dm_bsperf* h) {
     if (!h) return;
-    if (h->xy) {
-        (void)hipSetDevice(h->xy->device);
-        (void)hipStreamSynchronize(h->xy->stream);
-    }
-    h->b.release();
-    for (hipEvent_t e : h->ev)
+    bsk::truth_release(h);                                           // (the device is set and the stream drained first)
+    h->c.release();
+    for (hipEvent_t e : h->cev)
         if (e) (void)hipEventDestroy(e);
-    dm_xy_destroy(h->xy);
     delete h;
 }
 
@@ -293,21 +492,19 @@ dm_bsperf* dm_bsperf_create(int device, int n_contigs, const char* const* names,
              bsk::MAX_NAME, which - 1, n_contigs);
         return nullptr;
     }
-    dm_xyrows* xy = dm_xy_create(device);
-    if (!xy) return nullptr;
     dm_bsperf* h = new dm_bsperf;
-    h->xy = xy;
     h->par = par;
-    h->names = nm;
+    if (!bsk::truth_init(h, device, nm, par.n_rep, "dm_bsperf", "dm_bsperf_create")) {
+        dm_bsperf_destroy(h);
+        return nullptr;
+    }
     bool ok = true;
-    for (hipEvent_t& e : h->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+    for (hipEvent_t& e : h->cev) ok = ok && hipEventCreate(&e) == hipSuccess;
     const size_t hist_bytes = bsk::hist_counters(h) * 8, mom_bytes = bsk::mom_counters(h) * 8;
-    ok = ok && h->b.ensure(B::HIST, hist_bytes) == DM_OK && h->b.ensure(B::MOM, mom_bytes) == DM_OK && h->b.ensure(B::STAT, bsk::N_STAT * 8) == DM_OK &&
-         h->b.ensure(B::LSTAT, bsk::N_LINE * 8) == DM_OK && h->b.ensure(B::NAMES, sizeof(bsk::Names)) == DM_OK;
-    hipStream_t s = xy->stream;
-    ok = ok && hipMemsetAsync(h->b.buf[B::HIST], 0, hist_bytes, s) == hipSuccess && hipMemsetAsync(h->b.buf[B::MOM], 0, mom_bytes, s) == hipSuccess &&
-         hipMemsetAsync(h->b.buf[B::STAT], 0, bsk::N_STAT * 8, s) == hipSuccess &&
-         hipMemcpyAsync(h->b.buf[B::NAMES], &h->names, sizeof(bsk::Names), hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+    ok = ok && h->c.ensure(B::HIST, hist_bytes) == DM_OK && h->c.ensure(B::MOM, mom_bytes) == DM_OK && h->c.ensure(B::STAT, bsk::N_STAT * 8) == DM_OK;
+    hipStream_t s = h->xy->stream;
+    ok = ok && hipMemsetAsync(h->c.buf[B::HIST], 0, hist_bytes, s) == hipSuccess && hipMemsetAsync(h->c.buf[B::MOM], 0, mom_bytes, s) == hipSuccess &&
+         hipMemsetAsync(h->c.buf[B::STAT], 0, bsk::N_STAT * 8, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         fail(DM_EDEVICE, "dm_bsperf_create: events or counters on device %d", device);
@@ -336,113 +533,30 @@ int64_t dm_bsperf_parse_host(const char* text, int64_t n_bytes, int n_contigs, c
 
 int dm_bsperf_add_truth_text(dm_bsperf* h, int replicate, const char* text, int64_t n_bytes, int is_first_chunk, int64_t* lines, int64_t* n_records, int32_t* flag,
                              int64_t* first_bad_line) {
-    using B = dm_bsperf;
     if (!h) return fail(DM_EINVAL, "null handle");
-    if (lines)
-        for (int k = 0; k < bsk::N_LINE; ++k) lines[k] = 0;
-    if (n_records) *n_records = 0;
-    if (flag) *flag = 0;
-    if (first_bad_line) *first_bad_line = -1;
-    if (replicate < 0 || replicate >= h->par.n_rep) return fail(DM_EINVAL, "dm_bsperf_add_truth_text: replicate %d of %d", replicate, h->par.n_rep);
-    h->n_records = 0;
-    HIP_TRY(hipSetDevice(h->xy->device));
-    hipStream_t s = h->xy->stream;
-    unsigned long long* d_lstat = h->b.ptr<unsigned long long>(B::LSTAT);
-    if (n_bytes > 0) HIP_TRY(hipMemsetAsync(d_lstat, 0, bsk::N_LINE * 8, s));
-    int rc;
-    long long rows = 0;
-    if ((rc = xlk::split(h->xy, h->b, text, n_bytes, bsk::MAX_RECORDS, "dm_bsperf_add_truth_text", "lines in one chunk", h->ev[0], &rows)) != DM_OK || rows == 0) return rc;
-    for (int which : {int(B::RPOS), int(B::RMETA), int(B::POS), int(B::META)})
-        if ((rc = h->b.ensure(which, size_t(rows) * 4)) != DM_OK) return rc;
-    if ((rc = h->b.ensure(xlk::STATUS, size_t(rows))) != DM_OK || (rc = h->b.ensure(B::WANT, size_t(rows + 1) * 8)) != DM_OK) return rc;
-    long long* d_want = h->b.ptr<long long>(B::WANT);
-    const dim3 row_grid{unsigned((rows + bsk::THREADS - 1) / bsk::THREADS)};
-    hipLaunchKernelGGL(bsk::bs_parse_kernel, row_grid, dim3(bsk::THREADS), 0, s, h->b.ptr<const char>(xlk::TEXT), h->b.ptr<const long long>(xlk::START), rows,
-                       h->b.ptr<const bsk::Names>(B::NAMES), is_first_chunk != 0 ? 1 : 0, h->b.ptr<int>(B::RPOS), h->b.ptr<unsigned>(B::RMETA), d_want,
-                       h->b.ptr<unsigned char>(xlk::STATUS), d_lstat);
-    HIP_TRY(hipGetLastError());
-    if ((rc = xlk::first_bad(h->xy, h->b, rows)) != DM_OK) return rc;
-    if ((rc = xyk::scan_in_place(h->xy, d_want, rows)) != DM_OK) return rc;
-    hipLaunchKernelGGL(bsk::bs_compact_kernel, row_grid, dim3(bsk::THREADS), 0, s, h->b.ptr<const int>(B::RPOS), h->b.ptr<const unsigned>(B::RMETA), d_want, rows,
-                       h->b.ptr<int>(B::POS), h->b.ptr<unsigned>(B::META));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->ev[1], s));
-    long long first = -1, recs = 0;
-    unsigned long long counted[bsk::N_LINE] = {};
-    HIP_TRY(hipMemcpyAsync(&first, h->b.buf[xlk::OUT], 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&recs, d_want + rows, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(counted, d_lstat, sizeof counted, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if ((rc = add_time(h->ev[0], h->ev[1], h->parse_ms)) != DM_OK) return rc;
-    if (first >= 0) {                                                // outside the grammar: nothing of this chunk is taken
-        if (flag) *flag = 1;
-        if (first_bad_line) *first_bad_line = first + 1;
-        return DM_OK;
-    }
-    if (recs < 0 || recs > rows || recs != (long long)counted[bsk::L_RECORD])
-        return fail(DM_ESTATE, "dm_bsperf_add_truth_text: %lld records of %lld lines (%llu counted)", recs, rows, counted[bsk::L_RECORD]);
-    for (int k = 0; k < bsk::N_LINE; ++k) {
-        h->lines[k] += int64_t(counted[k]);
-        if (lines) lines[k] = int64_t(counted[k]);
-    }
-    h->n_records = recs;
-    if (n_records) *n_records = recs;
-    return DM_OK;
+    return bsk::truth_add_text(h, "dm_bsperf_add_truth_text", replicate, text, n_bytes, is_first_chunk, lines, n_records, flag, first_bad_line);
 }
 
 int dm_bsperf_add_truth_records(dm_bsperf* h, int replicate, int64_t n, const uint8_t* contig, const uint8_t* strand, const int32_t* pos, const int32_t* cov,
                                 const int32_t* pct, const int64_t* lines) {
-    using B = dm_bsperf;
     if (!h) return fail(DM_EINVAL, "null handle");
-    if (replicate < 0 || replicate >= h->par.n_rep) return fail(DM_EINVAL, "dm_bsperf_add_truth_records: replicate %d of %d", replicate, h->par.n_rep);
-    if (n < 0 || n > bsk::MAX_RECORDS || (n > 0 && (!contig || !strand || !pos || !cov || !pct)) || !lines)
-        return fail(DM_EINVAL, "dm_bsperf_add_truth_records: %lld records", (long long)n);
-    if (lines[bsk::L_RECORD] != n) return fail(DM_EINVAL, "dm_bsperf_add_truth_records: %lld records, %lld record lines", (long long)n, (long long)lines[bsk::L_RECORD]);
-    for (int k = 0; k < bsk::N_LINE; ++k)
-        if (lines[k] < 0) return fail(DM_EINVAL, "dm_bsperf_add_truth_records: line counter %d is %lld", k, (long long)lines[k]);
-    for (int64_t i = 0; i < n; ++i)                                  // what the kernels index with, checked before any launch
-        if (contig[i] >= h->names.n || strand[i] > 1 || pos[i] < 0 || pos[i] >= h->names.limit[contig[i]] || cov[i] < 1 || pct[i] < 0 || pct[i] > 100)
-            return fail(DM_EINVAL, "dm_bsperf_add_truth_records: record %lld (contig %d of %d, strand %d, position %d, coverage %d, percentage %d)", (long long)i,
-                        int(contig[i]), h->names.n, int(strand[i]), pos[i], cov[i], pct[i]);
-    h->n_records = 0;
-    if (n > 0) {
-        std::vector<uint32_t> meta(size_t(n), 0u);
-        for (int64_t i = 0; i < n; ++i) meta[size_t(i)] = bsk::pack_meta(contig[i], strand[i], cov[i], pct[i]);
-        HIP_TRY(hipSetDevice(h->xy->device));
-        int rc;
-        if ((rc = h->b.ensure(B::POS, size_t(n) * 4)) != DM_OK || (rc = h->b.ensure(B::META, size_t(n) * 4)) != DM_OK) return rc;
-        hipStream_t s = h->xy->stream;
-        HIP_TRY(hipMemcpyAsync(h->b.buf[B::POS], pos, size_t(n) * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(h->b.buf[B::META], meta.data(), size_t(n) * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    for (int k = 0; k < bsk::N_LINE; ++k) h->lines[k] += lines[k];
-    h->n_records = n;
-    return DM_OK;
+    return bsk::truth_add_records(h, "dm_bsperf_add_truth_records", replicate, n, contig, strand, pos, cov, pct, lines);
 }
 
 int dm_bsperf_fetch_records(dm_bsperf* h, int32_t* pos, uint32_t* meta) {
-    using B = dm_bsperf;
     if (!h) return fail(DM_EINVAL, "null handle");
-    const size_t n = size_t(h->n_records);
-    if (n == 0) return DM_OK;
-    HIP_TRY(hipSetDevice(h->xy->device));
-    if (pos) HIP_TRY(hipMemcpy(pos, h->b.buf[B::POS], n * 4, hipMemcpyDeviceToHost));
-    if (meta) HIP_TRY(hipMemcpy(meta, h->b.buf[B::META], n * 4, hipMemcpyDeviceToHost));
-    return DM_OK;
+    return bsk::truth_fetch_records(h, pos, meta);
 }
 
 int dm_bsperf_close_contig(dm_bsperf* h) {
     if (!h) return fail(DM_EINVAL, "null handle");
     h->plus = h->minus = nullptr;
-    h->contig = -1;
-    h->length = 0;
-    h->refused = h->counted = h->scored = false;
+    bsk::truth_close(h);
+    h->counted = h->scored = false;
     return DM_OK;
 }
 
 int dm_bsperf_open(dm_bsperf* h, int contig_index, dm_summary* plus, dm_summary* minus) {
-    using B = dm_bsperf;
     if (!h) return fail(DM_EINVAL, "null handle");
     (void)dm_bsperf_close_contig(h);
     if (contig_index < 0 || contig_index >= h->names.n) return fail(DM_EINVAL, "dm_bsperf_open: contig %d of %d", contig_index, h->names.n);
@@ -453,60 +567,23 @@ int dm_bsperf_open(dm_bsperf* h, int contig_index, dm_summary* plus, dm_summary*
         return fail(DM_EINVAL, "dm_bsperf_open: tables of %lld and %lld positions (equal, 1 to 2^31 - 1)", (long long)length, (long long)dm_summary_length(minus));
     if (length > h->names.limit[contig_index])
         return fail(DM_EINVAL, "dm_bsperf_open: tables of %lld positions for a contig of %lld", (long long)length, (long long)h->names.limit[contig_index]);
-    HIP_TRY(hipSetDevice(h->xy->device));
-    const size_t slots = size_t(h->par.n_rep) * 2 * size_t(length);
-    int rc;
-    if ((rc = h->b.ensure(B::TRUTH, slots * 4)) != DM_OK) return rc;
-    hipStream_t s = h->xy->stream;
-    HIP_TRY(hipMemsetAsync(h->b.buf[B::TRUTH], 0, slots * 4, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    const int rc = bsk::truth_open(h, contig_index, length);
+    if (rc != DM_OK) {
+        bsk::truth_close(h);
+        return rc;
+    }
     h->plus = plus;
     h->minus = minus;
-    h->contig = contig_index;
-    h->length = length;
     return DM_OK;
 }
 
 int dm_bsperf_fill(dm_bsperf* h, int replicate, int64_t n, const int32_t* pos, const uint32_t* meta, int64_t* dup_pos, int32_t* dup_strand) {
-    using B = dm_bsperf;
     if (!h) return fail(DM_EINVAL, "null handle");
     if (dup_pos) *dup_pos = -1;
     if (dup_strand) *dup_strand = -1;
     if (!h->plus) return fail(DM_ESTATE, "dm_bsperf_fill: no contig");
     if (h->counted) return fail(DM_ESTATE, "dm_bsperf_fill: the contig has been counted");
-    if (replicate < 0 || replicate >= h->par.n_rep) return fail(DM_EINVAL, "dm_bsperf_fill: replicate %d of %d", replicate, h->par.n_rep);
-    if (n < 0 || n > bsk::MAX_RECORDS || (n > 0 && (!pos || !meta))) return fail(DM_EINVAL, "dm_bsperf_fill: %lld records", (long long)n);
-    for (int64_t i = 0; i < n; ++i)                                  // what the kernel indexes with, checked before any launch
-        if (pos[i] < 0 || pos[i] >= h->length || bsk::meta_contig(meta[i]) != h->contig || bsk::meta_cov(meta[i]) < 1 || bsk::meta_pct(meta[i]) > 100)
-            return fail(DM_EINVAL, "dm_bsperf_fill: record %lld (contig %d, the open one is %d; position %d of %lld; coverage %d, percentage %d)", (long long)i,
-                        bsk::meta_contig(meta[i]), h->contig, pos[i], (long long)h->length, bsk::meta_cov(meta[i]), bsk::meta_pct(meta[i]));
-    if (n == 0) return DM_OK;
-    HIP_TRY(hipSetDevice(h->xy->device));
-    int rc;
-    if ((rc = h->b.ensure(B::POS, size_t(n) * 4)) != DM_OK || (rc = h->b.ensure(B::META, size_t(n) * 4)) != DM_OK) return rc;
-    h->n_records = 0;                                                // the record buffers now hold this fill
-    hipStream_t s = h->xy->stream;
-    unsigned long long* d_stat = h->b.ptr<unsigned long long>(B::STAT);
-    HIP_TRY(hipMemcpyAsync(h->b.buf[B::POS], pos, size_t(n) * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->b.buf[B::META], meta, size_t(n) * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(d_stat + bsk::S_DUP, 0xff, 8, s));
-    const dim3 grid{unsigned(std::min<int64_t>((n + bsk::THREADS - 1) / bsk::THREADS, bsk::MAX_BLOCKS))};
-    HIP_TRY(hipEventRecord(h->ev[2], s));
-    hipLaunchKernelGGL(bsk::bs_fill_kernel, grid, dim3(bsk::THREADS), 0, s, h->b.ptr<const int>(B::POS), h->b.ptr<const unsigned>(B::META), (long long)n,
-                       h->b.ptr<unsigned>(B::TRUTH) + size_t(replicate) * 2 * size_t(h->length), (long long)h->length, d_stat);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->ev[3], s));
-    unsigned long long dup = ~0ull;
-    HIP_TRY(hipMemcpyAsync(&dup, d_stat + bsk::S_DUP, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if ((rc = add_time(h->ev[2], h->ev[3], h->fill_ms)) != DM_OK) return rc;
-    if (dup != ~0ull) {
-        h->refused = true;
-        if (dup_pos) *dup_pos = int64_t(dup >> 1);
-        if (dup_strand) *dup_strand = int32_t(dup & 1);
-        return fail(DM_EINVAL, "dm_bsperf_fill: replicate %d holds position %llu of strand %c twice: the contig is refused", replicate, dup >> 1, (dup & 1) ? '-' : '+');
-    }
-    return DM_OK;
+    return bsk::truth_fill(h, "dm_bsperf_fill", replicate, n, pos, meta, dup_pos, dup_strand);
 }
 
 int dm_bsperf_count(dm_bsperf* h) {
@@ -540,18 +617,18 @@ int dm_bsperf_add_scores(dm_bsperf* h, int64_t n, const int32_t* pos, const uint
     if (twice != key.end()) return fail(DM_EINVAL, "dm_bsperf_add_scores: position %lld of strand %c occurs twice", (long long)(*twice >> 1), (*twice & 1) ? '-' : '+');
     HIP_TRY(hipSetDevice(h->xy->device));
     int rc;
-    if ((rc = h->b.ensure(B::SCORE, size_t(h->length) * 2)) != DM_OK || (rc = h->b.ensure(B::SPOS, size_t(n) * 4 + 4)) != DM_OK ||
-        (rc = h->b.ensure(B::SSTRAND, size_t(n) + 1)) != DM_OK || (rc = h->b.ensure(B::SPCT, size_t(n) + 1)) != DM_OK)
+    if ((rc = h->c.ensure(B::SCORE, size_t(h->length) * 2)) != DM_OK || (rc = h->c.ensure(B::SPOS, size_t(n) * 4 + 4)) != DM_OK ||
+        (rc = h->c.ensure(B::SSTRAND, size_t(n) + 1)) != DM_OK || (rc = h->c.ensure(B::SPCT, size_t(n) + 1)) != DM_OK)
         return rc;
     hipStream_t s = h->xy->stream;
-    HIP_TRY(hipMemsetAsync(h->b.buf[B::SCORE], 0, size_t(h->length) * 2, s));
+    HIP_TRY(hipMemsetAsync(h->c.buf[B::SCORE], 0, size_t(h->length) * 2, s));
     if (n > 0) {
-        HIP_TRY(hipMemcpyAsync(h->b.buf[B::SPOS], pos, size_t(n) * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(h->b.buf[B::SSTRAND], strand, size_t(n), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(h->b.buf[B::SPCT], value.data(), size_t(n), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(h->c.buf[B::SPOS], pos, size_t(n) * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(h->c.buf[B::SSTRAND], strand, size_t(n), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(h->c.buf[B::SPCT], value.data(), size_t(n), hipMemcpyHostToDevice, s));
         const dim3 grid{unsigned(std::min<int64_t>((n + bsk::THREADS - 1) / bsk::THREADS, bsk::MAX_BLOCKS))};
-        hipLaunchKernelGGL(bsk::bs_score_kernel, grid, dim3(bsk::THREADS), 0, s, h->b.ptr<const int>(B::SPOS), h->b.ptr<const unsigned char>(B::SSTRAND),
-                           h->b.ptr<const unsigned char>(B::SPCT), (long long)n, h->b.ptr<unsigned char>(B::SCORE), (long long)h->length);
+        hipLaunchKernelGGL(bsk::bs_score_kernel, grid, dim3(bsk::THREADS), 0, s, h->c.ptr<const int>(B::SPOS), h->c.ptr<const unsigned char>(B::SSTRAND),
+                           h->c.ptr<const unsigned char>(B::SPCT), (long long)n, h->c.ptr<unsigned char>(B::SCORE), (long long)h->length);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipStreamSynchronize(s));                                // the host arrays of this call are read by now
@@ -568,9 +645,9 @@ int dm_bsperf_fetch(dm_bsperf* h, int64_t* hist, int64_t* unpredicted, int64_t* 
     const int T = h->par.n_thr, per_kind = bsk::kind_bins(T), hist_part = 3 * T * bsk::NPCT;
     std::vector<long long> all(bsk::hist_counters(h));
     long long stat[bsk::N_STAT];
-    HIP_TRY(hipMemcpy(all.data(), h->b.buf[B::HIST], all.size() * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(stat, h->b.buf[B::STAT], sizeof stat, hipMemcpyDeviceToHost));
-    if (moments) HIP_TRY(hipMemcpy(moments, h->b.buf[B::MOM], bsk::mom_counters(h) * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(all.data(), h->c.buf[B::HIST], all.size() * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(stat, h->c.buf[B::STAT], sizeof stat, hipMemcpyDeviceToHost));
+    if (moments) HIP_TRY(hipMemcpy(moments, h->c.buf[B::MOM], bsk::mom_counters(h) * 8, hipMemcpyDeviceToHost));
     for (int kind = 0; kind < 2; ++kind) {
         if (hist)
             for (int j = 0; j < hist_part; ++j) hist[kind * hist_part + j] = all[size_t(kind) * per_kind + j];

@@ -1,6 +1,7 @@
 // offline.hip — libdeepmod_hip.so, training and the offline commands: the BiLSTM trainer, the cluster trainer, getfeatures (the .xy writer), the
 // line splitter of every text parsed on the device (textlines.hip.inc), predict (the .xy parser), the resident gather of train --resident,
-// siteperf, merge, bsperf (their line grammars: siteperf.inc, bedmerge.inc, bsperf.inc on bedline.inc).  Interface to the other units: host.h.
+// siteperf, merge, bsperf, bslabels (their line grammars and routines: siteperf.inc, bedmerge.inc, bsperf.inc, bslabels.inc on bedline.inc).  Interface to the other
+// units: host.h.
 #include "train.hip.inc"
 #include "cluster_train.hip.inc"
 #include "xyrows.inc"
@@ -11,3 +12,4 @@
 #include "siteperf.hip.inc"
 #include "bedmerge.hip.inc"
 #include "bsperf.hip.inc"
+#include "bslabels.hip.inc"

@@ -251,6 +251,24 @@ struct dm_siteperf {
 namespace spk {
 
 constexpr int64_t MAX_RECORDS = 0x7fffffffLL;
+
+// motif[0 .. m) (1 <= m <= MAX_MOTIF, 0 <= k < m: the caller's check) in upper case and its reverse complement -> mo; -> -1, or the offset
+// the reverse complement meets first of a letter that is none of A, C, G, T.  What sp_code_kernel takes: dm_siteperf_set_contig and dm_bslabels_open (bslabels.hip.inc)
+inline int make_motif(Motif& mo, const char* motif, const int m, const int k) {
+    mo = {};
+    mo.m = m;
+    mo.k = k;
+    mo.B = (unsigned char)motif[k];
+    for (int j = 0; j < m; ++j) {
+        const unsigned char c = (unsigned char)motif[j];
+        mo.pat[j] = (c >= 'a' && c <= 'z') ? c - 32 : c;
+    }
+    for (int j = 0; j < m; ++j) {
+        mo.rc[j] = complement(mo.pat[m - 1 - j]);
+        if (!mo.rc[j]) return m - 1 - j;
+    }
+    return -1;
+}
 constexpr int64_t MAX_CONTROL_FILES = int64_t(1) << 16;              // the key holds 16 bits of file index, 40 of line index, 8 of base
 
 int record_buffers(dm_siteperf* h, int64_t n) {
@@ -359,17 +377,8 @@ int dm_siteperf_set_contig(dm_siteperf* h, const uint8_t* seq, int64_t len, cons
     if (!motif || m < 1 || m > spk::MAX_MOTIF || k < 0 || k >= m)
         return fail(DM_EINVAL, "dm_siteperf_set_contig: motif of %d bases (1 to %d), modified offset %d", m, spk::MAX_MOTIF, k);
     spk::Motif mo = {};
-    mo.m = m;
-    mo.k = k;
-    mo.B = (unsigned char)motif[k];
-    for (int j = 0; j < m; ++j) {
-        const unsigned char c = (unsigned char)motif[j];
-        mo.pat[j] = (c >= 'a' && c <= 'z') ? c - 32 : c;
-    }
-    for (int j = 0; j < m; ++j) {
-        mo.rc[j] = spk::complement(mo.pat[m - 1 - j]);
-        if (!mo.rc[j]) return fail(DM_EINVAL, "dm_siteperf_set_contig: motif base %d is none of A, C, G, T", m - 1 - j);
-    }
+    const int other = spk::make_motif(mo, motif, m, k);
+    if (other >= 0) return fail(DM_EINVAL, "dm_siteperf_set_contig: motif base %d is none of A, C, G, T", other);
     h->motif = mo;
     h->lo = start < 0 ? 0 : start;                                    // a negative bound: none (the reference's -1)
     h->hi = (end < 0 || end > len - 1) ? len - 1 : end;

@@ -845,6 +845,58 @@ int64_t dm_bsperf_parse_host(const char* text, int64_t n_bytes, int n_contigs, c
 int dm_bsperf_tile_bytes(void);
 int dm_bsperf_times(dm_bsperf* h, double* parse_ms, double* fill_ms, double* count_ms);
 
+/* ------------------------------------------------------------------------- bslabels -- */
+/* Training position lists from bisulfite replicates: the fulmod / anymod / nomod files getfeatures --motifORPos 2 reads (`chr strand pos`
+ * lines; csrc/bslabels.hip.inc, bslabels.inc).  The truth side is dm_bsperf's, one copy of the code: 1 - 4 bedMethyl replicates,
+ * parsed in chunks into records that the caller buckets by contig, then one 32-bit slot per (replicate, strand, position) of the open contig.
+ * The reference bytes of the contig give one site code per position (bit 0: the motif lies on '+' with its modified base here, bit 1: on '-';
+ * the kernel dm_siteperf_set_contig runs, on the bytes as they are handed over).  Per key (strand, position), one class byte:
+ *   0  no replicate has a record                    4  a record somewhere, but the key is no site of the motif (off_motif; in no list)
+ *   1  fulmod: every replicate has a record, the smallest coverage is >= cov, every percentage is >= methylated
+ *   3  nomod:  every replicate has a record, the smallest coverage is >= cov, every percentage is <= unmethylated
+ *   2  anymod: every other site with a record in at least one replicate (partial, disagreeing, low coverage, missing from a replicate)
+ * Integer atomics for the counters only, none in the text: two runs give identical bytes.  deepmod_amd/bslabels.py (HostEngine) states the semantics.
+ *   create         1 - 64 distinct contig names of 1 - 63 printable bytes; lengths: per contig its positions, every one known, 1 to 2^31 - 1;
+ *                  1 - 4 replicates; 1 <= cov <= 65535 (a record's coverage saturates there); 0 <= unmethylated < methylated <= 100.
+ *   add_truth_text, add_truth_records, fetch_records   the contracts of the dm_bsperf calls of the same names: grammar, line classes, lines [6],
+ *                  a flagged chunk adds nothing.
+ *   open           the open contig: its index, its reference bytes (len == the contig's length), the motif (m = 1 - 8 letters of A, C, G, T, either
+ *                  case) and the offset k of the modified base in it.  Zeroed slots, the site codes.  DM_ENOMEM, before any launch, with the bytes
+ *                  needed if the device cannot hold 8 R + 4 bytes per position.  close_contig ends it.
+ *   fill           records of the open contig (as fetch_records gave them) into the slots of `replicate`: the contract of dm_bsperf_fill, the
+ *                  duplicate key included; not after classify.
+ *   classify       the sweep, once per open; counts [2 strands][5] of this contig alone: fulmod, anymod, nomod, off_motif, sites
+ *                  without truth.  DM_EINVAL without an open contig or a second time; DM_ESTATE after a duplicate key.
+ *   fetch_classes  cls [2 strands][len] of the classified contig.
+ *   format_begin   list 1 fulmod, 2 anymod, 3 nomod: lines and bytes of its text, and the bytes of its largest tile (dm_bslabels_tile_positions()
+ *                  positions each).  A line '%s %s %d\n' (name, strand, 0-based position) per key of the class, ascending position, '+' before
+ *                  '-' at one position.  An empty list: 0 lines, 0 bytes.
+ *   format_next    the next run of whole tiles that fits `cap` bytes -> out, *got bytes; returns 1 while more follows, 0 after the last run (or
+ *                  when there is no text), < 0 on error: a cap below the next tile's bytes is DM_EINVAL, and dm_last_error names the size needed.
+ *   format_host    the line routine compiled for the host (no GPU needed): class arrays of positions first_pos .. first_pos + length - 1 (a
+ *                  strand may be NULL; first_pos + length <= 2^31 - 1) -> the bytes of the list's text; written only if out is given and cap
+ *                  holds them all.
+ *   times          ms of the parse / fill (with the site codes of open) / class (the sweep) / format kernels so far (HIP events).
+ * Every argument is checked before any launch (DM_EINVAL, dm_last_error names the fault): contig index, replicate, len, motif letters, list. */
+typedef struct dm_bslabels dm_bslabels;
+dm_bslabels* dm_bslabels_create(int device, int n_contigs, const char* const* names, const int64_t* lengths, int n_replicates, int cov, int methylated, int unmethylated);
+void dm_bslabels_destroy(dm_bslabels* h);
+int dm_bslabels_add_truth_text(dm_bslabels* h, int replicate, const char* text, int64_t n_bytes, int is_first_chunk, int64_t* lines, int64_t* n_records, int32_t* flag,
+                               int64_t* first_bad_line);
+int dm_bslabels_add_truth_records(dm_bslabels* h, int replicate, int64_t n, const uint8_t* contig, const uint8_t* strand, const int32_t* pos, const int32_t* cov,
+                                  const int32_t* pct, const int64_t* lines);
+int dm_bslabels_fetch_records(dm_bslabels* h, int32_t* pos, uint32_t* meta);
+int dm_bslabels_open(dm_bslabels* h, int contig_index, const uint8_t* seq, int64_t len, const char* motif, int m, int k);
+int dm_bslabels_fill(dm_bslabels* h, int replicate, int64_t n, const int32_t* pos, const uint32_t* meta, int64_t* dup_pos, int32_t* dup_strand);
+int dm_bslabels_classify(dm_bslabels* h, int64_t* counts);
+int dm_bslabels_fetch_classes(dm_bslabels* h, uint8_t* cls);
+int dm_bslabels_format_begin(dm_bslabels* h, int list, int64_t* n_lines, int64_t* n_bytes, int64_t* largest_tile_bytes);
+int dm_bslabels_format_next(dm_bslabels* h, char* out, int64_t cap, int64_t* got);
+int dm_bslabels_close_contig(dm_bslabels* h);
+int64_t dm_bslabels_format_host(const char* name, int list, const uint8_t* cls_plus, const uint8_t* cls_minus, int64_t first_pos, int64_t length, char* out, int64_t cap);
+int dm_bslabels_tile_positions(void);
+int dm_bslabels_times(dm_bslabels* h, double* parse_ms, double* fill_ms, double* class_ms, double* format_ms);
+
 #ifdef __cplusplus
 }
 #endif
