@@ -61,6 +61,15 @@ replicate, every replicate at coverage >= --cov), O/id.nomod.<chr>.txt (<= --unm
 (every other site of the motif that has a record in a replicate: getfeatures --posneg 1 labels a position of anymod not at all, so every site one
 cannot be sure of belongs there).  Lines are `chr strand pos` with the 0-based position, classified and formatted on one GPU; O/id_bslabels.json has the
 line and class counters (deepmod_amd/bslabels.py).  The workflow closes: bslabels -> getfeatures -> train -> detect -> bsperf.
+
+`motifs --predFolder RUNS [--control C1[,C2..]] --Ref genome.fa --Base A --outFolder O --FileID id [--chr ..] [--flank 3,3] [--cov 5] [--minPct 50]
+[--maxCtrlPct 10] [--minFrac 50] [--minSites 20] [--maxMotifs 8] [--threads T]` answers the question every command above leaves to the user: in which
+sequence contexts are the modified bases?  The *.<chr>+.<Base>.bed / *.<chr>-.<Base>.bed files below RUNS are summed as `merge` sums them, the control
+folders pooled the same way; one sweep per contig on one GPU counts, per oriented context of --flank bases around every --Base, the sites tested
+(coverage >= --cov in the sample and in the controls) and those called modified (percentage >= --minPct, and <= --maxCtrlPct in the controls).  The motifs
+are then picked from the counts by an exact integer rule (deepmod_amd/motifs.py).  O/id_motifs.txt lists them with the ready
+`--motif <label> --ModinMotif <k>` arguments of siteperf / getfeatures; O/id_motifs.json has every counter, the non-zero contexts and notes.  Hand in the
+mod_pos.* files of `detect` runs (summed files drop every position with a modified count of 0).  The threshold defaults have not been tuned on real data.
 """
 import argparse
 import os
@@ -255,7 +264,40 @@ def build_parser():
     bsl.add_argument('--methylated', type=int, default=90, help='fulmod: this percentage or more in every replicate (default 90)')
     bsl.add_argument('--unmethylated', type=int, default=0, help='nomod: this percentage or less in every replicate (default 0)')
     bsl.set_defaults(func=mBsLabels)
+    mot = sub.add_parser('motifs', parents=[com], help='de novo discovery of the modified motifs from a run and its controls on the GPU',
+                         description='Per contig: every *.<chr>-.<Base>.bed and *.<chr>+.<Base>.bed one to three levels below --predFolder (and below every '
+                                     '--control folder, pooled) is summed as merge sums them and joined with --Ref on one GPU: per oriented sequence context of '
+                                     '--flank bases around each --Base, the sites tested and the sites called modified.  The motifs are picked from those counts by '
+                                     'an integer rule: the pattern with the fewest fixed letters among those with --minSites modified sites that are --minFrac '
+                                     'percent of its tested sites, its contexts removed, and again.  Writes <outFolder>/<FileID>_motifs.txt (rank, motif, '
+                                     'ModinMotif, label, sites, modified, percent, the arguments for siteperf / getfeatures) and <outFolder>/<FileID>_motifs.json.  '
+                                     'Hand in the mod_pos.* files of detect runs.  The threshold defaults have not been tuned on real data.')
+    mot.add_argument('--predFolder', default=None, help='folder of the sample\'s runs: the BED files are searched one to three levels below it')
+    mot.add_argument('--control', default=None, help='folder(s) of control runs, separated by commas; pooled (default: none)')
+    mot.add_argument('--Ref', default=None, help='reference genome FASTA (needed: the contexts are read from it)')
+    mot.add_argument('--Base', default='A', choices=['A', 'C', 'G', 'T'], help='the modified base: names the files (default A)')
+    mot.add_argument('--chr', default=None, help='contigs, separated by commas (default: every contig of --Ref)')
+    mot.add_argument('--flank', default='3,3', help='bases upstream,downstream of the modified base in a context, 8 in all at most (default 3,3)')
+    mot.add_argument('--cov', type=int, default=5, help='least coverage of a tested site, in the sample and in the pooled controls (default 5)')
+    mot.add_argument('--minPct', type=int, default=50, help='a site is called modified at this percentage or more in the sample (default 50)')
+    mot.add_argument('--maxCtrlPct', type=int, default=10, help='and at this percentage or less in the controls (default 10)')
+    mot.add_argument('--minFrac', type=int, default=50, help='a motif: at least this percentage of its tested sites is modified (default 50)')
+    mot.add_argument('--minSites', type=int, default=20, help='a motif: at least this many modified sites (default 20)')
+    mot.add_argument('--maxMotifs', type=int, default=8, help='motifs reported at most (default 8)')
+    mot.set_defaults(func=mMotifs)
     return parser
+
+
+def mMotifs(args):
+    from deepmod_amd import motifs
+    mo = {k: getattr(args, k) for k in ('predFolder', 'Ref', 'Base', 'outFolder', 'FileID', 'flank', 'cov', 'minPct', 'maxCtrlPct', 'minFrac', 'minSites', 'maxMotifs',
+                                         'threads')}
+    mo['chr'] = [c for c in (args.chr or '').split(',') if c] or None
+    mo['control'] = [c for c in (args.control or '').split(',') if c]
+    try:
+        motifs.motifs(mo)                                # checks the options (the FASTA is read once), then refuses without a gfx950 GPU
+    except motifs.MotifsError as exc:
+        raise SystemExit('Error: %s' % exc)
 
 
 def mBsLabels(args):

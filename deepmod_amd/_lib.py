@@ -234,6 +234,14 @@ SIGNATURES = [
     ("dm_bslabels_format_host", _i64, [_c.c_char_p, _c.c_int, _vp, _vp, _i64, _i64, _vp, _i64]),
     ("dm_bslabels_tile_positions", _c.c_int, []),
     ("dm_bslabels_times", _c.c_int, [_vp, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
+    ("dm_motifs_create", _vp, [_c.c_int, _c.c_int, _c.c_int, _c.c_char, _c.c_int, _c.c_int, _c.c_int]),
+    ("dm_motifs_destroy", None, [_vp]),
+    ("dm_motifs_count", _c.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("dm_motifs_fetch", _c.c_int, [_vp, _vp]),
+    ("dm_motifs_reset", _c.c_int, [_vp]),
+    ("dm_motifs_tile_positions", _c.c_int, []),
+    ("dm_motifs_times", _c.c_int, [_vp, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
+    ("dm_motifs_count_host", _c.c_int, [_c.c_int, _c.c_int, _c.c_char, _c.c_int, _c.c_int, _c.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 ]
 
 

@@ -1,6 +1,6 @@
 // offline.hip — libdeepmod_hip.so, training and the offline commands: the BiLSTM trainer, the cluster trainer, getfeatures (the .xy writer), the
 // line splitter of every text parsed on the device (textlines.hip.inc), predict (the .xy parser), the resident gather of train --resident,
-// siteperf, merge, bsperf, bslabels (their line grammars and routines: siteperf.inc, bedmerge.inc, bsperf.inc, bslabels.inc on bedline.inc).  Interface to the other
+// siteperf, merge, bsperf, bslabels (their line grammars and routines: siteperf.inc, bedmerge.inc, bsperf.inc, bslabels.inc on bedline.inc), motifs (motifs.inc).  Interface to the other
 // units: host.h.
 #include "train.hip.inc"
 #include "cluster_train.hip.inc"
@@ -13,3 +13,5 @@
 #include "bedmerge.hip.inc"
 #include "bsperf.hip.inc"
 #include "bslabels.hip.inc"
+#include "motifs.hip.inc"
+#include "motifs.inc"

@@ -897,6 +897,40 @@ int64_t dm_bslabels_format_host(const char* name, int list, const uint8_t* cls_p
 int dm_bslabels_tile_positions(void);
 int dm_bslabels_times(dm_bslabels* h, double* parse_ms, double* fill_ms, double* class_ms, double* format_ms);
 
+/* --------------------------------------------------------------------------- motifs -- */
+/* De novo modified-motif discovery, the counting half (csrc/motifs.hip.inc, motifs.inc): one sweep over a contig joins the sample's
+ * and optionally the pooled controls' tables with the contig's bytes and counts, per oriented sequence context of `up` bases upstream and `down`
+ * bases downstream of `base`, the keys (strand, position) that were tested and those called modified.  Per key, the first rule that applies:
+ *   1  the oriented letter (seq[p] on '+', its complement on '-') is not `base`: off_base if the sample's coverage is > 0, else ignored
+ *   2  an offset of the context ('+': seq[p + j]; '-': the complement of seq[p - j]) is outside the contig or none of A, C, G, T (upper case; the
+ *      bytes are taken as handed over): edge
+ *   3  sample coverage < cov: shallow             4  controls given and their coverage < cov: no_control
+ *   5  tested; modified too if 100 mod / cov (integer division) >= min_pct and (no controls or 100 cmod / ccov <= max_ctrl_pct)
+ * The context index has its most significant base-4 digit at offset -up, A < C < G < T.  Everything is an integer sum in 64 bits: exact for
+ * coverages and counts up to 2^31 - 1 and for any number of contigs.  deepmod_amd/motifs.py (HostEngine) states the semantics.
+ *   create      0 <= up, down, up + down <= 8; base one of A, C, G, T; cov >= 1; 0 <= min_pct, max_ctrl_pct <= 100.  A zeroed histogram.
+ *   count       one contig: len bytes (1 to 2^31 - 1), the sample's '+' and '-' tables and the controls' (both or neither), every table on the
+ *               handle's device and of exactly len positions.  hist += ; counters [2 strands][5] (tested, modified, shallow, no_control, edge)
+ *               and off_base [2] are those of this contig alone.
+ *   fetch       hist int64 [4^(up+down)][2] (tested, modified), summed over the contigs since create / reset.      reset   zeroes it.
+ *   count_host  the same sweep compiled for the host (no GPU needed), on plain arrays: len >= 0, the four control arrays all given or all null;
+ *               hist is added to, counters and off_base are set.
+ *   times       ms of the uploads of the contigs' bytes / of the sweeps so far (HIP events).
+ * Every argument is checked before any launch (DM_EINVAL, dm_last_error names the fault): null handles, a table on another device or of another
+ * length, exactly one control table, options out of range. */
+typedef struct dm_motifs dm_motifs;
+dm_motifs* dm_motifs_create(int device, int up, int down, char base, int cov, int min_pct, int max_ctrl_pct);
+void dm_motifs_destroy(dm_motifs* h);
+int dm_motifs_count(dm_motifs* h, const uint8_t* seq, int64_t len, dm_summary* plus, dm_summary* minus, dm_summary* ctrl_plus, dm_summary* ctrl_minus, int64_t* counters,
+                    int64_t* off_base);
+int dm_motifs_fetch(dm_motifs* h, int64_t* hist);
+int dm_motifs_reset(dm_motifs* h);
+int dm_motifs_tile_positions(void);
+int dm_motifs_times(dm_motifs* h, double* upload_ms, double* count_ms);
+int dm_motifs_count_host(int up, int down, char base, int cov, int min_pct, int max_ctrl_pct, const uint8_t* seq, int64_t len, const int32_t* cov_plus,
+                         const int32_t* mod_plus, const int32_t* cov_minus, const int32_t* mod_minus, const int32_t* ctrl_cov_plus, const int32_t* ctrl_mod_plus,
+                         const int32_t* ctrl_cov_minus, const int32_t* ctrl_mod_minus, int64_t* hist, int64_t* counters, int64_t* off_base);
+
 #ifdef __cplusplus
 }
 #endif
