@@ -4,6 +4,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import sys
 from typing import Optional
 
 # Multi-process GPU work on this stack (RCCL communicators between the ranks of a node) needs the ROCr runtime in its dmabuf IPC mode: the
@@ -292,3 +293,36 @@ def pci_bus_id(device: int) -> str:
 
 def last_error() -> str:
     return load().dm_last_error().decode("utf-8", "replace")
+
+
+class Handle:
+    """A handle of the C ABI whose entry points are PREFIX_create / PREFIX_destroy / PREFIX_times (N_TIMES doubles): created or DeepModHipError with
+    the library's message; close() may be called again and is what __del__ does."""
+    PREFIX = None
+    N_TIMES = 0
+
+    def _create(self, *args):
+        self._ct, self._libmod, self._lib = ctypes, sys.modules[__name__], load()
+        self._h = getattr(self._lib, self.PREFIX + "_create")(*args)
+        if not self._h:
+            raise DeepModHipError(self.PREFIX + "_create: " + last_error())
+
+    def _fn(self, name: str):
+        return getattr(self._lib, "%s_%s" % (self.PREFIX, name))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._fn("destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def times(self):
+        """ms of the handle's kernels so far, one figure per phase."""
+        v = [ctypes.c_double(0.0) for _ in range(self.N_TIMES)]
+        check(self._fn("times")(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)

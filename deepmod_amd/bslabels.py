@@ -21,7 +21,7 @@ from typing import Dict, List, Tuple
 
 import numpy as np
 
-from . import bsperf, merge, siteperf
+from . import _lib, bsperf, merge, siteperf
 
 MAX_REPLICATES, MAX_CONTIGS, MAX_NAME, MAX_COV, MAX_MOTIF = bsperf.MAX_REPLICATES, bsperf.MAX_CONTIGS, bsperf.MAX_NAME, bsperf.MAX_COV, 8
 MAX_LENGTH = bsperf.MAX_LENGTH
@@ -164,7 +164,6 @@ def format_host_routine(name: str, which: int, cls_plus, cls_minus, first_pos: i
     """The device's line routine compiled for the host (dm_bslabels_format_host; no GPU needed) -> (bytes of the text, the buffer of cap bytes
     it was handed, which was filled with 0xa5; cap None: a buffer of exactly the size).  A write behind the buffer is an error."""
     import ctypes
-    from . import _lib
     lib = _lib.load()
     arrs = [None if a is None else np.ascontiguousarray(a, np.uint8) for a in (cls_plus, cls_minus)]
     n = len(arrs[0] if arrs[0] is not None else arrs[1])
@@ -184,64 +183,21 @@ def format_host_routine(name: str, which: int, cls_plus, cls_minus, first_pos: i
 
 
 def tile_positions() -> int:
-    from . import _lib
     return _lib.load().dm_bslabels_tile_positions()
 
 
-class DeviceEngine:
-    """The same on one GPU (dm_bslabels_* of the C ABI).  add_truth_text / add_truth_records / records are what bsperf.read_truth_device drives."""
+class DeviceEngine(bsperf.DeviceTruth, _lib.Handle):
+    """The same on one GPU (dm_bslabels_* of the C ABI).  add_truth_text / add_truth_records / records are what bsperf.read_truth_device drives.
+    times(): ms of the parse / fill / class / format kernels so far."""
+    PREFIX, N_TIMES, ERROR = 'dm_bslabels', 4, BsLabelsError
 
     def __init__(self, names, lengths, replicates: int = 2, cov: int = 5, methylated: int = 90, unmethylated: int = 0, device: int = 0):
-        import ctypes
-        from . import _lib
-        self._ct, self._libmod = ctypes, _lib
         self.names = list(names)
         self.limit = _check_engine_options(self.names, lengths, replicates, cov, methylated, unmethylated)
         self.R = int(replicates)
-        self._lib = _lib.load()
         arr, lens = bsperf._names_args(self.names, self.limit)
-        self._h = self._lib.dm_bslabels_create(device, len(self.names), arr, lens.ctypes.data, self.R, int(cov), int(methylated), int(unmethylated))
-        if not self._h:
-            raise _lib.DeepModHipError('dm_bslabels_create: ' + _lib.last_error())
+        self._create(device, len(self.names), arr, lens.ctypes.data, self.R, int(cov), int(methylated), int(unmethylated))
         self._n, self.length, self.name = 0, 0, None
-
-    def close(self):
-        if getattr(self, '_h', None):
-            self._lib.dm_bslabels_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def add_truth_text(self, replicate: int, text: bytes, first_chunk: bool):
-        """-> (lines int64 [6], records, flag, first bad line (1-based, -1: none)); a flagged chunk adds nothing."""
-        ct = self._ct
-        lines = np.zeros(len(LINE_KEYS), np.int64)
-        n, flag, bad = ct.c_int64(0), ct.c_int32(0), ct.c_int64(-1)
-        self._n = 0
-        self._libmod.check(self._lib.dm_bslabels_add_truth_text(self._h, replicate, ct.c_char_p(text), len(text), int(bool(first_chunk)), lines.ctypes.data, ct.byref(n),
-                                                                ct.byref(flag), ct.byref(bad)))
-        self._n = n.value
-        return lines, n.value, flag.value, bad.value
-
-    def add_truth_records(self, replicate: int, pos, meta, lines):
-        pos, lines = np.ascontiguousarray(pos, np.int32), np.ascontiguousarray(lines, np.int64)
-        contig, strand, cov, pct = bsperf.unpack_meta(meta)
-        cols = [np.ascontiguousarray(contig, np.uint8), np.ascontiguousarray(strand, np.uint8), pos, np.ascontiguousarray(cov, np.int32), np.ascontiguousarray(pct, np.int32)]
-        if len({len(a) for a in cols}) != 1 or len(lines) != len(LINE_KEYS):
-            raise BsLabelsError('bslabels: record arrays of different lengths')
-        self._n = 0
-        self._libmod.check(self._lib.dm_bslabels_add_truth_records(self._h, replicate, len(pos), *[a.ctypes.data for a in cols], lines.ctypes.data))
-        self._n = len(pos)
-
-    def records(self):
-        """(pos, meta) of the last add_truth_text / add_truth_records as they lie on the device."""
-        pos, meta = np.zeros(self._n, np.int32), np.zeros(self._n, np.uint32)
-        self._libmod.check(self._lib.dm_bslabels_fetch_records(self._h, pos.ctypes.data, meta.ctypes.data))
-        return pos, meta
 
     def open(self, contig: int, seq, motif: str, k: int = 0):
         seq = np.frombuffer(bytes(seq), np.uint8) if not isinstance(seq, np.ndarray) else np.ascontiguousarray(seq, np.uint8)
@@ -252,18 +208,6 @@ class DeviceEngine:
     def close_contig(self):
         self.length = 0
         self._libmod.check(self._lib.dm_bslabels_close_contig(self._h))
-
-    def fill(self, replicate: int, pos, meta):
-        ct = self._ct
-        pos, meta = np.ascontiguousarray(pos, np.int32), np.ascontiguousarray(meta, np.uint32)
-        if len(pos) != len(meta):
-            raise BsLabelsError('bslabels: record arrays of different lengths')
-        dup, strand = ct.c_int64(-1), ct.c_int32(-1)
-        self._n = 0
-        rc = self._lib.dm_bslabels_fill(self._h, int(replicate), len(pos), pos.ctypes.data, meta.ctypes.data, ct.byref(dup), ct.byref(strand))
-        if dup.value >= 0:
-            raise BsLabelsError('bslabels: replicate %d holds position %d of strand %s twice' % (replicate, dup.value, '+-'[strand.value & 1]))
-        self._libmod.check(rc)
 
     def classify(self) -> np.ndarray:
         counts = np.zeros((2, len(COUNT_KEYS)), np.int64)
@@ -302,13 +246,6 @@ class DeviceEngine:
             more, text = self.format_next(cap, buf)
             if text:
                 yield text
-
-    def times(self) -> Tuple[float, float, float, float]:
-        """ms of the parse / fill / class / format kernels so far."""
-        ct = self._ct
-        v = [ct.c_double(0.0) for _ in range(4)]
-        self._libmod.check(self._lib.dm_bslabels_times(self._h, *[ct.byref(x) for x in v]))
-        return tuple(x.value for x in v)
 
 
 def check_options(mo: Dict[str, object]):
@@ -362,7 +299,6 @@ def bslabels(mo: Dict[str, object], device: int = 0, chunk_bytes: int = CHUNK_BY
     chrkeys, truth, seqs, motif, k = check_options(mo)
     base, fileid, out_folder = str(mo.get('Base') or 'C'), str(mo.get('FileID') or 'mod'), str(mo['outFolder'])
     cov, methylated, unmethylated = int(mo.get('cov', 5)), int(mo.get('methylated', 90)), int(mo.get('unmethylated', 0))
-    from . import _lib
     if _lib.load().dm_device_count() < 1:
         raise BsLabelsError('no gfx950 GPU visible (this build has no CPU path)')
     lengths = [len(seqs[ck]) for ck in chrkeys]

@@ -19,7 +19,7 @@ from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
 
-from . import merge, siteperf
+from . import _lib, merge, siteperf
 
 NPCT, MAX_THRESHOLDS, MAX_REPLICATES, MAX_CONTIGS, MAX_NAME, MAX_COV, SHORT_LINE = 101, 8, 4, 64, 63, 65535, 20
 MAX_LENGTH = merge.MAX_LENGTH
@@ -108,7 +108,6 @@ def _names_args(names: Sequence[str], lengths):
 def parse_device_grammar(text: bytes, names: Sequence[str], lengths=None, first_chunk: bool = True):
     """The device's line routine compiled for the host (no GPU needed) -> ((pos, meta), lines int64 [6], flag, first bad line)."""
     import ctypes
-    from . import _lib
     lib = _lib.load()
     arr, lens = _names_args(names, lengths)
     flag, bad = ctypes.c_int32(0), ctypes.c_int64(-1)
@@ -124,7 +123,6 @@ def parse_device_grammar(text: bytes, names: Sequence[str], lengths=None, first_
 
 
 def tile_bytes() -> int:
-    from . import _lib
     return _lib.load().dm_bsperf_tile_bytes()
 
 
@@ -269,35 +267,13 @@ class HostEngine:
                 'below_threshold': self.below_threshold.copy(), 'lines': self.lines.copy()}
 
 
-class DeviceEngine:
-    """The same counting on one GPU (dm_bsperf_* of the C ABI); add_truth_text is the device parser.  open takes the two summary.PositionSummary
-    tables of merge.DeviceMerge."""
+class DeviceTruth:
+    """The truth side of a device handle (bsk::Truth of csrc/bsperf.hip.inc: one copy of the code behind PREFIX_add_truth_text / _add_truth_records /
+    _fetch_records / _fill), for a _lib.Handle whose command raises ERROR; read_truth_device drives the first three."""
+    ERROR = None
 
-    def __init__(self, names, thresholds=(1, 5, 10), replicates: int = 2, methylated: int = 90, unmethylated: int = 0, pred_cov: int = 1, lengths=None, device: int = 0):
-        import ctypes
-        from . import _lib
-        self._ct, self._libmod = ctypes, _lib
-        self.names = list(names)
-        self.thresholds = _check_engine_options(self.names, thresholds, replicates, methylated, unmethylated, pred_cov)
-        self.R = int(replicates)
-        self._lib = _lib.load()
-        arr, lens = _names_args(self.names, lengths)
-        t = np.asarray(self.thresholds, np.int32)
-        self._h = self._lib.dm_bsperf_create(device, len(self.names), arr, lens.ctypes.data, len(t), t.ctypes.data, self.R, int(methylated), int(unmethylated), int(pred_cov))
-        if not self._h:
-            raise _lib.DeepModHipError('dm_bsperf_create: ' + _lib.last_error())
-        self._n = 0
-
-    def close(self):
-        if getattr(self, '_h', None):
-            self._lib.dm_bsperf_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _refuse(self, what: str):
+        return self.ERROR('%s: %s' % (self.PREFIX[3:], what))
 
     def add_truth_text(self, replicate: int, text: bytes, first_chunk: bool):
         """-> (lines int64 [6], records, flag, first bad line (1-based, -1: none)); a flagged chunk adds nothing."""
@@ -305,8 +281,8 @@ class DeviceEngine:
         lines = np.zeros(len(LINE_KEYS), np.int64)
         n, flag, bad = ct.c_int64(0), ct.c_int32(0), ct.c_int64(-1)
         self._n = 0
-        self._libmod.check(self._lib.dm_bsperf_add_truth_text(self._h, replicate, ct.c_char_p(text), len(text), int(bool(first_chunk)), lines.ctypes.data, ct.byref(n),
-                                                              ct.byref(flag), ct.byref(bad)))
+        self._libmod.check(self._fn('add_truth_text')(self._h, replicate, ct.c_char_p(text), len(text), int(bool(first_chunk)), lines.ctypes.data, ct.byref(n),
+                                                      ct.byref(flag), ct.byref(bad)))
         self._n = n.value
         return lines, n.value, flag.value, bad.value
 
@@ -315,34 +291,49 @@ class DeviceEngine:
         contig, strand, cov, pct = unpack_meta(meta)
         cols = [np.ascontiguousarray(contig, np.uint8), np.ascontiguousarray(strand, np.uint8), pos, np.ascontiguousarray(cov, np.int32), np.ascontiguousarray(pct, np.int32)]
         if len({len(a) for a in cols}) != 1 or len(lines) != len(LINE_KEYS):
-            raise BsPerfError('bsperf: record arrays of different lengths')
+            raise self._refuse('record arrays of different lengths')
         self._n = 0
-        self._libmod.check(self._lib.dm_bsperf_add_truth_records(self._h, replicate, len(pos), *[a.ctypes.data for a in cols], lines.ctypes.data))
+        self._libmod.check(self._fn('add_truth_records')(self._h, replicate, len(pos), *[a.ctypes.data for a in cols], lines.ctypes.data))
         self._n = len(pos)
 
     def records(self):
         """(pos, meta) of the last add_truth_text / add_truth_records as they lie on the device."""
         pos, meta = np.zeros(self._n, np.int32), np.zeros(self._n, np.uint32)
-        self._libmod.check(self._lib.dm_bsperf_fetch_records(self._h, pos.ctypes.data, meta.ctypes.data))
+        self._libmod.check(self._fn('fetch_records')(self._h, pos.ctypes.data, meta.ctypes.data))
         return pos, meta
+
+    def fill(self, replicate: int, pos, meta):
+        ct = self._ct
+        pos, meta = np.ascontiguousarray(pos, np.int32), np.ascontiguousarray(meta, np.uint32)
+        if len(pos) != len(meta):
+            raise self._refuse('record arrays of different lengths')
+        dup, strand = ct.c_int64(-1), ct.c_int32(-1)
+        self._n = 0
+        rc = self._fn('fill')(self._h, int(replicate), len(pos), pos.ctypes.data, meta.ctypes.data, ct.byref(dup), ct.byref(strand))
+        if dup.value >= 0:
+            raise self._refuse('replicate %d holds position %d of strand %s twice' % (replicate, dup.value, '+-'[strand.value & 1]))
+        self._libmod.check(rc)
+
+
+class DeviceEngine(DeviceTruth, _lib.Handle):
+    """The same counting on one GPU (dm_bsperf_* of the C ABI); add_truth_text is the device parser.  open takes the two summary.PositionSummary
+    tables of merge.DeviceMerge.  times(): ms of the parse / fill / count kernels so far."""
+    PREFIX, N_TIMES, ERROR = 'dm_bsperf', 3, BsPerfError
+
+    def __init__(self, names, thresholds=(1, 5, 10), replicates: int = 2, methylated: int = 90, unmethylated: int = 0, pred_cov: int = 1, lengths=None, device: int = 0):
+        self.names = list(names)
+        self.thresholds = _check_engine_options(self.names, thresholds, replicates, methylated, unmethylated, pred_cov)
+        self.R = int(replicates)
+        arr, lens = _names_args(self.names, lengths)
+        t = np.asarray(self.thresholds, np.int32)
+        self._create(device, len(self.names), arr, lens.ctypes.data, len(t), t.ctypes.data, self.R, int(methylated), int(unmethylated), int(pred_cov))
+        self._n = 0
 
     def open(self, contig: int, plus, minus):
         self._libmod.check(self._lib.dm_bsperf_open(self._h, int(contig), plus._h, minus._h))
 
     def close_contig(self):
         self._libmod.check(self._lib.dm_bsperf_close_contig(self._h))
-
-    def fill(self, replicate: int, pos, meta):
-        ct = self._ct
-        pos, meta = np.ascontiguousarray(pos, np.int32), np.ascontiguousarray(meta, np.uint32)
-        if len(pos) != len(meta):
-            raise BsPerfError('bsperf: record arrays of different lengths')
-        dup, strand = ct.c_int64(-1), ct.c_int32(-1)
-        self._n = 0
-        rc = self._lib.dm_bsperf_fill(self._h, int(replicate), len(pos), pos.ctypes.data, meta.ctypes.data, ct.byref(dup), ct.byref(strand))
-        if dup.value >= 0:
-            raise BsPerfError('bsperf: replicate %d holds position %d of strand %s twice' % (replicate, dup.value, '+-'[strand.value & 1]))
-        self._libmod.check(rc)
 
     def count(self):
         self._libmod.check(self._lib.dm_bsperf_count(self._h))
@@ -359,13 +350,6 @@ class DeviceEngine:
                'untruthed': np.zeros(2, np.int64), 'below_threshold': np.zeros(2, np.int64), 'lines': np.zeros(len(LINE_KEYS), np.int64)}
         self._libmod.check(self._lib.dm_bsperf_fetch(self._h, *[out[k].ctypes.data for k in ('hist', 'unpredicted', 'moments', 'untruthed', 'below_threshold', 'lines')]))
         return out
-
-    def times(self) -> Tuple[float, float, float]:
-        """ms of the parse / fill / count kernels so far."""
-        ct = self._ct
-        a, b, c = ct.c_double(0.0), ct.c_double(0.0), ct.c_double(0.0)
-        self._libmod.check(self._lib.dm_bsperf_times(self._h, ct.byref(a), ct.byref(b), ct.byref(c)))
-        return a.value, b.value, c.value
 
 
 def correlation(mom, replicates: int) -> Tuple[float, float]:

@@ -3,9 +3,8 @@
 //   readbed2 (:37-46)    bm_parse_kernel    one line per lane (bmk::parse_line, bedmerge.inc) -> position, strand, coverage, modified, a status byte;
 //                                           the largest position and coverage of the text (one integer atomic max per wave)
 //   mergeMod (:48-54)    bm_add_kernel      a record -> int32 atomic adds into cov and mod of its strand's table, +1 into touch
-//   save_mod (:56-66)    bm_length_kernel   a block per tile of bmk::TILE_POS positions: bytes and lines of the tile (bmk::emit_position, counting sink)
-//                        the 64-bit scan over the tiles
-//                        bm_write_kernel    the same routine with a writing sink at tile offset + block scan of the lanes' bytes
+//   save_mod (:56-66)    the tiled writer of textout.hip.inc (txo::Run) on bmk::Emitter: the lines of a position from the four sum tables; a tile
+//                        with a sum outside 0 <= mod <= cov is counted, and format_begin refuses the contig
 // The text of a file is split into lines by textlines.hip.inc (xlk::split).  The grammar and the line are stated in bedmerge.inc; a text with a line outside the grammar adds nothing (first line reported), and the caller hands its own parse over through
 // dm_bedmerge_add_records.
 // Exactness and determinism.  Every sum is an int32 integer: additions commute, so the order the atomics land in does not matter.  The guard of
@@ -20,12 +19,12 @@
 #include "blockscan.hip.inc"
 #include "xyrows.hip.inc"
 #include "textlines.hip.inc"
+#include "textout.hip.inc"
 #include "bedmerge.inc"
 
 namespace bmk {
 
 constexpr int THREADS = 256;
-constexpr int POS_PER_LANE = TILE_POS / THREADS;
 constexpr int MAX_BLOCKS = 1024;
 enum { S_MAXPOS, S_MAXCOV, S_BADSUM, N_STAT };
 
@@ -73,64 +72,12 @@ __global__ __launch_bounds__(THREADS) void bm_add_kernel(const int* __restrict__
     }
 }
 
-// the bytes and lines of the lane's POS_PER_LANE consecutive positions of tile blockIdx.x; bad: a sum outside 0 <= mod <= cov
-__device__ inline void lane_count(const Name& name, const char base, const int* __restrict__ plus, const int* __restrict__ minus, const long long length, long long& bytes,
-                                  int& lines, int& bad) {
-    const long long q0 = (long long)blockIdx.x * TILE_POS + (long long)threadIdx.x * POS_PER_LANE;
-    CountSink s;
-    lines = 0;
-    bad = 0;
-    for (int k = 0; k < POS_PER_LANE; ++k) {
-        const long long q = q0 + k;
-        if (q >= length) break;
-        if (!sum_ok(plus[length + q], plus[2 * length + q]) || !sum_ok(minus[length + q], minus[2 * length + q])) {
-            bad = 1;
-            continue;
-        }
-        lines += emit_position(s, name, base, q, q, plus + length, plus + 2 * length, minus + length, minus + 2 * length);
-    }
-    bytes = s.n;
-}
-
-__global__ __launch_bounds__(THREADS) void bm_length_kernel(const Name name, const char base, const int* __restrict__ plus, const int* __restrict__ minus, const long long length,
-                                                           long long* __restrict__ tile_bytes, long long* __restrict__ tile_lines, unsigned long long* __restrict__ stat) {
-    __shared__ long long wave_total[THREADS / 64];
-    long long bytes, total_bytes, total_lines;
-    int lines, bad;
-    lane_count(name, base, plus, minus, length, bytes, lines, bad);
-    (void)csites::block_exclusive_scan<THREADS>(bytes, wave_total, total_bytes);
-    (void)csites::block_exclusive_scan<THREADS>((long long)lines, wave_total, total_lines);
-    bad = __syncthreads_or(bad);
-    if (threadIdx.x == 0) {
-        tile_bytes[blockIdx.x] = total_bytes;
-        tile_lines[blockIdx.x] = total_lines;
-        if (bad) atomicAdd(stat + S_BADSUM, 1ull);
-    }
-}
-
-// tiles first_tile .. of the grid: their text at out + (tile_off[tile] - tile_off[first_tile])
-__global__ __launch_bounds__(THREADS) void bm_write_kernel(const Name name, const char base, const int* __restrict__ plus, const int* __restrict__ minus, const long long length,
-                                                          const long long* __restrict__ tile_off, const long long first_tile, char* __restrict__ out) {
-    __shared__ long long wave_total[THREADS / 64];
-    const long long tile = first_tile + blockIdx.x;
-    const long long q0 = tile * TILE_POS + (long long)threadIdx.x * POS_PER_LANE;
-    CountSink c;
-    for (int k = 0; k < POS_PER_LANE; ++k)
-        if (q0 + k < length) emit_position(c, name, base, q0 + k, q0 + k, plus + length, plus + 2 * length, minus + length, minus + 2 * length);
-    long long total;
-    const long long ex = csites::block_exclusive_scan<THREADS>(c.n, wave_total, total);
-    if (c.n == 0 || ex + c.n > tile_off[tile + 1] - tile_off[tile]) return;      // (never past the counted length, whatever became of the tables since)
-    WriteSink w{out + (tile_off[tile] - tile_off[first_tile]) + ex};
-    for (int k = 0; k < POS_PER_LANE; ++k)
-        if (q0 + k < length) emit_position(w, name, base, q0 + k, q0 + k, plus + length, plus + 2 * length, minus + length, minus + 2 * length);
-}
-
 }  // namespace bmk
 
 struct dm_bedmerge {
     dm_xyrows* xy = nullptr;                            // stream, the scan and its block sums
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // parse, add, format: begin / end
-    enum { POS = xlk::N_SPLIT, COV, MOD, STRAND, STAT, TBYTES, TLINES, FTEXT, N_BUF };
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};          // parse, add: begin / end
+    enum { POS = xlk::N_SPLIT, COV, MOD, STRAND, STAT, N_BUF };
     DevBufs<N_BUF> b{"dm_bedmerge"};
     dm_summary *plus = nullptr, *minus = nullptr;       // the open contig's tables (null: none), the caller's
     bool fixed = false;                                 // the table length is the contig's: a line beyond it is outside the grammar
@@ -138,16 +85,22 @@ struct dm_bedmerge {
     int64_t n_records = 0;                              // records on the device, of the last add_text / add_records
     int64_t cov_bound = 0;                              // of the open contig: the sum of the largest coverages of its texts
     int64_t lines_seen = 0;
-    // the format in progress
-    std::vector<long long> tile_off;                    // [tiles + 1]: the first text byte of every tile (empty: no format begun)
-    int64_t next_tile = 0, format_length = 0;
+    txo::Run text;                                      // the format in progress, of tables of format_length positions
+    int64_t format_length = 0;
     char format_base = 0;
-    double parse_ms = 0.0, add_ms = 0.0, format_ms = 0.0;
+    double parse_ms = 0.0, add_ms = 0.0;
 };
 
 namespace bmk {
 
 constexpr int64_t MAX_RECORDS = 0x7fffffffLL;
+
+// the lines of the open contig's tables of `length` positions, as the tables lie now: read for every call, a table that grew has moved
+Emitter emitter(const dm_bedmerge* h, const char base, const int64_t length) {
+    const int* p = static_cast<const int*>(dm_summary_device_ptr(h->plus));
+    const int* m = static_cast<const int*>(dm_summary_device_ptr(h->minus));
+    return {h->name, base, p + length, p + 2 * length, m + length, m + 2 * length, h->b.ptr<unsigned long long>(dm_bedmerge::STAT) + S_BADSUM};
+}
 
 int record_buffers(dm_bedmerge* h, int64_t n) {
     using B = dm_bedmerge;
@@ -186,7 +139,7 @@ int add_device_records(dm_bedmerge* h, int64_t n, int64_t max_pos, int64_t max_c
     if ((rc = add_time(h->ev[2], h->ev[3], h->add_ms)) != DM_OK) return rc;
     h->cov_bound += max_cov;
     h->lines_seen += n;
-    h->tile_off.clear();                                              // a format begun before this add is over
+    h->text.clear();                                                  // a format begun before this add is over
     return DM_OK;
 }
 
@@ -194,7 +147,7 @@ int add_device_records(dm_bedmerge* h, int64_t n, int64_t max_pos, int64_t max_c
 
 extern "C" {
 
-int dm_bedmerge_tile_positions(void) { return bmk::TILE_POS; }
+int dm_bedmerge_tile_positions(void) { return txo::TILE_POS; }
 
 void dm_bedmerge_destroy(dm_bedmerge* h) {
     if (!h) return;
@@ -203,6 +156,7 @@ void dm_bedmerge_destroy(dm_bedmerge* h) {
         (void)hipStreamSynchronize(h->xy->stream);
     }
     h->b.release();
+    h->text.release();
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
     dm_xy_destroy(h->xy);
@@ -214,7 +168,7 @@ dm_bedmerge* dm_bedmerge_create(int device) {
     if (!xy) return nullptr;
     dm_bedmerge* h = new dm_bedmerge;
     h->xy = xy;
-    bool ok = true;
+    bool ok = h->text.init("dm_bedmerge");
     for (hipEvent_t& e : h->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
     ok = ok && h->b.ensure(dm_bedmerge::STAT, bmk::N_STAT * 8) == DM_OK;
     if (!ok) {
@@ -229,7 +183,7 @@ dm_bedmerge* dm_bedmerge_create(int device) {
 int dm_bedmerge_open(dm_bedmerge* h, dm_summary* plus, dm_summary* minus, const char* contig_name, int fixed_length) {
     if (!h) return fail(DM_EINVAL, "null handle");
     h->plus = h->minus = nullptr;
-    h->tile_off.clear();
+    h->text.clear();
     h->n_records = 0;
     if (!plus || !minus || plus == minus) return fail(DM_EINVAL, "dm_bedmerge_open: two tables, one per strand");
     if (plus->device != h->xy->device || minus->device != h->xy->device) return fail(DM_EINVAL, "dm_bedmerge_open: the tables are on another device than the handle (%d)", h->xy->device);
@@ -354,9 +308,8 @@ int dm_bedmerge_fetch_records(dm_bedmerge* h, int32_t* pos, uint8_t* strand, int
 }
 
 int dm_bedmerge_format_begin(dm_bedmerge* h, char base, int64_t* n_lines, int64_t* n_bytes, int64_t* largest_tile_bytes) {
-    using B = dm_bedmerge;
     if (!h) return fail(DM_EINVAL, "null handle");
-    h->tile_off.clear();
+    h->text.clear();
     if (n_lines) *n_lines = 0;
     if (n_bytes) *n_bytes = 0;
     if (largest_tile_bytes) *largest_tile_bytes = 0;
@@ -368,91 +321,36 @@ int dm_bedmerge_format_begin(dm_bedmerge* h, char base, int64_t* n_lines, int64_
     const int64_t length = dm_summary_length(h->plus);
     if (length != dm_summary_length(h->minus) || length < 1 || length > bmk::MAX_LENGTH)
         return fail(DM_ESTATE, "dm_bedmerge_format_begin: tables of %lld and %lld positions", (long long)length, (long long)dm_summary_length(h->minus));
-    const int64_t tiles = (length + bmk::TILE_POS - 1) / bmk::TILE_POS;
-    if ((rc = h->b.ensure(B::TBYTES, size_t(tiles + 1) * 8)) != DM_OK || (rc = h->b.ensure(B::TLINES, size_t(tiles + 1) * 8)) != DM_OK) return rc;
-    hipStream_t s = h->xy->stream;
-    long long* d_bytes = h->b.ptr<long long>(B::TBYTES);
-    long long* d_lines = h->b.ptr<long long>(B::TLINES);
-    unsigned long long* d_stat = h->b.ptr<unsigned long long>(B::STAT);
-    HIP_TRY(hipMemsetAsync(d_stat + bmk::S_BADSUM, 0, 8, s));
-    HIP_TRY(hipEventRecord(h->ev[4], s));
-    hipLaunchKernelGGL(bmk::bm_length_kernel, dim3(unsigned(tiles)), dim3(bmk::THREADS), 0, s, h->name, base, static_cast<const int*>(dm_summary_device_ptr(h->plus)),
-                       static_cast<const int*>(dm_summary_device_ptr(h->minus)), (long long)length, d_bytes, d_lines, d_stat);
-    HIP_TRY(hipGetLastError());
-    if ((rc = xyk::scan_in_place(h->xy, d_bytes, tiles)) != DM_OK || (rc = xyk::scan_in_place(h->xy, d_lines, tiles)) != DM_OK) return rc;
-    HIP_TRY(hipEventRecord(h->ev[5], s));
-    std::vector<long long> off(size_t(tiles) + 1);
-    long long lines = 0;
-    unsigned long long bad = 0;
-    HIP_TRY(hipMemcpyAsync(off.data(), d_bytes, off.size() * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&lines, d_lines + tiles, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&bad, d_stat + bmk::S_BADSUM, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if ((rc = add_time(h->ev[4], h->ev[5], h->format_ms)) != DM_OK) return rc;
-    if (bad) return fail(DM_EINVAL, "dm_bedmerge_format_begin: the sums of %llu tiles left 0 <= modified <= coverage (int32 overflow through repeated keys)", bad);
-    long long largest = 0;
-    for (int64_t t = 0; t < tiles; ++t) {
-        if (off[t + 1] < off[t]) return fail(DM_ESTATE, "dm_bedmerge_format_begin: descending tile offsets");
-        largest = std::max(largest, off[t + 1] - off[t]);
+    HIP_TRY(hipMemsetAsync(h->b.ptr<unsigned long long>(dm_bedmerge::STAT) + bmk::S_BADSUM, 0, 8, h->xy->stream));
+    txo::Totals t;
+    if ((rc = h->text.begin(h->xy, bmk::emitter(h, base, length), length, "dm_bedmerge_format_begin", t)) != DM_OK) return rc;
+    if (t.bad_tiles) {
+        h->text.clear();
+        return fail(DM_EINVAL, "dm_bedmerge_format_begin: the sums of %llu tiles left 0 <= modified <= coverage (int32 overflow through repeated keys)", t.bad_tiles);
     }
-    h->tile_off.swap(off);
-    h->next_tile = 0;
     h->format_length = length;
     h->format_base = base;
-    if (n_lines) *n_lines = lines;
-    if (n_bytes) *n_bytes = h->tile_off[size_t(tiles)];
-    if (largest_tile_bytes) *largest_tile_bytes = largest;
+    if (n_lines) *n_lines = t.lines;
+    if (n_bytes) *n_bytes = t.bytes;
+    if (largest_tile_bytes) *largest_tile_bytes = t.largest_tile;
     return DM_OK;
 }
 
 // -> 1: text was returned and more follows, 0: this was the last run (or there is no text), < 0: an error
 int dm_bedmerge_format_next(dm_bedmerge* h, char* out, int64_t cap, int64_t* got) {
-    using B = dm_bedmerge;
     if (!h) return fail(DM_EINVAL, "null handle");
     if (got) *got = 0;
-    if (h->tile_off.empty() || !h->plus) return fail(DM_ESTATE, "dm_bedmerge_format_next: no format begun (or the tables changed since)");
-    if (cap < 0 || (cap > 0 && !out) || !got) return fail(DM_EINVAL, "dm_bedmerge_format_next: null argument");
-    const int64_t tiles = int64_t(h->tile_off.size()) - 1;
-    const std::vector<long long>& off = h->tile_off;
-    int64_t t0 = h->next_tile;
-    while (t0 < tiles && off[size_t(t0) + 1] == off[size_t(t0)]) ++t0;                     // tiles without text
-    if (t0 >= tiles) {
-        h->next_tile = tiles;
-        return 0;
-    }
-    if (off[size_t(t0) + 1] - off[size_t(t0)] > cap)
-        return fail(DM_EINVAL, "dm_bedmerge_format_next: a buffer of %lld bytes does not hold the tile at position %lld: %lld bytes are needed", (long long)cap,
-                    (long long)(t0 * bmk::TILE_POS), (long long)(off[size_t(t0) + 1] - off[size_t(t0)]));
-    // the last tile whose end still fits: off is ascending
-    const int64_t t1 = int64_t(std::upper_bound(off.begin() + t0 + 1, off.end(), off[size_t(t0)] + cap) - off.begin()) - 1;
-    const int64_t bytes = off[size_t(t1)] - off[size_t(t0)];
-    if (t1 <= t0 || bytes <= 0 || bytes > cap) return fail(DM_ESTATE, "dm_bedmerge_format_next: tiles %lld .. %lld of %lld bytes", (long long)t0, (long long)t1, (long long)bytes);
+    if (!h->text.begun() || !h->plus) return fail(DM_ESTATE, "dm_bedmerge_format_next: no format begun (or the tables changed since)");
     if (dm_summary_length(h->plus) != h->format_length || dm_summary_length(h->minus) != h->format_length)
         return fail(DM_ESTATE, "dm_bedmerge_format_next: the tables changed since format_begin");
-    HIP_TRY(hipSetDevice(h->xy->device));
-    int rc;
-    if ((rc = h->b.ensure(B::FTEXT, size_t(bytes))) != DM_OK) return rc;
-    hipStream_t s = h->xy->stream;
-    HIP_TRY(hipEventRecord(h->ev[4], s));
-    hipLaunchKernelGGL(bmk::bm_write_kernel, dim3(unsigned(t1 - t0)), dim3(bmk::THREADS), 0, s, h->name, h->format_base, static_cast<const int*>(dm_summary_device_ptr(h->plus)),
-                       static_cast<const int*>(dm_summary_device_ptr(h->minus)), (long long)h->format_length, h->b.ptr<const long long>(B::TBYTES), (long long)t0,
-                       h->b.ptr<char>(B::FTEXT));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->ev[5], s));
-    HIP_TRY(hipMemcpyAsync(out, h->b.buf[B::FTEXT], size_t(bytes), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if ((rc = add_time(h->ev[4], h->ev[5], h->format_ms)) != DM_OK) return rc;
-    *got = bytes;
-    h->next_tile = t1;
-    while (h->next_tile < tiles && off[size_t(h->next_tile) + 1] == off[size_t(h->next_tile)]) ++h->next_tile;
-    return h->next_tile < tiles ? 1 : 0;
+    return h->text.next(h->xy, bmk::emitter(h, h->format_base, h->format_length), h->format_length, "dm_bedmerge_format_next", out, cap, got);
 }
 
 int dm_bedmerge_times(dm_bedmerge* h, double* parse_ms, double* add_ms, double* format_ms) {
     if (!h) return fail(DM_EINVAL, "null handle");
     if (parse_ms) *parse_ms = h->parse_ms;
     if (add_ms) *add_ms = h->add_ms;
-    if (format_ms) *format_ms = h->format_ms;
+    if (format_ms) *format_ms = h->text.ms;
     return DM_OK;
 }
 

@@ -17,14 +17,15 @@
 // Python's int(mod * 100 / cov).
 #pragma once
 #include "bedline.inc"
+#include "textout.inc"
 
 #define BM_HD BED_HD
 
 namespace bmk {
 
 using bed::Name;
+using txo::put_uint;
 constexpr long long MAX_LENGTH = 0x7fffffffLL;      // positions 0 .. 2^31 - 2
-constexpr int TILE_POS = 1024;                      // positions of one format tile (dm_bedmerge_tile_positions)
 
 struct Rec {
     int pos, cov, mod;
@@ -56,27 +57,6 @@ BM_HD inline bool parse_line(const char* p, const long long n, const Name& name,
     r.cov = int(num[1]);
     r.mod = int(num[2]);
     return true;
-}
-
-struct CountSink {
-    long long n = 0;
-    BM_HD void put(char) { ++n; }
-};
-struct WriteSink {
-    char* p;
-    BM_HD void put(const char c) { *p++ = c; }
-};
-
-template <class Sink>
-BM_HD inline void put_uint(Sink& s, unsigned long long v) {        // the decimal digits of v, most significant first
-    unsigned long long p = 1;
-    while (p <= v / 10) p *= 10;
-    while (p) {
-        const unsigned long long d = v / p;
-        s.put(char('0' + int(d)));
-        v -= d * p;
-        p /= 10;
-    }
 }
 
 // The line of (pos, strand) with the sums cov, mod (0 < mod <= cov).  The same routine counts and writes: the two cannot disagree on a length.
@@ -132,6 +112,22 @@ BM_HD inline int emit_position(Sink& s, const Name& name, const char base, const
     return lines;
 }
 
+// The lines of `merge` as an emitter (textout.inc): the four tables, a null strand holds nothing.  The text is defined for sums that are ok; the
+// tile writer (textout.hip.inc) skips a position whose sums are not and counts its tile into *bad_tiles (device memory; null on the host, whose
+// format_tables looks at the sums before it formats).
+struct Emitter {
+    Name name;
+    char base;
+    const int32_t *cov_p, *mod_p, *cov_m, *mod_m;
+    unsigned long long* bad_tiles;
+    static constexpr bool CHECKED = true;
+    BM_HD bool ok(const long long i) const { return (!mod_p || sum_ok(cov_p[i], mod_p[i])) && (!mod_m || sum_ok(cov_m[i], mod_m[i])); }
+    template <class Sink>
+    BM_HD int operator()(Sink& s, const long long q, const long long i) const {
+        return emit_position(s, name, base, q, i, cov_p, mod_p, cov_m, mod_m);
+    }
+};
+
 // a contig name for `merge`: 1 to bed::MAX_NAME bytes, all of them printable (the name is written into every line of the output)
 inline bool set_name(Name& name, const char* contig_name) { return bed::set_name(name, contig_name) && bed::printable(name.s, name.n); }
 
@@ -156,21 +152,13 @@ inline int64_t parse_text(const char* text, const int64_t n_bytes, const Name& n
 // -> bytes of the text, -1: a sum outside 0 <= mod <= cov (*bad_index: its index).
 inline int64_t format_tables(const Name& name, const char base, const int64_t first_pos, const int64_t length, const int32_t* cov_p, const int32_t* mod_p,
                              const int32_t* cov_m, const int32_t* mod_m, char* out, const int64_t cap, int64_t* lines, int64_t* bad_index) {
-    CountSink count;
-    int64_t n_lines = 0;
-    for (int64_t i = 0; i < length; ++i) {
-        if ((mod_p && !sum_ok(cov_p[i], mod_p[i])) || (mod_m && !sum_ok(cov_m[i], mod_m[i]))) {
+    const Emitter em = {name, base, cov_p, mod_p, cov_m, mod_m, nullptr};
+    for (int64_t i = 0; i < length; ++i)
+        if (!em.ok(i)) {
             *bad_index = i;
             return -1;
         }
-        n_lines += emit_position(count, name, base, first_pos + i, i, cov_p, mod_p, cov_m, mod_m);
-    }
-    if (lines) *lines = n_lines;
-    if (out && cap >= count.n) {
-        WriteSink w{out};
-        for (int64_t i = 0; i < length; ++i) emit_position(w, name, base, first_pos + i, i, cov_p, mod_p, cov_m, mod_m);
-    }
-    return count.n;
+    return txo::format_range(em, first_pos, length, out, cap, lines);
 }
 
 }  // namespace bmk

@@ -5,9 +5,7 @@
 //   the motif         spk::sp_code_kernel of siteperf.hip.inc on the contig's bytes: one code byte per position, bit 0 '+' site, bit 1 '-' site
 //   the classes       bl_class_kernel    one sweep over (strand, position): the R slots and the code byte -> one class byte per key
 //                                        (blk::class_of, bslabels.inc); the counters of either strand reduced per wave and per block, one 64-bit atomic per block
-//   a list's text     bl_length_kernel   a block per tile of blk::TILE_POS positions: bytes and lines of the tile (blk::emit_position, counting sink)
-//                     the 64-bit scan over the tiles
-//                     bl_write_kernel    the same routine with a writing sink at tile offset + block scan of the lanes' bytes
+//   a list's text     the tiled writer of textout.hip.inc (txo::Run) on blk::Emitter: the lines of a position from the class bytes of its two keys
 // deepmod_amd/bslabels.py (HostEngine) is the numpy twin and the statement of the semantics.
 // Memory of the open contig: 8 R bytes of slots, 1 byte of reference, 1 code byte and 2 class bytes per position.  The sweep reads 8 R + 1 and
 // writes 2 bytes per position; lane i of a wave reads slot i of a replicate's row (the replicate / strand-major table of bs_fill_kernel), so every
@@ -21,12 +19,12 @@
 #include "xyrows.hip.inc"
 #include "siteperf.hip.inc"
 #include "bsperf.hip.inc"
+#include "textout.hip.inc"
 #include "bslabels.inc"
 
 namespace blk {
 
 constexpr int THREADS = 256;
-constexpr int POS_PER_LANE = TILE_POS / THREADS;
 constexpr int MAX_BLOCKS = 2048;                    // grid of the sweep: a block loops over its share and flushes once
 
 // truth [R][2 strands][length], code [length] -> cls [2 strands][length], counts [2 strands][N_COUNT] +=
@@ -71,63 +69,41 @@ __global__ __launch_bounds__(THREADS) void bl_class_kernel(const unsigned* __res
     }
 }
 
-__global__ __launch_bounds__(THREADS) void bl_length_kernel(const Name name, const int list, const unsigned char* __restrict__ cls, const long long length,
-                                                           long long* __restrict__ tile_bytes, long long* __restrict__ tile_lines) {
-    __shared__ long long wave_total[THREADS / 64];
-    const long long q0 = (long long)blockIdx.x * TILE_POS + (long long)threadIdx.x * POS_PER_LANE;
-    CountSink c;
-    int lines = 0;
-    for (int k = 0; k < POS_PER_LANE; ++k)
-        if (q0 + k < length) lines += emit_position(c, name, list, q0 + k, q0 + k, cls, cls + length);
-    long long total_bytes, total_lines;
-    (void)csites::block_exclusive_scan<THREADS>(c.n, wave_total, total_bytes);
-    (void)csites::block_exclusive_scan<THREADS>((long long)lines, wave_total, total_lines);
-    if (threadIdx.x == 0) {
-        tile_bytes[blockIdx.x] = total_bytes;
-        tile_lines[blockIdx.x] = total_lines;
-    }
-}
+}  // namespace blk
 
-// tiles first_tile .. of the grid: their text at out + (tile_off[tile] - tile_off[first_tile])
-__global__ __launch_bounds__(THREADS) void bl_write_kernel(const Name name, const int list, const unsigned char* __restrict__ cls, const long long length,
-                                                          const long long* __restrict__ tile_off, const long long first_tile, char* __restrict__ out) {
-    __shared__ long long wave_total[THREADS / 64];
-    const long long tile = first_tile + blockIdx.x;
-    const long long q0 = tile * TILE_POS + (long long)threadIdx.x * POS_PER_LANE;
-    CountSink c;
-    for (int k = 0; k < POS_PER_LANE; ++k)
-        if (q0 + k < length) emit_position(c, name, list, q0 + k, q0 + k, cls, cls + length);
-    long long total;
-    const long long ex = csites::block_exclusive_scan<THREADS>(c.n, wave_total, total);
-    if (c.n == 0 || ex + c.n > tile_off[tile + 1] - tile_off[tile]) return;      // (never past the counted length)
-    WriteSink w{out + (tile_off[tile] - tile_off[first_tile]) + ex};
-    for (int k = 0; k < POS_PER_LANE; ++k)
-        if (q0 + k < length) emit_position(w, name, list, q0 + k, q0 + k, cls, cls + length);
+struct dm_bslabels : bsk::Truth {
+    hipEvent_t cev[2] = {nullptr, nullptr};             // class: begin / end
+    enum { SEQ, CODE, CLS, COUNTS, N_OWN };
+    DevBufs<N_OWN> c{"dm_bslabels"};                    // what the classes need on top of the truth side
+    blk::Rule rule = {};
+    bool classified = false;
+    txo::Run text;                                      // the format in progress, of list format_list
+    int format_list = 0;
+    double class_ms = 0.0;
+};
+
+namespace blk {
+
+// the lines of list `list` of the classified contig; false: its name is none a line can hold
+bool emitter(const dm_bslabels* h, const int list, Emitter& em) {
+    const unsigned char* cls = h->c.ptr<const unsigned char>(dm_bslabels::CLS);
+    em.list = list;
+    em.cls_p = cls;
+    em.cls_m = cls + h->length;
+    return blk::set_name(em.name, h->names.s[h->contig]);
 }
 
 }  // namespace blk
 
-struct dm_bslabels : bsk::Truth {
-    hipEvent_t cev[4] = {nullptr, nullptr, nullptr, nullptr};        // class, format: begin / end
-    enum { SEQ, CODE, CLS, COUNTS, TBYTES, TLINES, FTEXT, N_OWN };
-    DevBufs<N_OWN> c{"dm_bslabels"};                    // what the classes and the text need on top of the truth side
-    blk::Rule rule = {};
-    bool classified = false;
-    // the format in progress
-    std::vector<long long> tile_off;                    // [tiles + 1]: the first text byte of every tile (empty: no format begun)
-    int64_t next_tile = 0;
-    int format_list = 0;
-    double class_ms = 0.0, format_ms = 0.0;
-};
-
 extern "C" {
 
-int dm_bslabels_tile_positions(void) { return blk::TILE_POS; }
+int dm_bslabels_tile_positions(void) { return txo::TILE_POS; }
 
 void dm_bslabels_destroy(dm_bslabels* h) {
     if (!h) return;
     bsk::truth_release(h);                                           // (the device is set and the stream drained first)
     h->c.release();
+    h->text.release();
     for (hipEvent_t e : h->cev)
         if (e) (void)hipEventDestroy(e);
     delete h;
@@ -161,7 +137,7 @@ dm_bslabels* dm_bslabels_create(int device, int n_contigs, const char* const* na
         dm_bslabels_destroy(h);
         return nullptr;
     }
-    bool ok = true;
+    bool ok = h->text.init("dm_bslabels");
     for (hipEvent_t& e : h->cev) ok = ok && hipEventCreate(&e) == hipSuccess;
     ok = ok && h->c.ensure(dm_bslabels::COUNTS, 2 * blk::N_COUNT * 8) == DM_OK;
     if (!ok) {
@@ -194,7 +170,7 @@ int dm_bslabels_close_contig(dm_bslabels* h) {
     if (!h) return fail(DM_EINVAL, "null handle");
     bsk::truth_close(h);
     h->classified = false;
-    h->tile_off.clear();
+    h->text.clear();
     return DM_OK;
 }
 
@@ -296,91 +272,33 @@ int64_t dm_bslabels_format_host(const char* name, int list, const uint8_t* cls_p
 }
 
 int dm_bslabels_format_begin(dm_bslabels* h, int list, int64_t* n_lines, int64_t* n_bytes, int64_t* largest_tile_bytes) {
-    using B = dm_bslabels;
     if (!h) return fail(DM_EINVAL, "null handle");
-    h->tile_off.clear();
+    h->text.clear();
     if (n_lines) *n_lines = 0;
     if (n_bytes) *n_bytes = 0;
     if (largest_tile_bytes) *largest_tile_bytes = 0;
     if (list < blk::C_FUL || list > blk::C_NO) return fail(DM_EINVAL, "dm_bslabels_format_begin: list %d (1 fulmod, 2 anymod, 3 nomod)", list);
     if (h->contig < 0 || !h->classified) return fail(DM_ESTATE, "dm_bslabels_format_begin: no classified contig");
-    blk::Name name = {};
-    if (!blk::set_name(name, h->names.s[h->contig])) return fail(DM_ESTATE, "dm_bslabels_format_begin: the name of contig %d", h->contig);
-    HIP_TRY(hipSetDevice(h->xy->device));
-    const int64_t length = h->length, tiles = (length + blk::TILE_POS - 1) / blk::TILE_POS;
-    int rc;
-    if ((rc = h->c.ensure(B::TBYTES, size_t(tiles + 1) * 8)) != DM_OK || (rc = h->c.ensure(B::TLINES, size_t(tiles + 1) * 8)) != DM_OK) return rc;
-    hipStream_t s = h->xy->stream;
-    long long* d_bytes = h->c.ptr<long long>(B::TBYTES);
-    long long* d_lines = h->c.ptr<long long>(B::TLINES);
-    HIP_TRY(hipEventRecord(h->cev[2], s));
-    hipLaunchKernelGGL(blk::bl_length_kernel, dim3(unsigned(tiles)), dim3(blk::THREADS), 0, s, name, list, h->c.ptr<const unsigned char>(B::CLS), (long long)length, d_bytes,
-                       d_lines);
-    HIP_TRY(hipGetLastError());
-    if ((rc = xyk::scan_in_place(h->xy, d_bytes, tiles)) != DM_OK || (rc = xyk::scan_in_place(h->xy, d_lines, tiles)) != DM_OK) return rc;
-    HIP_TRY(hipEventRecord(h->cev[3], s));
-    std::vector<long long> off(size_t(tiles) + 1);
-    long long lines = 0;
-    HIP_TRY(hipMemcpyAsync(off.data(), d_bytes, off.size() * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&lines, d_lines + tiles, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if ((rc = add_time(h->cev[2], h->cev[3], h->format_ms)) != DM_OK) return rc;
-    long long largest = 0;
-    if (off[0] != 0) return fail(DM_ESTATE, "dm_bslabels_format_begin: the first tile starts at byte %lld", off[0]);
-    for (int64_t t = 0; t < tiles; ++t) {
-        if (off[t + 1] < off[t]) return fail(DM_ESTATE, "dm_bslabels_format_begin: descending tile offsets");
-        largest = std::max(largest, off[t + 1] - off[t]);
-    }
-    h->tile_off.swap(off);
-    h->next_tile = 0;
+    blk::Emitter em = {};
+    if (!blk::emitter(h, list, em)) return fail(DM_ESTATE, "dm_bslabels_format_begin: the name of contig %d", h->contig);
+    txo::Totals t;
+    const int rc = h->text.begin(h->xy, em, h->length, "dm_bslabels_format_begin", t);
+    if (rc != DM_OK) return rc;
     h->format_list = list;
-    if (n_lines) *n_lines = lines;
-    if (n_bytes) *n_bytes = h->tile_off[size_t(tiles)];
-    if (largest_tile_bytes) *largest_tile_bytes = largest;
+    if (n_lines) *n_lines = t.lines;
+    if (n_bytes) *n_bytes = t.bytes;
+    if (largest_tile_bytes) *largest_tile_bytes = t.largest_tile;
     return DM_OK;
 }
 
 // -> 1: text was returned and more follows, 0: this was the last run (or there is no text), < 0: an error
 int dm_bslabels_format_next(dm_bslabels* h, char* out, int64_t cap, int64_t* got) {
-    using B = dm_bslabels;
     if (!h) return fail(DM_EINVAL, "null handle");
     if (got) *got = 0;
-    if (h->tile_off.empty() || h->contig < 0 || !h->classified) return fail(DM_ESTATE, "dm_bslabels_format_next: no format begun");
-    if (cap < 0 || (cap > 0 && !out) || !got) return fail(DM_EINVAL, "dm_bslabels_format_next: null argument");
-    const int64_t tiles = int64_t(h->tile_off.size()) - 1;
-    const std::vector<long long>& off = h->tile_off;
-    int64_t t0 = h->next_tile;
-    while (t0 < tiles && off[size_t(t0) + 1] == off[size_t(t0)]) ++t0;                     // tiles without text
-    if (t0 >= tiles) {
-        h->next_tile = tiles;
-        return 0;
-    }
-    if (off[size_t(t0) + 1] - off[size_t(t0)] > cap)
-        return fail(DM_EINVAL, "dm_bslabels_format_next: a buffer of %lld bytes does not hold the tile at position %lld: %lld bytes are needed", (long long)cap,
-                    (long long)(t0 * blk::TILE_POS), (long long)(off[size_t(t0) + 1] - off[size_t(t0)]));
-    // the last tile whose end still fits: off is ascending
-    const int64_t t1 = int64_t(std::upper_bound(off.begin() + t0 + 1, off.end(), off[size_t(t0)] + cap) - off.begin()) - 1;
-    const int64_t bytes = off[size_t(t1)] - off[size_t(t0)];
-    if (t1 <= t0 || t1 > tiles || bytes <= 0 || bytes > cap)
-        return fail(DM_ESTATE, "dm_bslabels_format_next: tiles %lld .. %lld of %lld bytes", (long long)t0, (long long)t1, (long long)bytes);
-    blk::Name name = {};
-    if (!blk::set_name(name, h->names.s[h->contig])) return fail(DM_ESTATE, "dm_bslabels_format_next: the name of contig %d", h->contig);
-    HIP_TRY(hipSetDevice(h->xy->device));
-    int rc;
-    if ((rc = h->c.ensure(B::FTEXT, size_t(bytes))) != DM_OK) return rc;
-    hipStream_t s = h->xy->stream;
-    HIP_TRY(hipEventRecord(h->cev[2], s));
-    hipLaunchKernelGGL(blk::bl_write_kernel, dim3(unsigned(t1 - t0)), dim3(blk::THREADS), 0, s, name, h->format_list, h->c.ptr<const unsigned char>(B::CLS),
-                       (long long)h->length, h->c.ptr<const long long>(B::TBYTES), (long long)t0, h->c.ptr<char>(B::FTEXT));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->cev[3], s));
-    HIP_TRY(hipMemcpyAsync(out, h->c.buf[B::FTEXT], size_t(bytes), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if ((rc = add_time(h->cev[2], h->cev[3], h->format_ms)) != DM_OK) return rc;
-    *got = bytes;
-    h->next_tile = t1;
-    while (h->next_tile < tiles && off[size_t(h->next_tile) + 1] == off[size_t(h->next_tile)]) ++h->next_tile;
-    return h->next_tile < tiles ? 1 : 0;
+    if (!h->text.begun() || h->contig < 0 || !h->classified) return fail(DM_ESTATE, "dm_bslabels_format_next: no format begun");
+    blk::Emitter em = {};
+    if (!blk::emitter(h, h->format_list, em)) return fail(DM_ESTATE, "dm_bslabels_format_next: the name of contig %d", h->contig);
+    return h->text.next(h->xy, em, h->length, "dm_bslabels_format_next", out, cap, got);
 }
 
 int dm_bslabels_times(dm_bslabels* h, double* parse_ms, double* fill_ms, double* class_ms, double* format_ms) {
@@ -388,7 +306,7 @@ int dm_bslabels_times(dm_bslabels* h, double* parse_ms, double* fill_ms, double*
     if (parse_ms) *parse_ms = h->parse_ms;
     if (fill_ms) *fill_ms = h->fill_ms;
     if (class_ms) *class_ms = h->class_ms;
-    if (format_ms) *format_ms = h->format_ms;
+    if (format_ms) *format_ms = h->text.ms;
     return DM_OK;
 }
 

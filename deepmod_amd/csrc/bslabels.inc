@@ -14,17 +14,15 @@
 // A line of a list (emit_line): '%s %s %d\n' % (chr, strand, pos), the `chr strand pos` line getfeatures.readPosFiles reads; pos is the 0-based
 // position (the bedMethyl start), 1 - 10 digits.  Ascending position, '+' before '-' at one position (emit_position).
 #pragma once
-#include "bedmerge.inc"
+#include "bedline.inc"
+#include "textout.inc"
 
 #define BL_HD BED_HD
 
 namespace blk {
 
 using bed::Name;
-using bmk::CountSink;
-using bmk::WriteSink;
 constexpr long long MAX_LENGTH = 0x7fffffffLL;      // positions 0 .. 2^31 - 2
-constexpr int TILE_POS = 1024;                      // positions of one format tile (dm_bslabels_tile_positions)
 constexpr int MAX_MOTIF = 8;
 constexpr int MAX_REP = 4;
 constexpr unsigned PRESENT = 0x80000000u;           // a truth slot with a record (bsk::PRESENT)
@@ -62,7 +60,7 @@ BL_HD inline void emit_line(Sink& s, const Name& name, const int strand, const l
     s.put(' ');
     s.put(strand ? '-' : '+');
     s.put(' ');
-    bmk::put_uint(s, (unsigned long long)pos);
+    txo::put_uint(s, (unsigned long long)pos);
     s.put('\n');
 }
 
@@ -84,19 +82,23 @@ BL_HD inline int emit_position(Sink& s, const Name& name, const int list, const 
 // a contig name for `bslabels`: 1 to bsk::MAX_NAME (63) printable bytes, as dm_bslabels_create takes them
 inline bool set_name(Name& name, const char* contig_name) { return bed::set_name(name, contig_name) && name.n <= 63 && bed::printable(name.s, name.n); }
 
+// The lines of list `list` as an emitter (textout.inc): the class arrays of the two strands, a null strand holds nothing
+struct Emitter {
+    Name name;
+    int list;
+    const unsigned char *cls_p, *cls_m;
+    static constexpr bool CHECKED = false;
+    template <class Sink>
+    BL_HD int operator()(Sink& s, const long long q, const long long i) const {
+        return emit_position(s, name, list, q, i, cls_p, cls_m);
+    }
+};
+
 // The text of list `list` for positions first_pos .. first_pos + length - 1 from the two class arrays: counted first; written only if it fits `cap`.
 // -> bytes of the text
 inline int64_t format_classes(const Name& name, const int list, const int64_t first_pos, const int64_t length, const unsigned char* cls_p, const unsigned char* cls_m, char* out,
                               const int64_t cap, int64_t* lines) {
-    CountSink count;
-    int64_t n_lines = 0;
-    for (int64_t i = 0; i < length; ++i) n_lines += emit_position(count, name, list, first_pos + i, i, cls_p, cls_m);
-    if (lines) *lines = n_lines;
-    if (out && cap >= count.n) {
-        WriteSink w{out};
-        for (int64_t i = 0; i < length; ++i) emit_position(w, name, list, first_pos + i, i, cls_p, cls_m);
-    }
-    return count.n;
+    return txo::format_range(Emitter{name, list, cls_p, cls_m}, first_pos, length, out, cap, lines);
 }
 
 }  // namespace blk

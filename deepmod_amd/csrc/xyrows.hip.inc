@@ -19,6 +19,7 @@
 #pragma once
 #include "host.h"
 #include "blockscan.hip.inc"
+#include "textout.inc"
 #include "xyrows.inc"
 
 struct dm_xyrows {
@@ -132,26 +133,9 @@ __global__ __launch_bounds__(THREADS) void xy_rule_kernel(const long long* __res
     rcount[r] = mode == 2 ? n : kept;
 }
 
-struct CountSink {
-    long long n = 0;
-    __device__ void put(char) { ++n; }
-};
-struct WriteSink {
-    char* p;
-    __device__ void put(const char c) { *p++ = c; }
-};
-
-template <class Sink, class U>
-__device__ inline void put_uint(Sink& s, U v) {                      // the decimal digits of v, most significant first, without a digit buffer
-    U p = 1;
-    while (p <= v / 10) p *= 10;
-    while (p) {
-        const U d = v / p;
-        s.put(char('0' + int(d)));
-        v -= d * p;
-        p /= 10;
-    }
-}
+using txo::CountSink;                                                // the sinks and the digits of every text writer (textout.inc)
+using txo::WriteSink;
+using txo::put_uint;
 
 template <class Sink>
 __device__ inline void put_flag(Sink& s, const bool one) {           // 0.000 / 1.000 and the space behind it

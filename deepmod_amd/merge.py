@@ -20,6 +20,8 @@ from typing import Iterable, List
 
 import numpy as np
 
+from . import _lib
+
 
 def find_bed_files(pred_folder: str, ck: str, base: str) -> List[str]:
     files: List[str] = []
@@ -103,7 +105,6 @@ class MergeError(ValueError):
 def parse_device_grammar(text: bytes, contig_name: str, table_length: int = -1):
     """The device's line routine compiled for the host (no GPU needed) -> ((pos, strand, cov, mod), flag, first bad line)."""
     import ctypes
-    from . import _lib
     lib = _lib.load()
     flag, bad = ctypes.c_int32(0), ctypes.c_int64(-1)
     buf, name = ctypes.c_char_p(text), contig_name.encode('ascii')
@@ -122,7 +123,6 @@ def format_host(contig_name: str, base: str, cov_plus, mod_plus, cov_minus, mod_
     """The device's line routine compiled for the host: the merged text of positions first_pos .. from the four tables (a strand may be None).
     cap: the capacity offered (default: what the sizing call asks for); a text that does not fit raises."""
     import ctypes
-    from . import _lib
     lib = _lib.load()
     tabs = [None if a is None else np.ascontiguousarray(a, np.int32) for a in (cov_plus, mod_plus, cov_minus, mod_minus)]
     length = max([len(a) for a in tabs if a is not None] + [0])
@@ -143,37 +143,23 @@ def format_host(contig_name: str, base: str, cov_plus, mod_plus, cov_minus, mod_
 
 
 def tile_positions() -> int:
-    from . import _lib
     return _lib.load().dm_bedmerge_tile_positions()
 
 
-class DeviceMerge:
+class DeviceMerge(_lib.Handle):
     """One contig at a time on one GPU (dm_bedmerge_* of the C ABI): open, add_text / add_records per file, format, optionally the cluster stage on
-    .plus / .minus (summary.PositionSummary, the handles ClusterModel.sites takes)."""
+    .plus / .minus (summary.PositionSummary, the handles ClusterModel.sites takes).  times(): ms of the parse / add / format kernels so far."""
+    PREFIX, N_TIMES = 'dm_bedmerge', 3
 
     def __init__(self, device: int = 0):
-        import ctypes
-        from . import _lib
-        self._ct, self._libmod = ctypes, _lib
-        self._lib = _lib.load()
         self.device = device
-        self._h = self._lib.dm_bedmerge_create(device)
-        if not self._h:
-            raise _lib.DeepModHipError('dm_bedmerge_create: ' + _lib.last_error())
+        self._create(device)
         self.plus = self.minus = None
         self._n = 0
 
     def close(self):
         self.close_contig()
-        if getattr(self, '_h', None):
-            self._lib.dm_bedmerge_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
     def close_contig(self):
         for s in (getattr(self, 'plus', None), getattr(self, 'minus', None)):
@@ -262,13 +248,6 @@ class DeviceMerge:
             more, part = self.format_next(buf)
             yield part
 
-    def times(self):
-        """ms of the parse / add / format kernels so far."""
-        ct = self._ct
-        a, b, c = ct.c_double(0.0), ct.c_double(0.0), ct.c_double(0.0)
-        self._libmod.check(self._lib.dm_bedmerge_times(self._h, ct.byref(a), ct.byref(b), ct.byref(c)))
-        return a.value, b.value, c.value
-
 
 def host_rows(path: str, contig_name: str, limit: int):
     """A file the device parser passed on: readbed2's rows as records, if they meet the conditions of the device grammar; else MergeError
@@ -340,7 +319,6 @@ def merge_runs(mo, device: int = 0):
     from concurrent.futures import ThreadPoolExecutor
     chrkeys, prefix, fasta = check_options(mo)
     folder, base, fileid = mo['predFolder'], str(mo['Base']), str(mo.get('FileID') or 'mod')
-    from . import _lib
     if _lib.load().dm_device_count() < 1:
         raise MergeError('no gfx950 GPU visible (this build has no CPU path)')
 

@@ -31,7 +31,7 @@ from typing import Dict, List, Tuple
 
 import numpy as np
 
-from . import merge, siteperf
+from . import _lib, merge, siteperf
 
 MAX_FLANK = 8
 MAX_LENGTH = merge.MAX_LENGTH
@@ -172,13 +172,11 @@ class HostEngine:
 
 
 def tile_positions() -> int:
-    from . import _lib
     return _lib.load().dm_motifs_tile_positions()
 
 
 def count_host_routine(up, down, base, cov, min_pct, max_ctrl_pct, seq, plus, minus, ctrl_plus=None, ctrl_minus=None):
     """The sweep compiled for the host (dm_motifs_count_host: the routine the kernel runs per key; no GPU needed) -> (hist, counters, off_base)."""
-    from . import _lib
     lib = _lib.load()
     s = _seq_array(seq)
     tabs = [plus, minus] + ([ctrl_plus, ctrl_minus] if ctrl_plus is not None else [])
@@ -191,21 +189,17 @@ def count_host_routine(up, down, base, cov, min_pct, max_ctrl_pct, seq, plus, mi
     return hist, counters, off_base
 
 
-class DeviceEngine:
-    """The same on one GPU (dm_motifs_* of the C ABI).  A table is a summary.PositionSummary (the handles merge.DeviceMerge fills)."""
+class DeviceEngine(_lib.Handle):
+    """The same on one GPU (dm_motifs_* of the C ABI).  A table is a summary.PositionSummary (the handles merge.DeviceMerge fills).
+    times(): ms of the uploads of the contigs' bytes / of the sweeps so far."""
+    PREFIX, N_TIMES = 'dm_motifs', 2
 
     def __init__(self, up: int = 3, down: int = 3, base: str = 'A', cov: int = 5, min_pct: int = 50, max_ctrl_pct: int = 10, device: int = 0):
-        import ctypes
-        from . import _lib
         check_engine_options(up, down, base, cov, min_pct, max_ctrl_pct)
-        self._ct, self._libmod = ctypes, _lib
-        self._lib = _lib.load()
         self.up, self.down, self.base, self.device = int(up), int(down), base, device
         self.bins = 4 ** (self.up + self.down)
         self._merge = {}
-        self._h = self._lib.dm_motifs_create(device, self.up, self.down, base.encode('ascii'), int(cov), int(min_pct), int(max_ctrl_pct))
-        if not self._h:
-            raise _lib.DeepModHipError('dm_motifs_create: ' + _lib.last_error())
+        self._create(device, self.up, self.down, base.encode('ascii'), int(cov), int(min_pct), int(max_ctrl_pct))
         self.counters = np.zeros((2, len(COUNT_KEYS)), np.int64)
         self.off_base = np.zeros(2, np.int64)
 
@@ -213,15 +207,7 @@ class DeviceEngine:
         for dm in getattr(self, '_merge', {}).values():
             dm.close()
         self._merge = {}
-        if getattr(self, '_h', None):
-            self._lib.dm_motifs_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
     def new_tables(self, role: str, name: str, length: int):
         """Fresh tables of `length` positions for the contig, in the merge handle kept for `role` (the tables of the contig before are closed)."""
@@ -248,12 +234,6 @@ class DeviceEngine:
         self._libmod.check(self._lib.dm_motifs_reset(self._h))
         self.counters[:] = 0
         self.off_base[:] = 0
-
-    def times(self) -> Tuple[float, float]:
-        """ms of the uploads of the contigs' bytes / of the sweeps so far."""
-        a, b = self._ct.c_double(0.0), self._ct.c_double(0.0)
-        self._libmod.check(self._lib.dm_motifs_times(self._h, self._ct.byref(a), self._ct.byref(b)))
-        return a.value, b.value
 
 
 # ---- the search ----------------------------------------------------------------------------------------------------------------------------
@@ -432,7 +412,6 @@ def motifs(mo: Dict[str, object], engine=None) -> Dict[str, object]:
     controls = [c for c in (mo.get('control') or []) if c]
     own = engine is None
     if own:
-        from . import _lib
         if _lib.load().dm_device_count() < 1:
             raise MotifsError('no gfx950 GPU visible (this build has no CPU path)')
         engine = DeviceEngine(up, down, base, o['cov'], o['minPct'], o['maxCtrlPct'])

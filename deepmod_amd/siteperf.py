@@ -11,6 +11,8 @@ from typing import Dict, Iterable, Optional, Tuple
 
 import numpy as np
 
+from . import _lib
+
 
 def bed_sites(bed: bytes) -> Dict[str, np.ndarray]:
     """Columns of a mod_pos.*.bed file (myDetect.py:1112-1120): position (col 2), coverage (col 10), percentage (col 11),
@@ -259,31 +261,15 @@ class HostEngine:
                 'base_mismatch': int(self.base_mismatch)}
 
 
-class DeviceEngine:
+class DeviceEngine(_lib.Handle):
     """The same interface on one GPU (dm_siteperf_* of the C ABI); add_text is the device parser."""
+    PREFIX, N_TIMES = 'dm_siteperf', 2
 
     def __init__(self, thresholds=(1, 5), device: int = 0):
-        import ctypes
-        from . import _lib
-        self._ct, self._libmod = ctypes, _lib
-        self._lib = _lib.load()
         self.thresholds = _check_thresholds(thresholds)
         t = np.asarray(self.thresholds, np.int32)
-        self._h = self._lib.dm_siteperf_create(device, len(t), t.ctypes.data)
-        if not self._h:
-            raise _lib.DeepModHipError('dm_siteperf_create: ' + _lib.last_error())
+        self._create(device, len(t), t.ctypes.data)
         self.length = -1
-
-    def close(self):
-        if getattr(self, '_h', None):
-            self._lib.dm_siteperf_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_contig(self, seq, motif: str, k: int, start: Optional[int] = None, end: Optional[int] = None):
         check_motif(motif, k)
@@ -334,22 +320,14 @@ class DeviceEngine:
         self._libmod.check(self._lib.dm_siteperf_fetch(self._h, hist.ctypes.data, counts.ctypes.data, ct.byref(seen), ct.byref(skipped), ct.byref(mism)))
         return {'hist': hist, 'counts': counts, 'lines_seen': seen.value, 'lines_skipped': skipped.value, 'base_mismatch': mism.value}
 
-    def times(self) -> Tuple[float, float]:
-        ct = self._ct
-        a, b = ct.c_double(0.0), ct.c_double(0.0)
-        self._libmod.check(self._lib.dm_siteperf_times(self._h, ct.byref(a), ct.byref(b)))
-        return a.value, b.value
-
 
 def tile_bytes() -> int:
-    from . import _lib
     return _lib.load().dm_siteperf_tile_bytes()
 
 
 def parse_device_grammar(text: bytes, contig_name: str, contig_len: int):
     """The device's line routine compiled for the host (no GPU needed) -> ((pos, strand, base, cov, pct, mod), flag, first bad line)."""
     import ctypes
-    from . import _lib
     lib = _lib.load()
     flag, bad = ctypes.c_int32(0), ctypes.c_int64(-1)
     buf, name = ctypes.c_char_p(text), contig_name.encode('ascii')

@@ -771,7 +771,7 @@ int dm_siteperf_times(dm_siteperf* h, double* parse_ms, double* count_ms);
  *   parse_host / format_host   the two line routines compiled for the host (no GPU needed).  parse_host -> lines, records as far as cap reaches
  *                  (table_length < 0: none given).  format_host: tables of positions first_pos .. first_pos + length - 1 (a strand may be NULL) ->
  *                  the bytes of the text; written only if out is given and cap holds them all.
- *   times          ms of the parse / add / format kernels so far (HIP events). */
+ *   times          ms of the parse / add / format kernels so far (HIP events); a format_begin that finds no line adds nothing. */
 typedef struct dm_bedmerge dm_bedmerge;
 dm_bedmerge* dm_bedmerge_create(int device);
 void dm_bedmerge_destroy(dm_bedmerge* h);
@@ -876,7 +876,8 @@ int dm_bsperf_times(dm_bsperf* h, double* parse_ms, double* fill_ms, double* cou
  *   format_host    the line routine compiled for the host (no GPU needed): class arrays of positions first_pos .. first_pos + length - 1 (a
  *                  strand may be NULL; first_pos + length <= 2^31 - 1) -> the bytes of the list's text; written only if out is given and cap
  *                  holds them all.
- *   times          ms of the parse / fill (with the site codes of open) / class (the sweep) / format kernels so far (HIP events).
+ *   times          ms of the parse / fill (with the site codes of open) / class (the sweep) / format kernels so far (HIP events); a format_begin
+ *                  of a list without a line adds nothing.
  * Every argument is checked before any launch (DM_EINVAL, dm_last_error names the fault): contig index, replicate, len, motif letters, list. */
 typedef struct dm_bslabels dm_bslabels;
 dm_bslabels* dm_bslabels_create(int device, int n_contigs, const char* const* names, const int64_t* lengths, int n_replicates, int cov, int methylated, int unmethylated);
