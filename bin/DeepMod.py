@@ -70,6 +70,14 @@ folders pooled the same way; one sweep per contig on one GPU counts, per oriente
 are then picked from the counts by an exact integer rule (deepmod_amd/motifs.py).  O/id_motifs.txt lists them with the ready
 `--motif <label> --ModinMotif <k>` arguments of siteperf / getfeatures; O/id_motifs.json has every counter, the non-zero contexts and notes.  Hand in the
 mod_pos.* files of `detect` runs (summed files drop every position with a modified count of 0).  The threshold defaults have not been tuned on real data.
+
+`diffmod --predFolder RUNS --control C1[,C2..] --Base C --outFolder O --FileID id [--chr ..] [--Ref genome.fa] [--cov 5] [--fdr 0.05] [--minDelta 10]
+[--all 0|1] [--threads T]` answers what a user with a sample and a control asks first: which sites differ, and how sure are we?  The files below RUNS
+are summed as `merge` sums them, the control folders pooled into a second pair of tables; every (strand, position) with --cov reads in both gets the
+two-sided p of Fisher's exact test on one GPU (R's fisher.test rule) and a Benjamini-Hochberg q-value over all tested keys.  O/id_diffmod.txt lists the
+keys with q <= --fdr whose percentages differ by --minDelta points or more (--all 1: every tested key); O/id_diffmod.json has the counters, the p
+histogram and notes (deepmod_amd/diffmod.py).  Hand in mod_pos.* files.  Pooling runs before an exact test ignores the variation between
+replicates: the p-values are those of the pooled counts.
 """
 import argparse
 import os
@@ -285,7 +293,38 @@ def build_parser():
     mot.add_argument('--minSites', type=int, default=20, help='a motif: at least this many modified sites (default 20)')
     mot.add_argument('--maxMotifs', type=int, default=8, help='motifs reported at most (default 8)')
     mot.set_defaults(func=mMotifs)
+    dif = sub.add_parser('diffmod', parents=[com], help='per-site differential modification of a run against controls: Fisher\'s exact test on the GPU, BH q-values',
+                         description='Per contig: every *.<chr>-.<Base>.bed and *.<chr>+.<Base>.bed one to three levels below --predFolder is summed as merge sums '
+                                     'them, every --control folder pooled the same way into a second pair of tables.  Every (strand, position) with --cov reads in '
+                                     'both gets the two-sided p of Fisher\'s exact test (the rule of R\'s fisher.test) on one GPU, and a Benjamini-Hochberg q-value '
+                                     'over all tested keys of the run.  Writes <outFolder>/<FileID>_diffmod.txt (chr, 0-based pos, strand, coverage, modified and '
+                                     'percentage of the sample and of the controls, delta, p, q of every key with q <= --fdr whose percentages differ by --minDelta '
+                                     'points or more) and <outFolder>/<FileID>_diffmod.json (counters, the p histogram, notes, kernel times).  Hand in the mod_pos.* '
+                                     'files of detect runs (summed files drop every position with a modified count of 0).  Pooling runs before an exact test ignores '
+                                     'the variation between replicates: the p-values are those of the pooled counts.  No replicate-aware (beta-binomial) test, no '
+                                     'motif restriction, and the two strands of a CpG are not merged.')
+    dif.add_argument('--predFolder', default=None, help='folder of the sample\'s runs: the BED files are searched one to three levels below it')
+    dif.add_argument('--control', default=None, help='folder(s) of control runs, separated by commas; pooled (needed)')
+    dif.add_argument('--Ref', default=None, help='reference genome FASTA: only fixes the contigs and their lengths (default: the tables grow with the files)')
+    dif.add_argument('--Base', default='C', choices=['A', 'C', 'G', 'T'], help='the modified base: names the files (default C)')
+    dif.add_argument('--chr', default=None, help='contigs, separated by commas (default: those of --Ref, or those the sample\'s file names hold)')
+    dif.add_argument('--cov', type=int, default=5, help='least coverage of a tested key, in the sample and in the pooled controls (default 5)')
+    dif.add_argument('--fdr', type=float, default=0.05, help='a key is listed at this q-value or less, above 0 and at most 1 (default 0.05)')
+    dif.add_argument('--minDelta', type=int, default=10, help='and when its percentages differ by this many points or more (default 10)')
+    dif.add_argument('--all', type=int, default=0, help='1: write every tested key with its q, whatever --fdr and --minDelta (default 0)')
+    dif.set_defaults(func=mDiffmod)
     return parser
+
+
+def mDiffmod(args):
+    from deepmod_amd import diffmod
+    mo = {k: getattr(args, k) for k in ('predFolder', 'Ref', 'Base', 'outFolder', 'FileID', 'cov', 'fdr', 'minDelta', 'all', 'threads')}
+    mo['chr'] = [c for c in (args.chr or '').split(',') if c] or None
+    mo['control'] = [c for c in (args.control or '').split(',') if c]
+    try:
+        diffmod.diffmod(mo)                              # checks the options, then refuses without a gfx950 GPU
+    except diffmod.DiffmodError as exc:
+        raise SystemExit('Error: %s' % exc)
 
 
 def mMotifs(args):

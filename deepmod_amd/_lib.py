@@ -243,6 +243,17 @@ SIGNATURES = [
     ("dm_motifs_tile_positions", _c.c_int, []),
     ("dm_motifs_times", _c.c_int, [_vp, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
     ("dm_motifs_count_host", _c.c_int, [_c.c_int, _c.c_int, _c.c_char, _c.c_int, _c.c_int, _c.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("dm_diffmod_create", _vp, [_c.c_int, _c.c_int, _c.c_double]),
+    ("dm_diffmod_destroy", None, [_vp]),
+    ("dm_diffmod_run", _c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(_i64)]),
+    ("dm_diffmod_fetch_records", _c.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("dm_diffmod_fetch_hist", _c.c_int, [_vp, _vp]),
+    ("dm_diffmod_reset", _c.c_int, [_vp]),
+    ("dm_diffmod_times", _c.c_int, [_vp, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
+    ("dm_diffmod_max_total", _c.c_int, []),
+    ("dm_diffmod_tile_positions", _c.c_int, []),
+    ("dm_diffmod_small_support", _c.c_int, []),
+    ("dm_diffmod_test_host", _c.c_int, [_c.c_int, _c.c_double, _i64] + [_vp] * 10 + [_i64] + [_vp] * 7 + [_c.POINTER(_i64)]),
 ]
 
 

@@ -932,6 +932,46 @@ int dm_motifs_count_host(int up, int down, char base, int cov, int min_pct, int 
                          const int32_t* mod_plus, const int32_t* cov_minus, const int32_t* mod_minus, const int32_t* ctrl_cov_plus, const int32_t* ctrl_mod_plus,
                          const int32_t* ctrl_cov_minus, const int32_t* ctrl_mod_minus, int64_t* hist, int64_t* counters, int64_t* off_base);
 
+/* -------------------------------------------------------------------------- diffmod -- */
+/* Per-site differential modification of a run against pooled controls (csrc/diffmod.hip.inc, diffmod.inc): one run joins the
+ * sample's and the controls' tables of a contig and tests every key (strand, position) that is deep enough in both with Fisher's exact test.
+ * With cA, mA the sample's coverage and modified count and cB, mB the controls', the first rule that applies decides:
+ *   1  cA == 0 and cB == 0: ignored       2  cA < cov: shallow_sample       3  cB < cov: shallow_control
+ *   4  cA + cB > dm_diffmod_max_total() (2^20): too_deep                    5  tested
+ * p of a tested key is the two-sided p of R's fisher.test: n1 = cA, n2 = cB, M = mA + mB, N = n1 + n2, x in [max(0, M - n2), min(n1, M)],
+ *   L(x) = lf[n1] + lf[n2] + lf[M] + lf[N-M] - lf[N] - lf[x] - lf[n1-x] - lf[M-x] - lf[n2-M+x],   lf[k] = lgamma(k + 1) in fp64,
+ *   p = min(1, sum of exp(L(x)) over the x with L(x) <= L(mA) + 1e-7); a support of one table is p = 1.
+ * The table lf is computed once on the host and uploaded: the kernels and the host twin read the same doubles.  Within about 1.3e-10 relative of
+ * the exact value for N <= 4096 and 6.7e-8 for N <= 2^20; a p that underflows is 0.  deepmod_amd/diffmod.py (HostEngine) states
+ * the semantics in exact integers.
+ *   create         cov >= 1; 0 < alpha <= 1.  A zeroed p histogram.
+ *   run            one contig: the sample's '+' and '-' tables and the controls', all four on the handle's device and of one length.
+ *                  counters [2 strands][4] (tested, shallow_sample, shallow_control, too_deep) are those of this contig; the p histogram grows by
+ *                  every tested key; *n_records = the tested keys with p <= alpha, held on the device until the next run.
+ *   fetch_records  records first .. first + count - 1 of the last run, in key order (ascending position, '+' before '-'): position, strand (0 '+',
+ *                  1 '-'), cA, mA, cB, mB, p.
+ *   fetch_hist     int64 [20]: bin min(19, int(20 p)) of every key tested since create / reset.      reset   zeroes it.
+ *   test_host      the same run compiled for the host (no GPU needed), on plain arrays of len >= 0 entries: counters are set, hist is added to,
+ *                  *n_records is the number of records, of which the first cap are written.
+ *   times          ms of the select kernels (with their scans) / of the test kernels (with theirs) so far (HIP events).
+ *   tile_positions, small_support   positions of a tile of the select kernel; the largest support a 16-lane group sums (above: a workgroup).
+ * Every argument is checked before any launch (DM_EINVAL, dm_last_error names the fault): null handles, the controls missing, tables of different
+ * lengths or on another device, cov < 1, alpha outside (0, 1]. */
+typedef struct dm_diffmod dm_diffmod;
+dm_diffmod* dm_diffmod_create(int device, int cov, double alpha);
+void dm_diffmod_destroy(dm_diffmod* h);
+int dm_diffmod_run(dm_diffmod* h, dm_summary* plus, dm_summary* minus, dm_summary* ctrl_plus, dm_summary* ctrl_minus, int64_t* counters, int64_t* n_records);
+int dm_diffmod_fetch_records(dm_diffmod* h, int64_t first, int64_t count, int32_t* pos, uint8_t* strand, int32_t* cA, int32_t* mA, int32_t* cB, int32_t* mB, double* p);
+int dm_diffmod_fetch_hist(dm_diffmod* h, int64_t* hist);
+int dm_diffmod_reset(dm_diffmod* h);
+int dm_diffmod_times(dm_diffmod* h, double* select_ms, double* fisher_ms);
+int dm_diffmod_max_total(void);
+int dm_diffmod_tile_positions(void);
+int dm_diffmod_small_support(void);
+int dm_diffmod_test_host(int cov, double alpha, int64_t len, const int32_t* cov_plus, const int32_t* mod_plus, const int32_t* cov_minus, const int32_t* mod_minus,
+                         const int32_t* ctrl_cov_plus, const int32_t* ctrl_mod_plus, const int32_t* ctrl_cov_minus, const int32_t* ctrl_mod_minus, int64_t* counters,
+                         int64_t* hist, int64_t cap, int32_t* pos, uint8_t* strand, int32_t* cA, int32_t* mA, int32_t* cB, int32_t* mB, double* p, int64_t* n_records);
+
 #ifdef __cplusplus
 }
 #endif
