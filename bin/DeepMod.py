@@ -78,6 +78,14 @@ two-sided p of Fisher's exact test on one GPU (R's fisher.test rule) and a Benja
 keys with q <= --fdr whose percentages differ by --minDelta points or more (--all 1: every tested key); O/id_diffmod.json has the counters, the p
 histogram and notes (deepmod_amd/diffmod.py).  Hand in mod_pos.* files.  Pooling runs before an exact test ignores the variation between
 replicates: the p-values are those of the pooled counts.
+
+`diffmod --replicates 1 --predFolder S1,S2[,..] --control C1,C2[,..] [--minReps a,b] ...` keeps the replicates apart instead: every folder of
+--predFolder is one sample replicate and every folder of --control one control replicate (1 to 8 each, 3 or more together).  A replicate counts at a
+key when it has --cov reads there; a key with a sample and b control replicates that count (--minReps, default all of them) gets the quasi-binomial
+F test of a two-group logistic model on one GPU: the deviance of the pooled 2 x 2 table over the dispersion phi = max(1, Pearson X2 / (replicates
+- 2)) between the replicates, p from F(1, replicates - 2).  The report gains the columns repA, repB and phi; q-values, --fdr, --minDelta and --all
+work as before.  The test reads 16 bytes of device memory per position and replicate
+(the tables of an open contig hold 24).
 """
 import argparse
 import os
@@ -301,10 +309,14 @@ def build_parser():
                                      'percentage of the sample and of the controls, delta, p, q of every key with q <= --fdr whose percentages differ by --minDelta '
                                      'points or more) and <outFolder>/<FileID>_diffmod.json (counters, the p histogram, notes, kernel times).  Hand in the mod_pos.* '
                                      'files of detect runs (summed files drop every position with a modified count of 0).  Pooling runs before an exact test ignores '
-                                     'the variation between replicates: the p-values are those of the pooled counts.  No replicate-aware (beta-binomial) test, no '
-                                     'motif restriction, and the two strands of a CpG are not merged.')
-    dif.add_argument('--predFolder', default=None, help='folder of the sample\'s runs: the BED files are searched one to three levels below it')
-    dif.add_argument('--control', default=None, help='folder(s) of control runs, separated by commas; pooled (needed)')
+                                     'the variation between replicates: the p-values are those of the pooled counts.  --replicates 1 keeps the replicates apart: '
+                                     'every folder of --predFolder and of --control is one replicate (1 to 8 each, 3 or more together), and every key with '
+                                     '--minReps replicates of --cov reads gets a quasi-binomial F test (the deviance of the pooled table over the dispersion between '
+                                     'the replicates); the report gains the columns repA, repB and phi.  No motif restriction, and the two strands of a CpG are not '
+                                     'merged.')
+    dif.add_argument('--predFolder', default=None, help='folder of the sample\'s runs: the BED files are searched one to three levels below it (--replicates 1: one folder per sample '
+                                                         'replicate, separated by commas)')
+    dif.add_argument('--control', default=None, help='folder(s) of control runs, separated by commas; pooled, or one replicate each under --replicates 1 (needed)')
     dif.add_argument('--Ref', default=None, help='reference genome FASTA: only fixes the contigs and their lengths (default: the tables grow with the files)')
     dif.add_argument('--Base', default='C', choices=['A', 'C', 'G', 'T'], help='the modified base: names the files (default C)')
     dif.add_argument('--chr', default=None, help='contigs, separated by commas (default: those of --Ref, or those the sample\'s file names hold)')
@@ -312,13 +324,17 @@ def build_parser():
     dif.add_argument('--fdr', type=float, default=0.05, help='a key is listed at this q-value or less, above 0 and at most 1 (default 0.05)')
     dif.add_argument('--minDelta', type=int, default=10, help='and when its percentages differ by this many points or more (default 10)')
     dif.add_argument('--all', type=int, default=0, help='1: write every tested key with its q, whatever --fdr and --minDelta (default 0)')
+    dif.add_argument('--replicates', type=int, default=0, help='1: every folder of --predFolder (separated by commas) and of --control is one replicate, tested by a '
+                                                                'quasi-binomial F test; 0: the folders are pooled (default 0)')
+    dif.add_argument('--minReps', default=None, help='with --replicates 1: a,b - a key is tested with at least a sample and b control replicates of --cov reads '
+                                                     '(default: every replicate)')
     dif.set_defaults(func=mDiffmod)
     return parser
 
 
 def mDiffmod(args):
     from deepmod_amd import diffmod
-    mo = {k: getattr(args, k) for k in ('predFolder', 'Ref', 'Base', 'outFolder', 'FileID', 'cov', 'fdr', 'minDelta', 'all', 'threads')}
+    mo = {k: getattr(args, k) for k in ('predFolder', 'Ref', 'Base', 'outFolder', 'FileID', 'cov', 'fdr', 'minDelta', 'all', 'threads', 'replicates', 'minReps')}
     mo['chr'] = [c for c in (args.chr or '').split(',') if c] or None
     mo['control'] = [c for c in (args.control or '').split(',') if c]
     try:

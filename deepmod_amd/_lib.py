@@ -254,6 +254,15 @@ SIGNATURES = [
     ("dm_diffmod_tile_positions", _c.c_int, []),
     ("dm_diffmod_small_support", _c.c_int, []),
     ("dm_diffmod_test_host", _c.c_int, [_c.c_int, _c.c_double, _i64] + [_vp] * 10 + [_i64] + [_vp] * 7 + [_c.POINTER(_i64)]),
+    ("dm_diffrep_create", _vp, [_c.c_int, _c.c_int, _c.c_double, _c.c_int, _c.c_int]),
+    ("dm_diffrep_destroy", None, [_vp]),
+    ("dm_diffrep_run", _c.c_int, [_vp, _c.c_int, _c.c_int, _vp, _vp, _vp, _c.POINTER(_i64)]),
+    ("dm_diffrep_fetch_records", _c.c_int, [_vp, _i64, _i64] + [_vp] * 10),
+    ("dm_diffrep_fetch_hist", _c.c_int, [_vp, _vp]),
+    ("dm_diffrep_reset", _c.c_int, [_vp]),
+    ("dm_diffrep_times", _c.c_int, [_vp, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
+    ("dm_diffrep_max_replicates", _c.c_int, []),
+    ("dm_diffrep_test_host", _c.c_int, [_c.c_int, _c.c_double] + [_c.c_int] * 4 + [_i64] + [_vp] * 6 + [_i64] + [_vp] * 10 + [_c.POINTER(_i64)]),
 ]
 
 

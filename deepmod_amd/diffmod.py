@@ -12,8 +12,9 @@ over the weight of all of them.  The engines hand back the counters, the tested 
 position, '+' before '-') and a 20-bin histogram of the p of every tested key.
 
 Pooling runs before an exact test ignores the variation between replicates: the p-values are those of the pooled counts, and they are smaller
-than a replicate-aware (beta-binomial) test would give when replicates disagree.  Such a test, a motif restriction and merging the two strands of
-a CpG are out of scope here.
+than a replicate-aware test gives when replicates disagree.  --replicates 1 is that test: every folder a replicate, a quasi-binomial F test per
+key (RepHostEngine below, csrc/diffrep.hip.inc on the GPU).  A motif restriction and merging the two strands of a CpG are out of
+scope in both.
 
 On the host (bh_qvalues): the records of all contigs are sorted by p (stable: ties keep contig, position, strand order), m is the number of
 tested keys of the whole run, q_j = min(1, min over k >= j of p_k m / k).  The records with p <= alpha suffice: a q-value is >= its p, and a
@@ -273,6 +274,275 @@ class DeviceEngine(_lib.Handle):
         self.n_records = 0
 
 
+# ---- the replicate-aware test (--replicates 1) ------------------------------------------------------------------------------------
+# Quasi-binomial F test of a two-group logistic model, the McCullagh-Nelder overdispersion correction, in closed form.  Every folder of --predFolder
+# is one sample replicate (KA of them), every folder of --control one control replicate (KB), 1..8 each and 3 or more together.  A key is (strand,
+# position); a modified count is first held to 0..coverage; replicate i is used at the key iff c_i >= cov; nA, nB are the used replicates of either
+# group, C_g and M_g the sums of c and m over them.  The first rule that applies decides:
+#   1  every c_i == 0: ignored       2  nA < a: shallow_sample       3  nB < b: shallow_control       4  C_A + C_B > MAX_TOTAL: too_deep       5  tested
+# with (a, b) = --minReps (default KA, KB).  A tested key: nu = nA + nB - 2, C = C_A + C_B, M = M_A + M_B.  M_A C_B == M_B C_A: p = 1, phi = 1.  Else
+#   h(M, C) = M ln(M / C) + (C - M) ln((C - M) / C)  (a term whose factor is 0 is 0),      D = max(0, 2 [h(M_A, C_A) + h(M_B, C_B) - h(M, C)]),
+#   X2 = sum over groups and used i of r_i^2 / (c_i M_g (C_g - M_g)),  r_i = m_i C_g - c_i M_g  (a group with M_g in {0, C_g} adds 0),
+#   phi = max(1, X2 / nu),  F = D / phi,  p = I_x(nu / 2, 1 / 2) at x = nu / (nu + F): the regularized incomplete beta, P(F(1, nu) >= F).
+# A record carries the sums over the used replicates as cA, mA, cB, mB, then nA, nB, phi and p.
+
+MAX_REPS = 8
+REP_RECORD_FIELDS = RECORD_FIELDS[:6] + (('nA', np.uint8), ('nB', np.uint8), ('phi', np.float64), ('p', np.float64))
+REP_HEADER = 'chr\tpos\tstrand\tcovA\tmodA\tpctA\tcovB\tmodB\tpctB\tdelta\trepA\trepB\tphi\tp\tq'
+REP_DIGITS = 50
+_PI = '3.14159265358979323846264338327950288419716898596868385569518'
+
+
+def check_rep_counts(n_a, n_b, min_a, min_b) -> None:
+    if not (1 <= int(n_a) <= MAX_REPS and 1 <= int(n_b) <= MAX_REPS):
+        raise DiffmodError('diffmod: --replicates 1: 1 to %d folders in --predFolder and in --control (got %d and %d)' % (MAX_REPS, n_a, n_b))
+    if int(n_a) + int(n_b) < 3:
+        raise DiffmodError('diffmod: --replicates 1: 3 or more replicates together (got %d and %d): no variation between replicates can be seen in fewer' % (n_a, n_b))
+    if not (1 <= int(min_a) <= int(n_a) and 1 <= int(min_b) <= int(n_b) and int(min_a) + int(min_b) >= 3):
+        raise DiffmodError('diffmod: --minReps: a,b with 1 <= a <= %d, 1 <= b <= %d and a + b >= 3 (got %d,%d)' % (n_a, n_b, min_a, min_b))
+
+
+def _rep_context():
+    import decimal
+    return decimal.Context(prec=REP_DIGITS, Emin=-999999, Emax=999999)
+
+
+def rep_beta(nu: int):
+    """B(nu / 2, 1 / 2) as a decimal: a rational for even nu, a rational times pi for odd nu."""
+    import decimal
+    from fractions import Fraction
+    ctx = _rep_context()
+    k = int(nu) // 2
+    half = Fraction(math.factorial(2 * k), 4 ** k * math.factorial(k))                    # Gamma(k + 1/2) / sqrt(pi)
+    if nu % 2 == 0:
+        b = Fraction(math.factorial(k - 1)) / half                                        # Gamma(k) sqrt(pi) / Gamma(k + 1/2)
+        return ctx.divide(decimal.Decimal(b.numerator), decimal.Decimal(b.denominator))
+    b = half / math.factorial(k)                                                          # Gamma(k + 1/2) sqrt(pi) / Gamma(k + 1), over pi
+    return ctx.multiply(ctx.divide(decimal.Decimal(b.numerator), decimal.Decimal(b.denominator)), decimal.Decimal(_PI))
+
+
+def rep_tail(nu: int, F):
+    """P(F(1, nu) >= F) = I_x(nu / 2, 1 / 2) at x = nu / (nu + F), as a 50-digit decimal: the hypergeometric series
+    I_x(a, b) = x^a (1 - x)^b / (a B(a, b)) sum over n of x^n (a + b)_n / (a + 1)_n for x <= 1/2, and 1 - I_(1-x)(b, a) by the same series above."""
+    import decimal
+    ctx = _rep_context()
+    D = decimal.Decimal
+    F = D(F) if not isinstance(F, decimal.Decimal) else F
+    if F <= 0:
+        return D(1)
+    den = ctx.add(D(int(nu)), F)
+    x, y = ctx.divide(D(int(nu)), den), ctx.divide(F, den)
+    rx, ry = ctx.sqrt(x), ctx.sqrt(y)
+
+    def series(a2, b2, z):                                            # sum of z^n (a2 / 2)_n / (b2 / 2)_n
+        t = s = D(1)
+        n = 0
+        while True:
+            t = ctx.divide(ctx.multiply(ctx.multiply(t, z), D(a2 + 2 * n)), D(b2 + 2 * n))
+            s = ctx.add(s, t)
+            n += 1
+            if t < s.scaleb(-(REP_DIGITS + 4)):
+                return s
+
+    front = ctx.divide(ctx.multiply(ctx.power(rx, int(nu)), ry), rep_beta(nu))              # x^a (1 - x)^(1/2) / B
+    if x <= D('0.5'):
+        return ctx.divide(ctx.multiply(ctx.multiply(front, D(2)), series(nu + 1, nu + 2, x)), D(int(nu)))
+    return ctx.subtract(D(1), ctx.multiply(ctx.multiply(front, D(2)), series(nu + 1, 3, y)))
+
+
+def rep_fate(cov: int, min_a: int, min_b: int, c_a, m_a, c_b, m_b):
+    """The fate of a key from the counts of its replicates as the tables hold them -> (index into COUNT_KEYS or -1 for ignored, the used (c, m) of
+    the sample, those of the controls), modified counts held to 0..coverage."""
+    groups = []
+    for cs, ms in ((c_a, m_a), (c_b, m_b)):
+        cs = [max(int(c), 0) for c in cs]
+        groups.append([(c, min(max(int(m), 0), c)) for c, m in zip(cs, ms)])
+    if not any(c for g in groups for c, _ in g):
+        return -1, [], []
+    used = [[(c, m) for c, m in g if c >= cov] for g in groups]
+    if len(used[0]) < min_a:
+        return 1, used[0], used[1]
+    if len(used[1]) < min_b:
+        return 2, used[0], used[1]
+    if sum(c for g in used for c, _ in g) > MAX_TOTAL:
+        return 3, used[0], used[1]
+    return 0, used[0], used[1]
+
+
+def rep_deviance(MA: int, CA: int, MB: int, CB: int):
+    """D of the contract as a 50-digit decimal."""
+    import decimal
+    ctx = _rep_context()
+    D = decimal.Decimal
+
+    def h(M, C):
+        v = D(0)
+        for k in (M, C - M):
+            if k > 0:
+                v = ctx.add(v, ctx.multiply(D(k), ctx.ln(ctx.divide(D(k), D(C)))))
+        return v
+
+    d = ctx.multiply(D(2), ctx.subtract(ctx.add(h(MA, CA), h(MB, CB)), h(MA + MB, CA + CB)))
+    return max(d, D(0))
+
+
+@functools.lru_cache(maxsize=1 << 16)
+def rep_exact(used_a: tuple, used_b: tuple) -> dict:
+    """The test of one tested key from its used replicates ((c, m), ..) of either group -> {'cA', 'mA', 'cB', 'mB', 'nA', 'nB', 'nu', 'equal',
+    'D', 'phi', 'p'}: integers, and 50-digit decimals for D, phi and p."""
+    import decimal
+    from fractions import Fraction
+    ctx = _rep_context()
+    CA, MA = sum(c for c, _ in used_a), sum(m for _, m in used_a)
+    CB, MB = sum(c for c, _ in used_b), sum(m for _, m in used_b)
+    nu = len(used_a) + len(used_b) - 2
+    out = {'cA': CA, 'mA': MA, 'cB': CB, 'mB': MB, 'nA': len(used_a), 'nB': len(used_b), 'nu': nu, 'equal': MA * CB == MB * CA}
+    if out['equal']:
+        out.update(D=decimal.Decimal(0), phi=decimal.Decimal(1), p=decimal.Decimal(1))
+        return out
+    x2 = Fraction(0)
+    for used, Cg, Mg in ((used_a, CA, MA), (used_b, CB, MB)):
+        if 0 < Mg < Cg:
+            x2 += sum(Fraction((m * Cg - c * Mg) ** 2, c * Mg * (Cg - Mg)) for c, m in used)
+    phi = max(Fraction(1), x2 / nu)
+    phi = ctx.divide(decimal.Decimal(phi.numerator), decimal.Decimal(phi.denominator))
+    d = rep_deviance(MA, CA, MB, CB)
+    out.update(D=d, phi=phi, p=rep_tail(nu, ctx.divide(d, phi)))
+    return out
+
+
+def rep_exact_p(used_a, used_b) -> float:
+    """p of a tested key from its used replicates ((c, m), ..) of either group, rounded once."""
+    return float(rep_exact(tuple(map(tuple, used_a)), tuple(map(tuple, used_b)))['p'])
+
+
+def empty_rep_records() -> Dict[str, np.ndarray]:
+    return {k: np.zeros(0, t) for k, t in REP_RECORD_FIELDS}
+
+
+class RepHostEngine:
+    """The semantics of --replicates 1, one contig per run(): integers for the fates and r_i, decimals at 50 digits for ln and the incomplete beta
+    (slow and correct: the oracle of every test; standard library and numpy only).  A table is a pair (coverage, modified) of integer arrays."""
+
+    def __init__(self, cov: int = 5, alpha: float = 0.05, min_a: int = 1, min_b: int = 2):
+        check_engine_options(cov, alpha)
+        if not (1 <= int(min_a) <= MAX_REPS and 1 <= int(min_b) <= MAX_REPS and int(min_a) + int(min_b) >= 3):
+            raise DiffmodError('diffmod: --minReps: a,b of 1 to %d each and 3 or more together (got %s,%s)' % (MAX_REPS, min_a, min_b))
+        self.cov, self.alpha, self.min_a, self.min_b = int(cov), float(alpha), int(min_a), int(min_b)
+        self.reset()
+
+    def close(self):
+        pass
+
+    def reset(self):
+        self.hist = np.zeros(HIST_BINS, np.int64)
+        self.counters = np.zeros((2, len(COUNT_KEYS)), np.int64)
+
+    def new_tables(self, role: str, name: str, length: Optional[int]) -> HostTables:
+        return HostTables(name, length)
+
+    def run(self, sample, control) -> Tuple[np.ndarray, Dict[str, np.ndarray]]:
+        """sample, control: [(plus, minus), ..], one pair of tables per replicate -> (counters [2][4] of this contig, the records with p <= alpha in
+        key order); hist and counters of the engine grow."""
+        n_a, n_b = len(sample), len(control)
+        check_rep_counts(n_a, n_b, self.min_a, self.min_b)
+        counters = np.zeros((2, len(COUNT_KEYS)), np.int64)
+        rows = []
+        for s in range(2):
+            tabs, n = _padded([rep[s] for rep in list(sample) + list(control)])
+            cs, ms = np.stack([t[0] for t in tabs]), np.stack([t[1] for t in tabs])
+            for q in np.nonzero((cs > 0).any(axis=0))[0].tolist():
+                c, m = cs[:, q].tolist(), ms[:, q].tolist()
+                f, ua, ub = rep_fate(self.cov, self.min_a, self.min_b, c[:n_a], m[:n_a], c[n_a:], m[n_a:])
+                counters[s, f] += 1
+                if f != 0:
+                    continue
+                e = rep_exact(tuple(ua), tuple(ub))
+                p = float(e['p'])
+                self.hist[min(HIST_BINS - 1, int(HIST_BINS * p))] += 1
+                if p <= self.alpha:
+                    rows.append((q, s, e['cA'], e['mA'], e['cB'], e['mB'], e['nA'], e['nB'], float(e['phi']), p))
+        rows.sort(key=lambda r: (r[0], r[1]))
+        self.counters += counters
+        return counters, {k: np.array([r[j] for r in rows], t) for j, (k, t) in enumerate(REP_RECORD_FIELDS)}
+
+    def fetch_hist(self) -> np.ndarray:
+        return self.hist.copy()
+
+    def times(self) -> Tuple[float, float]:
+        return 0.0, 0.0
+
+
+def max_replicates() -> int:
+    return _lib.load().dm_diffrep_max_replicates()
+
+
+def rep_host_routine(cov, alpha, min_a, min_b, sample, control):
+    """The run compiled for the host (dm_diffrep_test_host: the routine the kernel runs per key; no GPU needed).  sample, control: [(plus, minus),
+    ..] -> (counters [2][4], hist [20], records)."""
+    lib = _lib.load()
+    reps = list(sample) + list(control)
+    tabs, n = _padded([rep[s] for rep in reps for s in range(2)])                        # replicate j: '+' at 2 j, '-' at 2 j + 1
+    arrs = [[np.ascontiguousarray(a, np.int32) for a in t] for t in tabs]
+    ptrs = [(ctypes.c_void_p * len(reps))(*[arrs[2 * j + s][col].ctypes.data for j in range(len(reps))]) for s in range(2) for col in range(2)]
+    counters, hist = np.zeros((2, len(COUNT_KEYS)), np.int64), np.zeros(HIST_BINS, np.int64)
+    cap = 2 * n
+    rec = {k: np.zeros(max(cap, 1), t) for k, t in REP_RECORD_FIELDS}
+    got = ctypes.c_int64(0)
+    _lib.check(lib.dm_diffrep_test_host(int(cov), float(alpha), int(min_a), int(min_b), len(sample), len(control), n, *ptrs, counters.ctypes.data, hist.ctypes.data, cap,
+                                        *[rec[k].ctypes.data for k, _ in REP_RECORD_FIELDS], ctypes.byref(got)))
+    return counters, hist, {k: v[:got.value].copy() for k, v in rec.items()}
+
+
+class RepDeviceEngine(DeviceEngine):
+    """The same on one GPU (dm_diffrep_* of the C ABI): one merge.DeviceMerge per replicate (new_tables with a role per replicate); the sweep reads
+    16 bytes per position and replicate.  times(): ms of the counting pass / of the writing pass so far."""
+    PREFIX, N_TIMES = 'dm_diffrep', 2
+
+    def __init__(self, cov: int = 5, alpha: float = 0.05, min_a: int = 1, min_b: int = 2, device: int = 0):
+        check_engine_options(cov, alpha)
+        self.cov, self.alpha, self.min_a, self.min_b, self.device = int(cov), float(alpha), int(min_a), int(min_b), device
+        self._merge = {}
+        self._create(device, self.cov, self.alpha, self.min_a, self.min_b)
+        self.counters = np.zeros((2, len(COUNT_KEYS)), np.int64)
+        self.n_records = 0
+
+    def run(self, sample, control, fetch_run: int = FETCH_RUN) -> Tuple[np.ndarray, Dict[str, np.ndarray]]:
+        """sample, control: [(plus, minus), ..] of summary.PositionSummary, one pair per replicate."""
+        reps = list(sample) + list(control)
+        tabs = [t for rep in reps for t in rep]
+        if tabs and all(t is not None for t in tabs):
+            n = max(t.length for t in tabs)
+            for t in tabs:
+                if t.length < n:                                      # tables that grew with their files: to one length
+                    t.grow(n)
+        plus = (ctypes.c_void_p * max(len(reps), 1))(*[None if rep[0] is None else rep[0]._h for rep in reps])
+        minus = (ctypes.c_void_p * max(len(reps), 1))(*[None if rep[1] is None else rep[1]._h for rep in reps])
+        counters, got = np.zeros((2, len(COUNT_KEYS)), np.int64), ctypes.c_int64(0)
+        self._libmod.check(self._lib.dm_diffrep_run(self._h, len(sample), len(control), plus, minus, counters.ctypes.data, ctypes.byref(got)))
+        self.counters += counters
+        self.n_records = got.value
+        return counters, self.fetch_records(0, self.n_records, fetch_run)
+
+    def fetch_records(self, first: int, count: int, fetch_run: int = FETCH_RUN) -> Dict[str, np.ndarray]:
+        """Records first .. first + count - 1 of the last run, fetched in runs of fetch_run at most."""
+        rec = {k: np.zeros(count, t) for k, t in REP_RECORD_FIELDS}
+        for lo in range(0, count, max(int(fetch_run), 1)):
+            n = min(int(fetch_run), count - lo)
+            self._libmod.check(self._lib.dm_diffrep_fetch_records(self._h, first + lo, n, *[rec[k][lo:lo + n].ctypes.data for k, _ in REP_RECORD_FIELDS]))
+        return rec
+
+    def fetch_hist(self) -> np.ndarray:
+        hist = np.zeros(HIST_BINS, np.int64)
+        self._libmod.check(self._lib.dm_diffrep_fetch_hist(self._h, hist.ctypes.data))
+        return hist
+
+    def reset(self):
+        self._libmod.check(self._lib.dm_diffrep_reset(self._h))
+        self.counters[:] = 0
+        self.n_records = 0
+
+
 # ---- q-values -----------------------------------------------------------------------------------------------------------------------------------
 
 def bh_qvalues(p, m: int) -> np.ndarray:
@@ -304,9 +574,7 @@ def _contigs_of(folder: str, base: str) -> List[str]:
     return sorted(found)
 
 
-def check_options(mo: Dict[str, object]):
-    """What can be refused before a BED file is read or any GPU asked for -> (options dict, contigs, {contig: length or None}, {contig: sample
-    files}, {contig: control files})."""
+def _scalar_options(mo: Dict[str, object]) -> Dict[str, object]:
     base = str(mo.get('Base') or 'C')
     try:
         o = {'Base': base, 'cov': int(mo.get('cov', 5)), 'fdr': float(mo.get('fdr', 0.05)), 'minDelta': int(mo.get('minDelta', 10)), 'all': int(mo.get('all') or 0)}
@@ -319,15 +587,11 @@ def check_options(mo: Dict[str, object]):
         raise DiffmodError('diffmod: --minDelta: percentage points, 0 to 100 (got %d)' % o['minDelta'])
     if o['all'] not in (0, 1):
         raise DiffmodError('diffmod: --all: 0 or 1 (got %d)' % o['all'])
-    folder = mo.get('predFolder')
-    if not folder or not os.path.isdir(folder):
-        raise DiffmodError('diffmod: --predFolder: the folder of the sample\'s runs does not exist (%s)' % folder)
-    controls = [c for c in (mo.get('control') or []) if c]
-    if not controls:
-        raise DiffmodError('diffmod: --control: the folder(s) of the control runs are needed (the test is of the sample against them)')
-    for c in controls:
-        if not os.path.isdir(c):
-            raise DiffmodError('diffmod: --control: no folder %s' % c)
+    return o
+
+
+def _contigs(mo: Dict[str, object], base: str, folders: List[str]):
+    """-> (contigs, {contig: length or None}) from --Ref and --chr, or from the file names below `folders`."""
     ref = mo.get('Ref')
     if ref and not os.path.isfile(ref):
         raise DiffmodError('diffmod: --Ref: reference file does not exist (%s)' % ref)
@@ -337,11 +601,29 @@ def check_options(mo: Dict[str, object]):
         missing = [ck for ck in named if ck not in fasta]
         if missing:
             raise DiffmodError('diffmod: --chr: %s holds no contig %s' % (ref, ', '.join(missing)))
-    chrkeys = named or list(fasta) or _contigs_of(folder, base)
+    chrkeys = named or list(fasta) or sorted({ck for f in folders for ck in _contigs_of(f, base)})
     lengths = {ck: (len(fasta[ck]) if ck in fasta else None) for ck in chrkeys}
     for ck in chrkeys:
         if lengths[ck] is not None and not 1 <= lengths[ck] <= MAX_LENGTH:
             raise DiffmodError('diffmod: --Ref: contig %s has %d bases (1 to 2^31 - 1)' % (ck, lengths[ck]))
+    return chrkeys, lengths
+
+
+def check_options(mo: Dict[str, object]):
+    """What can be refused before a BED file is read or any GPU asked for -> (options dict, contigs, {contig: length or None}, {contig: sample
+    files}, {contig: control files})."""
+    o = _scalar_options(mo)
+    base = o['Base']
+    folder = mo.get('predFolder')
+    if not folder or not os.path.isdir(folder):
+        raise DiffmodError('diffmod: --predFolder: the folder of the sample\'s runs does not exist (%s)' % folder)
+    controls = [c for c in (mo.get('control') or []) if c]
+    if not controls:
+        raise DiffmodError('diffmod: --control: the folder(s) of the control runs are needed (the test is of the sample against them)')
+    for c in controls:
+        if not os.path.isdir(c):
+            raise DiffmodError('diffmod: --control: no folder %s' % c)
+    chrkeys, lengths = _contigs(mo, base, [folder])
     files = {ck: sorted(merge.find_bed_files(folder, ck, base)) for ck in chrkeys}          # (sorted: the order of the notes)
     ctrl_files = {ck: [p for c in controls for p in sorted(merge.find_bed_files(c, ck, base))] for ck in chrkeys}
     if not any(files.values()):
@@ -349,6 +631,43 @@ def check_options(mo: Dict[str, object]):
     if not any(ctrl_files.values()):
         raise DiffmodError('diffmod: --control: no *.<chr>+.%s.bed / *.<chr>-.%s.bed one to three levels below %s' % (base, base, ', '.join(controls)))
     return o, chrkeys, lengths, files, ctrl_files
+
+
+def check_rep_options(mo: Dict[str, object]):
+    """The same for --replicates 1 -> (options dict with `replicates` and `minReps`, contigs, lengths, {contig: [files of sample replicate 0, ..]},
+    {contig: [files of control replicate 0, ..]})."""
+    o = _scalar_options(mo)
+    base = o['Base']
+    pred = mo.get('predFolder') or []
+    samples = [f for f in (pred.split(',') if isinstance(pred, str) else list(pred)) if f]
+    controls = [c for c in (mo.get('control') or []) if c]
+    if not samples:
+        raise DiffmodError('diffmod: --predFolder: the folders of the sample replicates are needed, separated by commas')
+    if not controls:
+        raise DiffmodError('diffmod: --control: the folder(s) of the control replicates are needed (the test is of the sample against them)')
+    min_reps = mo.get('minReps')
+    try:
+        a, b = (len(samples), len(controls)) if min_reps in (None, '') else (int(v) for v in (min_reps.split(',') if isinstance(min_reps, str) else min_reps))
+    except (TypeError, ValueError):
+        raise DiffmodError('diffmod: --minReps: two integers a,b (got %r)' % (min_reps,))
+    check_rep_counts(len(samples), len(controls), a, b)
+    seen = {}
+    for option, folders in (('--predFolder', samples), ('--control', controls)):
+        for f in folders:
+            if not os.path.isdir(f):
+                raise DiffmodError('diffmod: %s: no folder %s' % (option, f))
+            real = os.path.realpath(f)
+            if real in seen:
+                raise DiffmodError('diffmod: %s: the folder %s is named twice (in %s and in %s): a replicate is one folder of its own' % (option, f, seen[real], option))
+            seen[real] = option
+    chrkeys, lengths = _contigs(mo, base, samples)
+    files = {ck: [sorted(merge.find_bed_files(f, ck, base)) for f in samples] for ck in chrkeys}
+    ctrl_files = {ck: [sorted(merge.find_bed_files(c, ck, base)) for c in controls] for ck in chrkeys}
+    for option, folders, found in (('--predFolder', samples, files), ('--control', controls, ctrl_files)):
+        for j, f in enumerate(folders):
+            if not any(found[ck][j] for ck in chrkeys):
+                raise DiffmodError('diffmod: %s: no *.<chr>+.%s.bed / *.<chr>-.%s.bed one to three levels below %s' % (option, base, base, f))
+    return dict(o, replicates={'sample': samples, 'control': controls}, minReps=[a, b]), chrkeys, lengths, files, ctrl_files
 
 
 def _read_into(tables, path: str, text: bytes, name: str, length: Optional[int], notes: List[str]) -> int:
@@ -374,13 +693,142 @@ def report_text(rows) -> str:
     return ''.join(r + '\n' for r in out)
 
 
-def diffmod(mo: Dict[str, object], engine=None) -> Dict[str, object]:
-    """The command.  mo: predFolder, control (list of folders), Base, outFolder, FileID, chr (list; None: the contigs of --Ref, or without it those
-    the sample's file names hold), Ref (None: the tables grow with the files), cov, fdr, minDelta, all, threads.  engine: an object with
-    HostEngine's interface (default: DeviceEngine on GPU 0), made with cov and alpha = fdr (1 under all).  Writes
-    <outFolder>/<FileID>_diffmod.txt / _diffmod.json -> the JSON document."""
+def replicates_option(mo: Dict[str, object]) -> int:
+    """--replicates, 0 or 1; --minReps belongs to 1 alone."""
+    try:
+        rep = int(mo.get('replicates') or 0)
+    except (TypeError, ValueError):
+        rep = -1
+    if rep not in (0, 1):
+        raise DiffmodError('diffmod: --replicates: 0 or 1 (got %s)' % (mo.get('replicates'),))
+    if not rep and mo.get('minReps') not in (None, ''):
+        raise DiffmodError('diffmod: --minReps: only with --replicates 1 (pooled runs have no replicates to count)')
+    return rep
+
+
+def rep_report_text(rows) -> str:
+    """rows: (chr, pos, strand 0 / 1, cA, mA, cB, mB, nA, nB, phi, p, q) -> the header and one line per row."""
+    out = [REP_HEADER]
+    for ck, pos, s, cA, mA, cB, mB, nA, nB, phi, p, q in rows:
+        out.append('%s\t%d\t%s\t%d\t%d\t%d\t%d\t%d\t%d\t%.2f\t%d\t%d\t%.4f\t%.6e\t%.6e' % (ck, pos, '+-'[s], cA, mA, 100 * mA // cA, cB, mB, 100 * mB // cB,
+                                                                                                100.0 * mA / cA - 100.0 * mB / cB, nA, nB, phi, p, q))
+    return ''.join(r + '\n' for r in out)
+
+
+def diffmod_replicates(mo: Dict[str, object], engine=None) -> Dict[str, object]:
+    """The command under --replicates 1.  mo as for diffmod(), with predFolder the sample replicates' folders (a list, or one string with commas),
+    control the control replicates' folders and minReps (a,b; None: every replicate).  engine: an object with RepHostEngine's interface (default:
+    RepDeviceEngine on GPU 0), made with cov, alpha = fdr (1 under all) and minReps.  On the device the test reads 16 bytes per position and
+    replicate of the open contig (its tables hold 24)."""
     import json
     from concurrent.futures import ThreadPoolExecutor
+    replicates_option(mo)
+    o, chrkeys, lengths, files, ctrl_files = check_rep_options(mo)
+    alpha = 1.0 if o['all'] else o['fdr']
+    (a, b), reps = o['minReps'], o['replicates']
+    own = engine is None
+    if own:
+        if _lib.load().dm_device_count() < 1:
+            raise DiffmodError('no gfx950 GPU visible (this build has no CPU path)')
+        try:
+            engine = RepDeviceEngine(o['cov'], alpha, a, b)
+        except _lib.DeepModHipError as exc:
+            raise DiffmodError('diffmod: %s' % exc)
+    elif (engine.cov, engine.alpha, engine.min_a, engine.min_b) != (o['cov'], alpha, a, b):
+        raise DiffmodError('diffmod: the engine was made for cov %d alpha %g minReps %d,%d' % (engine.cov, engine.alpha, engine.min_a, engine.min_b))
+
+    def read(path):
+        with open(path, 'rb') as fh:
+            return fh.read()
+
+    notes: List[str] = []
+    doc = {'test': 'quasibinomial-F',
+           'inputs': dict(o, predFolder=reps['sample'], control=reps['control'], Ref=mo.get('Ref'), chr=chrkeys, FileID=str(mo.get('FileID') or 'mod'),
+                          files=[p for ck in chrkeys for rep in files[ck] for p in rep], control_files=[p for ck in chrkeys for rep in ctrl_files[ck] for p in rep]),
+           'replicates': reps, 'minReps': [a, b], 'contigs': {}}
+    per_contig = []
+    try:
+        engine.reset()
+        with ThreadPoolExecutor(max(int(mo.get('threads') or 1), 1)) as pool:
+            for ck in chrkeys:
+                if not any(files[ck]) and not any(ctrl_files[ck]):
+                    continue
+                entry = {'length': lengths[ck], 'files': [len(rep) for rep in files[ck]], 'control_files': [len(rep) for rep in ctrl_files[ck]],
+                         'lines_read': [0] * len(files[ck]), 'control_lines_read': [0] * len(ctrl_files[ck])}
+                groups = {'sample': [], 'control': []}
+                try:
+                    for role, found, key in (('sample', files[ck], 'lines_read'), ('control', ctrl_files[ck], 'control_lines_read')):
+                        for j, paths in enumerate(found):
+                            t = engine.new_tables('%s%d' % (role, j), ck, lengths[ck])
+                            for path, text in zip(paths, pool.map(read, paths)):      # the threads read ahead
+                                try:
+                                    entry[key][j] += _read_into(t, path, text, ck, lengths[ck], notes)
+                                except DiffmodError:
+                                    raise
+                                except (ValueError, RuntimeError) as exc:             # the tables' own refusals (a coverage sum past int32)
+                                    raise DiffmodError('diffmod: %s: %s' % (path, exc))
+                            groups[role].append((t.plus, t.minus))
+                    counters, rec = engine.run(groups['sample'], groups['control'])
+                except _lib.DeepModHipError as exc:                                   # device memory that ran out, for one: a line, not a trace
+                    raise DiffmodError('diffmod: %s: %s' % (ck, exc))
+                for s, strand in enumerate('+-'):
+                    entry[strand] = dict(zip(COUNT_KEYS, (int(v) for v in counters[s])))
+                    if counters[s][3]:
+                        notes.append('%s %s: %d keys whose used replicates sum to a coverage above %d were not tested' % (ck, strand, int(counters[s][3]), MAX_TOTAL))
+                doc['contigs'][ck] = entry
+                per_contig.append((ck, rec))
+        hist = engine.fetch_hist()
+        times = engine.times()
+    finally:
+        if own:
+            engine.close()
+    m = int(sum(doc['contigs'][ck][s]['tested'] for ck in doc['contigs'] for s in '+-'))
+    p_all = np.concatenate([rec['p'] for _, rec in per_contig]) if per_contig else np.zeros(0)
+    q_all = bh_qvalues(p_all, m)
+    rows, hyper, hypo, at = [], 0, 0, 0
+    for ck, rec in per_contig:
+        n = len(rec['p'])
+        q = q_all[at:at + n]
+        at += n
+        cA, mA, cB, mB = (rec[k].astype(np.int64) for k in ('cA', 'mA', 'cB', 'mB'))
+        keep = np.ones(n, bool) if o['all'] else (q <= o['fdr']) & delta_passes(cA, mA, cB, mB, o['minDelta'])
+        sign = np.sign(mA * cB - mB * cA)
+        for s, strand in enumerate('+-'):
+            doc['contigs'][ck][strand]['listed'] = int((keep & (rec['strand'] == s)).sum())
+        hyper += int((keep & (sign > 0)).sum())
+        hypo += int((keep & (sign < 0)).sum())
+        for i in np.nonzero(keep)[0].tolist():
+            rows.append((ck, int(rec['pos'][i]), int(rec['strand'][i]), int(cA[i]), int(mA[i]), int(cB[i]), int(mB[i]), int(rec['nA'][i]), int(rec['nB'][i]),
+                         float(rec['phi'][i]), float(rec['p'][i]), float(q[i])))
+    if m == 0:
+        notes.append('no key had --cov %d reads in %d sample and %d control replicates' % (o['cov'], a, b))
+    doc['m'] = m
+    doc['listed'], doc['hyper'], doc['hypo'] = len(rows), hyper, hypo
+    doc['p_histogram'] = [int(v) for v in hist]
+    doc['notes'] = notes
+    doc['times'] = {'count_ms': round(times[0], 4), 'write_ms': round(times[1], 4)}
+    out_folder = str(mo['outFolder'])
+    os.makedirs(out_folder, exist_ok=True)
+    prefix = os.path.join(out_folder, doc['inputs']['FileID'])
+    with open(prefix + '_diffmod.txt', 'w') as fh:
+        fh.write(rep_report_text(rows))
+    with open(prefix + '_diffmod.json', 'w') as fh:
+        json.dump(doc, fh, indent=1)
+    for ln in notes:
+        print(ln, flush=True)
+    print('diffmod: %d keys tested, %d listed (%d above the controls, %d below) -> %s_diffmod.txt' % (m, len(rows), hyper, hypo, prefix), flush=True)
+    return doc
+
+
+def diffmod(mo: Dict[str, object], engine=None) -> Dict[str, object]:
+    """The command.  mo: predFolder, control (list of folders), Base, outFolder, FileID, chr (list; None: the contigs of --Ref, or without it those
+    the sample's file names hold), Ref (None: the tables grow with the files), cov, fdr, minDelta, all, threads; replicates 1 with minReps: the
+    replicate-aware test (diffmod_replicates).  engine: an object with HostEngine's interface (default: DeviceEngine on GPU 0), made with cov and
+    alpha = fdr (1 under all).  Writes <outFolder>/<FileID>_diffmod.txt / _diffmod.json -> the JSON document."""
+    import json
+    from concurrent.futures import ThreadPoolExecutor
+    if replicates_option(mo):
+        return diffmod_replicates(mo, engine)
     o, chrkeys, lengths, files, ctrl_files = check_options(mo)
     alpha = 1.0 if o['all'] else o['fdr']
     controls = [c for c in (mo.get('control') or []) if c]

@@ -972,6 +972,49 @@ int dm_diffmod_test_host(int cov, double alpha, int64_t len, const int32_t* cov_
                          const int32_t* ctrl_cov_plus, const int32_t* ctrl_mod_plus, const int32_t* ctrl_cov_minus, const int32_t* ctrl_mod_minus, int64_t* counters,
                          int64_t* hist, int64_t cap, int32_t* pos, uint8_t* strand, int32_t* cA, int32_t* mA, int32_t* cB, int32_t* mB, double* p, int64_t* n_records);
 
+/* -------------------------------------------------------------------------- diffmod --replicates -- */
+/* The replicate-aware per-site test (csrc/diffrep.hip.inc, diffrep.inc): one run joins the tables of n_a sample and n_b control
+ * replicates of a contig (1..8 each, 3 or more together) and gives every key (strand, position) the quasi-binomial F test of a two-group
+ * logistic model (the McCullagh-Nelder overdispersion correction), in closed form.  A modified count is held to 0..coverage; replicate i is used
+ * at the key iff c_i >= cov; nA, nB are the used replicates of either group, C_g and M_g the sums over them.  The first rule that applies decides:
+ *   1  every c_i == 0: ignored       2  nA < min_a: shallow_sample       3  nB < min_b: shallow_control
+ *   4  C_A + C_B > dm_diffmod_max_total() (2^20, formed in 64 bits): too_deep              5  tested
+ * A tested key: nu = nA + nB - 2, C = C_A + C_B, M = M_A + M_B.  M_A C_B == M_B C_A in integers: p = 1 and phi = 1 exactly.  Else, with
+ * h(M, C) = M ln(M / C) + (C - M) ln((C - M) / C) (a term whose factor is 0 is 0):
+ *   D = max(0, 2 [h(M_A, C_A) + h(M_B, C_B) - h(M, C)]),   X2 = sum over groups and used i of r_i^2 / (c_i M_g (C_g - M_g)),  r_i = m_i C_g - c_i M_g
+ *   (a group with M_g in {0, C_g} adds 0),   phi = max(1, X2 / nu),   F = D / phi,   p = I_x(nu / 2, 1 / 2) at x = nu / (nu + F).
+ * All in fp64; the incomplete beta is a power series, reflected at x = 1/2, whose terms depend on the key alone, so two runs give the same bits.
+ * D is within 18 * 2^-53 * C of its value, phi and the evaluation of p at that D and phi within 2.5e-11 relative.
+ * deepmod_amd/diffmod.py (RepHostEngine) states the semantics in integers and 50-digit decimals.
+ *   create         cov >= 1; 0 < alpha <= 1; 1 <= min_a, min_b <= 8, min_a + min_b >= 3.  A zeroed p histogram.
+ *   run            one contig: plus[j], minus[j] are the tables of replicate j, the n_a sample replicates first, then the n_b control replicates;
+ *                  2 (n_a + n_b) different tables on the handle's device and of one length; min_a <= n_a, min_b <= n_b.  counters
+ *                  [2 strands][4] (tested, shallow_sample, shallow_control, too_deep) are those of this contig; the p histogram grows by every
+ *                  tested key; *n_records = the tested keys with p <= alpha, held on the device until the next run.
+ *   fetch_records  records first .. first + count - 1 of the last run, in key order (ascending position, '+' before '-'): position, strand (0 '+',
+ *                  1 '-'), cA, mA, cB, mB (the sums over the used replicates), nA, nB, phi, p.
+ *   fetch_hist     int64 [20]: bin min(19, int(20 p)) of every key tested since create / reset.      reset   zeroes it.
+ *   test_host      the same run compiled for the host (no GPU needed): cov_plus .. mod_minus are n_a + n_b pointers each, sample replicates first,
+ *                  to plain arrays of len >= 0 entries; counters are set, hist is added to, *n_records is the number of records, of which the
+ *                  first cap are written.
+ *   times          ms of the counting pass (with its scan) / of the writing pass so far (HIP events).
+ *   max_replicates replicates of a group at most (8).  A tile of the sweep has dm_diffmod_tile_positions() positions.
+ * Every argument is checked before any launch (DM_EINVAL, dm_last_error names the fault): null or repeated handles, n_a or n_b outside 1..8,
+ * n_a + n_b < 3, least counts outside their ranges, tables of different lengths or on another device, cov < 1, alpha outside (0, 1]. */
+typedef struct dm_diffrep dm_diffrep;
+dm_diffrep* dm_diffrep_create(int device, int cov, double alpha, int min_a, int min_b);
+void dm_diffrep_destroy(dm_diffrep* h);
+int dm_diffrep_run(dm_diffrep* h, int n_a, int n_b, dm_summary* const* plus, dm_summary* const* minus, int64_t* counters, int64_t* n_records);
+int dm_diffrep_fetch_records(dm_diffrep* h, int64_t first, int64_t count, int32_t* pos, uint8_t* strand, int32_t* cA, int32_t* mA, int32_t* cB, int32_t* mB, uint8_t* nA,
+                             uint8_t* nB, double* phi, double* p);
+int dm_diffrep_fetch_hist(dm_diffrep* h, int64_t* hist);
+int dm_diffrep_reset(dm_diffrep* h);
+int dm_diffrep_times(dm_diffrep* h, double* count_ms, double* write_ms);
+int dm_diffrep_max_replicates(void);
+int dm_diffrep_test_host(int cov, double alpha, int min_a, int min_b, int n_a, int n_b, int64_t len, const int32_t* const* cov_plus, const int32_t* const* mod_plus,
+                         const int32_t* const* cov_minus, const int32_t* const* mod_minus, int64_t* counters, int64_t* hist, int64_t cap, int32_t* pos, uint8_t* strand,
+                         int32_t* cA, int32_t* mA, int32_t* cB, int32_t* mB, uint8_t* nA, uint8_t* nB, double* phi, double* p, int64_t* n_records);
+
 #ifdef __cplusplus
 }
 #endif
