@@ -19,7 +19,7 @@ from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
 
-from . import _lib, merge, siteperf
+from . import _lib, merge, siteperf, tables
 
 NPCT, MAX_THRESHOLDS, MAX_REPLICATES, MAX_CONTIGS, MAX_NAME, MAX_COV, SHORT_LINE = 101, 8, 4, 64, 63, 65535, 20
 MAX_LENGTH = merge.MAX_LENGTH
@@ -497,10 +497,6 @@ def bsperf(mo: Dict[str, object], device: int = 0, chunk_bytes: int = CHUNK_BYTE
     R = len(truth)
     phase = {k: 0.0 for k in ('read', 'parse', 'bucket', 'fill', 'merge', 'count', 'cluster')}
 
-    def read(path):
-        with open(path, 'rb') as fh:
-            return fh.read()
-
     eng = DeviceEngine(chrkeys, thresholds, R, methylated, unmethylated, pred_cov, lengths, device)
     dev = merge.DeviceMerge(device)
     model = cluster.ClusterModel.from_checkpoint(prefix, device) if prefix else None
@@ -523,19 +519,11 @@ def bsperf(mo: Dict[str, object], device: int = 0, chunk_bytes: int = CHUNK_BYTE
                     continue
                 t0 = time.perf_counter()
                 seq = fasta.get(ck)
-                limit = len(seq) if seq is not None else MAX_LENGTH
                 dev.open(ck, len(seq) if seq is not None else None)
-                for path, text in zip(files, pool.map(read, files)):                  # the threads read ahead
-                    lines, flag, bad = dev.add_text(text)
-                    if flag:
-                        entry['notes'].append('%s: line %d is outside the device grammar: the file is parsed on the host' % (path, bad))
-                        try:
-                            rec = merge.host_rows(path, ck, limit)
-                        except merge.MergeError as exc:
-                            raise BsPerfError(str(exc))
-                        dev.add_records(*rec)
-                        lines = len(rec[0])
-                    entry['lines_read'] += int(lines)
+                try:
+                    entry['lines_read'] = tables.fill(dev, files, pool, ck, len(seq) if seq is not None else MAX_LENGTH, entry['notes'])
+                except merge.MergeError as exc:
+                    raise BsPerfError(str(exc))
                 if seq is None:                                                        # the contig is as long as the largest position seen + 1
                     need = max([dev.plus.length] + [int(h[0].max()) + 1 for h in have if h is not None and len(h[0])])
                     dev.plus.grow(need)

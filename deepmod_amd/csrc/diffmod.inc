@@ -160,16 +160,15 @@ extern "C" int dm_diffmod_test_host(int cov, double alpha, int64_t len, const in
 #if defined(__HIP__) && !defined(DM_DIFFMOD_HANDLE_INC) && !defined(DM_DIFFMOD_RULE_ONLY)
 #define DM_DIFFMOD_HANDLE_INC
 #include "diffmod.hip.inc"
+#include "tablestage.hip.inc"
 
-struct dm_diffmod {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};        // select: count pass, write pass; fisher: begin / end each
+struct dm_diffmod_buf {
     // LF: the table; HIST [20]; COUNTS: the counters [2][4], then n_work, n_large, n_records; TILE_N / TILE_OFF: tested keys per tile and their scan;
     // the work list: KEY (2 pos + strand), CA, MA, CB, MB, P; LARGE: indices of the keys above SMALL_S; CHUNK_N / CHUNK_OFF: records per chunk of the
     // work list and their scan; the records: R_POS .. R_P
     enum { LF, HIST, COUNTS, TILE_N, TILE_OFF, KEY, CA, MA, CB, MB, P, LARGE, CHUNK_N, CHUNK_OFF, R_POS, R_STRAND, R_CA, R_MA, R_CB, R_MB, R_P, N_BUF };
-    DevBufs<N_BUF> b{"dm_diffmod"};
+};
+struct dm_diffmod : dm_diffmod_buf, TableStage<6, dm_diffmod_buf::N_BUF> {    // events: select: count pass, write pass; fisher: begin / end each
     int cov = 0;
     double alpha = 0.0;
     long long n_records = 0;                        // of the last run
@@ -183,12 +182,7 @@ int dm_diffmod_small_support(void) { return dfk::SMALL_S; }
 
 void dm_diffmod_destroy(dm_diffmod* h) {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->b.release();
-    for (hipEvent_t e : h->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    h->shut();
     delete h;
 }
 
@@ -198,23 +192,16 @@ dm_diffmod* dm_diffmod_create(int device, int cov, double alpha) {
         fail(DM_EINVAL, "dm_diffmod_create: %s (got cov %d alpha %g)", why, cov, alpha);
         return nullptr;
     }
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) {
-        (void)hipGetLastError();
-        fail(DM_EDEVICE, "dm_diffmod_create: no device %d", device);
-        return nullptr;
-    }
+    if (!table_stage_device("dm_diffmod", device)) return nullptr;
     using B = dm_diffmod;
     dm_diffmod* h = new dm_diffmod;
-    h->device = device;
     h->cov = cov;
     h->alpha = alpha;
     const size_t lf_bytes = (size_t(dfk::MAX_TOTAL) + 1) * sizeof(double);
-    bool ok = hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess;
-    for (hipEvent_t& e : h->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+    bool ok = h->open(device, "dm_diffmod");
     ok = ok && h->b.ensure(B::LF, lf_bytes) == DM_OK && h->b.ensure(B::HIST, dfk::HIST_BINS * 8) == DM_OK && h->b.ensure(B::COUNTS, dfk::N_WORDS * 8) == DM_OK;
     ok = ok && hipMemcpyAsync(h->b.buf[B::LF], dfk::lf_table(), lf_bytes, hipMemcpyHostToDevice, h->stream) == hipSuccess;
-    ok = ok && hipMemsetAsync(h->b.buf[B::HIST], 0, dfk::HIST_BINS * 8, h->stream) == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess;
+    ok = ok && h->zero_block(B::HIST, dfk::HIST_BINS * 8) == DM_OK;
     if (!ok) {
         (void)hipGetLastError();
         fail(DM_EDEVICE, "dm_diffmod_create: stream, events, table or counters on device %d", device);
@@ -235,14 +222,11 @@ int dm_diffmod_run(dm_diffmod* h, dm_summary* plus, dm_summary* minus, dm_summar
     dm_summary* tab[4] = {plus, minus, ctrl_plus, ctrl_minus};
     const long long len = dm_summary_length(plus);
     if (len < 1 || len > dfk::MAX_LENGTH) return fail(DM_EINVAL, "dm_diffmod_run: tables of %lld positions (1 to 2^31 - 1)", len);
-    for (int j = 0; j < 4; ++j) {
-        if (tab[j]->device != h->device) return fail(DM_EINVAL, "dm_diffmod_run: table %d is on device %d, the handle on device %d", j, tab[j]->device, h->device);
+    for (int j = 0; j < 4; ++j)
         if (dm_summary_length(tab[j]) != len)
             return fail(DM_EINVAL, "dm_diffmod_run: tables of different lengths: table %d has %lld positions, table 0 %lld", j, (long long)dm_summary_length(tab[j]), len);
-    }
     int rc;
-    for (int j = 0; j < 4; ++j)
-        if ((rc = dm_summary_sync(tab[j])) != DM_OK) return rc;       // the tables have streams of their own
+    if ((rc = h->tables_ready("dm_diffmod_run", tab, 4)) != DM_OK) return rc;
     HIP_TRY(hipSetDevice(h->device));
     h->n_records = 0;
     const long long tiles = (len + dfk::TILE_POS - 1) / dfk::TILE_POS;
@@ -339,19 +323,13 @@ int dm_diffmod_fetch_records(dm_diffmod* h, int64_t first, int64_t count, int32_
 int dm_diffmod_fetch_hist(dm_diffmod* h, int64_t* hist) {
     if (!h) return fail(DM_EINVAL, "null handle");
     if (!hist) return fail(DM_EINVAL, "dm_diffmod_fetch_hist: null argument");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemcpyAsync(hist, h->b.buf[dm_diffmod::HIST], dfk::HIST_BINS * 8, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return DM_OK;
+    return h->fetch_block(dm_diffmod::HIST, hist, dfk::HIST_BINS * 8);
 }
 
 int dm_diffmod_reset(dm_diffmod* h) {
     if (!h) return fail(DM_EINVAL, "null handle");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemsetAsync(h->b.buf[dm_diffmod::HIST], 0, dfk::HIST_BINS * 8, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
     h->n_records = 0;
-    return DM_OK;
+    return h->zero_block(dm_diffmod::HIST, dfk::HIST_BINS * 8);
 }
 
 int dm_diffmod_times(dm_diffmod* h, double* select_ms, double* fisher_ms) {

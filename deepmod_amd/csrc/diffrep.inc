@@ -230,14 +230,13 @@ extern "C" int dm_diffrep_test_host(int cov, double alpha, int min_a, int min_b,
 #if defined(__HIP__) && !defined(DM_DIFFREP_HANDLE_INC) && !defined(DM_DIFFREP_RULE_ONLY)
 #define DM_DIFFREP_HANDLE_INC
 #include "diffrep.hip.inc"
+#include "tablestage.hip.inc"
 
-struct dm_diffrep {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};         // the count pass with its scan, the write pass: begin / end each
+struct dm_diffrep_buf {
     // HIST [20]; COUNTS: the counters [2][4], then n_records; TILE_N / TILE_OFF: records per tile and their scan; the records: R_POS .. R_P
     enum { HIST, COUNTS, TILE_N, TILE_OFF, R_POS, R_STRAND, R_CA, R_MA, R_CB, R_MB, R_NA, R_NB, R_PHI, R_P, N_BUF };
-    DevBufs<N_BUF> b{"dm_diffrep"};
+};
+struct dm_diffrep : dm_diffrep_buf, TableStage<4, dm_diffrep_buf::N_BUF> {    // events: the count pass with its scan, the write pass: begin / end each
     int cov = 0, min_a = 0, min_b = 0;
     double alpha = 0.0;
     long long n_records = 0;                        // of the last run
@@ -248,12 +247,7 @@ extern "C" {
 
 void dm_diffrep_destroy(dm_diffrep* h) {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->b.release();
-    for (hipEvent_t e : h->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    h->shut();
     delete h;
 }
 
@@ -262,20 +256,13 @@ dm_diffrep* dm_diffrep_create(int device, int cov, double alpha, int min_a, int 
         fail(DM_EINVAL, "dm_diffrep_create: %s (got cov %d alpha %g least counts %d, %d)", why, cov, alpha, min_a, min_b);
         return nullptr;
     }
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) {
-        (void)hipGetLastError();
-        fail(DM_EDEVICE, "dm_diffrep_create: no device %d", device);
-        return nullptr;
-    }
+    if (!table_stage_device("dm_diffrep", device)) return nullptr;
     using B = dm_diffrep;
     dm_diffrep* h = new dm_diffrep;
-    h->device = device;
     h->cov = cov, h->alpha = alpha, h->min_a = min_a, h->min_b = min_b;
-    bool ok = hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess;
-    for (hipEvent_t& e : h->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+    bool ok = h->open(device, "dm_diffrep");
     ok = ok && h->b.ensure(B::HIST, dfr::HIST_BINS * 8) == DM_OK && h->b.ensure(B::COUNTS, dfr::N_WORDS * 8) == DM_OK;
-    ok = ok && hipMemsetAsync(h->b.buf[B::HIST], 0, dfr::HIST_BINS * 8, h->stream) == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess;
+    ok = ok && h->zero_block(B::HIST, dfr::HIST_BINS * 8) == DM_OK;
     if (!ok) {
         (void)hipGetLastError();
         fail(DM_EDEVICE, "dm_diffrep_create: stream, events or counters on device %d", device);
@@ -302,14 +289,11 @@ int dm_diffrep_run(dm_diffrep* h, int n_a, int n_b, dm_summary* const* plus, dm_
             if (tab[j] == tab[k]) return fail(DM_EINVAL, "dm_diffrep_run: the same table twice (replicate %d and replicate %d): every replicate has two tables of its own", k / 2, j / 2);
     const long long len = dm_summary_length(tab[0]);
     if (len < 1 || len > dfr::MAX_LENGTH) return fail(DM_EINVAL, "dm_diffrep_run: tables of %lld positions (1 to 2^31 - 1)", len);
-    for (int j = 0; j < 2 * reps; ++j) {
-        if (tab[j]->device != h->device) return fail(DM_EINVAL, "dm_diffrep_run: table %d is on device %d, the handle on device %d", j, tab[j]->device, h->device);
+    for (int j = 0; j < 2 * reps; ++j)
         if (dm_summary_length(tab[j]) != len)
             return fail(DM_EINVAL, "dm_diffrep_run: tables of different lengths: table %d has %lld positions, table 0 %lld", j, (long long)dm_summary_length(tab[j]), len);
-    }
     int rc;
-    for (int j = 0; j < 2 * reps; ++j)
-        if ((rc = dm_summary_sync(tab[j])) != DM_OK) return rc;       // the tables have streams of their own
+    if ((rc = h->tables_ready("dm_diffrep_run", tab, 2 * reps)) != DM_OK) return rc;
     HIP_TRY(hipSetDevice(h->device));
     h->n_records = 0;
     const long long tiles = (len + dfr::TILE_POS - 1) / dfr::TILE_POS;
@@ -389,19 +373,13 @@ int dm_diffrep_fetch_records(dm_diffrep* h, int64_t first, int64_t count, int32_
 int dm_diffrep_fetch_hist(dm_diffrep* h, int64_t* hist) {
     if (!h) return fail(DM_EINVAL, "null handle");
     if (!hist) return fail(DM_EINVAL, "dm_diffrep_fetch_hist: null argument");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemcpyAsync(hist, h->b.buf[dm_diffrep::HIST], dfr::HIST_BINS * 8, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return DM_OK;
+    return h->fetch_block(dm_diffrep::HIST, hist, dfr::HIST_BINS * 8);
 }
 
 int dm_diffrep_reset(dm_diffrep* h) {
     if (!h) return fail(DM_EINVAL, "null handle");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemsetAsync(h->b.buf[dm_diffrep::HIST], 0, dfr::HIST_BINS * 8, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
     h->n_records = 0;
-    return DM_OK;
+    return h->zero_block(dm_diffrep::HIST, dfr::HIST_BINS * 8);
 }
 
 int dm_diffrep_times(dm_diffrep* h, double* count_ms, double* write_ms) {

@@ -137,13 +137,12 @@ extern "C" int dm_motifs_count_host(int up, int down, char base, int cov, int mi
 #if defined(__HIP__) && !defined(DM_MOTIFS_HANDLE_INC) && !defined(DM_MOTIFS_RULE_ONLY)
 #define DM_MOTIFS_HANDLE_INC
 #include "motifs.hip.inc"
+#include "tablestage.hip.inc"
 
-struct dm_motifs {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};        // upload, count: begin / end
+struct dm_motifs_buf {
     enum { SEQ, HIST, COUNTS, N_BUF };
-    DevBufs<N_BUF> b{"dm_motifs"};
+};
+struct dm_motifs : dm_motifs_buf, TableStage<4, dm_motifs_buf::N_BUF> {       // events: upload, count: begin / end
     mok::Rule rule = {};
     long long bins = 0;
     double upload_ms = 0.0, count_ms = 0.0;
@@ -155,12 +154,7 @@ int dm_motifs_tile_positions(void) { return mok::TILE_POS; }
 
 void dm_motifs_destroy(dm_motifs* h) {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->b.release();
-    for (hipEvent_t e : h->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    h->shut();
     delete h;
 }
 
@@ -171,20 +165,13 @@ dm_motifs* dm_motifs_create(int device, int up, int down, char base, int cov, in
              max_ctrl_pct);
         return nullptr;
     }
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) {
-        (void)hipGetLastError();
-        fail(DM_EDEVICE, "dm_motifs_create: no device %d", device);
-        return nullptr;
-    }
+    if (!table_stage_device("dm_motifs", device)) return nullptr;
     dm_motifs* h = new dm_motifs;
-    h->device = device;
     h->rule = {up, down, cov, min_pct, max_ctrl_pct, mok::code_of((unsigned char)base)};
     h->bins = mok::bins_of(up, down);
-    bool ok = hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess;
-    for (hipEvent_t& e : h->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+    bool ok = h->open(device, "dm_motifs");
     ok = ok && h->b.ensure(dm_motifs::HIST, size_t(h->bins) * 16) == DM_OK && h->b.ensure(dm_motifs::COUNTS, mok::N_SWEEP * 8) == DM_OK;
-    ok = ok && hipMemsetAsync(h->b.buf[dm_motifs::HIST], 0, size_t(h->bins) * 16, h->stream) == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess;
+    ok = ok && h->zero_block(dm_motifs::HIST, size_t(h->bins) * 16) == DM_OK;
     if (!ok) {
         (void)hipGetLastError();
         fail(DM_EDEVICE, "dm_motifs_create: stream, events or counters on device %d", device);
@@ -206,14 +193,11 @@ int dm_motifs_count(dm_motifs* h, const uint8_t* seq, int64_t len, dm_summary* p
     if (len < 1 || len > mok::MAX_LENGTH) return fail(DM_EINVAL, "dm_motifs_count: a contig of %lld positions (1 to 2^31 - 1)", (long long)len);
     dm_summary* tab[4] = {plus, minus, ctrl_plus, ctrl_minus};
     const int n_tab = ctrl_plus ? 4 : 2;
-    for (int j = 0; j < n_tab; ++j) {
-        if (tab[j]->device != h->device) return fail(DM_EINVAL, "dm_motifs_count: table %d is on device %d, the handle on device %d", j, tab[j]->device, h->device);
+    for (int j = 0; j < n_tab; ++j)
         if (dm_summary_length(tab[j]) != len)
             return fail(DM_EINVAL, "dm_motifs_count: table %d has %lld positions, the contig %lld", j, (long long)dm_summary_length(tab[j]), (long long)len);
-    }
     int rc;
-    for (int j = 0; j < n_tab; ++j)
-        if ((rc = dm_summary_sync(tab[j])) != DM_OK) return rc;     // the tables have streams of their own
+    if ((rc = h->tables_ready("dm_motifs_count", tab, n_tab)) != DM_OK) return rc;
     HIP_TRY(hipSetDevice(h->device));
     if ((rc = h->b.ensure(B::SEQ, size_t(len))) != DM_OK) return rc;
     hipStream_t s = h->stream;
@@ -248,18 +232,12 @@ int dm_motifs_count(dm_motifs* h, const uint8_t* seq, int64_t len, dm_summary* p
 int dm_motifs_fetch(dm_motifs* h, int64_t* hist) {
     if (!h) return fail(DM_EINVAL, "null handle");
     if (!hist) return fail(DM_EINVAL, "dm_motifs_fetch: null argument");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemcpyAsync(hist, h->b.buf[dm_motifs::HIST], size_t(h->bins) * 16, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return DM_OK;
+    return h->fetch_block(dm_motifs::HIST, hist, size_t(h->bins) * 16);
 }
 
 int dm_motifs_reset(dm_motifs* h) {
     if (!h) return fail(DM_EINVAL, "null handle");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemsetAsync(h->b.buf[dm_motifs::HIST], 0, size_t(h->bins) * 16, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return DM_OK;
+    return h->zero_block(dm_motifs::HIST, size_t(h->bins) * 16);
 }
 
 int dm_motifs_times(dm_motifs* h, double* upload_ms, double* count_ms) {

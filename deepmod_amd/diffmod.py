@@ -27,12 +27,11 @@ import ctypes
 import functools
 import math
 import os
-import re
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from . import _lib, merge, motifs, siteperf
+from . import _lib, merge, tables
 
 MAX_TOTAL = 1 << 20
 MAX_LENGTH = merge.MAX_LENGTH
@@ -93,44 +92,6 @@ def fates(cov: int, cA, cB) -> np.ndarray:
     return f
 
 
-class HostTables:
-    """The two tables of a contig on the host, filled as merge.DeviceMerge fills its own (motifs.HostTables); length None: they grow with the files."""
-
-    def __init__(self, name: str, length: Optional[int]):
-        self.name, self.fixed = name, length is not None
-        self.length = int(length) if self.fixed else 1
-        self.plus = (np.zeros(self.length, np.int64), np.zeros(self.length, np.int64))
-        self.minus = (np.zeros(self.length, np.int64), np.zeros(self.length, np.int64))
-        self.cov_bound = 0
-
-    def close(self):
-        pass
-
-    def add_text(self, text: bytes):
-        rec, flag, bad = merge.parse_device_grammar(text, self.name, self.length if self.fixed else -1)
-        if not flag:
-            self.add_records(*rec)
-        return len(rec[0]), flag, bad
-
-    def add_records(self, pos, strand, cov, mod):
-        pos, strand, cov, mod = (np.asarray(a).astype(np.int64) for a in (pos, strand, cov, mod))
-        if len(pos) == 0:
-            return
-        if not self.fixed and int(pos.max()) >= self.length:
-            self.length = int(pos.max()) + 1
-            self.plus = tuple(np.concatenate([a, np.zeros(self.length - len(a), np.int64)]) for a in self.plus)
-            self.minus = tuple(np.concatenate([a, np.zeros(self.length - len(a), np.int64)]) for a in self.minus)
-        if (pos < 0).any() or (pos >= self.length).any() or (mod < 0).any() or (mod > cov).any():
-            raise DiffmodError('diffmod: a record outside the contig or outside 0 <= modified <= coverage')
-        self.cov_bound += int(cov.max())
-        if self.cov_bound >= 2 ** 31:
-            raise DiffmodError('diffmod: the largest coverages of this contig\'s files sum to %d (2^31 or more): the int32 tables cannot hold them' % self.cov_bound)
-        for s, tab in enumerate((self.plus, self.minus)):
-            sel = strand == s
-            np.add.at(tab[0], pos[sel], cov[sel])
-            np.add.at(tab[1], pos[sel], mod[sel])
-
-
 def _padded(tabs):
     tabs = [(np.asarray(t[0]).astype(np.int64), np.asarray(t[1]).astype(np.int64)) for t in tabs]
     n = max(len(t[0]) for t in tabs)
@@ -156,8 +117,8 @@ class HostEngine:
         self.hist = np.zeros(HIST_BINS, np.int64)
         self.counters = np.zeros((2, len(COUNT_KEYS)), np.int64)
 
-    def new_tables(self, role: str, name: str, length: Optional[int]) -> HostTables:
-        return HostTables(name, length)
+    def new_tables(self, role: str, name: str, length: Optional[int]) -> tables.HostTables:
+        return tables.HostTables(name, length)
 
     def run(self, plus, minus, ctrl_plus, ctrl_minus) -> Tuple[np.ndarray, Dict[str, np.ndarray]]:
         """-> (counters [2][4] of this contig, the records with p <= alpha in key order); hist and counters of the engine grow."""
@@ -216,60 +177,57 @@ def host_routine(cov, alpha, plus, minus, ctrl_plus, ctrl_minus):
     return counters, hist, {k: v[:got.value].copy() for k, v in rec.items()}
 
 
-class DeviceEngine(_lib.Handle):
+def _to_one_length(tabs) -> None:
+    """Device tables that grew with their files: to one length."""
+    if tabs and all(t is not None for t in tabs):
+        n = max(t.length for t in tabs)
+        for t in tabs:
+            if t.length < n:
+                t.grow(n)
+
+
+class DeviceEngine(tables.MergeHandles, _lib.Handle):
     """The same on one GPU (dm_diffmod_* of the C ABI).  A table is a summary.PositionSummary (the handles merge.DeviceMerge fills).
     times(): ms of the select kernels / of the test kernels so far."""
-    PREFIX, N_TIMES = 'dm_diffmod', 2
+    PREFIX, N_TIMES, FIELDS = 'dm_diffmod', 2, RECORD_FIELDS
 
     def __init__(self, cov: int = 5, alpha: float = 0.05, device: int = 0):
+        self._made(device, cov, alpha)
+
+    def _made(self, device: int, cov, alpha, *more):
         check_engine_options(cov, alpha)
         self.cov, self.alpha, self.device = int(cov), float(alpha), device
-        self._merge = {}
-        self._create(device, self.cov, self.alpha)
+        self._create(device, self.cov, self.alpha, *more)
         self.counters = np.zeros((2, len(COUNT_KEYS)), np.int64)
         self.n_records = 0
 
-    def close(self):
-        for dm in getattr(self, '_merge', {}).values():
-            dm.close()
-        self._merge = {}
-        super().close()
-
-    def new_tables(self, role: str, name: str, length: Optional[int]):
-        """Fresh tables for the contig in the merge handle kept for `role` (the tables of the contig before are closed); length None: they grow."""
-        if role not in self._merge:
-            self._merge[role] = merge.DeviceMerge(self.device)
-        self._merge[role].open(name, None if length is None else int(length))
-        return self._merge[role]
-
-    def run(self, plus, minus, ctrl_plus, ctrl_minus, fetch_run: int = FETCH_RUN) -> Tuple[np.ndarray, Dict[str, np.ndarray]]:
-        tabs = [plus, minus, ctrl_plus, ctrl_minus]
-        if all(t is not None for t in tabs):
-            n = max(t.length for t in tabs)
-            for t in tabs:
-                if t.length < n:                                      # tables that grew with their files: to one length
-                    t.grow(n)
+    def _run(self, fetch_run: int, *args) -> Tuple[np.ndarray, Dict[str, np.ndarray]]:
         counters, got = np.zeros((2, len(COUNT_KEYS)), np.int64), ctypes.c_int64(0)
-        self._libmod.check(self._lib.dm_diffmod_run(self._h, *[None if t is None else t._h for t in tabs], counters.ctypes.data, ctypes.byref(got)))
+        self._libmod.check(self._fn('run')(self._h, *args, counters.ctypes.data, ctypes.byref(got)))
         self.counters += counters
         self.n_records = got.value
         return counters, self.fetch_records(0, self.n_records, fetch_run)
 
+    def run(self, plus, minus, ctrl_plus, ctrl_minus, fetch_run: int = FETCH_RUN) -> Tuple[np.ndarray, Dict[str, np.ndarray]]:
+        tabs = [plus, minus, ctrl_plus, ctrl_minus]
+        _to_one_length(tabs)
+        return self._run(fetch_run, *[None if t is None else t._h for t in tabs])
+
     def fetch_records(self, first: int, count: int, fetch_run: int = FETCH_RUN) -> Dict[str, np.ndarray]:
         """Records first .. first + count - 1 of the last run, fetched in runs of fetch_run at most."""
-        rec = {k: np.zeros(count, t) for k, t in RECORD_FIELDS}
+        rec = {k: np.zeros(count, t) for k, t in self.FIELDS}
         for lo in range(0, count, max(int(fetch_run), 1)):
             n = min(int(fetch_run), count - lo)
-            self._libmod.check(self._lib.dm_diffmod_fetch_records(self._h, first + lo, n, *[rec[k][lo:lo + n].ctypes.data for k, _ in RECORD_FIELDS]))
+            self._libmod.check(self._fn('fetch_records')(self._h, first + lo, n, *[rec[k][lo:lo + n].ctypes.data for k, _ in self.FIELDS]))
         return rec
 
     def fetch_hist(self) -> np.ndarray:
         hist = np.zeros(HIST_BINS, np.int64)
-        self._libmod.check(self._lib.dm_diffmod_fetch_hist(self._h, hist.ctypes.data))
+        self._libmod.check(self._fn('fetch_hist')(self._h, hist.ctypes.data))
         return hist
 
     def reset(self):
-        self._libmod.check(self._lib.dm_diffmod_reset(self._h))
+        self._libmod.check(self._fn('reset')(self._h))
         self.counters[:] = 0
         self.n_records = 0
 
@@ -420,7 +378,7 @@ def empty_rep_records() -> Dict[str, np.ndarray]:
     return {k: np.zeros(0, t) for k, t in REP_RECORD_FIELDS}
 
 
-class RepHostEngine:
+class RepHostEngine(HostEngine):
     """The semantics of --replicates 1, one contig per run(): integers for the fates and r_i, decimals at 50 digits for ln and the incomplete beta
     (slow and correct: the oracle of every test; standard library and numpy only).  A table is a pair (coverage, modified) of integer arrays."""
 
@@ -430,16 +388,6 @@ class RepHostEngine:
             raise DiffmodError('diffmod: --minReps: a,b of 1 to %d each and 3 or more together (got %s,%s)' % (MAX_REPS, min_a, min_b))
         self.cov, self.alpha, self.min_a, self.min_b = int(cov), float(alpha), int(min_a), int(min_b)
         self.reset()
-
-    def close(self):
-        pass
-
-    def reset(self):
-        self.hist = np.zeros(HIST_BINS, np.int64)
-        self.counters = np.zeros((2, len(COUNT_KEYS)), np.int64)
-
-    def new_tables(self, role: str, name: str, length: Optional[int]) -> HostTables:
-        return HostTables(name, length)
 
     def run(self, sample, control) -> Tuple[np.ndarray, Dict[str, np.ndarray]]:
         """sample, control: [(plus, minus), ..], one pair of tables per replicate -> (counters [2][4] of this contig, the records with p <= alpha in
@@ -466,12 +414,6 @@ class RepHostEngine:
         self.counters += counters
         return counters, {k: np.array([r[j] for r in rows], t) for j, (k, t) in enumerate(REP_RECORD_FIELDS)}
 
-    def fetch_hist(self) -> np.ndarray:
-        return self.hist.copy()
-
-    def times(self) -> Tuple[float, float]:
-        return 0.0, 0.0
-
 
 def max_replicates() -> int:
     return _lib.load().dm_diffrep_max_replicates()
@@ -497,50 +439,19 @@ def rep_host_routine(cov, alpha, min_a, min_b, sample, control):
 class RepDeviceEngine(DeviceEngine):
     """The same on one GPU (dm_diffrep_* of the C ABI): one merge.DeviceMerge per replicate (new_tables with a role per replicate); the sweep reads
     16 bytes per position and replicate.  times(): ms of the counting pass / of the writing pass so far."""
-    PREFIX, N_TIMES = 'dm_diffrep', 2
+    PREFIX, N_TIMES, FIELDS = 'dm_diffrep', 2, REP_RECORD_FIELDS
 
     def __init__(self, cov: int = 5, alpha: float = 0.05, min_a: int = 1, min_b: int = 2, device: int = 0):
-        check_engine_options(cov, alpha)
-        self.cov, self.alpha, self.min_a, self.min_b, self.device = int(cov), float(alpha), int(min_a), int(min_b), device
-        self._merge = {}
-        self._create(device, self.cov, self.alpha, self.min_a, self.min_b)
-        self.counters = np.zeros((2, len(COUNT_KEYS)), np.int64)
-        self.n_records = 0
+        self.min_a, self.min_b = int(min_a), int(min_b)
+        self._made(device, cov, alpha, self.min_a, self.min_b)
 
     def run(self, sample, control, fetch_run: int = FETCH_RUN) -> Tuple[np.ndarray, Dict[str, np.ndarray]]:
         """sample, control: [(plus, minus), ..] of summary.PositionSummary, one pair per replicate."""
         reps = list(sample) + list(control)
-        tabs = [t for rep in reps for t in rep]
-        if tabs and all(t is not None for t in tabs):
-            n = max(t.length for t in tabs)
-            for t in tabs:
-                if t.length < n:                                      # tables that grew with their files: to one length
-                    t.grow(n)
+        _to_one_length([t for rep in reps for t in rep])
         plus = (ctypes.c_void_p * max(len(reps), 1))(*[None if rep[0] is None else rep[0]._h for rep in reps])
         minus = (ctypes.c_void_p * max(len(reps), 1))(*[None if rep[1] is None else rep[1]._h for rep in reps])
-        counters, got = np.zeros((2, len(COUNT_KEYS)), np.int64), ctypes.c_int64(0)
-        self._libmod.check(self._lib.dm_diffrep_run(self._h, len(sample), len(control), plus, minus, counters.ctypes.data, ctypes.byref(got)))
-        self.counters += counters
-        self.n_records = got.value
-        return counters, self.fetch_records(0, self.n_records, fetch_run)
-
-    def fetch_records(self, first: int, count: int, fetch_run: int = FETCH_RUN) -> Dict[str, np.ndarray]:
-        """Records first .. first + count - 1 of the last run, fetched in runs of fetch_run at most."""
-        rec = {k: np.zeros(count, t) for k, t in REP_RECORD_FIELDS}
-        for lo in range(0, count, max(int(fetch_run), 1)):
-            n = min(int(fetch_run), count - lo)
-            self._libmod.check(self._lib.dm_diffrep_fetch_records(self._h, first + lo, n, *[rec[k][lo:lo + n].ctypes.data for k, _ in REP_RECORD_FIELDS]))
-        return rec
-
-    def fetch_hist(self) -> np.ndarray:
-        hist = np.zeros(HIST_BINS, np.int64)
-        self._libmod.check(self._lib.dm_diffrep_fetch_hist(self._h, hist.ctypes.data))
-        return hist
-
-    def reset(self):
-        self._libmod.check(self._lib.dm_diffrep_reset(self._h))
-        self.counters[:] = 0
-        self.n_records = 0
+        return self._run(fetch_run, len(sample), len(control), plus, minus)
 
 
 # ---- q-values -----------------------------------------------------------------------------------------------------------------------------------
@@ -567,13 +478,6 @@ def delta_passes(cA, mA, cB, mB, min_delta: int) -> np.ndarray:
 
 # ---- the command --------------------------------------------------------------------------------------------------------------------------------
 
-def _contigs_of(folder: str, base: str) -> List[str]:
-    found = set()
-    for path in motifs._stranded_beds(folder, base):
-        found.add(re.search(r'\.([^/.]*)[+-]\.%s\.bed$' % re.escape(base), path).group(1))
-    return sorted(found)
-
-
 def _scalar_options(mo: Dict[str, object]) -> Dict[str, object]:
     base = str(mo.get('Base') or 'C')
     try:
@@ -592,21 +496,20 @@ def _scalar_options(mo: Dict[str, object]) -> Dict[str, object]:
 
 def _contigs(mo: Dict[str, object], base: str, folders: List[str]):
     """-> (contigs, {contig: length or None}) from --Ref and --chr, or from the file names below `folders`."""
-    ref = mo.get('Ref')
-    if ref and not os.path.isfile(ref):
-        raise DiffmodError('diffmod: --Ref: reference file does not exist (%s)' % ref)
-    fasta = siteperf.read_fasta(ref) if ref else {}
-    named = list(mo.get('chr') or [])
-    if ref:
-        missing = [ck for ck in named if ck not in fasta]
-        if missing:
-            raise DiffmodError('diffmod: --chr: %s holds no contig %s' % (ref, ', '.join(missing)))
-    chrkeys = named or list(fasta) or sorted({ck for f in folders for ck in _contigs_of(f, base)})
-    lengths = {ck: (len(fasta[ck]) if ck in fasta else None) for ck in chrkeys}
-    for ck in chrkeys:
-        if lengths[ck] is not None and not 1 <= lengths[ck] <= MAX_LENGTH:
-            raise DiffmodError('diffmod: --Ref: contig %s has %d bases (1 to 2^31 - 1)' % (ck, lengths[ck]))
-    return chrkeys, lengths
+    try:
+        return tables.contigs(mo.get('Ref'), mo.get('chr'), base, folders)[:2]
+    except tables.TableError as exc:
+        raise DiffmodError('diffmod: %s' % exc)
+
+
+def _folders_exist(option: str, folders: List[str]) -> None:
+    for f in folders:
+        if not os.path.isdir(f):
+            raise DiffmodError('diffmod: %s: no folder %s' % (option, f))
+
+
+def _no_beds(option: str, base: str, below: str) -> DiffmodError:
+    return DiffmodError('diffmod: %s: no *.<chr>+.%s.bed / *.<chr>-.%s.bed one to three levels below %s' % (option, base, base, below))
 
 
 def check_options(mo: Dict[str, object]):
@@ -620,16 +523,14 @@ def check_options(mo: Dict[str, object]):
     controls = [c for c in (mo.get('control') or []) if c]
     if not controls:
         raise DiffmodError('diffmod: --control: the folder(s) of the control runs are needed (the test is of the sample against them)')
-    for c in controls:
-        if not os.path.isdir(c):
-            raise DiffmodError('diffmod: --control: no folder %s' % c)
+    _folders_exist('--control', controls)
     chrkeys, lengths = _contigs(mo, base, [folder])
     files = {ck: sorted(merge.find_bed_files(folder, ck, base)) for ck in chrkeys}          # (sorted: the order of the notes)
     ctrl_files = {ck: [p for c in controls for p in sorted(merge.find_bed_files(c, ck, base))] for ck in chrkeys}
     if not any(files.values()):
-        raise DiffmodError('diffmod: --predFolder: no *.<chr>+.%s.bed / *.<chr>-.%s.bed one to three levels below %s' % (base, base, folder))
+        raise _no_beds('--predFolder', base, folder)
     if not any(ctrl_files.values()):
-        raise DiffmodError('diffmod: --control: no *.<chr>+.%s.bed / *.<chr>-.%s.bed one to three levels below %s' % (base, base, ', '.join(controls)))
+        raise _no_beds('--control', base, ', '.join(controls))
     return o, chrkeys, lengths, files, ctrl_files
 
 
@@ -654,8 +555,7 @@ def check_rep_options(mo: Dict[str, object]):
     seen = {}
     for option, folders in (('--predFolder', samples), ('--control', controls)):
         for f in folders:
-            if not os.path.isdir(f):
-                raise DiffmodError('diffmod: %s: no folder %s' % (option, f))
+            _folders_exist(option, [f])
             real = os.path.realpath(f)
             if real in seen:
                 raise DiffmodError('diffmod: %s: the folder %s is named twice (in %s and in %s): a replicate is one folder of its own' % (option, f, seen[real], option))
@@ -666,31 +566,26 @@ def check_rep_options(mo: Dict[str, object]):
     for option, folders, found in (('--predFolder', samples, files), ('--control', controls, ctrl_files)):
         for j, f in enumerate(folders):
             if not any(found[ck][j] for ck in chrkeys):
-                raise DiffmodError('diffmod: %s: no *.<chr>+.%s.bed / *.<chr>-.%s.bed one to three levels below %s' % (option, base, base, f))
+                raise _no_beds(option, base, f)
     return dict(o, replicates={'sample': samples, 'control': controls}, minReps=[a, b]), chrkeys, lengths, files, ctrl_files
 
 
-def _read_into(tables, path: str, text: bytes, name: str, length: Optional[int], notes: List[str]) -> int:
-    """One file into the tables, as merge_runs adds it: the device grammar first, the host parse for a text outside it.  -> lines added"""
-    lines, flag, bad = tables.add_text(text)
-    if flag:
-        notes.append('%s: line %d is outside the device grammar: the file is parsed on the host' % (path, bad))
-        try:
-            rec = merge.host_rows(path, name, MAX_LENGTH if length is None else length)      # MergeError: `file:line: reason`
-        except merge.MergeError as exc:
-            raise DiffmodError('diffmod: %s' % exc)
-        tables.add_records(*rec)
-        lines = len(rec[0])
-    return int(lines)
+def _report_text(header: str, rows, middle: str = '') -> str:
+    out = [header]
+    for ck, pos, s, cA, mA, cB, mB, *rest in rows:
+        out.append(('%s\t%d\t%s\t%d\t%d\t%d\t%d\t%d\t%d\t%.2f\t' + middle + '%.6e\t%.6e') %
+                   ((ck, pos, '+-'[s], cA, mA, 100 * mA // cA, cB, mB, 100 * mB // cB, 100.0 * mA / cA - 100.0 * mB / cB) + tuple(rest)))
+    return ''.join(r + '\n' for r in out)
 
 
 def report_text(rows) -> str:
     """rows: (chr, pos, strand 0 / 1, cA, mA, cB, mB, p, q) -> the header and one line per row."""
-    out = [HEADER]
-    for ck, pos, s, cA, mA, cB, mB, p, q in rows:
-        out.append('%s\t%d\t%s\t%d\t%d\t%d\t%d\t%d\t%d\t%.2f\t%.6e\t%.6e' % (ck, pos, '+-'[s], cA, mA, 100 * mA // cA, cB, mB, 100 * mB // cB,
-                                                                              100.0 * mA / cA - 100.0 * mB / cB, p, q))
-    return ''.join(r + '\n' for r in out)
+    return _report_text(HEADER, rows)
+
+
+def rep_report_text(rows) -> str:
+    """rows: (chr, pos, strand 0 / 1, cA, mA, cB, mB, nA, nB, phi, p, q) -> the header and one line per row."""
+    return _report_text(REP_HEADER, rows, '%d\t%d\t%.4f\t')
 
 
 def replicates_option(mo: Dict[str, object]) -> int:
@@ -706,82 +601,60 @@ def replicates_option(mo: Dict[str, object]) -> int:
     return rep
 
 
-def rep_report_text(rows) -> str:
-    """rows: (chr, pos, strand 0 / 1, cA, mA, cB, mB, nA, nB, phi, p, q) -> the header and one line per row."""
-    out = [REP_HEADER]
-    for ck, pos, s, cA, mA, cB, mB, nA, nB, phi, p, q in rows:
-        out.append('%s\t%d\t%s\t%d\t%d\t%d\t%d\t%d\t%d\t%.2f\t%d\t%d\t%.4f\t%.6e\t%.6e' % (ck, pos, '+-'[s], cA, mA, 100 * mA // cA, cB, mB, 100 * mB // cB,
-                                                                                                100.0 * mA / cA - 100.0 * mB / cB, nA, nB, phi, p, q))
-    return ''.join(r + '\n' for r in out)
+# what the two tests word differently, by --replicates: the note of the too_deep keys, the keys of `times` in the document
+_TOO_DEEP = ('keys with a pooled coverage above %d were not tested', 'keys whose used replicates sum to a coverage above %d were not tested')
+_TIMES = (('select_ms', 'fisher_ms'), ('count_ms', 'write_ms'))
 
 
-def diffmod_replicates(mo: Dict[str, object], engine=None) -> Dict[str, object]:
-    """The command under --replicates 1.  mo as for diffmod(), with predFolder the sample replicates' folders (a list, or one string with commas),
-    control the control replicates' folders and minReps (a,b; None: every replicate).  engine: an object with RepHostEngine's interface (default:
-    RepDeviceEngine on GPU 0), made with cov, alpha = fdr (1 under all) and minReps.  On the device the test reads 16 bytes per position and
-    replicate of the open contig (its tables hold 24)."""
-    import json
-    from concurrent.futures import ThreadPoolExecutor
-    replicates_option(mo)
-    o, chrkeys, lengths, files, ctrl_files = check_rep_options(mo)
-    alpha = 1.0 if o['all'] else o['fdr']
-    (a, b), reps = o['minReps'], o['replicates']
-    own = engine is None
-    if own:
-        if _lib.load().dm_device_count() < 1:
-            raise DiffmodError('no gfx950 GPU visible (this build has no CPU path)')
-        try:
-            engine = RepDeviceEngine(o['cov'], alpha, a, b)
-        except _lib.DeepModHipError as exc:
-            raise DiffmodError('diffmod: %s' % exc)
-    elif (engine.cov, engine.alpha, engine.min_a, engine.min_b) != (o['cov'], alpha, a, b):
-        raise DiffmodError('diffmod: the engine was made for cov %d alpha %g minReps %d,%d' % (engine.cov, engine.alpha, engine.min_a, engine.min_b))
-
-    def read(path):
-        with open(path, 'rb') as fh:
-            return fh.read()
-
-    notes: List[str] = []
-    doc = {'test': 'quasibinomial-F',
-           'inputs': dict(o, predFolder=reps['sample'], control=reps['control'], Ref=mo.get('Ref'), chr=chrkeys, FileID=str(mo.get('FileID') or 'mod'),
-                          files=[p for ck in chrkeys for rep in files[ck] for p in rep], control_files=[p for ck in chrkeys for rep in ctrl_files[ck] for p in rep]),
-           'replicates': reps, 'minReps': [a, b], 'contigs': {}}
-    per_contig = []
+def _engine_for(o: Dict[str, object], rep: int, engine):
+    """-> (the engine: the one given, if it was made for these options, else one of the command's own on GPU 0; whether it is the command's own)."""
+    made_for = (o['cov'], 1.0 if o['all'] else o['fdr']) + (tuple(o['minReps']) if rep else ())
+    if engine is not None:
+        has = (engine.cov, engine.alpha) + ((engine.min_a, engine.min_b) if rep else ())
+        if has != made_for:
+            raise DiffmodError(('diffmod: the engine was made for cov %d alpha %g' + (' minReps %d,%d' if rep else '')) % has)
+        return engine, False
+    if _lib.load().dm_device_count() < 1:
+        raise DiffmodError('no gfx950 GPU visible (this build has no CPU path)')
+    if not rep:
+        return DeviceEngine(*made_for), True
     try:
-        engine.reset()
-        with ThreadPoolExecutor(max(int(mo.get('threads') or 1), 1)) as pool:
-            for ck in chrkeys:
-                if not any(files[ck]) and not any(ctrl_files[ck]):
-                    continue
-                entry = {'length': lengths[ck], 'files': [len(rep) for rep in files[ck]], 'control_files': [len(rep) for rep in ctrl_files[ck]],
-                         'lines_read': [0] * len(files[ck]), 'control_lines_read': [0] * len(ctrl_files[ck])}
-                groups = {'sample': [], 'control': []}
-                try:
-                    for role, found, key in (('sample', files[ck], 'lines_read'), ('control', ctrl_files[ck], 'control_lines_read')):
-                        for j, paths in enumerate(found):
-                            t = engine.new_tables('%s%d' % (role, j), ck, lengths[ck])
-                            for path, text in zip(paths, pool.map(read, paths)):      # the threads read ahead
-                                try:
-                                    entry[key][j] += _read_into(t, path, text, ck, lengths[ck], notes)
-                                except DiffmodError:
-                                    raise
-                                except (ValueError, RuntimeError) as exc:             # the tables' own refusals (a coverage sum past int32)
-                                    raise DiffmodError('diffmod: %s: %s' % (path, exc))
-                            groups[role].append((t.plus, t.minus))
-                    counters, rec = engine.run(groups['sample'], groups['control'])
-                except _lib.DeepModHipError as exc:                                   # device memory that ran out, for one: a line, not a trace
-                    raise DiffmodError('diffmod: %s: %s' % (ck, exc))
-                for s, strand in enumerate('+-'):
-                    entry[strand] = dict(zip(COUNT_KEYS, (int(v) for v in counters[s])))
-                    if counters[s][3]:
-                        notes.append('%s %s: %d keys whose used replicates sum to a coverage above %d were not tested' % (ck, strand, int(counters[s][3]), MAX_TOTAL))
-                doc['contigs'][ck] = entry
-                per_contig.append((ck, rec))
-        hist = engine.fetch_hist()
-        times = engine.times()
-    finally:
-        if own:
-            engine.close()
+        return RepDeviceEngine(*made_for), True
+    except _lib.DeepModHipError as exc:
+        raise DiffmodError('diffmod: %s' % exc)
+
+
+def _run_contig(engine, rep: int, ck: str, length: Optional[int], groups: Dict[str, list], pool, notes: List[str]):
+    """One contig: the files of every table set into tables of the engine (tables.fill), then its run.  groups: {'sample': [the files of one table
+    set, ..], 'control': [..]}, one set per replicate; the pooled test has one set per role, and its entry holds numbers where the replicate test's
+    holds a list per replicate.  -> (the contig's entry of the document, the records)"""
+    tabs, lines = {}, {}
+    for role in ('sample', 'control'):
+        tabs[role], lines[role] = [], []
+        for j, paths in enumerate(groups[role]):
+            t = engine.new_tables('%s%d' % (role, j) if rep else role, ck, length)
+            try:
+                lines[role].append(tables.fill(t, paths, pool, ck, MAX_LENGTH if length is None else length, notes))
+            except (merge.MergeError, tables.TableError) as exc:          # `file:line: reason`; the host tables' refusals
+                raise DiffmodError('diffmod: %s' % exc)
+            except (ValueError, RuntimeError) as exc:                     # the device tables' own (a coverage sum past int32)
+                raise DiffmodError('diffmod: %s: %s' % (exc.path, exc))
+            tabs[role].append((t.plus, t.minus))
+    counters, rec = engine.run(tabs['sample'], tabs['control']) if rep else engine.run(*tabs['sample'][0], *tabs['control'][0])
+    entry = {'length': length, 'files': [len(p) for p in groups['sample']], 'control_files': [len(p) for p in groups['control']],
+             'lines_read': lines['sample'], 'control_lines_read': lines['control']}
+    if not rep:
+        entry = {k: v[0] if isinstance(v, list) else v for k, v in entry.items()}
+    for s, strand in enumerate('+-'):
+        entry[strand] = dict(zip(COUNT_KEYS, (int(v) for v in counters[s])))
+        if counters[s][3]:
+            notes.append('%s %s: %d %s' % (ck, strand, int(counters[s][3]), _TOO_DEEP[rep] % MAX_TOTAL))
+    return entry, rec
+
+
+def _list_records(o: Dict[str, object], doc: Dict[str, object], per_contig, fields) -> list:
+    """BH over the tested keys of all contigs, then the keep rule: doc gets m, listed (per strand of every contig, and in all), hyper and hypo
+    -> the rows of the report, (chr, the record's fields, q)."""
     m = int(sum(doc['contigs'][ck][s]['tested'] for ck in doc['contigs'] for s in '+-'))
     p_all = np.concatenate([rec['p'] for _, rec in per_contig]) if per_contig else np.zeros(0)
     q_all = bh_qvalues(p_all, m)
@@ -798,119 +671,70 @@ def diffmod_replicates(mo: Dict[str, object], engine=None) -> Dict[str, object]:
         hyper += int((keep & (sign > 0)).sum())
         hypo += int((keep & (sign < 0)).sum())
         for i in np.nonzero(keep)[0].tolist():
-            rows.append((ck, int(rec['pos'][i]), int(rec['strand'][i]), int(cA[i]), int(mA[i]), int(cB[i]), int(mB[i]), int(rec['nA'][i]), int(rec['nB'][i]),
-                         float(rec['phi'][i]), float(rec['p'][i]), float(q[i])))
-    if m == 0:
-        notes.append('no key had --cov %d reads in %d sample and %d control replicates' % (o['cov'], a, b))
+            rows.append((ck,) + tuple(rec[k][i].item() for k, _ in fields) + (float(q[i]),))
     doc['m'] = m
     doc['listed'], doc['hyper'], doc['hypo'] = len(rows), hyper, hypo
-    doc['p_histogram'] = [int(v) for v in hist]
-    doc['notes'] = notes
-    doc['times'] = {'count_ms': round(times[0], 4), 'write_ms': round(times[1], 4)}
+    return rows
+
+
+def _write(mo: Dict[str, object], doc: Dict[str, object], text: str) -> None:
+    import json
     out_folder = str(mo['outFolder'])
     os.makedirs(out_folder, exist_ok=True)
     prefix = os.path.join(out_folder, doc['inputs']['FileID'])
     with open(prefix + '_diffmod.txt', 'w') as fh:
-        fh.write(rep_report_text(rows))
+        fh.write(text)
     with open(prefix + '_diffmod.json', 'w') as fh:
         json.dump(doc, fh, indent=1)
-    for ln in notes:
+    for ln in doc['notes']:
         print(ln, flush=True)
-    print('diffmod: %d keys tested, %d listed (%d above the controls, %d below) -> %s_diffmod.txt' % (m, len(rows), hyper, hypo, prefix), flush=True)
-    return doc
+    print('diffmod: %d keys tested, %d listed (%d above the controls, %d below) -> %s_diffmod.txt' % (doc['m'], doc['listed'], doc['hyper'], doc['hypo'], prefix), flush=True)
 
 
 def diffmod(mo: Dict[str, object], engine=None) -> Dict[str, object]:
     """The command.  mo: predFolder, control (list of folders), Base, outFolder, FileID, chr (list; None: the contigs of --Ref, or without it those
-    the sample's file names hold), Ref (None: the tables grow with the files), cov, fdr, minDelta, all, threads; replicates 1 with minReps: the
-    replicate-aware test (diffmod_replicates).  engine: an object with HostEngine's interface (default: DeviceEngine on GPU 0), made with cov and
-    alpha = fdr (1 under all).  Writes <outFolder>/<FileID>_diffmod.txt / _diffmod.json -> the JSON document."""
-    import json
+    the sample's file names hold), Ref (None: the tables grow with the files), cov, fdr, minDelta, all, threads.  replicates 1: the replicate-aware
+    test, with predFolder the sample replicates' folders (a list, or one string with commas), control the control replicates' folders and minReps (a,b;
+    None: every replicate); on the device it reads 16 bytes per position and replicate of the open contig (its tables hold 24).  engine: an object
+    with HostEngine's interface, or RepHostEngine's under replicates 1 (default: DeviceEngine / RepDeviceEngine on GPU 0), made with cov, alpha = fdr
+    (1 under all) and minReps.  Writes <outFolder>/<FileID>_diffmod.txt / _diffmod.json -> the JSON document."""
     from concurrent.futures import ThreadPoolExecutor
-    if replicates_option(mo):
-        return diffmod_replicates(mo, engine)
-    o, chrkeys, lengths, files, ctrl_files = check_options(mo)
-    alpha = 1.0 if o['all'] else o['fdr']
-    controls = [c for c in (mo.get('control') or []) if c]
-    own = engine is None
-    if own:
-        if _lib.load().dm_device_count() < 1:
-            raise DiffmodError('no gfx950 GPU visible (this build has no CPU path)')
-        engine = DeviceEngine(o['cov'], alpha)
-    elif (engine.cov, engine.alpha) != (o['cov'], alpha):
-        raise DiffmodError('diffmod: the engine was made for cov %d alpha %g' % (engine.cov, engine.alpha))
-
-    def read(path):
-        with open(path, 'rb') as fh:
-            return fh.read()
-
+    rep = replicates_option(mo)
+    o, chrkeys, lengths, files, ctrl_files = (check_rep_options if rep else check_options)(mo)
+    engine, own = _engine_for(o, rep, engine)
+    groups = {ck: {'sample': files[ck], 'control': ctrl_files[ck]} if rep else {'sample': [files[ck]], 'control': [ctrl_files[ck]]} for ck in chrkeys}
+    folders = o['replicates'] if rep else {'sample': mo['predFolder'], 'control': [c for c in (mo.get('control') or []) if c]}
     notes: List[str] = []
-    doc = {'inputs': dict(o, predFolder=mo['predFolder'], control=controls, Ref=mo.get('Ref'), chr=chrkeys, FileID=str(mo.get('FileID') or 'mod'),
-                          files=[p for ck in chrkeys for p in files[ck]], control_files=[p for ck in chrkeys for p in ctrl_files[ck]]),
-           'contigs': {}}
+    doc = {'test': 'quasibinomial-F'} if rep else {}
+    doc['inputs'] = dict(o, predFolder=folders['sample'], control=folders['control'], Ref=mo.get('Ref'), chr=chrkeys, FileID=str(mo.get('FileID') or 'mod'),
+                         files=[p for ck in chrkeys for g in groups[ck]['sample'] for p in g], control_files=[p for ck in chrkeys for g in groups[ck]['control'] for p in g])
+    if rep:
+        doc.update(replicates=o['replicates'], minReps=o['minReps'])
+    doc['contigs'] = {}
     per_contig = []
     try:
         engine.reset()
         with ThreadPoolExecutor(max(int(mo.get('threads') or 1), 1)) as pool:
             for ck in chrkeys:
-                if not files[ck] and not ctrl_files[ck]:
+                if not any(groups[ck]['sample']) and not any(groups[ck]['control']):
                     continue
-                entry = {'length': lengths[ck], 'files': len(files[ck]), 'control_files': len(ctrl_files[ck]), 'lines_read': 0, 'control_lines_read': 0}
-                tabs = []
-                for role, paths, key in (('sample', files[ck], 'lines_read'), ('control', ctrl_files[ck], 'control_lines_read')):
-                    t = engine.new_tables(role, ck, lengths[ck])
-                    for path, text in zip(paths, pool.map(read, paths)):          # the threads read ahead
-                        try:
-                            entry[key] += _read_into(t, path, text, ck, lengths[ck], notes)
-                        except DiffmodError:
-                            raise
-                        except (ValueError, RuntimeError) as exc:                 # the tables' own refusals (a coverage sum past int32)
-                            raise DiffmodError('diffmod: %s: %s' % (path, exc))
-                    tabs.extend([t.plus, t.minus])
-                counters, rec = engine.run(*tabs)
-                for s, strand in enumerate('+-'):
-                    entry[strand] = dict(zip(COUNT_KEYS, (int(v) for v in counters[s])))
-                    if counters[s][3]:
-                        notes.append('%s %s: %d keys with a pooled coverage above %d were not tested' % (ck, strand, int(counters[s][3]), MAX_TOTAL))
-                doc['contigs'][ck] = entry
+                try:
+                    doc['contigs'][ck], rec = _run_contig(engine, rep, ck, lengths[ck], groups[ck], pool, notes)
+                except _lib.DeepModHipError as exc:                   # device memory that ran out, for one: a line, not a trace
+                    if not rep:
+                        raise
+                    raise DiffmodError('diffmod: %s: %s' % (ck, exc))
                 per_contig.append((ck, rec))
         hist = engine.fetch_hist()
         times = engine.times()
     finally:
         if own:
             engine.close()
-    m = int(sum(doc['contigs'][ck][s]['tested'] for ck in doc['contigs'] for s in '+-'))
-    p_all = np.concatenate([rec['p'] for _, rec in per_contig]) if per_contig else np.zeros(0)
-    q_all = bh_qvalues(p_all, m)
-    rows, hyper, hypo, at = [], 0, 0, 0
-    for ck, rec in per_contig:
-        n = len(rec['p'])
-        q = q_all[at:at + n]
-        at += n
-        cA, mA, cB, mB = (rec[k].astype(np.int64) for k in ('cA', 'mA', 'cB', 'mB'))
-        keep = np.ones(n, bool) if o['all'] else (q <= o['fdr']) & delta_passes(cA, mA, cB, mB, o['minDelta'])
-        sign = np.sign(mA * cB - mB * cA)
-        for s, strand in enumerate('+-'):
-            doc['contigs'][ck][strand]['listed'] = int((keep & (rec['strand'] == s)).sum())
-        hyper += int((keep & (sign > 0)).sum())
-        hypo += int((keep & (sign < 0)).sum())
-        for i in np.nonzero(keep)[0].tolist():
-            rows.append((ck, int(rec['pos'][i]), int(rec['strand'][i]), int(cA[i]), int(mA[i]), int(cB[i]), int(mB[i]), float(rec['p'][i]), float(q[i])))
-    if m == 0:
-        notes.append('no key had --cov %d reads in both the sample and the controls' % o['cov'])
-    doc['m'] = m
-    doc['listed'], doc['hyper'], doc['hypo'] = len(rows), hyper, hypo
+    rows = _list_records(o, doc, per_contig, REP_RECORD_FIELDS if rep else RECORD_FIELDS)
+    if doc['m'] == 0:
+        notes.append('no key had --cov %d reads in %s' % (o['cov'], '%d sample and %d control replicates' % tuple(o['minReps']) if rep else 'both the sample and the controls'))
     doc['p_histogram'] = [int(v) for v in hist]
     doc['notes'] = notes
-    doc['times'] = {'select_ms': round(times[0], 4), 'fisher_ms': round(times[1], 4)}
-    out_folder = str(mo['outFolder'])
-    os.makedirs(out_folder, exist_ok=True)
-    prefix = os.path.join(out_folder, doc['inputs']['FileID'])
-    with open(prefix + '_diffmod.txt', 'w') as fh:
-        fh.write(report_text(rows))
-    with open(prefix + '_diffmod.json', 'w') as fh:
-        json.dump(doc, fh, indent=1)
-    for ln in notes:
-        print(ln, flush=True)
-    print('diffmod: %d keys tested, %d listed (%d above the controls, %d below) -> %s_diffmod.txt' % (m, len(rows), hyper, hypo, prefix), flush=True)
+    doc['times'] = dict(zip(_TIMES[rep], (round(t, 4) for t in times)))
+    _write(mo, doc, rep_report_text(rows) if rep else report_text(rows))
     return doc

@@ -321,12 +321,7 @@ def merge_runs(mo, device: int = 0):
     folder, base, fileid = mo['predFolder'], str(mo['Base']), str(mo.get('FileID') or 'mod')
     if _lib.load().dm_device_count() < 1:
         raise MergeError('no gfx950 GPU visible (this build has no CPU path)')
-
-    def read(path):
-        with open(path, 'rb') as fh:
-            return fh.read()
-
-    from . import cluster
+    from . import cluster, tables
     dev = DeviceMerge(device)
     model = cluster.ClusterModel.from_checkpoint(prefix, device) if prefix else None
     doc = {'inputs': {'predFolder': folder, 'Base': base, 'FileID': fileid, 'chr': chrkeys, 'Ref': mo.get('Ref'), 'clusterCpG': prefix}, 'contigs': {}}
@@ -340,16 +335,8 @@ def merge_runs(mo, device: int = 0):
                 before = dev.times()
                 if files:
                     seq = fasta.get(ck)
-                    limit = len(seq) if seq is not None else MAX_LENGTH
                     dev.open(ck, len(seq) if seq is not None else None)
-                    for path, text in zip(files, pool.map(read, files)):              # the threads read ahead
-                        lines, flag, bad = dev.add_text(text)
-                        if flag:
-                            entry['notes'].append('%s: line %d is outside the device grammar: the file is parsed on the host' % (path, bad))
-                            rec = host_rows(path, ck, limit)
-                            dev.add_records(*rec)
-                            lines = len(rec[0])
-                        entry['lines_read'] += int(lines)
+                    entry['lines_read'] = tables.fill(dev, files, pool, ck, len(seq) if seq is not None else MAX_LENGTH, entry['notes'])
                     with open(res_file, 'wb') as fh:
                         for part in dev.format(base):
                             fh.write(part)

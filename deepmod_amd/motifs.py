@@ -26,12 +26,11 @@ the specific one, because nothing weighs a pattern against the composition of th
 from __future__ import annotations
 
 import os
-import re
 from typing import Dict, List, Tuple
 
 import numpy as np
 
-from . import _lib, merge, siteperf
+from . import _lib, merge, tables
 
 MAX_FLANK = 8
 MAX_LENGTH = merge.MAX_LENGTH
@@ -63,41 +62,6 @@ def _seq_array(seq) -> np.ndarray:
     return np.frombuffer(bytes(seq), np.uint8) if not isinstance(seq, np.ndarray) else np.ascontiguousarray(seq, np.uint8)
 
 
-class HostTables:
-    """The two tables of a contig on the host, filled as merge.DeviceMerge fills its own: add_text is the device's line routine compiled for the host
-    (merge.parse_device_grammar: a text with a line outside the grammar adds nothing and is flagged), add_records takes a host parse.  .plus / .minus:
-    (coverage, modified) int64 arrays."""
-
-    def __init__(self, name: str, length: int):
-        self.name, self.length = name, int(length)
-        self.plus = (np.zeros(self.length, np.int64), np.zeros(self.length, np.int64))
-        self.minus = (np.zeros(self.length, np.int64), np.zeros(self.length, np.int64))
-        self.cov_bound = 0
-
-    def close(self):
-        pass
-
-    def add_text(self, text: bytes):
-        rec, flag, bad = merge.parse_device_grammar(text, self.name, self.length)
-        if not flag:
-            self.add_records(*rec)
-        return len(rec[0]), flag, bad
-
-    def add_records(self, pos, strand, cov, mod):
-        pos, strand, cov, mod = (np.asarray(a).astype(np.int64) for a in (pos, strand, cov, mod))
-        if len(pos) == 0:
-            return
-        if (pos < 0).any() or (pos >= self.length).any() or (mod < 0).any() or (mod > cov).any():
-            raise MotifsError('motifs: a record outside the contig or outside 0 <= modified <= coverage')
-        self.cov_bound += int(cov.max())
-        if self.cov_bound >= 2 ** 31:
-            raise MotifsError('motifs: the largest coverages of this contig\'s files sum to %d (2^31 or more): the int32 tables cannot hold them' % self.cov_bound)
-        for s, tab in enumerate((self.plus, self.minus)):
-            sel = strand == s
-            np.add.at(tab[0], pos[sel], cov[sel])
-            np.add.at(tab[1], pos[sel], mod[sel])
-
-
 class HostEngine:
     """The semantics in numpy, one contig per count().  A table is a pair (coverage, modified) of integer arrays of the contig's length."""
 
@@ -115,8 +79,8 @@ class HostEngine:
         self.counters = np.zeros((2, len(COUNT_KEYS)), np.int64)
         self.off_base = np.zeros(2, np.int64)
 
-    def new_tables(self, role: str, name: str, length: int) -> HostTables:
-        return HostTables(name, length)
+    def new_tables(self, role: str, name: str, length: int) -> tables.HostTables:
+        return tables.HostTables(name, length)
 
     def count(self, seq, plus, minus, ctrl_plus=None, ctrl_minus=None) -> Tuple[np.ndarray, np.ndarray]:
         """-> (counters [2][5], off_base [2]) of this contig; hist, counters and off_base of the engine grow by them."""
@@ -189,7 +153,7 @@ def count_host_routine(up, down, base, cov, min_pct, max_ctrl_pct, seq, plus, mi
     return hist, counters, off_base
 
 
-class DeviceEngine(_lib.Handle):
+class DeviceEngine(tables.MergeHandles, _lib.Handle):
     """The same on one GPU (dm_motifs_* of the C ABI).  A table is a summary.PositionSummary (the handles merge.DeviceMerge fills).
     times(): ms of the uploads of the contigs' bytes / of the sweeps so far."""
     PREFIX, N_TIMES = 'dm_motifs', 2
@@ -198,23 +162,9 @@ class DeviceEngine(_lib.Handle):
         check_engine_options(up, down, base, cov, min_pct, max_ctrl_pct)
         self.up, self.down, self.base, self.device = int(up), int(down), base, device
         self.bins = 4 ** (self.up + self.down)
-        self._merge = {}
         self._create(device, self.up, self.down, base.encode('ascii'), int(cov), int(min_pct), int(max_ctrl_pct))
         self.counters = np.zeros((2, len(COUNT_KEYS)), np.int64)
         self.off_base = np.zeros(2, np.int64)
-
-    def close(self):
-        for dm in getattr(self, '_merge', {}).values():
-            dm.close()
-        self._merge = {}
-        super().close()
-
-    def new_tables(self, role: str, name: str, length: int):
-        """Fresh tables of `length` positions for the contig, in the merge handle kept for `role` (the tables of the contig before are closed)."""
-        if role not in self._merge:
-            self._merge[role] = merge.DeviceMerge(self.device)
-        self._merge[role].open(name, int(length))
-        return self._merge[role]
 
     def count(self, seq, plus, minus, ctrl_plus=None, ctrl_minus=None) -> Tuple[np.ndarray, np.ndarray]:
         s = _seq_array(seq)
@@ -316,15 +266,6 @@ def parse_flank(value) -> Tuple[int, int]:
     return u, d
 
 
-def _stranded_beds(folder: str, base: str) -> List[str]:
-    """Every *.<contig>+.<Base>.bed / *.<contig>-.<Base>.bed one to three levels below the folder, of whatever contig."""
-    import glob
-    found = []
-    for depth in ('*/*/*/', '*/*/', '*/'):
-        found.extend(glob.glob(os.path.join(folder, '%s*.%s.bed' % (depth, base))))
-    return [p for p in found if re.search(r'\.[^/.]*[+-]\.%s\.bed$' % re.escape(base), p)]
-
-
 def check_options(mo: Dict[str, object]):
     """What can be refused before a BED file is read or any GPU asked for -> (options dict, contigs, {contig: upper-cased bases},
     {contig: sample files}, {contig: control files})."""
@@ -346,28 +287,21 @@ def check_options(mo: Dict[str, object]):
     for c in controls:
         if not os.path.isdir(c):
             raise MotifsError('motifs: --control: no folder %s' % c)
-    ref = mo.get('Ref')
+    ref, named = mo.get('Ref'), list(mo.get('chr') or [])
     if not ref:
         raise MotifsError('motifs: --Ref: the reference FASTA is needed (the sequence contexts are read from it)')
-    if not os.path.isfile(ref):
-        raise MotifsError('motifs: --Ref: reference file does not exist (%s)' % ref)
-    fasta = siteperf.read_fasta(ref)
-    named = list(mo.get('chr') or [])
-    missing = [ck for ck in named if ck not in fasta]
-    if missing:
-        raise MotifsError('motifs: --chr: %s holds no contig %s' % (ref, ', '.join(missing)))
-    chrkeys = named or list(fasta)
+    try:
+        chrkeys, _, fasta = tables.contigs(ref, named, base, [])
+    except tables.TableError as exc:
+        raise MotifsError('motifs: %s' % exc)
     if not chrkeys:
         raise MotifsError('motifs: --Ref: %s holds no contig' % ref)
-    for ck in chrkeys:
-        if not 1 <= len(fasta[ck]) <= MAX_LENGTH:
-            raise MotifsError('motifs: --Ref: contig %s has %d bases (1 to 2^31 - 1)' % (ck, len(fasta[ck])))
     files = {ck: sorted(merge.find_bed_files(folder, ck, base)) for ck in chrkeys}          # (sorted: the order of the notes)
     ctrl_files = {ck: [p for c in controls for p in sorted(merge.find_bed_files(c, ck, base))] for ck in chrkeys}
     if not named:                                                     # a file of a contig the reference does not hold: the wrong --Ref
         for fld, by_contig in [(folder, files)] + [(c, ctrl_files) for c in controls]:
             known = {p for ps in by_contig.values() for p in ps}
-            other = sorted(p for p in _stranded_beds(fld, base) if p not in known)
+            other = sorted(p for p in tables.stranded_beds(fld, base) if p not in known)
             if other:
                 raise MotifsError('motifs: --Ref: %s is the file of a contig that %s does not hold' % (other[0], ref))
     if not any(files.values()):
@@ -376,20 +310,6 @@ def check_options(mo: Dict[str, object]):
         raise MotifsError('motifs: --control: no *.<chr>+.%s.bed / *.<chr>-.%s.bed one to three levels below %s' % (base, base, ', '.join(controls)))
     seqs = {ck: fasta[ck].upper() for ck in chrkeys}
     return o, chrkeys, seqs, files, ctrl_files
-
-
-def _read_into(tables, path: str, text: bytes, name: str, length: int, notes: List[str]) -> int:
-    """One file into the tables, as merge_runs adds it: the device grammar first, the host parse for a text outside it.  -> lines added"""
-    lines, flag, bad = tables.add_text(text)
-    if flag:
-        notes.append('%s: line %d is outside the device grammar: the file is parsed on the host' % (path, bad))
-        try:
-            rec = merge.host_rows(path, name, length)                # MergeError: `file:line: reason`
-        except merge.MergeError as exc:
-            raise MotifsError('motifs: %s' % exc)
-        tables.add_records(*rec)
-        lines = len(rec[0])
-    return int(lines)
 
 
 def report_text(motifs: List[Dict[str, object]]) -> str:
@@ -418,10 +338,6 @@ def motifs(mo: Dict[str, object], engine=None) -> Dict[str, object]:
     elif (engine.up, engine.down, engine.base) != (up, down, base):
         raise MotifsError('motifs: the engine was made for flank %d,%d base %s' % (engine.up, engine.down, engine.base))
 
-    def read(path):
-        with open(path, 'rb') as fh:
-            return fh.read()
-
     notes: List[str] = []
     doc = {'inputs': dict(o, predFolder=mo['predFolder'], control=controls, Ref=mo['Ref'], chr=chrkeys, FileID=str(mo.get('FileID') or 'mod'),
                           files=[p for ck in chrkeys for p in files[ck]], control_files=[p for ck in chrkeys for p in ctrl_files[ck]]),
@@ -437,13 +353,12 @@ def motifs(mo: Dict[str, object], engine=None) -> Dict[str, object]:
                 tabs = []
                 for role, paths, key in (('sample', files[ck], 'lines_read'),) + ((('control', ctrl_files[ck], 'control_lines_read'),) if controls else ()):
                     t = engine.new_tables(role, ck, n)
-                    for path, text in zip(paths, pool.map(read, paths)):          # the threads read ahead
-                        try:
-                            entry[key] += _read_into(t, path, text, ck, n, notes)
-                        except MotifsError:
-                            raise
-                        except (ValueError, RuntimeError) as exc:                 # the tables' own refusals (a coverage sum past int32)
-                            raise MotifsError('motifs: %s: %s' % (path, exc))
+                    try:
+                        entry[key] = tables.fill(t, paths, pool, ck, n, notes)
+                    except (merge.MergeError, tables.TableError) as exc:          # `file:line: reason`; the host tables' refusals
+                        raise MotifsError('motifs: %s' % exc)
+                    except (ValueError, RuntimeError) as exc:                     # the device tables' own (a coverage sum past int32)
+                        raise MotifsError('motifs: %s: %s' % (exc.path, exc))
                     tabs.extend([t.plus, t.minus])
                 counters, off_base = engine.count(seq, *tabs)
                 for s, strand in enumerate('+-'):

@@ -3,7 +3,7 @@
 the oracle within the derived interval of DESIGN.md 22 (diffrep_synth.bounds: D within 18 * 2^-53 * C, phi and the incomplete beta within 2.5e-11),
 every fate on both strands, --minReps below the default, the command under RepHostEngine on the synthetic case of tests/diffrep_synth.py, the point
 of the feature (where one replicate disagrees, the replicate test's p exceeds the pooled Fisher p), the refusals of the command line, --replicates 0
-against the bytes of the parent's command, and the host twin under the address sanitizer (tests/diffrep_driver.cpp)."""
+and --replicates 1 against the bytes of the parent's commands, and the host twin under the address sanitizer (tests/diffrep_driver.cpp)."""
 import json
 import os
 import shutil
@@ -278,6 +278,20 @@ def test_replicates_0_writes_the_bytes_of_the_parent(tmp_path):
         assert got['txt'] == parent['txt'] and got['json'] == parent['json'], fileid
         with open(os.path.join(root, 'out', fileid + '_diffmod.json')) as fh:
             assert list(json.load(fh)) == ['inputs', 'contigs', 'm', 'listed', 'hyper', 'hypo', 'p_histogram', 'notes', 'times']
+
+
+def test_replicates_1_writes_the_bytes_of_the_parent(synthetic):
+    """tests/golden/diffrep_case.json['command'] holds the reports and the documents the command wrote when --replicates 1 had a driver of its own,
+    for three option sets of the synthetic case (make_golden_diffrep.command_case)."""
+    root, case, got = synthetic
+    parents = GOLDEN['command']
+    assert sorted(parents) == ['all', 'default', 'low']
+    for fileid, parent in parents.items():
+        parent['json']['inputs']['FileID'] = fileid
+        assert got[fileid]['txt'] == parent['txt'] and got[fileid]['json'] == parent['json'], fileid
+        assert json.dumps(got[fileid]['json']) == json.dumps(parent['json']), fileid          # and every key in the parent's order
+        with open(os.path.join(root, 'out', fileid + '_diffmod.json')) as fh:
+            assert list(json.load(fh)) == ['test', 'inputs', 'replicates', 'minReps', 'contigs', 'm', 'listed', 'hyper', 'hypo', 'p_histogram', 'notes', 'times']
 
 
 def test_host_twin_under_address_sanitizer(tmp_path):
