@@ -215,20 +215,6 @@ __global__ __launch_bounds__(THREADS) void site_feature_kernel(const Args a, con
 enum { B_SEQ, B_CODE, B_BCOUNT, B_OFFS, B_HALO, B_FEAT, B_POS, B_COV, B_MOD, B_PROB, B_COUNT };
 static_assert(B_COUNT <= dm_cluster::SITE_BUFFERS, "dm_cluster holds one slot per buffer");
 
-int ensure(dm_cluster* c, int which, size_t bytes) {
-    if (size_t(c->site_cap[which]) >= bytes && c->site_buf[which]) return DM_OK;
-    (void)hipFree(c->site_buf[which]);
-    c->site_buf[which] = nullptr;
-    c->site_cap[which] = 0;
-    bytes = std::max<size_t>(bytes, 256);
-    if (hipMalloc(&c->site_buf[which], bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(DM_ENOMEM, "dm_cluster_sites: hipMalloc(%zu) failed", bytes);
-    }
-    c->site_cap[which] = int64_t(bytes);
-    return DM_OK;
-}
-
 }  // namespace csites
 
 extern "C" {
@@ -259,8 +245,8 @@ int64_t dm_cluster_sites(dm_cluster* c, dm_summary* plus, dm_summary* minus, int
             if (t->slice_first != first || t->slice_count != count)
                 return fail(DM_EINVAL, "dm_cluster_sites: the '%c' summary holds the slice [%lld, +%lld), asked for [%lld, +%lld)", s ? '-' : '+',
                             (long long)t->slice_first, (long long)t->slice_count, (long long)first, (long long)count);
-            a.cov[s] = t->d_slice + t->slice_chunk;
-            a.mod[s] = t->d_slice + 2 * t->slice_chunk;
+            a.cov[s] = t->slice() + t->slice_chunk;
+            a.mod[s] = t->slice() + 2 * t->slice_chunk;
             a.len[s] = count;
         } else {
             a.len[s] = std::max<int64_t>(0, std::min<int64_t>(count, t->length - first));
@@ -276,19 +262,19 @@ int64_t dm_cluster_sites(dm_cluster* c, dm_summary* plus, dm_summary* minus, int
     if (count == 0 || seq_len == 0) return 0;
     const long long nblocks = (count + TILE - 1) / TILE;
     int rc;
-    if ((rc = ensure(c, B_SEQ, size_t(seq_len))) || (rc = ensure(c, B_CODE, size_t(count) + 2 * HALO)) ||
-        (rc = ensure(c, B_BCOUNT, sizeof(int) * 2 * size_t(nblocks))) || (rc = ensure(c, B_OFFS, sizeof(long long) * (2 * size_t(nblocks) + 1))) ||
-        (rc = ensure(c, B_HALO, sizeof(int) * 8 * HALO)))
+    if ((rc = c->sites.ensure(B_SEQ, size_t(seq_len))) || (rc = c->sites.ensure(B_CODE, size_t(count) + 2 * HALO)) ||
+        (rc = c->sites.ensure(B_BCOUNT, sizeof(int) * 2 * size_t(nblocks))) || (rc = c->sites.ensure(B_OFFS, sizeof(long long) * (2 * size_t(nblocks) + 1))) ||
+        (rc = c->sites.ensure(B_HALO, sizeof(int) * 8 * HALO)))
         return rc;
-    HIP_TRY(hipMemcpyAsync(c->site_buf[B_SEQ], seq, size_t(seq_len), hipMemcpyHostToDevice, c->stream));
-    a.seq = static_cast<const unsigned char*>(c->site_buf[B_SEQ]);
+    HIP_TRY(hipMemcpyAsync(c->sites.buf[B_SEQ], seq, size_t(seq_len), hipMemcpyHostToDevice, c->stream));
+    a.seq = static_cast<const unsigned char*>(c->sites.buf[B_SEQ]);
     if (halo) {
-        HIP_TRY(hipMemcpyAsync(c->site_buf[B_HALO], halo, sizeof(int) * 8 * HALO, hipMemcpyHostToDevice, c->stream));
-        a.halo = static_cast<const int*>(c->site_buf[B_HALO]);
+        HIP_TRY(hipMemcpyAsync(c->sites.buf[B_HALO], halo, sizeof(int) * 8 * HALO, hipMemcpyHostToDevice, c->stream));
+        a.halo = static_cast<const int*>(c->sites.buf[B_HALO]);
     }
-    unsigned char* d_code = static_cast<unsigned char*>(c->site_buf[B_CODE]);
-    int* d_bcount = static_cast<int*>(c->site_buf[B_BCOUNT]);
-    long long* d_offs = static_cast<long long*>(c->site_buf[B_OFFS]);
+    unsigned char* d_code = static_cast<unsigned char*>(c->sites.buf[B_CODE]);
+    int* d_bcount = static_cast<int*>(c->sites.buf[B_BCOUNT]);
+    long long* d_offs = static_cast<long long*>(c->sites.buf[B_OFFS]);
     hipLaunchKernelGGL(site_code_kernel, dim3((unsigned)nblocks), dim3(THREADS), 0, c->stream, a, d_code, d_bcount, nblocks);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(site_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, c->stream, d_bcount, d_offs, 2 * nblocks);
@@ -300,16 +286,16 @@ int64_t dm_cluster_sites(dm_cluster* c, dm_summary* plus, dm_summary* minus, int
     const long long n = totals[1];
     if (n < 0 || totals[0] < 0 || totals[0] > n || n > count) return fail(DM_EDEVICE, "dm_cluster_sites: inconsistent site counts (%lld, %lld)", totals[0], n);
     if (n == 0) return 0;
-    if ((rc = ensure(c, B_FEAT, sizeof(float) * 14 * size_t(n))) || (rc = ensure(c, B_POS, sizeof(long long) * size_t(n))) ||
-        (rc = ensure(c, B_COV, sizeof(int) * size_t(n))) || (rc = ensure(c, B_MOD, sizeof(int) * size_t(n))) || (rc = ensure(c, B_PROB, sizeof(float) * size_t(n))))
+    if ((rc = c->sites.ensure(B_FEAT, sizeof(float) * 14 * size_t(n))) || (rc = c->sites.ensure(B_POS, sizeof(long long) * size_t(n))) ||
+        (rc = c->sites.ensure(B_COV, sizeof(int) * size_t(n))) || (rc = c->sites.ensure(B_MOD, sizeof(int) * size_t(n))) || (rc = c->sites.ensure(B_PROB, sizeof(float) * size_t(n))))
         return rc;
-    float* d_feat = static_cast<float*>(c->site_buf[B_FEAT]);
+    float* d_feat = static_cast<float*>(c->sites.buf[B_FEAT]);
     hipLaunchKernelGGL(site_feature_kernel, dim3((unsigned)nblocks), dim3(THREADS), 0, c->stream, a, d_code, d_offs, nblocks, d_feat,
-                       static_cast<long long*>(c->site_buf[B_POS]), static_cast<int*>(c->site_buf[B_COV]), static_cast<int*>(c->site_buf[B_MOD]));
+                       static_cast<long long*>(c->sites.buf[B_POS]), static_cast<int*>(c->sites.buf[B_COV]), static_cast<int*>(c->sites.buf[B_MOD]));
     HIP_TRY(hipGetLastError());
     // the MLP of dm_cluster_predict, on the feature rows where they are
     const int blocks = int(std::min<int64_t>((n + 255) / 256, 4096));
-    hipLaunchKernelGGL(cluster_mlp_kernel, dim3(blocks), dim3(256), 0, c->stream, c->d_w, d_feat, n, static_cast<float*>(c->site_buf[B_PROB]));
+    hipLaunchKernelGGL(cluster_mlp_kernel, dim3(blocks), dim3(256), 0, c->stream, c->d_w, d_feat, n, static_cast<float*>(c->sites.buf[B_PROB]));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->n_sites = n;
@@ -324,13 +310,13 @@ int dm_cluster_sites_fetch(dm_cluster* c, int64_t* pos, int32_t* cov, int32_t* m
     const size_t n = size_t(c->n_sites);
     if (n == 0) return DM_OK;
     HIP_TRY(hipSetDevice(c->device));
-    if (pos) HIP_TRY(hipMemcpy(pos, c->site_buf[B_POS], sizeof(int64_t) * n, hipMemcpyDeviceToHost));
-    if (cov) HIP_TRY(hipMemcpy(cov, c->site_buf[B_COV], sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-    if (mod) HIP_TRY(hipMemcpy(mod, c->site_buf[B_MOD], sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-    if (features) HIP_TRY(hipMemcpy(features, c->site_buf[B_FEAT], sizeof(float) * 14 * n, hipMemcpyDeviceToHost));
+    if (pos) HIP_TRY(hipMemcpy(pos, c->sites.buf[B_POS], sizeof(int64_t) * n, hipMemcpyDeviceToHost));
+    if (cov) HIP_TRY(hipMemcpy(cov, c->sites.buf[B_COV], sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    if (mod) HIP_TRY(hipMemcpy(mod, c->sites.buf[B_MOD], sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    if (features) HIP_TRY(hipMemcpy(features, c->sites.buf[B_FEAT], sizeof(float) * 14 * n, hipMemcpyDeviceToHost));
     if (new_pct) {
         std::vector<float> p(n);
-        HIP_TRY(hipMemcpy(p.data(), c->site_buf[B_PROB], sizeof(float) * n, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(p.data(), c->sites.buf[B_PROB], sizeof(float) * n, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < n; ++i) new_pct[i] = int32_t(p[i] * 100.0f);      // int(float32 p * 100), hm_cluster_predict.py:170
     }
     return DM_OK;

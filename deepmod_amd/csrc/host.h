@@ -162,12 +162,14 @@ struct dm_summary {
     int64_t length = 0;
     int* d_counts = nullptr;  // touch | cov | mod  (+ SLACK ints: a reduce-scatter reads up to nranks - 1 positions past the last array)
     static constexpr int64_t SLACK = 64;
-    int* d_slice = nullptr;   // dm_summary_reduce_scatter: this rank's slice of the three arrays, [3][slice_chunk]
-    int64_t slice_chunk = 0, slice_first = 0, slice_count = -1;   // slice_count < 0: no scatter result held
     int* d_oob = nullptr;
-    long long* d_pos = nullptr;
-    unsigned char* d_flags = nullptr;
-    int64_t stage_cap = 0;
+    // grow-only blocks: POS i64 [n] and FLAGS u8 [2][n] (flags | cls) stage the host arrays of an add of n positions;
+    // SLICE int [3][slice_chunk] is this rank's slice of the three arrays after dm_summary_reduce_scatter
+    enum { POS, FLAGS, SLICE, N_BUF };
+    DevBufs<N_BUF> b{"dm_summary"};
+    static constexpr int64_t STAGE_FLOOR = int64_t(1) << 20;      // positions the staging pair holds at least
+    int64_t slice_chunk = 0, slice_first = 0, slice_count = -1;   // the last scatter's chunk; slice_count < 0: no scatter result held
+    int* slice() const { return b.ptr<int>(SLICE); }
     hipStream_t stream = nullptr;
     dm_model* follow = nullptr;   // dm_summary_follow: enqueue on this model's stream (in-order with its launches)
 };
@@ -176,13 +178,11 @@ struct dm_cluster {
     int device = 0;
     hipStream_t stream = nullptr;
     float* d_w = nullptr;
-    float* d_x = nullptr;
-    float* d_out = nullptr;
-    int64_t cap = 0;
-    // dm_cluster_sites (cluster_sites.hip.inc): device buffers of the last call, grown on demand, and its site counts
+    enum { X, OUT, N_STAGE };                  // dm_cluster_predict: staging of host rows f32 [n][14] and of their results f32 [n]
+    DevBufs<N_STAGE> stage{"dm_cluster_predict"};
+    // dm_cluster_sites (cluster_sites.hip.inc): device buffers of the last call (csites::B_* names the slots), grown on demand, and its site counts
     static constexpr int SITE_BUFFERS = 10;
-    void* site_buf[SITE_BUFFERS] = {};
-    int64_t site_cap[SITE_BUFFERS] = {};
+    DevBufs<SITE_BUFFERS> sites{"dm_cluster_sites"};
     int64_t n_sites = 0, n_plus = 0;
 };
 

@@ -1,6 +1,6 @@
 // signal.hip.inc — raw-signal normalisation and per-event statistics on the GPU (part of feed.hip).
 //
-// Reference: /root/reference/bin/DeepMod_scripts/myDetect.py
+// Reference: bin/DeepMod_scripts/myDetect.py
 //   :266-282  mnormalized(): over the event-covered slice raw[start_0 : start_last + length_last]
 //                 mshift = median(slice)            mscale = median(|slice - mshift|)
 //                 raw    = (raw - mshift) / mscale                                  (float64)
@@ -24,8 +24,13 @@
 //                           left to right, each with the 8-lane / 128-block pairwise scheme), so results are bit-identical
 //                           to the reference's np.mean / np.std, then rint(v * 1000) / 1000 and the cast to float32.
 // Nothing here is GEMM-shaped; the kernels are byte/integer work bounded by HBM and the LDS atomic rate.
+//
+// This file is the HIP half of the stage: the kernels, the handle (its device blocks are one DevBufs) and the calls, a batched call as a sequence of
+// named stages (signal_batch_impl).  What a call works out on the host before it touches the device - the checks, the covered slice, the first empty
+// event, the BatchPlan whose tables the upload stage copies as they are - is signalplan.inc, plain C++ that the host tests compile without HIP.
 #pragma once
 #include "host.h"
+#include "signalplan.inc"
 
 namespace sig {
 
@@ -335,7 +340,7 @@ __global__ void event_ev3_batch_kernel(const short* __restrict__ raw, const long
 // No atomics: every output has exactly one writer, so the tables are the same bits whatever the scheduling.  Every store is guarded by the read's
 // status and its expected event count.
 constexpr int MOVE_THREADS = 256;
-constexpr int MOVE_CHUNK = MOVE_THREADS * 16;       // table bytes per workgroup
+static_assert(MOVE_CHUNK == MOVE_THREADS * 16, "a workgroup takes one 16-byte word per lane: the table bytes the plan counts chunks in (signalplan.inc)");
 
 // the last read whose first chunk / event is <= c (reads without chunks / events share an offset with their successor and are never chosen)
 __device__ __forceinline__ int move_find_read(const long long* __restrict__ off, const int n_reads, const long long c) {
@@ -735,50 +740,68 @@ inline Norm norm_from_hist(const unsigned* hist) {
 struct dm_signal {
     int device = 0;
     hipStream_t stream = nullptr;
-    short* d_raw = nullptr;
-    int64_t cap_raw = 0;
-    unsigned long long* d_ev = nullptr;   // [2][cap_ev]: start, length
-    float* d_out = nullptr;               // [2][cap_ev]: mean, stdv
-    int64_t cap_ev = 0;
-    unsigned* d_hist = nullptr;           // [65536]
-    double* d_lut = nullptr;              // [65536]
-    double* d_norm = nullptr;             // optional normalised signal, [cap_norm]
-    int64_t cap_norm = 0;
+    // The device blocks, grow-only.  A paired table (EV, OUT, FB, MVCHUNK) holds its parts back to back at a stride of the call that fills it - its own
+    // event or chunk count - and every kernel takes the parts as separate pointers.
+    enum {
+        RAW,        // short: the samples, + RAW_SLACK
+        EV,         // u64 [2][events]: start | length
+        OUT,        // f32 [2][events]: mean | stdv
+        HIST,       // u32 [65536], LUT f64 [65536]: the single-read call's (allocated at create)
+        LUT,
+        NORM,       // f64 [samples]: the single-read call's optional normalised signal
+        // the per-read group of a batch (reserve_reads)
+        BHIST,      // u32 [reads][65536]
+        BLUT,       // f64 [reads][65536]
+        BMETA,      // i64 [3][reads + 1]: lo | hi | raw_off
+        BNORM,      // sig::Norm [reads]
+        BFLAG,      // int [reads]: 1 = this read needs the host order statistics
+        EVOFF,      // i64 [2][reads + 1]: ev_off | n_stat, the events a statistics kernel computes
+        VRANGE,     // int [2][reads]: smallest | largest sample value of a read's slice
+        BFULL,      // int [reads]: 1 = an event of the read reaches outside its slice, its value table is written whole
+        EVREAD,     // int [events]: host-table form, the read of every event
+        FB,         // f32 [2][events]: resident form, fall-back mean | stdv of the batch's events
+        RFLAG,      // int: resident form, range flag of the call
+        // move form: what the segmentation kernels read and write
+        MOVE,       // u8: the batch's move tables, + MOVE_SLACK
+        MVMETA,     // i64 [3][reads + 1]: mv_off | chunk_off | first
+        MVSTATUS,   // int [reads]
+        MVCHUNK,    // int [3][chunks]: count | last | base of every chunk
+        N_BUF
+    };
+    static constexpr size_t RAW_SLACK = 8 * sizeof(short);   // bytes behind the samples that belong to the block
+    static constexpr size_t MOVE_SLACK = 16;                 // the last aligned 16-byte word of a table may reach behind the tables
+    DevBufs<N_BUF> b{"dm_signal"};
     std::vector<unsigned> h_hist;
-    // dm_signal_event_stats_batch: grow-only device buffers
-    unsigned* d_bhist = nullptr;          // [cap_reads][65536]
-    double* d_blut = nullptr;             // [cap_reads][65536]
-    long long* d_bmeta = nullptr;         // [3][cap_reads + 1]: lo | hi | raw_off
-    sig::Norm* d_bnorm = nullptr;         // [cap_reads]
-    int* d_bflag = nullptr;               // [cap_reads]: 1 = this read needs the host order statistics
-    int* d_vrange = nullptr;              // [2][n_reads] of the call (capacity 2 * cap_reads): smallest | largest sample value of a read's slice
-    int* d_bfull = nullptr;               // [cap_reads]: 1 = an event of the read reaches outside its slice, its value table is written whole
     bool host_order_statistics = false;   // DEEPMOD_SIGNAL_HOST_NORM=1: always take the host path (the cross-check of the tests)
-    int* d_evread = nullptr;              // [cap_ev]
-    int64_t cap_reads = 0, cap_evread = 0;
-    float* d_fb = nullptr;                // resident form: fall-back mean | stdv of the batch's events, [2][cap_fb]
-    int64_t cap_fb = 0;
-    long long* d_evoff = nullptr;         // ev_off [cap_reads + 1] | n_stat [cap_reads + 1]: the events a statistics kernel computes
-    int* d_rflag = nullptr;               // resident form: range flag of the call
     unsigned* h_bhist = nullptr;          // page-locked, [cap_hbhist][65536]: the histograms come back by DMA
     int64_t cap_hbhist = 0;
-    // dm_signal_move_stats_device: grow-only device buffers of the segmentation kernels
-    unsigned char* d_move = nullptr;      // the batch's move tables, [cap_move + 16] (the last aligned 16-byte word may reach behind the tables)
-    int64_t cap_move = 0;
-    long long* d_mvmeta = nullptr;        // mv_off [n + 1] | chunk_off [n + 1] | first [n + 1] of the call (capacity 3 * (cap_mvreads + 1))
-    int* d_mvstatus = nullptr;            // [cap_mvreads]
-    int64_t cap_mvreads = 0;
-    int* d_mvchunk = nullptr;             // count | last | base of every chunk, [3][cap_chunks]
-    int64_t cap_chunks = 0;
 };
 
-// the move-table front of signal_batch_impl (dm_signal_move_stats_device): the event tables are built on the device
-struct MoveInput {
-    const uint8_t* move;
-    const int64_t* mv_off;
-    const int64_t* first;
-    int32_t* status;        // out, [n_reads]
-};
+namespace {
+
+using SB = dm_signal;
+
+int reserve_raw(dm_signal* s, int64_t n_raw) { return s->b.ensure(SB::RAW, size_t(n_raw) * sizeof(short) + SB::RAW_SLACK); }
+
+int reserve_events(dm_signal* s, int64_t n_ev) {
+    const int rc = s->b.ensure(SB::EV, size_t(n_ev) * 2 * sizeof(unsigned long long));
+    return rc != DM_OK ? rc : s->b.ensure(SB::OUT, size_t(n_ev) * 2 * sizeof(float));
+}
+
+// the eight blocks of a batch that are sized by its reads
+int reserve_reads(dm_signal* s, int64_t n_reads) {
+    const size_t n = size_t(n_reads);
+    const size_t bytes[][2] = {{SB::BHIST, n * 65536 * sizeof(unsigned)}, {SB::BLUT, n * 65536 * sizeof(double)}, {SB::BMETA, 3 * (n + 1) * sizeof(long long)},
+                               {SB::BNORM, n * sizeof(sig::Norm)},        {SB::BFLAG, n * sizeof(int)},           {SB::EVOFF, 2 * (n + 1) * sizeof(long long)},
+                               {SB::VRANGE, 2 * n * sizeof(int)},         {SB::BFULL, n * sizeof(int)}};
+    for (const auto& e : bytes) {
+        const int rc = s->b.ensure(int(e[0]), e[1]);
+        if (rc != DM_OK) return rc;
+    }
+    return DM_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -793,8 +816,7 @@ dm_signal* dm_signal_create(int device) {
     s->h_hist.resize(65536);
     if (const char* e = std::getenv("DEEPMOD_SIGNAL_HOST_NORM")) s->host_order_statistics = e[0] == '1';
     if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&s->stream) != hipSuccess ||
-        hipMalloc(&s->d_hist, 65536 * sizeof(unsigned)) != hipSuccess ||
-        hipMalloc(&s->d_lut, 65536 * sizeof(double)) != hipSuccess ||
+        s->b.ensure(SB::HIST, 65536 * sizeof(unsigned)) != DM_OK || s->b.ensure(SB::LUT, 65536 * sizeof(double)) != DM_OK ||
         hipFuncSetAttribute(reinterpret_cast<const void*>(sig::signal_hist_kernel),
                             hipFuncAttributeMaxDynamicSharedMemorySize, sig::LDS_COPIES * sig::LDS_BINS * 4) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void*>(sig::signal_hist_batch_kernel),
@@ -802,7 +824,7 @@ dm_signal* dm_signal_create(int device) {
         hipFuncSetAttribute(reinterpret_cast<const void*>(sig::signal_norm_batch_kernel),
                             hipFuncAttributeMaxDynamicSharedMemorySize, int(sig::NORM_LDS)) != hipSuccess) {
         fail(DM_EDEVICE, "dm_signal_create: device setup failed: %s", hipGetErrorString(hipGetLastError()));
-        delete s;
+        dm_signal_destroy(s);
         return nullptr;
     }
     return s;
@@ -811,41 +833,10 @@ dm_signal* dm_signal_create(int device) {
 void dm_signal_destroy(dm_signal* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
-    (void)hipFree(s->d_raw);
-    (void)hipFree(s->d_ev);
-    (void)hipFree(s->d_out);
-    (void)hipFree(s->d_hist);
-    (void)hipFree(s->d_lut);
-    (void)hipFree(s->d_norm);
-    (void)hipFree(s->d_bhist);
-    (void)hipFree(s->d_blut);
-    (void)hipFree(s->d_bmeta);
-    (void)hipFree(s->d_bnorm);
-    (void)hipFree(s->d_bflag);
-    (void)hipFree(s->d_vrange);
-    (void)hipFree(s->d_bfull);
-    (void)hipFree(s->d_evread);
-    (void)hipFree(s->d_fb);
-    (void)hipFree(s->d_evoff);
-    (void)hipFree(s->d_rflag);
-    (void)hipFree(s->d_move);
-    (void)hipFree(s->d_mvmeta);
-    (void)hipFree(s->d_mvstatus);
-    (void)hipFree(s->d_mvchunk);
+    s->b.release();
     if (s->h_bhist) (void)hipHostFree(s->h_bhist);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
-}
-
-// The slice of a read its events cover, cut as numpy cuts raw[start_0 : start_last + length_last] (myDetect.py:272): uint64 arithmetic (the sum wraps),
-// both ends clamped to the read.  A start or an end of 2^63 and more is a LARGE index, not a negative one.  -> false: the slice is empty
-static inline bool covered_slice(const uint64_t* ev_start, const uint64_t* ev_length, int64_t e0, int64_t e1, int64_t n_samples, long long* lo, long long* hi) {
-    unsigned long long l = ev_start[e0], h = ev_start[e1 - 1] + ev_length[e1 - 1];
-    if (l > (unsigned long long)n_samples) l = (unsigned long long)n_samples;
-    if (h > (unsigned long long)n_samples) h = (unsigned long long)n_samples;
-    *lo = (long long)l;
-    *hi = (long long)h;
-    return h > l;
 }
 
 int dm_signal_event_stats(dm_signal* s, const int16_t* raw, int64_t n_raw, const uint64_t* ev_start,
@@ -859,46 +850,37 @@ int dm_signal_event_stats(dm_signal* s, const int16_t* raw, int64_t n_raw, const
     HIP_TRY(hipSetDevice(s->device));
     // slice covered by the events (myDetect.py:272): [start_0, start_last + length_last), clamped like a numpy slice
     long long lo, hi;
-    if (!covered_slice(ev_start, ev_length, 0, n_events, n_raw, &lo, &hi)) return fail(DM_EINVAL, "events cover no signal (start %lld, end %lld, %lld samples)", lo, hi, (long long)n_raw);
+    if (!sig::covered_slice(ev_start, ev_length, 0, n_events, n_raw, &lo, &hi)) return fail(DM_EINVAL, "events cover no signal (start %lld, end %lld, %lld samples)", lo, hi, (long long)n_raw);
 
+    int rc;
     const short* d_raw = reinterpret_cast<const short*>(raw);
     if (!is_device_ptr(raw)) {
-        if (s->cap_raw < n_raw) {
-            (void)hipFree(s->d_raw);
-            s->d_raw = nullptr;
-            s->cap_raw = 0;
-            HIP_TRY(hipMalloc(&s->d_raw, size_t(n_raw + (n_raw >> 2) + 8) * sizeof(short)));
-            s->cap_raw = n_raw + (n_raw >> 2);
-        }
-        HIP_TRY(hipMemcpyAsync(s->d_raw, raw, size_t(n_raw) * sizeof(short), hipMemcpyHostToDevice, s->stream));
-        d_raw = s->d_raw;
+        if ((rc = reserve_raw(s, n_raw)) != DM_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(s->b.buf[SB::RAW], raw, size_t(n_raw) * sizeof(short), hipMemcpyHostToDevice, s->stream));
+        d_raw = s->b.ptr<short>(SB::RAW);
     } else if ((reinterpret_cast<size_t>(raw) & 15) != 0) {
         return fail(DM_EINVAL, "device raw signal must be 16-byte aligned");
     }
-    if (s->cap_ev < n_events) {
-        (void)hipFree(s->d_ev);
-        (void)hipFree(s->d_out);
-        s->d_ev = nullptr;
-        s->d_out = nullptr;
-        s->cap_ev = 0;
-        const int64_t cap = n_events + (n_events >> 2);
-        HIP_TRY(hipMalloc(&s->d_ev, size_t(cap) * 2 * sizeof(unsigned long long)));
-        HIP_TRY(hipMalloc(&s->d_out, size_t(cap) * 2 * sizeof(float)));
-        s->cap_ev = cap;
-    }
-    HIP_TRY(hipMemcpyAsync(s->d_ev, ev_start, size_t(n_events) * 8, hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(s->d_ev + s->cap_ev, ev_length, size_t(n_events) * 8, hipMemcpyHostToDevice, s->stream));
+    if ((rc = reserve_events(s, n_events)) != DM_OK) return rc;
+    unsigned long long* d_start = s->b.ptr<unsigned long long>(SB::EV);
+    unsigned long long* d_length = d_start + n_events;
+    float* d_mean = s->b.ptr<float>(SB::OUT);
+    float* d_stdv = d_mean + n_events;
+    unsigned* d_hist = s->b.ptr<unsigned>(SB::HIST);
+    double* d_lut = s->b.ptr<double>(SB::LUT);
+    HIP_TRY(hipMemcpyAsync(d_start, ev_start, size_t(n_events) * 8, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(d_length, ev_length, size_t(n_events) * 8, hipMemcpyHostToDevice, s->stream));
 
     // 1. histogram of the covered slice
-    HIP_TRY(hipMemsetAsync(s->d_hist, 0, 65536 * sizeof(unsigned), s->stream));
+    HIP_TRY(hipMemsetAsync(d_hist, 0, 65536 * sizeof(unsigned), s->stream));
     {
         const long long groups = (hi - lo + 7) / 8;
         int grid = int(std::min<long long>(256, (groups + 255) / 256));
         if (grid < 1) grid = 1;
-        hipLaunchKernelGGL(sig::signal_hist_kernel, dim3(grid), dim3(256), sig::LDS_COPIES * sig::LDS_BINS * 4, s->stream, d_raw, lo, hi, s->d_hist);
+        hipLaunchKernelGGL(sig::signal_hist_kernel, dim3(grid), dim3(256), sig::LDS_COPIES * sig::LDS_BINS * 4, s->stream, d_raw, lo, hi, d_hist);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipMemcpyAsync(s->h_hist.data(), s->d_hist, 65536 * sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->h_hist.data(), d_hist, 65536 * sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     // 2. order statistics
     const sig::Norm p = sig::norm_from_hist(s->h_hist.data());
@@ -911,421 +893,343 @@ int dm_signal_event_stats(dm_signal* s, const int16_t* raw, int64_t n_raw, const
         norm6[5] = p.upper;
     }
     // 3. value table, 4. per-event statistics
-    hipLaunchKernelGGL(sig::signal_lut_kernel, dim3(256), dim3(256), 0, s->stream, s->d_lut, p);
+    hipLaunchKernelGGL(sig::signal_lut_kernel, dim3(256), dim3(256), 0, s->stream, d_lut, p);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(sig::event_stats_kernel, dim3(unsigned((n_events + 255) / 256)), dim3(256), 0, s->stream, d_raw,
-                       (long long)n_raw, s->d_lut, s->d_ev, s->d_ev + s->cap_ev, (long long)n_events, s->d_out,
-                       s->d_out + s->cap_ev);
+                       (long long)n_raw, d_lut, d_start, d_length, (long long)n_events, d_mean, d_stdv);
     HIP_TRY(hipGetLastError());
-    if (ev_mean) HIP_TRY(hipMemcpyAsync(ev_mean, s->d_out, size_t(n_events) * 4, hipMemcpyDeviceToHost, s->stream));
-    if (ev_stdv) HIP_TRY(hipMemcpyAsync(ev_stdv, s->d_out + s->cap_ev, size_t(n_events) * 4, hipMemcpyDeviceToHost, s->stream));
+    if (ev_mean) HIP_TRY(hipMemcpyAsync(ev_mean, d_mean, size_t(n_events) * 4, hipMemcpyDeviceToHost, s->stream));
+    if (ev_stdv) HIP_TRY(hipMemcpyAsync(ev_stdv, d_stdv, size_t(n_events) * 4, hipMemcpyDeviceToHost, s->stream));
     if (normalized) {   // the whole normalised signal (the reference keeps it in f5data; nothing downstream reads it)
         double* dst = normalized;
         if (!is_device_ptr(normalized)) {
-            if (s->cap_norm < n_raw) {
-                (void)hipFree(s->d_norm);
-                s->d_norm = nullptr;
-                s->cap_norm = 0;
-                HIP_TRY(hipMalloc(&s->d_norm, size_t(n_raw) * sizeof(double)));
-                s->cap_norm = n_raw;
-            }
-            dst = s->d_norm;
+            if ((rc = s->b.ensure(SB::NORM, size_t(n_raw) * sizeof(double))) != DM_OK) return rc;
+            dst = s->b.ptr<double>(SB::NORM);
         }
-        hipLaunchKernelGGL(sig::signal_gather_kernel, dim3(512), dim3(256), 0, s->stream, d_raw, (long long)n_raw, s->d_lut, dst);
+        hipLaunchKernelGGL(sig::signal_gather_kernel, dim3(512), dim3(256), 0, s->stream, d_raw, (long long)n_raw, d_lut, dst);
         HIP_TRY(hipGetLastError());
         if (dst != normalized)
             HIP_TRY(hipMemcpyAsync(normalized, dst, size_t(n_raw) * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     }
     HIP_TRY(hipStreamSynchronize(s->stream));
-    if (first_empty) {
-        int64_t fe = n_events;
-        for (int64_t i = 0; i < n_events; ++i) {
-            const unsigned long long st = ev_start[i];
-            unsigned long long en = st + ev_length[i];
-            if (en > (unsigned long long)n_raw) en = (unsigned long long)n_raw;
-            if (st >= en) {
-                fe = i;
-                break;
-            }
-        }
-        *first_empty = fe;
-    }
-    return DM_OK;
-}
-
-// Host side of a batch of reads, no device involved: the checks dm_signal_event_stats_batch makes before it uploads anything (a read with no events
-// or no samples, events that cover no signal) and first_empty[r] = index of the first event of read r whose slice is empty (the reference's loop
-// stops there, myDetect.py:334-340; n events of the read if none).  What a feeder needs before it walks its alignments: with it the statistics
-// themselves can stay on the device (dm_signal_event_stats_device).
-int dm_signal_plan_batch(int64_t n_reads, const int64_t* raw_off, const int64_t* ev_off, const uint64_t* ev_start, const uint64_t* ev_length,
-                         int64_t* first_empty) {
-    if (n_reads < 0) return fail(DM_EINVAL, "negative read count");
-    if (n_reads == 0) return DM_OK;
-    if (!raw_off || !ev_off || !ev_start || !ev_length) return fail(DM_EINVAL, "null input");
-    if (raw_off[0] != 0 || ev_off[0] != 0) return fail(DM_EINVAL, "the offset tables of a batch start at 0");
-    if (raw_off[n_reads] <= 0 || ev_off[n_reads] <= 0) return fail(DM_EINVAL, "empty batch");
-    if (n_reads > 4096) return fail(DM_EINVAL, "at most 4096 reads per call (%lld given)", (long long)n_reads);
-    for (int64_t r = 0; r < n_reads; ++r) {
-        const int64_t e0 = ev_off[r], e1 = ev_off[r + 1], nr = raw_off[r + 1] - raw_off[r];
-        if (e1 <= e0 || nr <= 0) return fail(DM_EINVAL, "read %lld of the batch has no events or no samples", (long long)r);
-        long long l, h;
-        if (!covered_slice(ev_start, ev_length, e0, e1, nr, &l, &h)) return fail(DM_EINVAL, "read %lld: events cover no signal (start %lld, end %lld, %lld samples)", (long long)r, l, h, (long long)nr);
-        if (first_empty) {
-            int64_t fe = e1 - e0;
-            for (int64_t e = e0; e < e1; ++e) {
-                const unsigned long long st = ev_start[e];
-                unsigned long long en = st + ev_length[e];
-                if (en > (unsigned long long)nr) en = (unsigned long long)nr;
-                if (st >= en) {
-                    fe = e - e0;
-                    break;
-                }
-            }
-            first_empty[r] = fe;
-        }
-    }
+    if (first_empty) *first_empty = sig::first_empty_event(ev_start, ev_length, 0, n_events, n_raw);
     return DM_OK;
 }
 
 }  // extern "C"
 
-// Many reads per call: the reads' samples back to back in `raw` (read r = raw[raw_off[r] .. raw_off[r+1])), their event tables back
-// to back (events of read r = [ev_off[r], ev_off[r+1]), starts relative to the read's first sample).  One upload, one histogram
-// launch (blockIdx.y = read), one order-statistics launch (one workgroup per read), one table launch, one statistics launch over
-// all events, one download, ONE host wait: a typical 120 k-sample read costs 0.15 ms in launches and waits when it travels alone.  Same kernels'
-// arithmetic as dm_signal_event_stats: results are bit-identical to per-read calls.
-// d_ev3 != NULL: the resident form (dm_signal_event_stats_device) - no per-event download; first_empty is then an INPUT (dm_signal_plan_batch).
-static int signal_batch_impl(dm_signal* s, int64_t n_reads, const int16_t* raw, const int64_t* raw_off, const uint64_t* ev_start,
-                             const uint64_t* ev_length, const int64_t* ev_off, float* ev_mean, float* ev_stdv, double* norm6,
-                             int64_t* first_empty, const float* fb_mean, const float* fb_stdv, float* d_ev3, int32_t* flags_out,
-                             const MoveInput* mv = nullptr) {
-    const bool resident = d_ev3 != nullptr;
-    if (!s) return fail(DM_EINVAL, "null signal handle");
-    if (n_reads < 0) return fail(DM_EINVAL, "negative read count");
-    if (n_reads == 0) return DM_OK;
-    if (!raw || !raw_off || !ev_off || (mv ? (!mv->move || !mv->mv_off || !mv->first || !mv->status || !resident) : (!ev_start || !ev_length)))
-        return fail(DM_EINVAL, "null input");
-    if (is_device_ptr(raw) || is_device_ptr(ev_start) || is_device_ptr(ev_mean)) return fail(DM_EINVAL, "the batched call takes host arrays");
-    const int64_t n_raw = raw_off[n_reads], n_ev = ev_off[n_reads];
-    if (raw_off[0] != 0 || ev_off[0] != 0) return fail(DM_EINVAL, "the offset tables of a batch start at 0");
-    if (n_raw <= 0 || n_ev <= 0) return fail(DM_EINVAL, "empty batch");
-    if (n_reads > 4096) return fail(DM_EINVAL, "at most 4096 reads per call (%lld given)", (long long)n_reads);
-    if (resident && ((!first_empty && !mv) || !is_device_ptr(d_ev3))) return fail(DM_EINVAL, "the resident form takes first_empty (dm_signal_plan_batch) and a device block");
-    HIP_TRY(hipSetDevice(s->device));
-    // per-read slice covered by the events (myDetect.py:272), absolute sample indices
-    std::vector<long long> meta(size_t(3) * (n_reads + 1));
-    long long* lo = meta.data();
-    long long* hi = lo + (n_reads + 1);
-    long long* off = hi + (n_reads + 1);
-    std::vector<int> ev_read(resident ? 0 : n_ev);
-    std::vector<long long> evmeta(size_t(2) * (n_reads + 1));     // ev_off | n_stat (the events a statistics kernel computes: all of them outside the resident form)
-    std::vector<long long> mvmeta(mv ? size_t(3) * (n_reads + 1) : 0);       // mv_off | chunk_off | first
-    int64_t n_mv = 0, n_chunks = 0;
-    if (mv) {
-        if (mv->mv_off[0] != 0) return fail(DM_EINVAL, "the offset tables of a batch start at 0");
-        if (is_device_ptr(mv->move)) return fail(DM_EINVAL, "the batched call takes host arrays");
-        for (int64_t r = 0; r < n_reads; ++r) {
-            const int64_t t0 = mv->mv_off[r], t1 = mv->mv_off[r + 1], nr = raw_off[r + 1] - raw_off[r];
-            if (t1 < t0 || t1 - t0 >= (int64_t(1) << 30)) return fail(DM_EINVAL, "read %lld: the move offsets decrease (or a table of 2^30 entries and more)", (long long)r);
-            if (ev_off[r + 1] < ev_off[r] || nr <= 0) return fail(DM_EINVAL, "read %lld of the batch has no samples (or its event offsets decrease)", (long long)r);
-            // the normalisation slice is [first, samples) - known without the events; a read whose `first` lies outside its samples fails on the
-            // device (DM_MOVE_OUTSIDE) and shows no statistics: its whole signal stands in, so that the order statistics see an ordinary read
-            const int64_t f = mv->first[r];
-            lo[r] = raw_off[r] + (f >= 0 && f < nr ? f : 0);
-            hi[r] = raw_off[r + 1];
-            off[r] = raw_off[r];
-            evmeta[size_t(r)] = ev_off[r];
-            evmeta[size_t(n_reads + 1 + r)] = 0;            // n_stat: written by move_scan_kernel
-            mvmeta[size_t(r)] = t0;
-            mvmeta[size_t(n_reads + 1 + r)] = n_chunks;
-            mvmeta[size_t(2 * (n_reads + 1) + r)] = f;
-            n_chunks += (t1 - (t0 & ~int64_t(15)) + sig::MOVE_CHUNK - 1) / sig::MOVE_CHUNK * (t1 > t0 ? 1 : 0);
-        }
-        n_mv = mv->mv_off[n_reads];
-        mvmeta[size_t(n_reads)] = n_mv;
-        mvmeta[size_t(2 * n_reads + 1)] = n_chunks;
-        mvmeta[size_t(3 * n_reads + 2)] = 0;
-        if (n_chunks >= (int64_t(1) << 31)) return fail(DM_EINVAL, "move tables of %lld chunks", (long long)n_chunks);
+// ---- many reads per call ----
+// The reads' samples back to back in `raw` (read r = raw[raw_off[r] .. raw_off[r+1])), their event tables back to back (events of read r =
+// [ev_off[r], ev_off[r+1]), starts relative to the read's first sample).  One upload, one histogram launch (blockIdx.y = read), one order-statistics
+// launch (one workgroup per read), one table launch, one statistics launch over all events, one download, ONE host wait: a typical 120 k-sample read
+// costs 0.15 ms in launches and waits when it travels alone.  Same kernels' arithmetic as dm_signal_event_stats: results are bit-identical to
+// per-read calls.  Three forms behind one sequence of stages (signal_batch_impl):
+//   host tables   dm_signal_event_stats_batch   event tables in, mean | stdv | first_empty out;
+//   resident      dm_signal_event_stats_device  the statistics stay on the device (d_ev3); first_empty is an INPUT (dm_signal_plan_batch);
+//   move tables   dm_signal_move_stats_device   resident, and the event tables are cut on the device from the move tables.
+namespace {
+
+// the inputs and outputs of one batched call; a pointer its form does not have is null
+struct BatchCall {
+    int64_t n_reads;
+    const int16_t* raw;
+    const int64_t* raw_off;
+    const int64_t* ev_off;
+    double* norm6;                           // out, optional
+    const uint64_t* ev_start = nullptr;      // event forms
+    const uint64_t* ev_length = nullptr;
+    float* ev_mean = nullptr;                // host-table form: out, optional
+    float* ev_stdv = nullptr;
+    int64_t* first_empty_out = nullptr;
+    float* d_ev3 = nullptr;                  // resident forms: out, a device block of the caller
+    int32_t* flags = nullptr;                // out, optional
+    const int64_t* first_empty = nullptr;    // resident event form
+    const float* fb_mean = nullptr;
+    const float* fb_stdv = nullptr;
+    bool from_moves = false;                 // move form
+    const uint8_t* move = nullptr;
+    const int64_t* mv_off = nullptr;
+    const int64_t* first = nullptr;
+    int32_t* status = nullptr;               // out, [n_reads]
+    bool resident() const { return d_ev3 != nullptr; }
+    bool with_fb() const { return resident() && fb_mean && fb_stdv; }
+};
+
+// a call on its way through the stages: its plan, where the plan's tables lie on the device (batch_reserve), and what the downloads write into
+struct BatchRun {
+    const BatchCall& c;
+    sig::BatchPlan p;
+    short* raw = nullptr;
+    unsigned long long *start = nullptr, *length = nullptr;
+    float *mean = nullptr, *stdv = nullptr, *fb_mean = nullptr, *fb_stdv = nullptr;
+    long long *lo = nullptr, *hi = nullptr, *off = nullptr, *ev_off = nullptr, *n_stat = nullptr;
+    unsigned* hist = nullptr;
+    double* lut = nullptr;
+    sig::Norm* norm = nullptr;
+    int *flag = nullptr, *vrange = nullptr, *full = nullptr, *ev_read = nullptr, *rflag = nullptr;
+    unsigned char* move = nullptr;
+    long long *mv_off = nullptr, *chunk_off = nullptr, *first = nullptr;
+    int *mv_status = nullptr, *ccnt = nullptr, *clast = nullptr, *cbase = nullptr;
+    std::vector<sig::Norm> h_norm;
+    std::vector<int> h_flag, h_status;
+    int h_rflag = 0;
+};
+
+int batch_reserve(dm_signal* s, BatchRun& q) {
+    const BatchCall& c = q.c;
+    const sig::BatchPlan& p = q.p;
+    DevBufs<SB::N_BUF>& b = s->b;
+    const size_t n = size_t(p.n_reads), n_ev = size_t(p.n_ev), n_chunks = size_t(p.n_chunks);
+    int rc;
+    if ((rc = reserve_raw(s, p.n_raw)) != DM_OK || (rc = reserve_events(s, p.n_ev)) != DM_OK) return rc;
+    if (!c.resident() && (rc = b.ensure(SB::EVREAD, n_ev * sizeof(int))) != DM_OK) return rc;
+    if ((rc = reserve_reads(s, p.n_reads)) != DM_OK) return rc;
+    if (c.with_fb() && (rc = b.ensure(SB::FB, n_ev * 2 * sizeof(float))) != DM_OK) return rc;
+    if (c.resident() && (rc = b.ensure(SB::RFLAG, sizeof(int))) != DM_OK) return rc;
+    if (c.from_moves) {
+        if ((rc = b.ensure(SB::MOVE, size_t(p.n_mv) + SB::MOVE_SLACK)) != DM_OK || (rc = b.ensure(SB::MVMETA, 3 * (n + 1) * sizeof(long long))) != DM_OK ||
+            (rc = b.ensure(SB::MVSTATUS, n * sizeof(int))) != DM_OK || (rc = b.ensure(SB::MVCHUNK, 3 * n_chunks * sizeof(int))) != DM_OK)
+            return rc;
+        q.move = b.ptr<unsigned char>(SB::MOVE);
+        q.mv_off = b.ptr<long long>(SB::MVMETA);
+        q.chunk_off = q.mv_off + (n + 1);
+        q.first = q.mv_off + 2 * (n + 1);
+        q.mv_status = b.ptr<int>(SB::MVSTATUS);
+        q.ccnt = b.ptr<int>(SB::MVCHUNK);
+        q.clast = q.ccnt + n_chunks;
+        q.cbase = q.ccnt + 2 * n_chunks;
     }
-    for (int64_t r = 0; r < n_reads && !mv; ++r) {
-        const int64_t e0 = ev_off[r], e1 = ev_off[r + 1], nr = raw_off[r + 1] - raw_off[r];
-        if (e1 <= e0 || nr <= 0) return fail(DM_EINVAL, "read %lld of the batch has no events or no samples", (long long)r);
-        long long l, h;
-        if (!covered_slice(ev_start, ev_length, e0, e1, nr, &l, &h)) return fail(DM_EINVAL, "read %lld: events cover no signal (start %lld, end %lld, %lld samples)", (long long)r, l, h, (long long)nr);
-        lo[r] = raw_off[r] + l;
-        hi[r] = raw_off[r] + h;
-        off[r] = raw_off[r];
-        evmeta[size_t(r)] = e0;
-        evmeta[size_t(n_reads + 1 + r)] = e1 - e0;
-        if (resident) {
-            const int64_t fe = first_empty[r] < 0 ? 0 : std::min<int64_t>(first_empty[r], e1 - e0);
-            if (fe < e1 - e0 && (!fb_mean || !fb_stdv))
-                return fail(DM_EINVAL, "read %lld has an empty event (%lld of %lld) and the call has no fall-back values", (long long)r, (long long)fe, (long long)(e1 - e0));
-            evmeta[size_t(n_reads + 1 + r)] = fe;
-        } else {
-            for (int64_t e = e0; e < e1; ++e) ev_read[e] = int(r);
-        }
+    q.raw = b.ptr<short>(SB::RAW);
+    q.start = b.ptr<unsigned long long>(SB::EV);
+    q.length = q.start + n_ev;
+    q.mean = b.ptr<float>(SB::OUT);
+    q.stdv = q.mean + n_ev;
+    q.ev_read = b.ptr<int>(SB::EVREAD);
+    if (c.with_fb()) {
+        q.fb_mean = b.ptr<float>(SB::FB);
+        q.fb_stdv = q.fb_mean + n_ev;
     }
-    off[n_reads] = n_raw;
-    evmeta[size_t(n_reads)] = n_ev;
-    // buffers
-    if (s->cap_raw < n_raw) {
-        (void)hipFree(s->d_raw);
-        s->d_raw = nullptr;
-        s->cap_raw = 0;
-        HIP_TRY(hipMalloc(&s->d_raw, size_t(n_raw + (n_raw >> 2) + 8) * sizeof(short)));
-        s->cap_raw = n_raw + (n_raw >> 2);
+    q.rflag = b.ptr<int>(SB::RFLAG);
+    q.lo = b.ptr<long long>(SB::BMETA);
+    q.hi = q.lo + (n + 1);
+    q.off = q.lo + 2 * (n + 1);
+    q.ev_off = b.ptr<long long>(SB::EVOFF);
+    q.n_stat = q.ev_off + (n + 1);
+    q.hist = b.ptr<unsigned>(SB::BHIST);
+    q.lut = b.ptr<double>(SB::BLUT);
+    q.norm = b.ptr<sig::Norm>(SB::BNORM);
+    q.flag = b.ptr<int>(SB::BFLAG);
+    q.vrange = b.ptr<int>(SB::VRANGE);
+    q.full = b.ptr<int>(SB::BFULL);
+    return DM_OK;
+}
+
+int batch_upload(dm_signal* s, BatchRun& q) {
+    const BatchCall& c = q.c;
+    sig::BatchPlan& p = q.p;
+    const size_t n_ev = size_t(p.n_ev);
+    HIP_TRY(hipMemcpyAsync(q.raw, c.raw, size_t(p.n_raw) * sizeof(short), hipMemcpyHostToDevice, s->stream));
+    if (!c.from_moves) {
+        HIP_TRY(hipMemcpyAsync(q.start, c.ev_start, n_ev * 8, hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(q.length, c.ev_length, n_ev * 8, hipMemcpyHostToDevice, s->stream));
     }
-    if (s->cap_ev < n_ev) {
-        (void)hipFree(s->d_ev);
-        (void)hipFree(s->d_out);
-        s->d_ev = nullptr;
-        s->d_out = nullptr;
-        s->cap_ev = 0;
-        const int64_t cap = n_ev + (n_ev >> 2);
-        HIP_TRY(hipMalloc(&s->d_ev, size_t(cap) * 2 * sizeof(unsigned long long)));
-        HIP_TRY(hipMalloc(&s->d_out, size_t(cap) * 2 * sizeof(float)));
-        s->cap_ev = cap;
-    }
-    if (!resident && s->cap_evread < n_ev) {
-        (void)hipFree(s->d_evread);
-        s->d_evread = nullptr;
-        HIP_TRY(hipMalloc(&s->d_evread, size_t(n_ev + (n_ev >> 2)) * sizeof(int)));
-        s->cap_evread = n_ev + (n_ev >> 2);
-    }
-    if (s->cap_reads < n_reads) {
-        (void)hipFree(s->d_bhist);
-        (void)hipFree(s->d_blut);
-        (void)hipFree(s->d_bmeta);
-        (void)hipFree(s->d_bnorm);
-        (void)hipFree(s->d_bflag);
-        (void)hipFree(s->d_evoff);
-        (void)hipFree(s->d_vrange);
-        (void)hipFree(s->d_bfull);
-        s->d_vrange = nullptr;
-        s->d_bfull = nullptr;
-        s->d_bflag = nullptr;
-        s->d_bhist = nullptr;
-        s->d_blut = nullptr;
-        s->d_bmeta = nullptr;
-        s->d_bnorm = nullptr;
-        s->d_evoff = nullptr;
-        s->cap_reads = 0;
-        const int64_t cap = n_reads + (n_reads >> 1);
-        HIP_TRY(hipMalloc(&s->d_bhist, size_t(cap) * 65536 * sizeof(unsigned)));
-        HIP_TRY(hipMalloc(&s->d_blut, size_t(cap) * 65536 * sizeof(double)));
-        HIP_TRY(hipMalloc(&s->d_bmeta, size_t(3) * (cap + 1) * sizeof(long long)));
-        HIP_TRY(hipMalloc(&s->d_bnorm, size_t(cap) * sizeof(sig::Norm)));
-        HIP_TRY(hipMalloc(&s->d_bflag, size_t(cap) * sizeof(int)));
-        HIP_TRY(hipMalloc(&s->d_evoff, size_t(2) * (cap + 1) * sizeof(long long)));
-        HIP_TRY(hipMalloc(&s->d_vrange, size_t(2) * cap * sizeof(int)));
-        HIP_TRY(hipMalloc(&s->d_bfull, size_t(cap) * sizeof(int)));
-        s->cap_reads = cap;
-    }
-    const bool with_fb = resident && fb_mean && fb_stdv;
-    if (with_fb && s->cap_fb < n_ev) {
-        (void)hipFree(s->d_fb);
-        s->d_fb = nullptr;
-        s->cap_fb = 0;
-        const int64_t cap = n_ev + (n_ev >> 2);
-        HIP_TRY(hipMalloc(&s->d_fb, size_t(cap) * 2 * sizeof(float)));
-        s->cap_fb = cap;
-    }
-    if (resident && !s->d_rflag) HIP_TRY(hipMalloc(&s->d_rflag, sizeof(int)));
-    if (mv) {
-        if (s->cap_move < n_mv || !s->d_move) {
-            (void)hipFree(s->d_move);
-            s->d_move = nullptr;
-            s->cap_move = 0;
-            const int64_t cap = n_mv + (n_mv >> 2);
-            HIP_TRY(hipMalloc(&s->d_move, size_t(cap) + 16));
-            s->cap_move = cap;
-        }
-        if (s->cap_mvreads < n_reads) {
-            (void)hipFree(s->d_mvmeta);
-            (void)hipFree(s->d_mvstatus);
-            s->d_mvmeta = nullptr;
-            s->d_mvstatus = nullptr;
-            s->cap_mvreads = 0;
-            const int64_t cap = n_reads + (n_reads >> 1);
-            HIP_TRY(hipMalloc(&s->d_mvmeta, size_t(3) * (cap + 1) * sizeof(long long)));
-            HIP_TRY(hipMalloc(&s->d_mvstatus, size_t(cap) * sizeof(int)));
-            s->cap_mvreads = cap;
-        }
-        if (s->cap_chunks < n_chunks || !s->d_mvchunk) {
-            (void)hipFree(s->d_mvchunk);
-            s->d_mvchunk = nullptr;
-            s->cap_chunks = 0;
-            const int64_t cap = n_chunks + (n_chunks >> 2) + 1;
-            HIP_TRY(hipMalloc(&s->d_mvchunk, size_t(3) * cap * sizeof(int)));
-            s->cap_chunks = cap;
+    if (!c.resident()) HIP_TRY(hipMemcpyAsync(q.ev_read, p.ev_read.data(), n_ev * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(q.lo, p.meta.data(), p.meta.size() * sizeof(long long), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(q.ev_off, p.evmeta.data(), p.evmeta.size() * sizeof(long long), hipMemcpyHostToDevice, s->stream));
+    if (c.resident()) {
+        HIP_TRY(hipMemsetAsync(q.rflag, 0, sizeof(int), s->stream));
+        if (c.with_fb()) {
+            HIP_TRY(hipMemcpyAsync(q.fb_mean, c.fb_mean, n_ev * 4, hipMemcpyHostToDevice, s->stream));
+            HIP_TRY(hipMemcpyAsync(q.fb_stdv, c.fb_stdv, n_ev * 4, hipMemcpyHostToDevice, s->stream));
         }
     }
-    HIP_TRY(hipMemcpyAsync(s->d_raw, raw, size_t(n_raw) * sizeof(short), hipMemcpyHostToDevice, s->stream));
-    if (!mv) {
-        HIP_TRY(hipMemcpyAsync(s->d_ev, ev_start, size_t(n_ev) * 8, hipMemcpyHostToDevice, s->stream));
-        HIP_TRY(hipMemcpyAsync(s->d_ev + s->cap_ev, ev_length, size_t(n_ev) * 8, hipMemcpyHostToDevice, s->stream));
-    }
-    if (!resident) HIP_TRY(hipMemcpyAsync(s->d_evread, ev_read.data(), size_t(n_ev) * sizeof(int), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(s->d_bmeta, meta.data(), meta.size() * sizeof(long long), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(s->d_evoff, evmeta.data(), evmeta.size() * sizeof(long long), hipMemcpyHostToDevice, s->stream));
-    if (resident) {
-        HIP_TRY(hipMemsetAsync(s->d_rflag, 0, sizeof(int), s->stream));
-        if (with_fb) {
-            HIP_TRY(hipMemcpyAsync(s->d_fb, fb_mean, size_t(n_ev) * 4, hipMemcpyHostToDevice, s->stream));
-            HIP_TRY(hipMemcpyAsync(s->d_fb + s->cap_fb, fb_stdv, size_t(n_ev) * 4, hipMemcpyHostToDevice, s->stream));
-        }
-    }
-    long long* d_lo = s->d_bmeta;
-    long long* d_hi = s->d_bmeta + (n_reads + 1);
-    long long* d_off = s->d_bmeta + 2 * (n_reads + 1);
-    std::vector<int> mv_status(mv ? n_reads : 0, 0);
-    if (mv) {
-        // 0. the event tables from the move tables (behind the uploads of d_bmeta / d_evoff on the same stream; no host wait before the statistics)
-        if (n_mv > 0) HIP_TRY(hipMemcpyAsync(s->d_move, mv->move, size_t(n_mv), hipMemcpyHostToDevice, s->stream));
-        HIP_TRY(hipMemcpyAsync(s->d_mvmeta, mvmeta.data(), mvmeta.size() * sizeof(long long), hipMemcpyHostToDevice, s->stream));
-        const long long* d_mvoff = s->d_mvmeta;
-        const long long* d_choff = s->d_mvmeta + (n_reads + 1);
-        const long long* d_first = s->d_mvmeta + 2 * (n_reads + 1);
-        int* d_ccnt = s->d_mvchunk;
-        int* d_clast = s->d_mvchunk + s->cap_chunks;
-        int* d_cbase = s->d_mvchunk + 2 * s->cap_chunks;
-        if (n_chunks > 0) {
-            hipLaunchKernelGGL(sig::move_count_kernel, dim3(unsigned(n_chunks)), dim3(sig::MOVE_THREADS), 0, s->stream, s->d_move, d_mvoff, d_choff, int(n_reads),
-                               d_ccnt, d_clast);
-            HIP_TRY(hipGetLastError());
-        }
-        hipLaunchKernelGGL(sig::move_scan_kernel, dim3(unsigned(n_reads)), dim3(sig::MOVE_THREADS), 0, s->stream, d_ccnt, d_clast, d_choff, d_first, d_off,
-                           s->d_evoff, d_cbase, s->d_mvstatus, s->d_evoff + (n_reads + 1), s->d_ev, s->d_ev + s->cap_ev);
-        HIP_TRY(hipGetLastError());
-        if (n_chunks > 0) {
-            hipLaunchKernelGGL(sig::move_write_kernel, dim3(unsigned(n_chunks)), dim3(sig::MOVE_THREADS), 0, s->stream, s->d_move, d_mvoff, d_choff, int(n_reads),
-                               d_cbase, s->d_mvstatus, d_first, s->d_evoff, s->d_ev);
-            HIP_TRY(hipGetLastError());
-        }
-        hipLaunchKernelGGL(sig::move_length_kernel, dim3(unsigned((n_ev + 255) / 256)), dim3(256), 0, s->stream, s->d_ev, s->d_evoff, d_off, s->d_mvstatus,
-                           int(n_reads), (long long)n_ev, s->d_ev + s->cap_ev);
-        HIP_TRY(hipGetLastError());
-        // (the statuses come back behind the statistics kernels, next to the range flag: a download enqueued here would make the host wait for the
-        // segmentation before it launches them)
-    }
-    // 1. histograms of all reads
-    HIP_TRY(hipMemsetAsync(s->d_bhist, 0, size_t(n_reads) * 65536 * sizeof(unsigned), s->stream));
-    {
-        // value range of every read: the minima start at 0x7f7f7f7f, the maxima at 0x80808080 (byte fills: larger / smaller than any int16)
-        HIP_TRY(hipMemsetAsync(s->d_vrange, 0x7f, size_t(n_reads) * sizeof(int), s->stream));
-        HIP_TRY(hipMemsetAsync(s->d_vrange + n_reads, 0x80, size_t(n_reads) * sizeof(int), s->stream));
-        // a workgroup zeroes and flushes 128 KB of privatised bins whatever it counts: one per 32,768 samples of an average read (round 5: one per 2,048 -
-        // the fixed cost was 40x the samples' own bytes and the flush atomics of twenty workgroups per read met on the same few hundred bins)
-        const long long avg = n_raw / n_reads;
-        int gx = int(std::min<long long>(64, (avg + 32767) / 32768));
-        if (gx < 1) gx = 1;
-        hipLaunchKernelGGL(sig::signal_hist_batch_kernel, dim3(gx, unsigned(n_reads)), dim3(256), sig::LDS_COPIES * sig::LDS_BINS * 4, s->stream,
-                           s->d_raw, d_lo, d_hi, s->d_bhist, s->d_vrange);
-        HIP_TRY(hipGetLastError());
-    }
-    // reads whose value table the events need whole (an event outside the covered slice): a pass over the event tables on the device, 16 B per event
-    HIP_TRY(hipMemsetAsync(s->d_bfull, 0, size_t(n_reads) * sizeof(int), s->stream));
-    hipLaunchKernelGGL(sig::event_reach_batch_kernel, dim3(unsigned((n_ev + 255) / 256)), dim3(256), 0, s->stream, s->d_ev, s->d_ev + s->cap_ev, s->d_evoff,
-                       s->d_evoff + (n_reads + 1), d_lo, d_hi, d_off, int(n_reads), (long long)n_ev, s->d_bfull);
-    HIP_TRY(hipGetLastError());
-    // 2. order statistics of all reads on the device, 3. value tables, 4. statistics of all events: one stream, no host round trip
-    std::vector<sig::Norm> norms(n_reads);
-    std::vector<int> flags(n_reads, 0);
-    int range_flag = 0;
-    auto tables_and_stats = [&]() -> int {
-        hipLaunchKernelGGL(sig::signal_lut_batch_kernel, dim3(256, unsigned(n_reads)), dim3(256), 0, s->stream, s->d_blut, s->d_bnorm, s->d_vrange, s->d_bfull);
-        HIP_TRY(hipGetLastError());
-        if (resident) {
-            hipLaunchKernelGGL(sig::event_ev3_batch_kernel, dim3(unsigned((n_ev + 255) / 256)), dim3(256), 0, s->stream, s->d_raw, d_off, s->d_blut,
-                               s->d_ev, s->d_ev + s->cap_ev, s->d_evoff, s->d_evoff + (n_reads + 1), int(n_reads), (long long)n_ev,
-                               with_fb ? s->d_fb : nullptr, with_fb ? s->d_fb + s->cap_fb : nullptr, d_ev3, s->d_rflag);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(&range_flag, s->d_rflag, sizeof(int), hipMemcpyDeviceToHost, s->stream));
-            if (mv) HIP_TRY(hipMemcpyAsync(mv_status.data(), s->d_mvstatus, size_t(n_reads) * sizeof(int), hipMemcpyDeviceToHost, s->stream));
-            return DM_OK;
-        }
-        hipLaunchKernelGGL(sig::event_stats_batch_kernel, dim3(unsigned((n_ev + 255) / 256)), dim3(256), 0, s->stream, s->d_raw, d_off, s->d_blut,
-                           s->d_ev, s->d_ev + s->cap_ev, s->d_evread, (long long)n_ev, s->d_out, s->d_out + s->cap_ev);
-        HIP_TRY(hipGetLastError());
-        if (ev_mean) HIP_TRY(hipMemcpyAsync(ev_mean, s->d_out, size_t(n_ev) * 4, hipMemcpyDeviceToHost, s->stream));
-        if (ev_stdv) HIP_TRY(hipMemcpyAsync(ev_stdv, s->d_out + s->cap_ev, size_t(n_ev) * 4, hipMemcpyDeviceToHost, s->stream));
-        return DM_OK;
-    };
-    bool host_path = s->host_order_statistics;
-    if (!host_path) {
-        hipLaunchKernelGGL(sig::signal_norm_batch_kernel, dim3(unsigned(n_reads)), dim3(sig::NORM_THREADS), sig::NORM_LDS, s->stream, s->d_bhist,
-                           s->d_bnorm, s->d_bflag, s->d_vrange);
-        HIP_TRY(hipGetLastError());
-        int rc = tables_and_stats();
-        if (rc) return rc;
-        if (norm6 || !resident) HIP_TRY(hipMemcpyAsync(norms.data(), s->d_bnorm, size_t(n_reads) * sizeof(sig::Norm), hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipMemcpyAsync(flags.data(), s->d_bflag, size_t(n_reads) * sizeof(int), hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        for (int64_t r = 0; r < n_reads; ++r) host_path |= flags[r] != 0;       // > NORM_CAP distinct values or a zero scale: rare
-    }
-    if (host_path) {
-        // the histograms come back (page-locked), exact order statistics on the host, then the same two kernels
-        if (s->cap_hbhist < n_reads) {
-            if (s->h_bhist) (void)hipHostFree(s->h_bhist);
-            s->h_bhist = nullptr;
-            s->cap_hbhist = 0;
-            const int64_t cap = n_reads + (n_reads >> 1);
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_bhist), size_t(cap) * 65536 * sizeof(unsigned), hipHostMallocDefault));
-            s->cap_hbhist = cap;
-        }
-        HIP_TRY(hipMemcpyAsync(s->h_bhist, s->d_bhist, size_t(n_reads) * 65536 * sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        {
-            const int nthr = int(std::min<int64_t>(4, n_reads / 4 + 1));
-            auto work = [&](int t) {
-                for (int64_t r = t; r < n_reads; r += nthr) norms[r] = sig::norm_from_hist(s->h_bhist + size_t(r) * 65536);
-            };
-            std::vector<std::thread> pool;
-            for (int t = 1; t < nthr; ++t) pool.emplace_back(work, t);
-            work(0);
-            for (auto& th : pool) th.join();
-        }
-        HIP_TRY(hipMemcpyAsync(s->d_bnorm, norms.data(), size_t(n_reads) * sizeof(sig::Norm), hipMemcpyHostToDevice, s->stream));
-        if (resident) HIP_TRY(hipMemsetAsync(s->d_rflag, 0, sizeof(int), s->stream));
-        int rc = tables_and_stats();
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(s->stream));
-    }
-    if (flags_out) *flags_out = range_flag ? 1 : 0;
-    if (mv)
-        for (int64_t r = 0; r < n_reads; ++r) mv->status[r] = mv_status[r];
-    if (norm6)
-        for (int64_t r = 0; r < n_reads; ++r) {
-            double* o = norm6 + 6 * r;
-            o[0] = norms[r].mshift; o[1] = norms[r].mscale; o[2] = norms[r].med; o[3] = norms[r].mad; o[4] = norms[r].lower; o[5] = norms[r].upper;
-        }
-    if (first_empty && !resident) {
-        for (int64_t r = 0; r < n_reads; ++r) {
-            const int64_t e0 = ev_off[r], e1 = ev_off[r + 1];
-            const unsigned long long nr = (unsigned long long)(raw_off[r + 1] - raw_off[r]);
-            int64_t fe = e1 - e0;
-            for (int64_t e = e0; e < e1; ++e) {
-                const unsigned long long st = ev_start[e];
-                unsigned long long en = st + ev_length[e];
-                if (en > nr) en = nr;
-                if (st >= en) {
-                    fe = e - e0;
-                    break;
-                }
-            }
-            first_empty[r] = fe;
-        }
+    if (c.from_moves) {
+        if (p.n_mv > 0) HIP_TRY(hipMemcpyAsync(q.move, c.move, size_t(p.n_mv), hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(q.mv_off, p.mvmeta.data(), p.mvmeta.size() * sizeof(long long), hipMemcpyHostToDevice, s->stream));
     }
     return DM_OK;
 }
+
+// move form: the event tables from the move tables (behind the uploads on the same stream; no host wait before the statistics).  The statuses come
+// back behind the statistics kernels, next to the range flag (batch_tables_and_stats): a download enqueued here would make the host wait for the
+// segmentation before it launches them.
+int batch_segment(dm_signal* s, BatchRun& q) {
+    const int n_reads = int(q.p.n_reads);
+    const unsigned n_chunks = unsigned(q.p.n_chunks);
+    const long long n_ev = q.p.n_ev;
+    if (n_chunks > 0) {
+        hipLaunchKernelGGL(sig::move_count_kernel, dim3(n_chunks), dim3(sig::MOVE_THREADS), 0, s->stream, q.move, q.mv_off, q.chunk_off, n_reads, q.ccnt, q.clast);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(sig::move_scan_kernel, dim3(unsigned(n_reads)), dim3(sig::MOVE_THREADS), 0, s->stream, q.ccnt, q.clast, q.chunk_off, q.first, q.off,
+                       q.ev_off, q.cbase, q.mv_status, q.n_stat, q.start, q.length);
+    HIP_TRY(hipGetLastError());
+    if (n_chunks > 0) {
+        hipLaunchKernelGGL(sig::move_write_kernel, dim3(n_chunks), dim3(sig::MOVE_THREADS), 0, s->stream, q.move, q.mv_off, q.chunk_off, n_reads, q.cbase,
+                           q.mv_status, q.first, q.ev_off, q.start);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(sig::move_length_kernel, dim3(unsigned((n_ev + 255) / 256)), dim3(256), 0, s->stream, q.start, q.ev_off, q.off, q.mv_status, n_reads, n_ev,
+                       q.length);
+    HIP_TRY(hipGetLastError());
+    return DM_OK;
+}
+
+// 1. histograms of all reads, and the reads whose value table the events need whole
+int batch_histograms(dm_signal* s, BatchRun& q) {
+    const size_t n = size_t(q.p.n_reads);
+    const long long n_ev = q.p.n_ev;
+    HIP_TRY(hipMemsetAsync(q.hist, 0, n * 65536 * sizeof(unsigned), s->stream));
+    // value range of every read: the minima start at 0x7f7f7f7f, the maxima at 0x80808080 (byte fills: larger / smaller than any int16)
+    HIP_TRY(hipMemsetAsync(q.vrange, 0x7f, n * sizeof(int), s->stream));
+    HIP_TRY(hipMemsetAsync(q.vrange + n, 0x80, n * sizeof(int), s->stream));
+    // a workgroup zeroes and flushes 128 KB of privatised bins whatever it counts: one per 32,768 samples of an average read (round 5: one per 2,048 -
+    // the fixed cost was 40x the samples' own bytes and the flush atomics of twenty workgroups per read met on the same few hundred bins)
+    const long long avg = q.p.n_raw / q.p.n_reads;
+    int gx = int(std::min<long long>(64, (avg + 32767) / 32768));
+    if (gx < 1) gx = 1;
+    hipLaunchKernelGGL(sig::signal_hist_batch_kernel, dim3(gx, unsigned(n)), dim3(256), sig::LDS_COPIES * sig::LDS_BINS * 4, s->stream, q.raw, q.lo, q.hi, q.hist,
+                       q.vrange);
+    HIP_TRY(hipGetLastError());
+    // an event outside the covered slice: a pass over the event tables on the device, 16 B per event
+    HIP_TRY(hipMemsetAsync(q.full, 0, n * sizeof(int), s->stream));
+    hipLaunchKernelGGL(sig::event_reach_batch_kernel, dim3(unsigned((n_ev + 255) / 256)), dim3(256), 0, s->stream, q.start, q.length, q.ev_off, q.n_stat, q.lo, q.hi,
+                       q.off, int(n), n_ev, q.full);
+    HIP_TRY(hipGetLastError());
+    return DM_OK;
+}
+
+// 2. order statistics of all reads on the device: one stream with the tables and the statistics behind it, no host round trip
+int batch_normalise_device(dm_signal* s, BatchRun& q) {
+    hipLaunchKernelGGL(sig::signal_norm_batch_kernel, dim3(unsigned(q.p.n_reads)), dim3(sig::NORM_THREADS), sig::NORM_LDS, s->stream, q.hist, q.norm, q.flag,
+                       q.vrange);
+    HIP_TRY(hipGetLastError());
+    return DM_OK;
+}
+
+// 3. value tables, 4. statistics of all events, and the downloads of what they wrote
+int batch_tables_and_stats(dm_signal* s, BatchRun& q) {
+    const BatchCall& c = q.c;
+    const size_t n = size_t(q.p.n_reads);
+    const long long n_ev = q.p.n_ev;
+    hipLaunchKernelGGL(sig::signal_lut_batch_kernel, dim3(256, unsigned(n)), dim3(256), 0, s->stream, q.lut, q.norm, q.vrange, q.full);
+    HIP_TRY(hipGetLastError());
+    if (c.resident()) {
+        hipLaunchKernelGGL(sig::event_ev3_batch_kernel, dim3(unsigned((n_ev + 255) / 256)), dim3(256), 0, s->stream, q.raw, q.off, q.lut, q.start, q.length, q.ev_off,
+                           q.n_stat, int(n), n_ev, q.fb_mean, q.fb_stdv, c.d_ev3, q.rflag);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&q.h_rflag, q.rflag, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+        if (c.from_moves) HIP_TRY(hipMemcpyAsync(q.h_status.data(), q.mv_status, n * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+        return DM_OK;
+    }
+    hipLaunchKernelGGL(sig::event_stats_batch_kernel, dim3(unsigned((n_ev + 255) / 256)), dim3(256), 0, s->stream, q.raw, q.off, q.lut, q.start, q.length, q.ev_read,
+                       n_ev, q.mean, q.stdv);
+    HIP_TRY(hipGetLastError());
+    if (c.ev_mean) HIP_TRY(hipMemcpyAsync(c.ev_mean, q.mean, size_t(n_ev) * 4, hipMemcpyDeviceToHost, s->stream));
+    if (c.ev_stdv) HIP_TRY(hipMemcpyAsync(c.ev_stdv, q.stdv, size_t(n_ev) * 4, hipMemcpyDeviceToHost, s->stream));
+    return DM_OK;
+}
+
+// the one host wait of the device path; *host_path: a read the kernel handed back (> NORM_CAP distinct values or a zero scale: rare)
+int batch_wait_device(dm_signal* s, BatchRun& q, bool* host_path) {
+    const size_t n = size_t(q.p.n_reads);
+    if (q.c.norm6 || !q.c.resident()) HIP_TRY(hipMemcpyAsync(q.h_norm.data(), q.norm, n * sizeof(sig::Norm), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(q.h_flag.data(), q.flag, n * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    for (size_t r = 0; r < n; ++r) *host_path |= q.h_flag[r] != 0;
+    return DM_OK;
+}
+
+// the host fall-back of 2.: the histograms come back (page-locked), exact order statistics on the host, their results go up for the same two kernels
+int batch_normalise_host(dm_signal* s, BatchRun& q) {
+    const int64_t n_reads = q.p.n_reads;
+    if (s->cap_hbhist < n_reads) {
+        if (s->h_bhist) (void)hipHostFree(s->h_bhist);
+        s->h_bhist = nullptr;
+        s->cap_hbhist = 0;
+        const int64_t cap = n_reads + (n_reads >> 1);
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_bhist), size_t(cap) * 65536 * sizeof(unsigned), hipHostMallocDefault));
+        s->cap_hbhist = cap;
+    }
+    HIP_TRY(hipMemcpyAsync(s->h_bhist, q.hist, size_t(n_reads) * 65536 * sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    {
+        const int nthr = int(std::min<int64_t>(4, n_reads / 4 + 1));
+        auto work = [&](int t) {
+            for (int64_t r = t; r < n_reads; r += nthr) q.h_norm[r] = sig::norm_from_hist(s->h_bhist + size_t(r) * 65536);
+        };
+        std::vector<std::thread> pool;
+        for (int t = 1; t < nthr; ++t) pool.emplace_back(work, t);
+        work(0);
+        for (auto& th : pool) th.join();
+    }
+    HIP_TRY(hipMemcpyAsync(q.norm, q.h_norm.data(), size_t(n_reads) * sizeof(sig::Norm), hipMemcpyHostToDevice, s->stream));
+    if (q.c.resident()) HIP_TRY(hipMemsetAsync(q.rflag, 0, sizeof(int), s->stream));
+    return DM_OK;
+}
+
+// after the last host wait: what the call returns in host arrays that no download wrote
+void batch_copy_out(const BatchRun& q) {
+    const BatchCall& c = q.c;
+    const int64_t n_reads = q.p.n_reads;
+    if (c.flags) *c.flags = q.h_rflag ? 1 : 0;
+    if (c.from_moves)
+        for (int64_t r = 0; r < n_reads; ++r) c.status[r] = q.h_status[r];
+    if (c.norm6)
+        for (int64_t r = 0; r < n_reads; ++r) {
+            const sig::Norm& v = q.h_norm[r];
+            double* o = c.norm6 + 6 * r;
+            o[0] = v.mshift; o[1] = v.mscale; o[2] = v.med; o[3] = v.mad; o[4] = v.lower; o[5] = v.upper;
+        }
+    if (c.first_empty_out)
+        for (int64_t r = 0; r < n_reads; ++r)
+            c.first_empty_out[r] = sig::first_empty_event(c.ev_start, c.ev_length, c.ev_off[r], c.ev_off[r + 1], c.raw_off[r + 1] - c.raw_off[r]);
+}
+
+int signal_batch_impl(dm_signal* s, const BatchCall& c) {
+    if (!s) return fail(DM_EINVAL, "null signal handle");
+    if (c.n_reads > 0) {     // the arrays the plan does not look at, and what only this half can tell; every other check is the plan's (signalplan.inc)
+        if (!c.raw || (c.from_moves && (!c.move || !c.status))) return fail(DM_EINVAL, "null input");
+        if (is_device_ptr(c.raw) || is_device_ptr(c.ev_start) || is_device_ptr(c.ev_mean) || is_device_ptr(c.move)) return fail(DM_EINVAL, "the batched call takes host arrays");
+        if (c.resident() && ((!c.first_empty && !c.from_moves) || !is_device_ptr(c.d_ev3)))
+            return fail(DM_EINVAL, "the resident form takes first_empty (dm_signal_plan_batch) and a device block");
+    }
+    BatchRun q{c};
+    int rc = c.from_moves ? sig::plan_moves(q.p, c.n_reads, c.raw_off, c.ev_off, c.mv_off, c.first)
+                          : sig::plan_events(q.p, c.n_reads, c.raw_off, c.ev_off, c.ev_start, c.ev_length, c.resident(), c.first_empty, c.with_fb());
+    if (rc != DM_OK || c.n_reads == 0) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    q.h_norm.resize(size_t(c.n_reads));
+    q.h_flag.assign(size_t(c.n_reads), 0);
+    q.h_status.assign(c.from_moves ? size_t(c.n_reads) : 0, 0);
+    if ((rc = batch_reserve(s, q)) != DM_OK || (rc = batch_upload(s, q)) != DM_OK) return rc;
+    if (c.from_moves && (rc = batch_segment(s, q)) != DM_OK) return rc;
+    if ((rc = batch_histograms(s, q)) != DM_OK) return rc;
+    bool host_path = s->host_order_statistics;
+    if (!host_path && ((rc = batch_normalise_device(s, q)) != DM_OK || (rc = batch_tables_and_stats(s, q)) != DM_OK || (rc = batch_wait_device(s, q, &host_path)) != DM_OK))
+        return rc;
+    if (host_path) {
+        if ((rc = batch_normalise_host(s, q)) != DM_OK || (rc = batch_tables_and_stats(s, q)) != DM_OK) return rc;
+        HIP_TRY(hipStreamSynchronize(s->stream));
+    }
+    batch_copy_out(q);
+    return DM_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
 int dm_signal_event_stats_batch(dm_signal* s, int64_t n_reads, const int16_t* raw, const int64_t* raw_off, const uint64_t* ev_start,
                                 const uint64_t* ev_length, const int64_t* ev_off, float* ev_mean, float* ev_stdv, double* norm6,
                                 int64_t* first_empty) {
-    return signal_batch_impl(s, n_reads, raw, raw_off, ev_start, ev_length, ev_off, ev_mean, ev_stdv, norm6, first_empty, nullptr, nullptr, nullptr, nullptr);
+    BatchCall c{n_reads, raw, raw_off, ev_off, norm6};
+    c.ev_start = ev_start;
+    c.ev_length = ev_length;
+    c.ev_mean = ev_mean;
+    c.ev_stdv = ev_stdv;
+    c.first_empty_out = first_empty;
+    return signal_batch_impl(s, c);
 }
 
 // The RESIDENT form (round 6): the same four kernels, but the per-event statistics never leave the device - d_ev3 [n_events][3] (a device block of the
@@ -1337,8 +1241,15 @@ int dm_signal_event_stats_device(dm_signal* s, int64_t n_reads, const int16_t* r
                                  const uint64_t* ev_length, const int64_t* ev_off, const int64_t* first_empty, const float* fb_mean, const float* fb_stdv,
                                  float* d_ev3, double* norm6, int32_t* flags) {
     if (!d_ev3) return fail(DM_EINVAL, "dm_signal_event_stats_device: null device block");
-    return signal_batch_impl(s, n_reads, raw, raw_off, ev_start, ev_length, ev_off, nullptr, nullptr, norm6, const_cast<int64_t*>(first_empty), fb_mean, fb_stdv,
-                             d_ev3, flags);
+    BatchCall c{n_reads, raw, raw_off, ev_off, norm6};
+    c.ev_start = ev_start;
+    c.ev_length = ev_length;
+    c.d_ev3 = d_ev3;
+    c.flags = flags;
+    c.first_empty = first_empty;
+    c.fb_mean = fb_mean;
+    c.fb_stdv = fb_stdv;
+    return signal_batch_impl(s, c);
 }
 
 // The resident form for reads with move tables (detect --move): see include/deepmod_hip.h.  The segmentation kernels (sig::move_*_kernel) write the
@@ -1347,10 +1258,16 @@ int dm_signal_event_stats_device(dm_signal* s, int64_t n_reads, const int16_t* r
 int dm_signal_move_stats_device(dm_signal* s, int64_t n_reads, const int16_t* raw, const int64_t* raw_off, const uint8_t* move, const int64_t* mv_off,
                                 const int64_t* first, const int64_t* ev_off, float* d_ev3, int32_t* status, double* norm6, int32_t* flags) {
     if (!d_ev3) return fail(DM_EINVAL, "dm_signal_move_stats_device: null device block");
-    const MoveInput mv{move, mv_off, first, status};
-    return signal_batch_impl(s, n_reads, raw, raw_off, nullptr, nullptr, ev_off, nullptr, nullptr, norm6, nullptr, nullptr, nullptr, d_ev3, flags, &mv);
+    BatchCall c{n_reads, raw, raw_off, ev_off, norm6};
+    c.d_ev3 = d_ev3;
+    c.flags = flags;
+    c.from_moves = true;
+    c.move = move;
+    c.mv_off = mv_off;
+    c.first = first;
+    c.status = status;
+    return signal_batch_impl(s, c);
 }
 
-int64_t dm_signal_move_chunk(void) { return sig::MOVE_CHUNK; }
-
 }  // extern "C"
+

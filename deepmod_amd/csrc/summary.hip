@@ -139,10 +139,8 @@ void dm_summary_destroy(dm_summary* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     (void)hipFree(s->d_counts);
-    (void)hipFree(s->d_slice);
     (void)hipFree(s->d_oob);
-    (void)hipFree(s->d_pos);
-    (void)hipFree(s->d_flags);
+    s->b.release();
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
 }
@@ -161,27 +159,22 @@ static int summary_add_impl(dm_summary* s, const int64_t* pos, const uint8_t* fl
     const unsigned char* dcl = cls;
     const bool pd = is_device_ptr(pos), fd = is_device_ptr(flags), cd = cls ? is_device_ptr(cls) : true;
     if (!(pd && fd && cd)) {
-        if (n > s->stage_cap) {
-            (void)hipFree(s->d_pos);
-            (void)hipFree(s->d_flags);
-            s->d_pos = nullptr;
-            s->d_flags = nullptr;
-            const int64_t cap = std::max<int64_t>(n, 1 << 20);
-            HIP_TRY(hipMalloc(&s->d_pos, sizeof(long long) * cap));
-            HIP_TRY(hipMalloc(&s->d_flags, 2 * cap));
-            s->stage_cap = cap;
-        }
+        const size_t room = size_t(std::max<int64_t>(n, dm_summary::STAGE_FLOOR));     // small adds never regrow the pair
+        int rc;
+        if ((rc = s->b.ensure(dm_summary::POS, sizeof(long long) * room)) != DM_OK || (rc = s->b.ensure(dm_summary::FLAGS, 2 * room)) != DM_OK) return rc;
+        long long* d_pos = s->b.ptr<long long>(dm_summary::POS);
+        unsigned char* d_flags = s->b.ptr<unsigned char>(dm_summary::FLAGS);     // flags [n] | cls [n]
         if (!pd) {
-            HIP_TRY(hipMemcpyAsync(s->d_pos, pos, sizeof(long long) * n, hipMemcpyHostToDevice, s->stream));
-            dpos = s->d_pos;
+            HIP_TRY(hipMemcpyAsync(d_pos, pos, sizeof(long long) * n, hipMemcpyHostToDevice, s->stream));
+            dpos = d_pos;
         }
         if (!fd) {
-            HIP_TRY(hipMemcpyAsync(s->d_flags, flags, n, hipMemcpyHostToDevice, s->stream));
-            dfl = s->d_flags;
+            HIP_TRY(hipMemcpyAsync(d_flags, flags, n, hipMemcpyHostToDevice, s->stream));
+            dfl = d_flags;
         }
         if (cls && !cd) {
-            HIP_TRY(hipMemcpyAsync(s->d_flags + s->stage_cap, cls, n, hipMemcpyHostToDevice, s->stream));
-            dcl = s->d_flags + s->stage_cap;
+            HIP_TRY(hipMemcpyAsync(d_flags + n, cls, n, hipMemcpyHostToDevice, s->stream));
+            dcl = d_flags + n;
         }
     }
     const int threads = 256;
@@ -287,9 +280,8 @@ void dm_cluster_destroy(dm_cluster* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipFree(c->d_w);
-    (void)hipFree(c->d_x);
-    (void)hipFree(c->d_out);
-    for (void* b : c->site_buf) (void)hipFree(b);
+    c->stage.release();
+    c->sites.release();
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -301,25 +293,22 @@ int dm_cluster_predict(dm_cluster* c, const float* x, int64_t n, float* out) {
     if (!x || !out) return fail(DM_EINVAL, "null buffer");
     HIP_TRY(hipSetDevice(c->device));
     const bool xd = is_device_ptr(x), od = is_device_ptr(out);
-    if ((!xd || !od) && n > c->cap) {
-        (void)hipFree(c->d_x);
-        (void)hipFree(c->d_out);
-        c->d_x = c->d_out = nullptr;
-        HIP_TRY(hipMalloc(&c->d_x, sizeof(float) * 14 * n));
-        HIP_TRY(hipMalloc(&c->d_out, sizeof(float) * n));
-        c->cap = n;
-    }
+    int rc;
     const float* dx = x;
     float* dout = out;
     if (!xd) {
-        HIP_TRY(hipMemcpyAsync(c->d_x, x, sizeof(float) * 14 * n, hipMemcpyHostToDevice, c->stream));
-        dx = c->d_x;
+        if ((rc = c->stage.ensure(dm_cluster::X, sizeof(float) * 14 * n)) != DM_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(c->stage.buf[dm_cluster::X], x, sizeof(float) * 14 * n, hipMemcpyHostToDevice, c->stream));
+        dx = c->stage.ptr<float>(dm_cluster::X);
     }
-    if (!od) dout = c->d_out;
+    if (!od) {
+        if ((rc = c->stage.ensure(dm_cluster::OUT, sizeof(float) * n)) != DM_OK) return rc;
+        dout = c->stage.ptr<float>(dm_cluster::OUT);
+    }
     const int blocks = int(std::min<int64_t>((n + 255) / 256, 4096));
     hipLaunchKernelGGL(cluster_mlp_kernel, dim3(blocks), dim3(256), 0, c->stream, c->d_w, dx, (long long)n, dout);
     HIP_TRY(hipGetLastError());
-    if (!od) HIP_TRY(hipMemcpyAsync(out, c->d_out, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
+    if (!od) HIP_TRY(hipMemcpyAsync(out, dout, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return DM_OK;
 }
@@ -551,13 +540,10 @@ int dm_summary_reduce_scatter(dm_summary* s, dm_comm* c, int64_t* first, int64_t
     if (s->follow) HIP_TRY(hipStreamSynchronize(s->follow->stream));   // adds queued on the classifier's stream
     HIP_TRY(hipStreamSynchronize(s->stream));
     const int64_t chunk = (s->length + c->nranks - 1) / c->nranks;
-    if (chunk > s->slice_chunk) {
-        (void)hipFree(s->d_slice);
-        s->d_slice = nullptr;
-        s->slice_chunk = 0;
-        HIP_TRY(hipMalloc(&s->d_slice, sizeof(int) * 3 * chunk));
-        s->slice_chunk = chunk;
-    }
+    s->slice_count = -1;                              // whatever the block held is gone from here on
+    const int rcb = s->b.ensure(dm_summary::SLICE, sizeof(int) * 3 * size_t(chunk));
+    if (rcb != DM_OK) return rcb;
+    s->slice_chunk = chunk;
     // the three counter arrays as ONE group where librccl has the group calls (one fused launch per rank instead of three)
     const bool grouped = g_rccl.group_start && g_rccl.group_end;
     if (grouped) {
@@ -568,7 +554,7 @@ int dm_summary_reduce_scatter(dm_summary* s, dm_comm* c, int64_t* first, int64_t
     for (int k = 0; k < 3 && err == ncclSuccess; ++k) {
         // the send buffer of array k is read up to nranks * chunk <= length + nranks - 1 positions: past `length` that is the head of
         // the next array (or the allocation's slack) - sums of positions that do not exist, never looked at
-        err = g_rccl.reducescatter(s->d_counts + k * s->length, s->d_slice + k * s->slice_chunk, size_t(chunk), ncclInt32, ncclSum, c->comm, c->stream);
+        err = g_rccl.reducescatter(s->d_counts + k * s->length, s->slice() + k * s->slice_chunk, size_t(chunk), ncclInt32, ncclSum, c->comm, c->stream);
     }
     if (grouped) {
         const ncclResult_t e = g_rccl.group_end();     // always closed, also after a failed call inside the group
@@ -594,9 +580,9 @@ int dm_summary_fetch_slice(dm_summary* s, int32_t* touch, int32_t* cov, int32_t*
     if (rc0) return rc0;
     const size_t bytes = sizeof(int) * size_t(s->slice_count);
     if (bytes == 0) return DM_OK;
-    if (touch) HIP_TRY(hipMemcpy(touch, s->d_slice, bytes, hipMemcpyDeviceToHost));
-    if (cov) HIP_TRY(hipMemcpy(cov, s->d_slice + s->slice_chunk, bytes, hipMemcpyDeviceToHost));
-    if (mod) HIP_TRY(hipMemcpy(mod, s->d_slice + 2 * s->slice_chunk, bytes, hipMemcpyDeviceToHost));
+    if (touch) HIP_TRY(hipMemcpy(touch, s->slice(), bytes, hipMemcpyDeviceToHost));
+    if (cov) HIP_TRY(hipMemcpy(cov, s->slice() + s->slice_chunk, bytes, hipMemcpyDeviceToHost));
+    if (mod) HIP_TRY(hipMemcpy(mod, s->slice() + 2 * s->slice_chunk, bytes, hipMemcpyDeviceToHost));
     return DM_OK;
 }
 

@@ -261,3 +261,79 @@ def test_batch_of_4096_reads(edges):
     with pytest.raises(_lib.DeepModHipError, match='at most 4096'):
         nz.event_stats_batch([r[1:] for r in reads] + [reads[0][1:]])
     nz.close()
+
+
+def _small_read(i):
+    """200 to 500 samples, contiguous events of 1 to ~30 samples from a small offset on"""
+    rng = np.random.default_rng(7000 + i)
+    n = 200 + int(rng.integers(0, 301))
+    raw = np.round(rng.normal(450 + 11 * (i % 17), 25 + (i % 7), n)).astype(np.int16)
+    length = np.maximum(1, rng.geometric(1 / 8.0, n // 8 + 4)).astype(np.uint64)
+    start = (int(rng.integers(0, 12)) + np.concatenate([[0], np.cumsum(length[:-1])])).astype(np.uint64)
+    keep = start + length <= n
+    return raw, start[keep].copy(), length[keep].copy()
+
+
+def _small_move_read(i):
+    """the same sizes with a move table: -> (raw, move uint8[L], first, bases); every boundary's event starts inside the signal"""
+    rng = np.random.default_rng(7500 + i)
+    n = 200 + int(rng.integers(0, 301))
+    raw = np.round(rng.normal(500 + 9 * i, 30, n)).astype(np.int16)
+    first = int(rng.integers(0, 9))
+    move = (rng.random((n - first) // 2) < 0.3).astype(np.uint8)
+    return raw, move, first, 1 + int(move[1:].sum())
+
+
+def test_one_handle_through_every_form_equals_fresh_handles():
+    """One handle makes a single-read call, a host-table batch of 3 reads, a resident batch of 40, a move-table batch of 3 and the host-table batch
+    again; every result is, byte for byte, what the same call returns on a handle of its own.  The paired tables of the handle (start | length,
+    mean | stdv, the fall-back pair, the chunk triple) lie at a stride of the call, and the blocks they lie in were sized by other forms' calls."""
+    from deepmod_amd import signal
+    from deepmod_amd.model import DeviceArray
+    three = [_small_read(i) for i in range(3)]
+    forty = [_small_read(10 + i) for i in range(40)]
+    r5, s5, l5 = forty[5]
+    forty[5] = (r5, np.append(s5, np.uint64(len(r5))), np.append(l5, np.uint64(4)))          # an empty event: the fall-back values show behind it
+    moved = [_small_move_read(i) for i in range(3)]
+
+    def flat(res):
+        return b''.join(np.ascontiguousarray(a).tobytes() for a in res)
+
+    def single(nz):
+        mean, stdv, norm, fe, _ = nz.event_stats(*three[1])
+        return flat([mean, stdv, np.array(list(norm.values())), np.array([fe])])
+
+    def host_batch(nz):
+        return b''.join(flat([m, s, np.array(list(n.values())), np.array([f])]) for m, s, n, f in nz.event_stats_batch(three))
+
+    def resident(nz):
+        raw, raw_off, st, ln, ev_off = _batch_arrays([('r%d' % i,) + r for i, r in enumerate(forty)])
+        n_ev = int(ev_off[-1])
+        rng = np.random.default_rng(5)
+        blk = DeviceArray((n_ev, 3), np.float32, 0)
+        fe, flag = nz.event_stats_device(raw, raw_off, st, ln, ev_off, blk.ptr, rng.normal(0, 1, n_ev).astype(np.float32), rng.random(n_ev).astype(np.float32))
+        got = blk.to_host()
+        blk.free()
+        assert fe[5] == len(forty[5][1]) - 1 and flag == 0
+        return flat([got, fe])
+
+    def move_batch(nz):
+        raw = np.concatenate([m[0] for m in moved])
+        move = np.concatenate([m[1] for m in moved])
+        raw_off = np.cumsum([0] + [len(m[0]) for m in moved])
+        mv_off = np.cumsum([0] + [len(m[1]) for m in moved])
+        ev_off = np.cumsum([0] + [m[3] for m in moved])
+        blk = DeviceArray((int(ev_off[-1]), 3), np.float32, 0)
+        status, flag = nz.move_stats_device(raw, raw_off, move, mv_off, [m[2] for m in moved], ev_off, blk.ptr)
+        got = blk.to_host()
+        blk.free()
+        assert not status.any() and flag == 0 and (got[:, 2] > 0).all()
+        return flat([got, status])
+
+    nz = signal.SignalNormalizer(0)
+    for step, call in enumerate((single, host_batch, resident, move_batch, host_batch)):
+        fresh = signal.SignalNormalizer(0)
+        want = call(fresh)
+        fresh.close()
+        assert call(nz) == want, 'call %d (%s) on the shared handle differs from a fresh handle' % (step, call.__name__)
+    nz.close()

@@ -198,6 +198,49 @@ def test_plan_of_a_batch_treats_event_starts_as_unsigned():
     assert plan(np.array([0, 10, 20, 30], np.uint64), np.array([10, 2 ** 64 - 5, 10, 10], np.uint64)) == 0 and fe[0] == 1
 
 
+def test_plan_of_a_batch_answers_as_recorded():
+    """dm_signal_plan_batch against its own answers recorded before the stage's host half became signalplan.inc (tests/golden/signalplan.json,
+    make_golden_signalplan.py): the same return code, the same first_empty for every accepted batch, the same message, word for word, for every
+    refused one - one and three reads, a single event, starts of 2^63 and more, sums that wrap, the first empty event at 0, in the middle and
+    nowhere, reads without events or samples, offset tables that do not start at 0, 4,096 and 4,097 reads."""
+    import importlib.util
+    import json
+    from deepmod_amd import _lib
+    spec = importlib.util.spec_from_file_location('make_golden_signalplan', os.path.join(GOLDEN, 'make_golden_signalplan.py'))
+    maker = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(maker)
+    with open(os.path.join(GOLDEN, 'signalplan.json')) as f:
+        recorded = json.load(f)
+    cases = maker.cases()
+    assert sorted(cases) == sorted(recorded) and len(cases) >= 20
+    lib = _lib.load()
+    for name, tables in cases.items():
+        assert maker.answer(lib, _lib.last_error, *tables) == recorded[name], name
+    assert any(r['rc'] == 0 and r['first_empty'] == [0, 1, 2] for r in recorded.values())
+
+
+def test_host_half_under_address_sanitizer(tmp_path):
+    """tests/signalplan_asan_driver.cpp: the host-only half of the stage (csrc/signalplan.inc - the plan of an event-table and of a move-table batch,
+    the planner) as tests/asan/host_shim.cpp includes it, built as a PROGRAM with -fsanitize=address,undefined and the sanitizer runtime linked in
+    statically - every input table in a heap block of exactly its size, every table of the plan against a per-read restatement.  The program runs in
+    the environment of the test as it is (a statically linked runtime needs no place in the library order)."""
+    import shutil
+    import subprocess
+    from conftest import ROOT
+    gxx = shutil.which('g++')
+    runtime = subprocess.run([gxx, '-print-file-name=libasan.a'], capture_output=True, text=True).stdout.strip() if gxx else ''
+    if not gxx or not os.path.isabs(runtime) or not os.path.exists(runtime):
+        pytest.skip('g++ / static libasan not available')
+    exe = str(tmp_path / 'signalplan_asan_driver')
+    build = subprocess.run([gxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-static-libasan', '-fno-sanitize-recover=undefined',
+                            '-fno-omit-frame-pointer', '-pthread', '-o', exe, os.path.join(ROOT, 'tests', 'signalplan_asan_driver.cpp')],
+                           capture_output=True, text=True, timeout=600)
+    assert build.returncode == 0, build.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0:abort_on_error=1:verify_asan_link_order=0', UBSAN_OPTIONS='halt_on_error=1:print_stacktrace=1')
+    res = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0 and 'SIGNALPLAN-ASAN-OK' in res.stdout, res.stdout[-1500:] + res.stderr[-4000:]
+
+
 @pytest.mark.gpu
 def test_batched_call_is_bit_identical_to_per_read_calls():
     """dm_signal_event_stats_batch (all reads of a worker batch in one device round trip) against n per-read calls:
