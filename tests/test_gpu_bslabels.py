@@ -192,8 +192,53 @@ def test_text_reaches_seven_digits(gpu_device):
         dev.close()
 
 
+def make_long_contig(rng, length, R):
+    """make_contig for motif CG in numpy: random letters, SCENARIOS in turn on the sites of either strand, records off the motif on 8 % of the other
+    keys (each in 70 % of the replicates) -> (reference bytes, per replicate (pos, strand, cov, pct))."""
+    seq = rng.choice(np.frombuffer(b'ACGT', np.uint8), length).tobytes()
+    code = bslabels.siteperf.site_codes(seq, 'CG', 0)
+    first = np.array([v[0] if v[0] is not None else (0, 0) for v in SCENARIOS], np.int64)
+    others = np.array([v[1] if v[1] is not None else (0, 0) for v in SCENARIOS], np.int64)
+    off_motif = [np.nonzero((((code >> s) & 1) == 0) & (rng.random(length) < 0.08))[0] for s in range(2)]
+    out = []
+    for r in range(R):
+        parts = []
+        for s in range(2):
+            sites = np.nonzero((code >> s) & 1)[0]
+            v = (first if r == 0 else others)[np.arange(len(sites)) % len(SCENARIOS)]
+            have = v[:, 0] > 0                                                     # (None: no record)
+            parts.append((sites[have], np.full(int(have.sum()), s), v[have, 0], v[have, 1]))
+            off = off_motif[s][rng.random(len(off_motif[s])) < 0.7]
+            parts.append((off, np.full(len(off), s), rng.choice([1, 5, 30], len(off)), rng.choice([0, 50, 100], len(off))))
+        rows = [np.concatenate([p[j] for p in parts]).astype(np.int64) for j in range(4)]
+        order = rng.permutation(len(rows[0]))
+        out.append(tuple(a[order] for a in rows))
+    return seq, out
+
+
+def test_class_sweep_takes_a_second_pass_with_every_class(gpu_device):
+    """300,001 positions: bl_class_kernel walks 2 x length = 600,002 keys with a grid of 524,288 threads, so 75,714 threads classify two keys and fold
+    both into their counters (test_text_reaches_seven_digits crosses the cap too, with a handful of keys); every class in either pass."""
+    grid = 2048 * 256                                                              # blk::MAX_BLOCKS x blk::THREADS
+    length, R = 300001, 2
+    assert grid < 2 * length < 2 * grid
+    seq, recs = make_long_contig(np.random.default_rng(77), length, R)
+    dev = bslabels.DeviceEngine(['chrW'], [length], R, COV, HI, LO, gpu_device)
+    host = bslabels.HostEngine(['chrW'], [length], R, COV, HI, LO)
+    try:
+        (dcounts, dcls), (hcounts, hcls) = classify_both(dev, host, 0, seq, 'CG', 0, recs)
+        assert np.array_equal(dcounts, hcounts), (dcounts, hcounts)
+        assert dcls.shape == hcls.shape == (2, length) and np.array_equal(dcls, hcls), np.nonzero(dcls != hcls)
+        flat = hcls.reshape(-1)                                                    # key e = strand x length + position, as the kernel walks them
+        for part in (flat[:grid], flat[grid:]):
+            assert set(np.unique(part).tolist()) == {0, 1, 2, 3, 4}                 # no truth, and the four classes
+        assert (hcounts > 1000).all()
+    finally:
+        dev.close()
+
+
 # ---- the truth path shared with bsperf ----
-NAMES, LENGTHS = ['chr1', 'chr10', 'chrX'], [3000, 2000, 2500]
+NAMES, LENGTHS =['chr1', 'chr10', 'chrX'], [3000, 2000, 2500]
 
 
 def _truth_line(rng, i):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import cluster_fused_case as cf
+import long_cases
 from conftest import ROOT
 from deepmod_amd import _lib, bsperf, merge
 from test_bsperf_host import BLANKS, HEADER, NAMES, TABS, VIOLATIONS, load_golden
@@ -248,6 +249,22 @@ def test_random_sites_and_one_contended_bin(gpu_device, dm):
     got, want = _run_both(gpu_device, dm, length, cov, mod, recs, (1, 5, 10), 90, 0, 1, (pos, strand, np.full(2 * length, 77)))
     _assert_equal(got, want)
     assert want['hist'][0, 1, 1, 50] == 200000 == want['hist'][1, 1, 1, 77] and want['moments'][0, 1].tolist() == [200000, 10 ** 7, 4 * 10 ** 7, 2 * 10 ** 9, 5 * 10 ** 8, 8 * 10 ** 9]
+
+
+def test_every_capped_grid_takes_a_second_pass(gpu_device, dm):
+    """300,001 positions (long_cases.bsperf_case): bs_count_kernel<0/1> walks 2 x length elements in three passes of its grid, every replicate's one
+    fill call and the one score call carry more records than bs_fill_kernel's and bs_score_kernel's grids have threads."""
+    grid = 1024 * 256                                                 # bsk::MAX_BLOCKS x bsk::THREADS
+    cov, mod, recs, scores = long_cases.bsperf_case()
+    length = cov.shape[1]
+    assert 2 * length > 2 * grid and all(len(r[0]) > grid for r in recs) and len(scores[0]) > grid
+    assert len(np.unique(scores[1] * length + scores[0])) == len(scores[0])
+    e = long_cases.bsperf_joined_elements()
+    assert all(((e >= lo) & (e < hi)).any() for lo, hi in ((0, grid), (grid, 2 * grid), (2 * grid, 2 * length)))      # truth and a prediction in every pass
+    thresholds, methylated, unmethylated, pred_cov = long_cases.BSPERF_RULE
+    got, want = _run_both(gpu_device, dm, length, cov, mod, recs, thresholds, methylated, unmethylated, pred_cov, scores)
+    _assert_equal(got, want)                                          # both kinds: tables and scores
+    assert (want['hist'].sum(axis=(1, 2, 3)) > 100000).all() and (want['unpredicted'].sum(axis=(1, 2)) > 0).all() and (want['untruthed'] > 0).all()
 
 
 def test_duplicates_and_range(gpu_device, dm):

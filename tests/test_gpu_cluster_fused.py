@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import cluster_fused_case as cf
+import long_cases
 from conftest import ROOT
 from deepmod_amd import _lib, cluster, merge, motif, summary, synth, synth_reads, tfbundle
 from test_cluster import REAL, _synthetic_cluster_weights
@@ -115,6 +116,32 @@ def test_slices_with_halos_join_to_the_whole_contig(gpu_device, models, tmp_path
     assert len(empty['pos']) == 0 and empty['n_plus'] == 0
     plus.close()
     minus.close()
+
+
+def test_site_scan_carries_over_three_passes(gpu_device, models):
+    """1,030 tiles (long_cases.cluster_case): site_scan_kernel walks 2,060 values [tiles of '+' | tiles of '-'] in three passes of 1,024 and carries
+    its total twice; against cluster.sites_from_counters, which tests/test_cluster_fused.py pins to the chain of the three tools.  Then as two ranges
+    without a halo, cut at tile 512 (first > 0), joined."""
+    seq, cov_p, mod_p, cov_m, mod_m = long_cases.cluster_case()
+    count, tiles = len(seq), (len(seq) + 1023) // 1024
+    assert count == long_cases.SITE_COUNT and 2 * tiles > 2 * 1024 and tiles > 1024        # csites::SCAN_THREADS: a third pass; '+' tiles in a second one
+    want = long_cases.cluster_oracle()
+    model = models['synthetic'][1]
+    plus, minus = filled(cov_p, mod_p, gpu_device), filled(cov_m, mod_m, gpu_device)
+    try:
+        whole = model.sites(plus, minus, seq, want_features=True)
+        assert whole['n_plus'] == want['n_plus'] and whole['features'].shape == (len(want['pos']), 14) and len(want['pos']) > 8000
+        assert np.array_equal(whole['features'], want['features'].astype(np.float32))          # bit-equal to the float32 cast
+        assert all(np.array_equal(whole[k], want[k]) for k in ('pos', 'cov', 'mod'))
+        held = long_cases.scanned_indices(whole)
+        assert {1023, 1024, 2047, 2048, 2 * tiles - 1} <= held          # sites on both sides of either pass boundary, '+' sites in tiles >= 1,024 among them
+        assert (whole['pos'][:whole['n_plus']] // 1024 >= 1024).any() and any(i < 2047 for i in held if i >= tiles)
+        cut = long_cases.SITE_CUT
+        got = joined([model.sites(plus, minus, seq, f, c, want_features=True) for f, c in ((0, cut), (cut, count - cut))])
+        assert got['n_plus'] == whole['n_plus'] and all(np.array_equal(got[k], whole[k]) for k in ('pos', 'cov', 'mod', 'new', 'features'))
+    finally:
+        plus.close()
+        minus.close()
 
 
 # ---- the command ----

@@ -15,6 +15,7 @@ from deepmod_amd import _lib, diffmod, merge, summary
 
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import diffmod_synth  # noqa: E402
+import long_cases  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -95,6 +96,96 @@ def test_sweep_equals_host_engine(hip_lib, sweep_lengths, which):
     finally:
         tables.close()
         dev.close(), low.close()
+
+
+def test_sweep_wraps_the_grid_and_the_tile_scan_carries(hip_lib):
+    """2,050 tiles (long_cases.diffmod_wrap): select_kernel's workgroup 0 takes tiles 0 and 2,048, workgroup 1 tile 1 and the ragged 2,049, and
+    scan_kernel carries its total over nine groups of 256 tile counts.  The criterion of test_sweep_equals_host_engine."""
+    tile, small = diffmod.tile_positions(), diffmod.small_support()
+    n, recs = long_cases.diffmod_wrap(tile, small, diffmod.MAX_TOTAL)
+    tiles = (n + tile - 1) // tile
+    assert tiles > 2048 and tiles > 256                               # dfk::MAX_BLOCKS: the grid wraps; dfk::THREADS: the scan takes a second group
+    want_counters, want = long_cases.diffmod_wrap_oracle(tile, small, diffmod.MAX_TOTAL)
+    dev, low = diffmod.DeviceEngine(COV, 1.0), diffmod.DeviceEngine(COV, FDR)
+    tables = Tables()
+    try:
+        d = tables.fill(recs, n)
+        counters, got = dev.run(*d)
+        assert counters.tolist() == want_counters.tolist(), (n, counters, want_counters)
+        assert (want_counters > 0).all()                              # every fate, on both strands
+        assert len(got['p']) == dev.n_records == want_counters[:, 0].sum()
+        assert (np.diff(2 * got['pos'].astype(np.int64) + got['strand']) > 0).all()                  # key order
+        check_against_host(got, want, n)
+        assert (got['cA'].astype(np.int64) + got['cB']).max() == diffmod.MAX_TOTAL
+        assert set(long_cases.WRAP_TILE_SET) | {tiles - 1} <= long_cases.tiles_holding(got['pos'], tile)      # tiles 0 | 2,048, 2,047 | 2,049, 255 | 256 | 257
+        assert dev.fetch_hist().tolist() == hist_of(got['p']).tolist()                              # the histogram of the device's own p
+        counters2, part = low.run(*d)
+        keep = got['p'] <= FDR
+        assert counters2.tolist() == counters.tolist() and 0 < keep.sum() < len(keep)
+        for k in INT_FIELDS + ('p',):
+            assert part[k].tobytes() == got[k][keep].tobytes(), k
+        assert low.fetch_hist().tolist() == dev.fetch_hist().tolist()
+    finally:
+        tables.close()
+        dev.close(), low.close()
+
+
+def test_chunk_scan_carries_and_records_compact_across_groups(hip_lib):
+    """More than 65,536 + 256 tested keys in one run (long_cases.diffmod_chunks): scan_kernel over more than 256 chunk counts, records_kernel reading
+    chunk_off beyond the first group; records fetched in runs that straddle record 65,536."""
+    tile = diffmod.tile_positions()
+    n, recs, keys, dropped, tested = long_cases.diffmod_chunks(tile)
+    group = 256 * 256                                                 # dfk::THREADS counts per group of the scan x dfk::CHUNK work items per chunk
+    want_counters, want = long_cases.diffmod_chunks_oracle(tile)
+    dev, low = diffmod.DeviceEngine(COV, 1.0), diffmod.DeviceEngine(COV, FDR)
+    tables = Tables()
+    try:
+        d = tables.fill(recs, n)
+        counters, got = dev.run(*d)
+        assert counters.tolist() == want_counters.tolist()
+        assert counters[:, 0].sum() == tested > group + 256 == 65792
+        assert len(got['p']) == dev.n_records == tested               # alpha 1: every key is a record
+        assert (np.diff(2 * got['pos'].astype(np.int64) + got['strand']) > 0).all()
+        check_against_host(got, want, 'chunks')
+        assert dev.fetch_hist().tolist() == hist_of(got['p']).tolist()
+        counters2, part = low.run(*d)
+        keep = got['p'] <= FDR
+        assert counters2.tolist() == counters.tolist() and keep[:group].any() and keep[group:].any() and not keep.all()       # records of chunk groups 0 and 1
+        for k in INT_FIELDS + ('p',):
+            assert part[k].tobytes() == got[k][keep].tobytes(), k
+        assert low.fetch_hist().tolist() == dev.fetch_hist().tolist()
+        for first, count, run in ((group - 100, 300, 77), (group - 1, 2, 1), (0, dev.n_records, 50000)):
+            piece = dev.fetch_records(first, count, fetch_run=run)
+            for k in INT_FIELDS + ('p',):
+                assert piece[k].tobytes() == got[k][first:first + count].tobytes(), (k, first)
+    finally:
+        tables.close()
+        dev.close(), low.close()
+
+
+def test_large_keys_wrap_their_grid(hip_lib):
+    """1,200 keys above small_support() (long_cases.diffmod_large: three distinct ones, one of them underflowing) between small keys: fisher_kernel<true>
+    loops over its list with barriers and wave_sum reused; the list is filled by an atomic in no particular order, and p must not depend on it."""
+    n, recs, n_large = long_cases.diffmod_large()
+    small = diffmod.small_support()
+    assert all(long_cases.support_of(*k) > small for k in long_cases.LARGE_KEYS) and n_large > 1024          # dfk::LARGE_BLOCKS
+    dev, host = diffmod.DeviceEngine(COV, 1.0), diffmod.HostEngine(COV, 1.0)
+    tables = Tables()
+    try:
+        d = tables.fill(recs, n)
+        counters, got = dev.run(*d)
+        want_counters, want = host.run(*host_side(recs, n))
+        assert counters.tolist() == want_counters.tolist() and counters[:, 0].sum() == 2 * n
+        large = np.array([long_cases.support_of(*k) > small for k in zip(*(got[f].tolist() for f in ('cA', 'mA', 'cB', 'mB')))])
+        assert large.sum() == n_large and large[0::2].all() and not large[1::2].any()                     # interleaved with small keys
+        check_against_host(got, want, 'large')
+        assert (want['p'][large] < 1e-290).any() and (want['p'][large] >= 1e-290).any()                 # the underflowing key and the others
+        again = dev.run(*d)[1]
+        for k in INT_FIELDS + ('p',):
+            assert again[k].tobytes() == got[k].tobytes(), k        # two runs: the same bits
+    finally:
+        tables.close()
+        dev.close()
 
 
 def test_compaction_edges(hip_lib):

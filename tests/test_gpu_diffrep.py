@@ -16,6 +16,7 @@ from deepmod_amd import _lib, diffmod, merge, summary
 
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import diffrep_synth as synth  # noqa: E402
+import long_cases  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -87,6 +88,47 @@ def test_sweep_equals_rep_host_engine(hip_lib, sweep_lengths, which, shape):
         assert {0, n - 1} <= set(got['pos'].tolist()) and (n <= tile or {tile - 1, tile} <= set(got['pos'].tolist()))
         assert dev.fetch_hist().tolist() == hist_of(got['p']).tolist()                              # the histogram of the device's own p
         # alpha 0.05: exactly the records of alpha 1 with p <= alpha, bit for bit; the histogram is of every tested key all the same
+        counters2, part = low.run(d[:KA], d[KA:])
+        keep = got['p'] <= FDR
+        assert counters2.tolist() == counters.tolist() and 0 < keep.sum() < len(keep)
+        for k in ALL_FIELDS:
+            assert part[k].tobytes() == got[k][keep].tobytes(), k
+        assert low.fetch_hist().tolist() == dev.fetch_hist().tolist()
+    finally:
+        tables.close()
+        dev.close(), low.close()
+
+
+@pytest.mark.parametrize('shape,which,phase', long_cases.REP_CASES)
+def test_sweep_wraps_the_grid_and_the_tile_scan_carries(hip_lib, shape, which, phase):
+    """(2, 2) on 2,050 tiles: sweep_kernel's workgroup 0 takes tiles 0 and 2,048, workgroup 1 tile 1 and the ragged 2,049; (8, 8) on 258 tiles: the
+    scan of the tile counts carries into a second group with sixteen replicates' tables.  The criterion of test_sweep_equals_rep_host_engine."""
+    KA, KB = shape
+    tile = diffmod.tile_positions()
+    n, (a, b), recs = long_cases.diffrep_case(shape, which, phase, tile)
+    tiles = (n + tile - 1) // tile
+    assert tiles > 256 and (which != 'wrap' or tiles > 2048)          # dfk::THREADS: the scan takes a second group; dfk::MAX_BLOCKS: the grid wraps
+    host_tabs = long_cases.diffrep_host_tables(shape, which, phase, tile)
+    want_counters, want = long_cases.diffrep_oracle(shape, which, phase, tile)
+    dev, low = diffmod.RepDeviceEngine(COV, 1.0, a, b), diffmod.RepDeviceEngine(COV, FDR, a, b)
+    tables = Tables(KA + KB)
+    try:
+        d = tables.fill(recs, n)
+        counters, got = dev.run(d[:KA], d[KA:])
+        assert counters.tolist() == want_counters.tolist(), (n, counters, want_counters)
+        assert (want_counters > 0).all()                              # every fate, on both strands
+        assert len(got['p']) == dev.n_records == want_counters[:, 0].sum()
+        assert (np.diff(2 * got['pos'].astype(np.int64) + got['strand']) > 0).all()                  # key order
+        for k in INT_FIELDS:
+            assert got[k].tolist() == want[k].tolist(), (n, k)
+        synth.check_records(got, host_tabs, KA, COV, a, b, (shape, n))
+        ones = want['p'] == 1.0
+        assert ones.sum() >= 2 and (got['p'][ones] == 1.0).all() and (got['phi'][ones] == 1.0).all()          # the integer rule: exactly 1
+        assert (got['cA'].astype(np.int64) + got['cB']).max() == synth.MAX_TOTAL                     # a key exactly at MAX_TOTAL was tested
+        held = long_cases.tiles_holding(got['pos'], tile)
+        assert {0, n - 1, tile - 1, tile} <= set(got['pos'].tolist()) and {0, 255, 256, 257, tiles - 1} <= held
+        assert which != 'wrap' or set(long_cases.WRAP_TILE_SET) <= held                             # tiles 0 | 2,048 and 2,047 | 2,049 as well
+        assert dev.fetch_hist().tolist() == hist_of(got['p']).tolist()                              # the histogram of the device's own p
         counters2, part = low.run(d[:KA], d[KA:])
         keep = got['p'] <= FDR
         assert counters2.tolist() == counters.tolist() and 0 < keep.sum() < len(keep)

@@ -200,6 +200,24 @@ def test_adds_equal_numpy_sums_and_the_text_equals_save_mod(dev, tmp_path, lengt
     assert merge.format_host(contig, base, cov[0], mod[0], cov[1], mod[1]) == want
 
 
+def test_one_add_of_more_records_than_the_grid_has_threads(dev, tmp_path):
+    """300,000 records in one add: bm_add_kernel's grid is capped, every thread takes a second record and some none (the adds above carry 20,000 records
+    a call at most).  Three tiles and seven positions take them, so the second pass adds to sums the first pass made."""
+    grid = 1024 * 256                                                 # bmk::MAX_BLOCKS x bmk::THREADS
+    length, n = 3 * TILE_POS + 7, 300000
+    assert grid < n < 2 * grid
+    rng = np.random.default_rng(9)
+    pos, strand, cov = rng.integers(0, length, n), rng.integers(0, 2, n), rng.integers(0, 30, n)
+    mod = (cov * rng.random(n)).astype(np.int64)
+    pos[[0, grid - 1, grid, n - 1]] = [0, length - 1, 0, length - 1]               # the ends of both passes on the ends of the tables
+    dev.open('chr1', length)
+    dev.add_records(pos, strand, cov, mod)
+    touch, cov, mod = _sums(length, [(pos, strand, cov, mod)])
+    ct, cc, cm = _counters(dev)
+    assert np.array_equal(ct, touch) and np.array_equal(cc, cov) and np.array_equal(cm, mod) and touch.sum() == n and touch.min() > 0
+    assert b''.join(p.tobytes() for p in dev.format('C')) == _save_mod(tmp_path, 'chr1', 'C', cov, mod)
+
+
 def test_single_file_with_the_largest_coverage_and_growing_tables(dev, tmp_path):
     """coverage 2^31 - 1 fits one file alone; without a length the tables grow to the largest position + 1 of each file, sums kept."""
     dev.open('chr1')

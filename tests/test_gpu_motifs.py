@@ -13,6 +13,7 @@ from conftest import ROOT
 from deepmod_amd import _lib, merge, motifs, summary
 
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import long_cases  # noqa: E402
 import motifs_synth  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -169,6 +170,52 @@ def test_every_key_of_a_strand_in_one_bin(hip_lib, up, down):
     tables = Tables()
     try:
         for letter, base, strand in (('A', 'A', 0), ('A', 'T', 1), ('G', 'G', 0)):
+            dev, host = motifs.DeviceEngine(up, down, base, COV, T_PCT, U_PCT), motifs.HostEngine(up, down, base, COV, T_PCT, U_PCT)
+            pos = np.arange(n, dtype=np.int64)
+            strand_of = np.full(n, strand, np.int64)
+            mod = np.where(pos % 3 == 0, 30, 0)
+            recs = {'sample': (pos, strand_of, np.full(n, 30, np.int64), mod), 'control': (pos, strand_of, np.full(n, 30, np.int64), np.zeros(n, np.int64))}
+            counters, _ = both(dev, host, letter * n, recs, tables, True, (up, down, letter, base))
+            hist = dev.fetch()
+            assert counters[strand, 0] == n - up - down and (hist[:, 0] > 0).sum() == 1 and hist[:, 0].sum() == n - up - down
+            assert hist[:, 1].sum() == counters[strand, 1] > 0
+            dev.close()
+    finally:
+        tables.close()
+
+
+@pytest.mark.parametrize('up,down', [(3, 3), (4, 4)])
+def test_sweep_wraps_the_grid(hip_lib, up, down):
+    """2,050 tiles (long_cases.motifs_case): mo_count_kernel's workgroup 0 takes tiles 0 and 2,048, workgroup 1 tile 1 and the ragged 2,049 - the LDS
+    code buffer restaged per tile, the LDS histogram of (3, 3) kept across a workgroup's tiles and flushed once, the merged runs of (4, 4) - with and
+    without controls; one planted context puts tested keys of tile 0 and of tile 2,048 into one bin."""
+    t = tile()
+    seq, recs, planted = long_cases.motifs_case(t, tuple(RULE_EDGES))
+    n = len(seq)
+    assert (n + t - 1) // t > 2048                                    # mok::MAX_BLOCKS: the grid wraps
+    bins = [long_cases.motif_bin_of(seq, recs, p, up, down, (COV, T_PCT, U_PCT)) for p in planted['shared']]
+    assert bins[0] == bins[1] >= 0 and [p // t for p in planted['shared']] == [0, 2048]
+    dev, host = motifs.DeviceEngine(up, down, long_cases.MOTIF_BASE, COV, T_PCT, U_PCT), motifs.HostEngine(up, down, long_cases.MOTIF_BASE, COV, T_PCT, U_PCT)
+    tables = Tables()
+    try:
+        for with_control in (True, False):
+            counters, off_base = both(dev, host, seq.decode(), recs, tables, with_control, (up, down, 'long', with_control))
+            assert (counters[:, [0, 1, 2, 4]] > 0).all() and (off_base > 0).all() and (counters[:, 3] > 0).all() == with_control     # every counter, on both strands
+            assert host.fetch()[bins[0], 0] >= 2
+    finally:
+        tables.close()
+        dev.close()
+
+
+def test_every_key_of_a_strand_in_one_bin_across_the_wrap(hip_lib):
+    """The one-letter contig of test_every_key_of_a_strand_in_one_bin on 2,050 tiles, flank (4, 4): every lane of every tile of a workgroup adds to
+    one bin of the global histogram, and the run merge meets the wrap."""
+    up = down = 4
+    n = long_cases.wrap_length(tile())
+    assert (n + tile() - 1) // tile() > 2048                          # mok::MAX_BLOCKS
+    tables = Tables()
+    try:
+        for letter, base, strand in (('A', 'A', 0), ('A', 'T', 1)):
             dev, host = motifs.DeviceEngine(up, down, base, COV, T_PCT, U_PCT), motifs.HostEngine(up, down, base, COV, T_PCT, U_PCT)
             pos = np.arange(n, dtype=np.int64)
             strand_of = np.full(n, strand, np.int64)

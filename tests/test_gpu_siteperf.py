@@ -9,6 +9,7 @@ import sys
 import numpy as np
 import pytest
 
+import long_cases
 from conftest import ROOT
 from deepmod_amd import siteperf as sp
 from test_siteperf_host import CASES, golden_lines, write_case
@@ -205,6 +206,20 @@ def test_histograms_of_random_records(gpu_device, mixed_input):
     assert got["lines_seen"] == 50000 and got["hist"].sum() > 30000 and (got["hist"].sum(axis=(1, 2, 3)) > 0).all()
     got = run_both(gpu_device, (1, 5, 10), seq, "Cg", 0, (1000, 3000), batches)
     assert got["lines_skipped"] > 20000
+
+
+def test_every_capped_grid_takes_a_second_pass(gpu_device):
+    """150,001 bases, a RUN and a CONTROL batch of 300,000 records each and a second CONTROL batch (long_cases.siteperf_case): sp_count_kernel and
+    sp_scatter_kernel loop over more records than their grid has threads, sp_walk_kernel over the 2 x len elements of the control table."""
+    grid = 1024 * 256                                                 # spk::MAX_BLOCKS x spk::THREADS
+    seq, batches = long_cases.siteperf_case()
+    assert 2 * len(seq) > grid and len(batches[0][1][0]) > grid and len(batches[1][1][0]) > grid and [role for role, _ in batches] == [sp.RUN, sp.CONTROL, sp.CONTROL]
+    for role, rec in batches[:2]:                                     # records and control sites on both sides of element `grid` of 2 x len
+        e = 2 * rec[0] + rec[1]
+        assert (e < grid).sum() > 1000 and (e >= grid).sum() > 1000
+    got = run_both(gpu_device, (1, 5, 10), seq, "Cg", 0, (None, None), batches)
+    assert got["lines_seen"] == sum(len(rec[0]) for _, rec in batches) == 620000 and (got["hist"].sum(axis=(1, 2, 3)) > 0).all()
+    assert got["hist"].sum() > 400000                                 # the run's entries and the controls' sites
 
 
 def test_contention_on_one_bin(gpu_device):
