@@ -238,7 +238,7 @@ int64_t dm_cluster_sites(dm_cluster* c, dm_summary* plus, dm_summary* minus, int
         dm_summary* t = both[s];
         if (!t) continue;
         if (t->device != c->device) return fail(DM_EINVAL, "summary on device %d, cluster model on device %d", t->device, c->device);
-        if (t->follow) HIP_TRY(hipStreamSynchronize(t->follow->stream));       // adds queued on the classifier's stream
+        if (t->follow) HIP_TRY(hipStreamSynchronize(model_stream(t->follow)));       // adds queued on the classifier's stream
         HIP_TRY(hipStreamSynchronize(t->stream));
         if (from_slice) {
             if (t->slice_count < 0) return fail(DM_ESTATE, "dm_cluster_sites: no reduce-scatter result in the '%c' summary", s ? '-' : '+');

@@ -1,15 +1,105 @@
 // deepmod_hip.hip — the core unit of libdeepmod_hip.so: the error slot every unit reports through (host.h), device and host memory helpers, the
-// dm_model runtime (create, options, staging, launch_bilstm, range slots, marks, profile), the int8 calibration gate, the head kernel and
-// rows_assemble_kernel.  The other host units are summary.hip, feed.hip and offline.hip (interface: host.h); the three classifier kernel families
-// are translation units of their own (kern_*.hip, interface: kernels.h).  __graft_entry__.build() compiles all of them in parallel
-// (hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c) and links them.
+// dm_model runtime (the struct and its block owners, create, options, the staged loop, launch_bilstm, marks, profile; its host-only logic - range
+// slots, launch grid - is modelplan.inc), the int8 calibration gate, the head kernel and rows_assemble_kernel.  The other host units are
+// summary.hip, feed.hip and offline.hip (interface: host.h); the three classifier kernel families are translation units of their own
+// (kern_*.hip, interface: kernels.h).  __graft_entry__.build() compiles all of them in parallel (hipcc --offload-arch=gfx950 -O3 -std=c++17
+// -fPIC -c) and links them.
 #include "host.h"
+#include "modelplan.inc"
 #include "head.hip.inc"
 
 using dmk::Packed16;
 using dmk::Packed32;
 
+// The device blocks a handle allocates once, at their exact size.  upload() leaves a block behind only when its bytes are on the device: a failed
+// copy must not leave a non-null pointer to uninitialised memory (the next launch would take it for a finished block)
+template <int N>
+struct FixedBufs {
+    const char* who;
+    void* buf[N] = {};
+    int alloc(int which, size_t bytes) {
+        if (hipMalloc(&buf[which], bytes) == hipSuccess) return DM_OK;
+        (void)hipGetLastError();
+        buf[which] = nullptr;
+        return fail(DM_ENOMEM, "%s: hipMalloc(%zu) failed", who, bytes);
+    }
+    int upload(int which, const void* src, size_t bytes) {
+        int rc = alloc(which, bytes);
+        if (rc) return rc;
+        const hipError_t e = hipMemcpy(buf[which], src, bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess) return DM_OK;
+        drop(which);
+        return fail(DM_EDEVICE, "%s: uploading a block of %zu bytes failed: %s", who, bytes, hipGetErrorString(e));
+    }
+    template <class T>
+    T* ptr(int which) const { return static_cast<T*>(buf[which]); }
+    void drop(int which) {
+        if (buf[which]) (void)hipFree(buf[which]);
+        buf[which] = nullptr;
+    }
+    void release() {
+        for (int i = 0; i < N; ++i) drop(i);
+    }
+};
+
+// Device blocks of one call, in a DevBufs: released when the call returns - after the stream has drained, where work that uses them may still be queued
+template <int N>
+struct CallBufs {
+    DevBufs<N> b;
+    hipStream_t stream;
+    bool in_use = false;      // set by the call once it queues work on the blocks, cleared once it has waited for the stream
+    ~CallBufs() {
+        if (in_use) (void)hipStreamSynchronize(stream);
+        b.release();
+    }
+};
+
+struct dm_model {
+    int device = 0;
+    int num_cu = 0;
+    hipStream_t stream = nullptr;
+    // what is allocated once: the fp32 packs and the scratch (DM_TIMING builds: the debug block) in model_init, the head weights W[200][2] fp32 and the
+    // split-f16 weight pack of an (MFMA shape, mode) on its first launch (ensure_pack)
+    enum Pack { PACK_Q, PACK_QI, PACK_S, PACK_SI, N_PACKS };      // 16x16x32 layout (lstm_f16q.hip.inc) | 32x32x16 layout of experiment builds (DM_WITH_F16S); I: int8 cross-term records (DM_PREC_F16I8)
+    enum { WPACK, BPACK, HPACK, SCRATCH, DBG, WOUT, PACK0, N_FIXED = PACK0 + N_PACKS };
+    FixedBufs<N_FIXED> fixed{"dm_model"};
+    float i8s[N_PACKS][24] = {};          // fold scales [dir][layer][gate kind] of the int8 packs
+    bool f16_q = true;                    // the split-f16 modes run lstm16q::bilstm_f16q_kernel (16x16x32 MFMAs): always, except in an experiment build with DM_OPT_F16X3_SHAPE = 32
+    // what grows: staging for host-pointer callers (X2: H2D of chunk i+1 overlaps the kernel of chunk i), partial logits [2 directions][tiles * 128][2]
+    enum { X, X2, PROB, CLS, PLOGIT, N_GROW };
+    DevBufs<N_GROW> grow{"dm_model"};
+    static constexpr int64_t STAGE_WINDOWS = 65536;
+    hipStream_t copy_stream = nullptr;          // ensure_copy_stream
+    static constexpr int AHEAD_EVENTS = 8;      // dm_model_h2d_ahead: copy-done events, reused round robin (a wait captures the record it was queued behind)
+    hipEvent_t ahead_event[AHEAD_EVENTS] = {};
+    int ahead_next = 0;
+    float bout[2] = {0, 0};
+    int grid_cap = 0;
+    int last_grid = 0;                    // DM_INFO_LAST_GRID: workgroups of the last classifier launch (launch_bilstm)
+    std::vector<float> host_weights;      // canonical blob, kept for lazy packing of other precisions
+    // profiling
+    bool profile = false;
+    bool async = false;                   // DM_OPT_ASYNC: device-resident calls return after enqueue
+    int precision = DM_PREC_F16X3;        // default: fastest mode that meets the 1e-4 probability tolerance
+    float f16_max_abs = 0.0f;             // largest |packed weight| (x exponent scale)
+    bool f16_ok = true;                   // every packed weight is a finite f16 (checked at create; else the default is DM_PREC_F32)
+    bool i8_calibrated = false;           // DM_PREC_F16I8 was selected by dm_model_calibrate_i8 (for the MFMA shape of that moment)
+    int len_shift = 0;                    // DM_INFO_F16_LENGTH_SHIFT
+    // DM_ERANGE bookkeeping (modelplan.inc): the host-mapped words, their device address, and which of them the launches and the markers own
+    modelplan::RangeSlots range;          // range.word: the words [modelplan::RANGE_SLOTS]
+    int* d_range_flag = nullptr;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+    hipEvent_t marks[DM_MARKS] = {};     // dm_model_mark / dm_model_wait_mark
+    size_t events_used = 0;
+    double prof_ms = 0.0;
+    int64_t prof_launches = 0, prof_windows = 0;
+};
+
 namespace dmhost {
+
+int model_device(const dm_model* m) { return m->device; }
+hipStream_t model_stream(const dm_model* m) { return m->stream; }
+bool model_async(const dm_model* m) { return m->async; }
 
 thread_local std::string g_err;
 
@@ -67,20 +157,6 @@ __global__ void rows_assemble_kernel(float* __restrict__ rows, const unsigned ch
     o[6] = has ? ev3[3 * e + 2] : 0.0f;
 }
 
-int ensure_stage(dm_model* m, int64_t x_floats) {
-    if (!m->d_prob) {
-        HIP_TRY(hipMalloc(&m->d_prob, sizeof(float) * 2 * dm_model::STAGE_WINDOWS));
-        HIP_TRY(hipMalloc(&m->d_cls, dm_model::STAGE_WINDOWS));
-    }
-    if (x_floats > m->stage_rows) {
-        if (m->d_x) HIP_TRY(hipFree(m->d_x));
-        m->d_x = nullptr;
-        HIP_TRY(hipMalloc(&m->d_x, sizeof(float) * x_floats));
-        m->stage_rows = x_floats;
-    }
-    return DM_OK;
-}
-
 int flush_profile(dm_model* m) {
     for (size_t i = 0; i < m->events_used; ++i) {
         float ms = 0.f;
@@ -92,78 +168,50 @@ int flush_profile(dm_model* m) {
     return DM_OK;
 }
 
-// partial-logit buffer of direction-split launches: 16 B per window, grown on demand (a running launch may still use the
-// old buffer: wait for the stream before freeing it)
+// partial-logit block of direction-split launches: 16 B per window, grown on demand (a running launch may still use the old block: wait for
+// the stream before it is freed).  The block's own capacity is the record of its size: ntiles + ntiles / 4 tiles after a growth, 1,280 at least
 int ensure_plogit(dm_model* m, int64_t ntiles) {
-    if (ntiles <= m->plogit_tiles) return DM_OK;
+    const size_t bytes = size_t(std::max<int64_t>(ntiles, 1024)) * lstmhead::TILE_M * 2 * 2 * sizeof(float);
+    if (m->grow.cap[dm_model::PLOGIT] >= bytes) return DM_OK;
     HIP_TRY(hipStreamSynchronize(m->stream));
-    (void)hipFree(m->d_plogit);
-    m->d_plogit = nullptr;
-    m->plogit_tiles = 0;
-    const int64_t cap = std::max<int64_t>(ntiles + ntiles / 4, 1024);
-    HIP_TRY(hipMalloc(&m->d_plogit, size_t(2) * size_t(cap) * lstmhead::TILE_M * 2 * sizeof(float)));
-    m->plogit_tiles = cap;
+    return m->grow.ensure(dm_model::PLOGIT, bytes);
+}
+
+// the copy stream, on first need: the staged uploads of predict_common and dm_model_h2d_ahead
+int ensure_copy_stream(dm_model* m) {
+    if (!m->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&m->copy_stream, hipStreamNonBlocking));
     return DM_OK;
 }
 
-// what both split-f16 kernels need: weights that fit an f16 after the exponent-scale fold (checked once in model_init),
-// the fp32 head weights
-int ensure_f16_common(dm_model* m) {
+// What a split-f16 launch needs, built on first use: weights that fit an f16 after the exponent-scale fold (checked once in model_init), the fp32
+// head weights, the kernel prepared and the weight pack of its (shape, mode)
+int ensure_pack(dm_model* m, int pack) {
+    if (m->fixed.buf[dm_model::PACK0 + pack]) return DM_OK;
     if (!m->f16_ok)
         return fail(DM_EINVAL, "DM_PREC_F16X3: a packed weight (|w| x exponent scale = %g) is outside the f16 range; use DM_PREC_F32",
                     double(m->f16_max_abs));
-    if (m->d_wout) return DM_OK;
-    const float* wout = m->host_weights.data() + (DM_WEIGHT_FLOATS - 402);
-    HIP_TRY(hipMalloc(&m->d_wout, 400 * sizeof(float)));
-    HIP_TRY(hipMemcpy(m->d_wout, wout, 400 * sizeof(float), hipMemcpyHostToDevice));
-    return DM_OK;
-}
-
-// one weight pack per (shape, mode), built on first use
-int ensure_pack(unsigned char*& d_pack, const Packed16& P, hipError_t prepared) {
-    if (prepared != hipSuccess) return fail(DM_EDEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(prepared));
-    // the model's pointer is set only once the pack is on the device: a failed copy must not leave a non-null pointer to uninitialised memory
-    // behind (the next launch would take it for a finished pack)
-    unsigned char* d = nullptr;
-    HIP_TRY(hipMalloc(&d, P.w.size()));
-    const hipError_t e = hipMemcpy(d, P.w.data(), P.w.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return fail(DM_EDEVICE, "uploading a weight pack failed: %s", hipGetErrorString(e));
+    if (!m->fixed.buf[dm_model::WOUT]) {
+        int rc = m->fixed.upload(dm_model::WOUT, m->host_weights.data() + (DM_WEIGHT_FLOATS - 402), 400 * sizeof(float));
+        if (rc) return rc;
     }
-    d_pack = d;
-    return DM_OK;
-}
+    const bool i8 = pack == dm_model::PACK_QI || pack == dm_model::PACK_SI;
+    hipError_t prepared;
+    Packed16 P;
+    if (pack == dm_model::PACK_Q || pack == dm_model::PACK_QI) {
+        prepared = dmk::f16q_prepare(i8 ? 1 : 0);
+        P = dmk::pack_weights_f16q(m->host_weights.data(), i8, i8 ? m->i8s[pack] : nullptr);
+    } else {
 #ifdef DM_WITH_F16S
-int ensure_f16s(dm_model* m) {
-    if (m->d_wpack16s) return DM_OK;
-    int rc = ensure_f16_common(m);
-    if (rc) return rc;
-    rc = ensure_pack(m->d_wpack16s, dmk::pack_weights_f16s(m->host_weights.data()), dmk::f16s_prepare(0));
-    if (rc) return rc;
-    if (dmk::f16s_has_roles() && dmk::f16s_prepare(2) != hipSuccess) return fail(DM_EDEVICE, "the roles kernel cannot be prepared");
-    return DM_OK;
-}
-int ensure_f16i8(dm_model* m) {
-    if (m->d_wpack16i) return DM_OK;
-    int rc = ensure_f16_common(m);
-    if (rc) return rc;
-    return ensure_pack(m->d_wpack16i, dmk::pack_weights_f16s(m->host_weights.data(), true, m->i8s), dmk::f16s_prepare(1));
-}
+        prepared = dmk::f16s_prepare(i8 ? 1 : 0);
+        if (!i8 && dmk::f16s_has_roles() && dmk::f16s_prepare(2) != hipSuccess) return fail(DM_EDEVICE, "the roles kernel cannot be prepared");
+        P = dmk::pack_weights_f16s(m->host_weights.data(), i8, i8 ? m->i8s[pack] : nullptr);
+#else
+        return fail(DM_EINVAL, "the 32x32x16 kernels are not part of this build (tools/experiments/f16s: DM_WITH_F16S=1)");
 #endif
-int ensure_f16q(dm_model* m) {
-    if (m->d_wpack16q) return DM_OK;
-    int rc = ensure_f16_common(m);
-    if (rc) return rc;
-    return ensure_pack(m->d_wpack16q, dmk::pack_weights_f16q(m->host_weights.data()), dmk::f16q_prepare(0));
+    }
+    if (prepared != hipSuccess) return fail(DM_EDEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(prepared));
+    return m->fixed.upload(dm_model::PACK0 + pack, P.w.data(), P.w.size());
 }
-int ensure_f16qi(dm_model* m) {
-    if (m->d_wpack16qi) return DM_OK;
-    int rc = ensure_f16_common(m);
-    if (rc) return rc;
-    return ensure_pack(m->d_wpack16qi, dmk::pack_weights_f16q(m->host_weights.data(), true, m->i8s_q), dmk::f16q_prepare(1));
-}
-
 
 // launch on device-resident buffers
 int launch_bilstm(dm_model* m, const float* d_x, long long xstride, int64_t n, float* d_prob, uint8_t* d_cls, const int* d_widx = nullptr) {
@@ -192,48 +240,36 @@ int launch_bilstm(dm_model* m, const float* d_x, long long xstride, int64_t n, f
         if (rcp) return rcp;
     }
     const long long npad = (long long)ntiles * dmk::TILE_M;
-    // work item = (tile, direction); a persistent workgroup per CU takes items round robin.  When the items do not fill the last round, the launch takes
-    // ceil(items / cap) rounds whatever the grid: it is sized to that many rounds exactly (4,198 items on 256 CUs = 17 rounds: 247 workgroups of 17 items
-    // finish when 256 workgroups of 16 or 17 would) and the CUs left over run whatever else is queued - the signal stage's kernels of the next batches -
-    // instead of idling through the last round (round 6)
-    int grid = std::min(2 * ntiles, m->grid_cap);
-    if (2 * ntiles > m->grid_cap) {
-        const int rounds = (2 * ntiles + m->grid_cap - 1) / m->grid_cap;
-        grid = (2 * ntiles + rounds - 1) / rounds;
-    }
+    const int grid = modelplan::launch_grid(2 * ntiles, m->grid_cap);      // work item = (tile, direction)
     m->last_grid = grid;
+    float* const plogit = m->grow.ptr<float>(dm_model::PLOGIT);
     if (m->precision == DM_PREC_F16X3 || m->precision == DM_PREC_F16I8 || m->precision == DM_PREC_F16X3_ROLES) {
         const bool i8 = m->precision == DM_PREC_F16I8;
-        const bool q16 = m->precision == DM_PREC_F16X3 && m->f16_q;
-        const bool qi8 = i8 && m->f16_q;                 // DM_OPT_F16X3_SHAPE picks the MFMA shape of both modes
-#ifdef DM_WITH_F16S
-        int rc = qi8 ? ensure_f16qi(m) : i8 ? ensure_f16i8(m) : (q16 ? ensure_f16q(m) : ensure_f16s(m));
-#else
-        if (!m->f16_q || m->precision == DM_PREC_F16X3_ROLES) return fail(DM_EINVAL, "the 32x32x16 kernels are not part of this build (tools/experiments/f16s: DM_WITH_F16S=1)");
-        int rc = qi8 ? ensure_f16qi(m) : ensure_f16q(m);
-#endif
+        const bool q = m->f16_q && m->precision != DM_PREC_F16X3_ROLES;      // DM_OPT_F16X3_SHAPE picks the MFMA shape of both modes
+        const int pack = (q ? dm_model::PACK_Q : dm_model::PACK_S) + (i8 ? 1 : 0);
+        int rc = ensure_pack(m, pack);
         if (rc) return rc;
         dmk::F16Args a;
-        a.wpack = qi8 ? m->d_wpack16qi : i8 ? m->d_wpack16i : q16 ? m->d_wpack16q : m->d_wpack16s;
-        a.hpack = m->d_wout;
+        a.wpack = m->fixed.ptr<unsigned char>(dm_model::PACK0 + pack);
+        a.hpack = m->fixed.ptr<float>(dm_model::WOUT);
         a.x = d_x;
         a.xstride = xstride;
         a.widx = d_widx;
         a.n = n;
         a.ntiles = ntiles;
-        a.plogit = m->d_plogit;
+        a.plogit = plogit;
         a.len_shift = m->len_shift;
-        a.range_flag = m->d_range_flag + m->range_cur;
-        a.i8s = qi8 ? m->i8s_q : i8 ? m->i8s : nullptr;
-        if (q16 || qi8) dmk::f16q_launch(qi8 ? 1 : 0, a, grid, m->stream);
+        a.range_flag = m->d_range_flag + m->range.current();
+        a.i8s = i8 ? m->i8s[pack] : nullptr;
+        if (q) dmk::f16q_launch(i8 ? 1 : 0, a, grid, m->stream);
 #ifdef DM_WITH_F16S
         else dmk::f16s_launch(i8 ? 1 : (m->precision == DM_PREC_F16X3_ROLES ? 2 : 0), a, grid, m->stream);
 #endif
     } else {
         dmk::F32Args a;
-        a.wpack = m->d_wpack;
-        a.bpack = m->d_bpack;
-        a.hpack = m->d_hpack;
+        a.wpack = m->fixed.ptr<float>(dm_model::WPACK);
+        a.bpack = m->fixed.ptr<float>(dm_model::BPACK);
+        a.hpack = m->fixed.ptr<float>(dm_model::HPACK);
         a.bout0 = m->bout[0];
         a.bout1 = m->bout[1];
         a.x = d_x;
@@ -242,15 +278,15 @@ int launch_bilstm(dm_model* m, const float* d_x, long long xstride, int64_t n, f
         a.n = n;
         a.prob = d_prob;
         a.cls = d_cls;
-        a.scratch = m->d_scratch;
+        a.scratch = m->fixed.ptr<float>(dm_model::SCRATCH);
         a.ntiles = ntiles;
-        a.dbg = m->d_dbg;
+        a.dbg = m->fixed.ptr<unsigned long long>(dm_model::DBG);
         a.dir_split = 1;      // work item = (tile, direction), see above
-        a.plogit = m->d_plogit;
+        a.plogit = plogit;
         dmk::f32_launch(a, grid, m->stream);
     }
 #ifndef DM_ABL_NOHEAD      // timing only (prob / cls stay unwritten): what the finishing kernel and the dependency bubble in front of it cost a step - the most a kernel that finishes its own windows could gain
-    hipLaunchKernelGGL(lstmhead::head_finish_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, m->stream, m->d_plogit, (long long)n,
+    hipLaunchKernelGGL(lstmhead::head_finish_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, m->stream, plogit, (long long)n,
                        npad, m->bout[0], m->bout[1], d_prob, d_cls);
 #endif
     HIP_TRY(hipGetLastError());
@@ -267,33 +303,18 @@ int range_error(dm_model* m) {
                 "feature 6: |x| <= 65504 * 2^%d, no NaN); the results of these launches are invalid - repeat them with DM_PREC_F32",
                 m->len_shift);
 }
-// the launches that wrote `slot` have finished: did one of them meet an input it cannot represent?  The slot is cleared.
-bool take_range_slot(dm_model* m, int slot) {
-    volatile int* f = reinterpret_cast<volatile int*>(m->range_flag) + slot;
-    const bool bad = *f != 0;
-    *f = 0;
-    return bad;
-}
-// after the model's stream has been synchronised: every slot is final - the current one, the markers', the orphans'
-int check_range_all(dm_model* m) {
-    if (!m->range_flag) return DM_OK;
-    bool bad = take_range_slot(m, m->range_cur);
-    for (int i = 0; i < DM_MARKS; ++i)
-        if (m->mark_slot[i] >= 0) {
-            bad |= take_range_slot(m, m->mark_slot[i]);
-            m->slot_free[m->mark_slot[i]] = true;
-            m->mark_slot[i] = -1;
-        }
-    for (int sl : m->range_orphans) {
-        bad |= take_range_slot(m, sl);
-        m->slot_free[sl] = true;
-    }
-    m->range_orphans.clear();
-    return bad ? range_error(m) : DM_OK;
-}
+// wait for the model's stream: every range slot is final then
 int sync_and_check(dm_model* m) {
     HIP_TRY(hipStreamSynchronize(m->stream));
-    return check_range_all(m);
+    return m->range.take_all() ? range_error(m) : DM_OK;
+}
+
+// windows [off, off + STAGE_WINDOWS) of the n host windows x -> dst on the copy stream (beside the launches of the model's stream); the host waits for it
+int upload_chunk(dm_model* m, float* dst, const float* x, int64_t off, int64_t n) {
+    const int64_t cnt = std::min<int64_t>(dm_model::STAGE_WINDOWS, n - off), win_floats = DM_WINDOW * DM_NFEAT;
+    HIP_TRY(hipMemcpyAsync(dst, x + off * win_floats, sizeof(float) * cnt * win_floats, hipMemcpyHostToDevice, m->copy_stream));
+    HIP_TRY(hipStreamSynchronize(m->copy_stream));
+    return DM_OK;
 }
 
 int predict_common(dm_model* m, const float* x, long long xstride, int64_t x_floats_total, int64_t n,
@@ -312,62 +333,36 @@ int predict_common(dm_model* m, const float* x, long long xstride, int64_t x_flo
         if (!m->async) return sync_and_check(m);
         return DM_OK;
     }
-    // host buffers: stage through device memory in batches
-    if (!windows_materialised) {
-        // per-read rows: copy the whole row matrix once, classify, copy results back
-        int rc = ensure_stage(m, x_floats_total);
-        if (rc) return rc;
-        const float* dx = x;
-        if (!xdev) {
-            HIP_TRY(hipMemcpyAsync(m->d_x, x, sizeof(float) * x_floats_total, hipMemcpyHostToDevice, m->stream));
-            dx = m->d_x;
-        }
-        for (int64_t off = 0; off < n; off += dm_model::STAGE_WINDOWS) {
-            const int64_t cnt = std::min<int64_t>(dm_model::STAGE_WINDOWS, n - off);
-            float* dp = prob ? (pdev ? prob + 2 * off : m->d_prob) : nullptr;
-            uint8_t* dc = cls ? (cdev ? cls + off : m->d_cls) : nullptr;
-            rc = launch_bilstm(m, dx + off * xstride, xstride, cnt, dp, dc);
-            if (rc) return rc;
-            if (prob && !pdev)
-                HIP_TRY(hipMemcpyAsync(prob + 2 * off, m->d_prob, sizeof(float) * 2 * cnt, hipMemcpyDeviceToHost, m->stream));
-            if (cls && !cdev) HIP_TRY(hipMemcpyAsync(cls + off, m->d_cls, cnt, hipMemcpyDeviceToHost, m->stream));
-            rc = sync_and_check(m);
-            if (rc) return rc;
-        }
-        return DM_OK;
-    }
-    const int64_t stage_floats = int64_t(dm_model::STAGE_WINDOWS) * DM_WINDOW * DM_NFEAT;
-    int rc = ensure_stage(m, stage_floats);
+    // a host array among them: chunks of STAGE_WINDOWS, each classified, its results copied back and waited for.  How x gets to the device is the
+    // one thing the two forms differ in: it is there already (NONE); per-read rows are copied whole ahead of the loop, on the model's stream
+    // (WHOLE); materialised windows go chunk by chunk through two blocks on the copy stream, chunk i + 1 while chunk i is classified (CHUNKS)
+    enum Feed { NONE, WHOLE, CHUNKS };
+    const Feed feed = xdev ? NONE : windows_materialised ? CHUNKS : WHOLE;
+    const int64_t chunk_floats = int64_t(dm_model::STAGE_WINDOWS) * DM_WINDOW * DM_NFEAT;
+    int rc = DM_OK;
+    if (feed != NONE) rc = m->grow.ensure(dm_model::X, sizeof(float) * (feed == WHOLE ? x_floats_total : chunk_floats));
+    if (rc == DM_OK && feed == CHUNKS) rc = m->grow.ensure(dm_model::X2, sizeof(float) * chunk_floats);
+    if (rc == DM_OK && feed == CHUNKS) rc = ensure_copy_stream(m);
+    if (rc == DM_OK && prob && !pdev) rc = m->grow.ensure(dm_model::PROB, sizeof(float) * 2 * dm_model::STAGE_WINDOWS);
+    if (rc == DM_OK && cls && !cdev) rc = m->grow.ensure(dm_model::CLS, dm_model::STAGE_WINDOWS);
     if (rc) return rc;
-    if (!xdev && !m->d_x2) {
-        HIP_TRY(hipMalloc(&m->d_x2, sizeof(float) * stage_floats));
-        HIP_TRY(hipStreamCreateWithFlags(&m->copy_stream, hipStreamNonBlocking));
-    }
-    float* stage[2] = {m->d_x, m->d_x2};
-    const int64_t win_floats = DM_WINDOW * DM_NFEAT;
-    if (!xdev) {   // prime the pipeline: batch 0
-        const int64_t cnt0 = std::min<int64_t>(dm_model::STAGE_WINDOWS, n);
-        HIP_TRY(hipMemcpyAsync(stage[0], x, sizeof(float) * cnt0 * win_floats, hipMemcpyHostToDevice, m->copy_stream));
-        HIP_TRY(hipStreamSynchronize(m->copy_stream));
-    }
+    float* const stage[2] = {m->grow.ptr<float>(dm_model::X), m->grow.ptr<float>(dm_model::X2)};
+    float* const d_prob = m->grow.ptr<float>(dm_model::PROB);
+    uint8_t* const d_cls = m->grow.ptr<uint8_t>(dm_model::CLS);
+    if (feed == WHOLE) HIP_TRY(hipMemcpyAsync(stage[0], x, sizeof(float) * x_floats_total, hipMemcpyHostToDevice, m->stream));
+    if (feed == CHUNKS && (rc = upload_chunk(m, stage[0], x, 0, n))) return rc;      // prime the pipeline
     int b = 0;
     for (int64_t off = 0; off < n; off += dm_model::STAGE_WINDOWS, b ^= 1) {
         const int64_t cnt = std::min<int64_t>(dm_model::STAGE_WINDOWS, n - off);
-        const float* dx = xdev ? x + off * xstride : stage[b];
-        float* dp = prob ? (pdev ? prob + 2 * off : m->d_prob) : nullptr;
-        uint8_t* dc = cls ? (cdev ? cls + off : m->d_cls) : nullptr;
+        const float* dx = feed == CHUNKS ? stage[b] : (feed == WHOLE ? stage[0] : x) + off * xstride;
+        float* dp = prob ? (pdev ? prob + 2 * off : d_prob) : nullptr;
+        uint8_t* dc = cls ? (cdev ? cls + off : d_cls) : nullptr;
         rc = launch_bilstm(m, dx, xstride, cnt, dp, dc);          // asynchronous on the model's stream
         if (rc) return rc;
         const int64_t noff = off + dm_model::STAGE_WINDOWS;
-        if (!xdev && noff < n) {                                  // upload the next batch meanwhile
-            const int64_t ncnt = std::min<int64_t>(dm_model::STAGE_WINDOWS, n - noff);
-            HIP_TRY(hipMemcpyAsync(stage[b ^ 1], x + noff * xstride, sizeof(float) * ncnt * win_floats,
-                                   hipMemcpyHostToDevice, m->copy_stream));
-            HIP_TRY(hipStreamSynchronize(m->copy_stream));
-        }
-        if (prob && !pdev)
-            HIP_TRY(hipMemcpyAsync(prob + 2 * off, m->d_prob, sizeof(float) * 2 * cnt, hipMemcpyDeviceToHost, m->stream));
-        if (cls && !cdev) HIP_TRY(hipMemcpyAsync(cls + off, m->d_cls, cnt, hipMemcpyDeviceToHost, m->stream));
+        if (feed == CHUNKS && noff < n && (rc = upload_chunk(m, stage[b ^ 1], x, noff, n))) return rc;      // the next chunk meanwhile
+        if (prob && !pdev) HIP_TRY(hipMemcpyAsync(prob + 2 * off, d_prob, sizeof(float) * 2 * cnt, hipMemcpyDeviceToHost, m->stream));
+        if (cls && !cdev) HIP_TRY(hipMemcpyAsync(cls + off, d_cls, cnt, hipMemcpyDeviceToHost, m->stream));
         rc = sync_and_check(m);
         if (rc) return rc;
     }
@@ -387,28 +382,23 @@ int model_init(dm_model* m, const float* weights) {
     Packed32 P = dmk::pack_weights_f32(weights);
     m->bout[0] = P.bout[0];
     m->bout[1] = P.bout[1];
-    HIP_TRY(hipMalloc(&m->d_wpack, P.w.size() * sizeof(float)));
-    HIP_TRY(hipMalloc(&m->d_bpack, P.b.size() * sizeof(float)));
-    HIP_TRY(hipMalloc(&m->d_hpack, P.h.size() * sizeof(float)));
-    HIP_TRY(hipMemcpy(m->d_wpack, P.w.data(), P.w.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(m->d_bpack, P.b.data(), P.b.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(m->d_hpack, P.h.data(), P.h.size() * sizeof(float), hipMemcpyHostToDevice));
-    size_t scratch_bytes = size_t(m->grid_cap) * dmk::f32_scratch_floats_per_wg() * sizeof(float);      // h sequences of the fp32 kernel
-    HIP_TRY(hipMalloc(&m->d_scratch, scratch_bytes));
-    HIP_TRY(hipMemsetAsync(m->d_scratch, 0, scratch_bytes, m->stream));      // ordered with the launches of m->stream (non-blocking)
+    int rc = m->fixed.upload(dm_model::WPACK, P.w.data(), P.w.size() * sizeof(float));
+    if (rc == DM_OK) rc = m->fixed.upload(dm_model::BPACK, P.b.data(), P.b.size() * sizeof(float));
+    if (rc == DM_OK) rc = m->fixed.upload(dm_model::HPACK, P.h.data(), P.h.size() * sizeof(float));
+    const size_t scratch_bytes = size_t(m->grid_cap) * dmk::f32_scratch_floats_per_wg() * sizeof(float);      // h sequences of the fp32 kernel
+    if (rc == DM_OK) rc = m->fixed.alloc(dm_model::SCRATCH, scratch_bytes);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(m->fixed.buf[dm_model::SCRATCH], 0, scratch_bytes, m->stream));      // ordered with the launches of m->stream (non-blocking)
 #if defined(DM_TIMING) || defined(DM_TRACE) || defined(DM_TRACE2)
-    HIP_TRY(hipMalloc(&m->d_dbg, size_t(m->grid_cap) * dmk::f32_waves() * 8 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(m->d_dbg, 0, size_t(m->grid_cap) * dmk::f32_waves() * 8 * sizeof(unsigned long long), m->stream));
+    const size_t dbg_bytes = size_t(m->grid_cap) * dmk::f32_waves() * 8 * sizeof(unsigned long long);
+    if ((rc = m->fixed.alloc(dm_model::DBG, dbg_bytes))) return rc;
+    HIP_TRY(hipMemsetAsync(m->fixed.buf[dm_model::DBG], 0, dbg_bytes, m->stream));
 #endif
     HIP_TRY(dmk::f32_prepare());
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&m->range_flag), sizeof(int) * dm_model::RANGE_SLOTS, hipHostMallocMapped));
-    for (int i = 0; i < dm_model::RANGE_SLOTS; ++i) {
-        m->range_flag[i] = 0;
-        m->slot_free[i] = i != 0;
-    }
-    for (int i = 0; i < DM_MARKS; ++i) m->mark_slot[i] = -1;
-    m->range_cur = 0;
-    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&m->d_range_flag), m->range_flag, 0));
+    int* words = nullptr;
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&words), sizeof(int) * modelplan::RANGE_SLOTS, hipHostMallocMapped));
+    m->range.reset(words);
+    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&m->d_range_flag), words, 0));
     {   // trained kernels far outside the usual range cannot be split into f16 halves: such a model runs the fp32 kernel
         Packed16 P16 = dmk::pack_weights_f16q(weights);
         m->f16_ok = P16.finite && P16.max_abs <= 65504.0f;
@@ -507,25 +497,12 @@ void dm_model_destroy(dm_model* m) {
     }
     for (hipEvent_t e : m->marks)
         if (e) (void)hipEventDestroy(e);
-    (void)hipFree(m->d_wpack);
-    (void)hipFree(m->d_bpack);
-    (void)hipFree(m->d_hpack);
-    (void)hipFree(m->d_scratch);
-    (void)hipFree(m->d_wpack16s);
-    (void)hipFree(m->d_wpack16q);
-    (void)hipFree(m->d_wpack16qi);
-    (void)hipFree(m->d_wpack16i);
-    (void)hipFree(m->d_wout);
-    (void)hipFree(m->d_dbg);
-    (void)hipFree(m->d_plogit);
-    (void)hipFree(m->d_x);
-    (void)hipFree(m->d_x2);
+    m->fixed.release();
+    m->grow.release();
     for (hipEvent_t ev : m->ahead_event)
         if (ev) (void)hipEventDestroy(ev);
     if (m->copy_stream) (void)hipStreamDestroy(m->copy_stream);
-    if (m->range_flag) (void)hipHostFree(m->range_flag);
-    (void)hipFree(m->d_prob);
-    (void)hipFree(m->d_cls);
+    if (m->range.word) (void)hipHostFree(m->range.word);
     if (m->stream) (void)hipStreamDestroy(m->stream);
     delete m;
 }
@@ -615,52 +592,35 @@ int dm_predict_read_at(dm_model* m, const float* rows, int64_t m_rows, const int
         for (int64_t i = 0; i < count; ++i)
             if (centre[i] < DM_WINDOW / 2 || centre[i] >= m_rows - DM_WINDOW / 2)
                 return fail(DM_EINVAL, "window %lld: centre row %d +-10 outside the %lld feature rows", (long long)i, centre[i], (long long)m_rows);
-    float* d_rows = nullptr;
-    int* d_centre = nullptr;
-    float* d_prob = nullptr;
-    uint8_t* d_cls = nullptr;
+    enum { ROWS, CENTRE, PROB, CLS, N_TMP };
+    CallBufs<N_TMP> tmp{{"dm_predict_read_at"}, m->stream};
     int rc = DM_OK;
-    auto cleanup = [&]() {
-        if (!rd) (void)hipFree(d_rows);
-        if (!cd) (void)hipFree(d_centre);
-        if (prob && !pd) (void)hipFree(d_prob);
-        if (cls && !kd) (void)hipFree(d_cls);
-    };
-#define DM_TRY_CLEAN(expr)                                                                                   \
-    do {                                                                                                     \
-        hipError_t _e = (expr);                                                                              \
-        if (_e != hipSuccess) {                                                                              \
-            cleanup();                                                                                       \
-            return fail(DM_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(_e));                          \
-        }                                                                                                    \
-    } while (0)
-    if (!rd) {
-        DM_TRY_CLEAN(hipMalloc(&d_rows, sizeof(float) * size_t(m_rows) * DM_NFEAT));
-        DM_TRY_CLEAN(hipMemcpyAsync(d_rows, rows, sizeof(float) * size_t(m_rows) * DM_NFEAT, hipMemcpyHostToDevice, m->stream));
-    } else d_rows = const_cast<float*>(rows);
-    if (!cd) {
-        DM_TRY_CLEAN(hipMalloc(&d_centre, sizeof(int) * size_t(count)));
-        DM_TRY_CLEAN(hipMemcpyAsync(d_centre, centre, sizeof(int) * size_t(count), hipMemcpyHostToDevice, m->stream));
-    } else d_centre = const_cast<int*>(centre);
-    if (prob && !pd) DM_TRY_CLEAN(hipMalloc(&d_prob, sizeof(float) * 2 * size_t(count)));
-    else d_prob = prob;
-    if (cls && !kd) DM_TRY_CLEAN(hipMalloc(&d_cls, size_t(count)));
-    else d_cls = cls;
+    if (!rd) rc = tmp.b.ensure(ROWS, sizeof(float) * size_t(m_rows) * DM_NFEAT);
+    if (rc == DM_OK && !cd) rc = tmp.b.ensure(CENTRE, sizeof(int) * size_t(count));
+    if (rc == DM_OK && prob && !pd) rc = tmp.b.ensure(PROB, sizeof(float) * 2 * size_t(count));
+    if (rc == DM_OK && cls && !kd) rc = tmp.b.ensure(CLS, size_t(count));
+    if (rc) return rc;
+    const float* d_rows = rd ? rows : tmp.b.ptr<float>(ROWS);
+    const int* d_centre = cd ? centre : tmp.b.ptr<int>(CENTRE);
+    float* d_prob = prob && !pd ? tmp.b.ptr<float>(PROB) : prob;
+    uint8_t* d_cls = cls && !kd ? tmp.b.ptr<uint8_t>(CLS) : cls;
+    tmp.in_use = true;      // from here on a return waits for the stream before the temporaries go, a failed launch included
+    if (!rd) HIP_TRY(hipMemcpyAsync(tmp.b.buf[ROWS], rows, sizeof(float) * size_t(m_rows) * DM_NFEAT, hipMemcpyHostToDevice, m->stream));
+    if (!cd) HIP_TRY(hipMemcpyAsync(tmp.b.buf[CENTRE], centre, sizeof(int) * size_t(count), hipMemcpyHostToDevice, m->stream));
     rc = launch_bilstm(m, d_rows - (DM_WINDOW / 2) * DM_NFEAT, DM_NFEAT, count, d_prob, d_cls, d_centre);
-    if (rc == DM_OK && prob && !pd) DM_TRY_CLEAN(hipMemcpyAsync(prob, d_prob, sizeof(float) * 2 * size_t(count), hipMemcpyDeviceToHost, m->stream));
-    if (rc == DM_OK && cls && !kd) DM_TRY_CLEAN(hipMemcpyAsync(cls, d_cls, size_t(count), hipMemcpyDeviceToHost, m->stream));
-    if (rc == DM_OK) rc = sync_and_check(m);
-    else (void)hipStreamSynchronize(m->stream);
-    cleanup();
-#undef DM_TRY_CLEAN
+    if (rc) return rc;
+    if (prob && !pd) HIP_TRY(hipMemcpyAsync(prob, d_prob, sizeof(float) * 2 * size_t(count), hipMemcpyDeviceToHost, m->stream));
+    if (cls && !kd) HIP_TRY(hipMemcpyAsync(cls, d_cls, size_t(count), hipMemcpyDeviceToHost, m->stream));
+    rc = sync_and_check(m);
+    tmp.in_use = false;
     return rc;
 }
 
 // debug builds (-DDM_TIMING): copy the per-wave section cycle counters [grid][waves][8]; returns element count
 extern "C" long long dm_debug_timing(dm_model* m, unsigned long long* out, long long cap) {
-    if (!m || !m->d_dbg) return 0;
+    if (!m || !m->fixed.buf[dm_model::DBG]) return 0;
     const long long n = (long long)m->grid_cap * dmk::f32_waves() * 8;
-    if (out && cap >= n) (void)hipMemcpy(out, m->d_dbg, n * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    if (out && cap >= n) (void)hipMemcpy(out, m->fixed.buf[dm_model::DBG], n * sizeof(unsigned long long), hipMemcpyDeviceToHost);
     return n;
 }
 
@@ -724,24 +684,17 @@ int dm_model_calibrate_i8(dm_model* m, int64_t n_windows, double bound, double* 
     int rc = sync_and_check(m);
     if (rc) return rc;
     const int64_t B = 65536;
-    float *d_x = nullptr, *d_pa = nullptr, *d_pb = nullptr;
-    unsigned* d_max = nullptr;
-    auto cleanup = [&]() {
-        (void)hipFree(d_x); (void)hipFree(d_pa); (void)hipFree(d_pb); (void)hipFree(d_max);
-    };
-#define DM_TRY_CAL(expr)                                                                                     \
-    do {                                                                                                     \
-        hipError_t _e = (expr);                                                                              \
-        if (_e != hipSuccess) {                                                                              \
-            cleanup();                                                                                       \
-            return fail(DM_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(_e));                          \
-        }                                                                                                    \
-    } while (0)
-    DM_TRY_CAL(hipMalloc(&d_x, sizeof(float) * size_t(B) * DM_WINDOW * DM_NFEAT));
-    DM_TRY_CAL(hipMalloc(&d_pa, sizeof(float) * 2 * size_t(B)));
-    DM_TRY_CAL(hipMalloc(&d_pb, sizeof(float) * 2 * size_t(B)));
-    DM_TRY_CAL(hipMalloc(&d_max, sizeof(unsigned)));
-    DM_TRY_CAL(hipMemsetAsync(d_max, 0, sizeof(unsigned), m->stream));
+    enum { X, PA, PB, MAX, N_TMP };
+    CallBufs<N_TMP> tmp{{"dm_model_calibrate_i8"}, m->stream};
+    rc = tmp.b.ensure(X, sizeof(float) * size_t(B) * DM_WINDOW * DM_NFEAT);
+    if (rc == DM_OK) rc = tmp.b.ensure(PA, sizeof(float) * 2 * size_t(B));
+    if (rc == DM_OK) rc = tmp.b.ensure(PB, sizeof(float) * 2 * size_t(B));
+    if (rc == DM_OK) rc = tmp.b.ensure(MAX, sizeof(unsigned));
+    if (rc) return rc;
+    float *d_x = tmp.b.ptr<float>(X), *d_pa = tmp.b.ptr<float>(PA), *d_pb = tmp.b.ptr<float>(PB);
+    unsigned* d_max = tmp.b.ptr<unsigned>(MAX);
+    tmp.in_use = true;      // from here on a return waits for the stream before the temporaries go
+    HIP_TRY(hipMemsetAsync(d_max, 0, sizeof(unsigned), m->stream));
     const int keep_precision = m->precision;
     const bool keep_profile = m->profile;
     m->profile = false;
@@ -757,14 +710,12 @@ int dm_model_calibrate_i8(dm_model* m, int64_t n_windows, double bound, double* 
     }
     m->precision = keep_precision;
     m->profile = keep_profile;
-    unsigned bits = 0x7F800000u;
-    if (rc == DM_OK) {
-        rc = sync_and_check(m);
-        if (rc == DM_OK) DM_TRY_CAL(hipMemcpy(&bits, d_max, sizeof(unsigned), hipMemcpyDeviceToHost));
-    }
-#undef DM_TRY_CAL
-    cleanup();
+    if (rc) return rc;                                      // (precision and profile are the caller's again on every way out)
+    rc = sync_and_check(m);
+    tmp.in_use = false;
     if (rc) return rc;
+    unsigned bits = 0x7F800000u;
+    HIP_TRY(hipMemcpy(&bits, d_max, sizeof(unsigned), hipMemcpyDeviceToHost));
     float err;
     std::memcpy(&err, &bits, 4);
     if (max_abs_dp) *max_abs_dp = double(err);
@@ -774,9 +725,8 @@ int dm_model_calibrate_i8(dm_model* m, int64_t n_windows, double bound, double* 
     }
     if (selected) *selected = m->precision == DM_PREC_F16I8 ? 1 : 0;      // the mode the model runs after the call
     if (m->precision != DM_PREC_F16I8) {                    // a refused model does not keep the int8 weight packs (1.7 MB)
-        (void)hipFree(m->d_wpack16i);
-        (void)hipFree(m->d_wpack16qi);
-        m->d_wpack16i = m->d_wpack16qi = nullptr;
+        m->fixed.drop(dm_model::PACK0 + dm_model::PACK_SI);
+        m->fixed.drop(dm_model::PACK0 + dm_model::PACK_QI);
     }
     return DM_OK;
 }
@@ -887,7 +837,8 @@ int dm_model_h2d_ahead(dm_model* m, void* dst, const void* src, size_t bytes) {
     if (bytes == 0) return DM_OK;
     if (!dst || !src) return fail(DM_EINVAL, "null buffer");
     HIP_TRY(hipSetDevice(m->device));
-    if (!m->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&m->copy_stream, hipStreamNonBlocking));
+    int rc = ensure_copy_stream(m);
+    if (rc) return rc;
     hipEvent_t& ev = m->ahead_event[m->ahead_next];
     if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     m->ahead_next = (m->ahead_next + 1) % dm_model::AHEAD_EVENTS;
@@ -924,24 +875,7 @@ int dm_model_mark(dm_model* m, int i) {
     HIP_TRY(hipSetDevice(m->device));
     if (!m->marks[i]) HIP_TRY(hipEventCreateWithFlags(&m->marks[i], hipEventDisableTiming));
     HIP_TRY(hipEventRecord(m->marks[i], m->stream));
-    // the launches queued since the marker before this one wrote range slot range_cur: it now belongs to marker i
-    if (m->mark_slot[i] >= 0) m->range_orphans.push_back(m->mark_slot[i]);      // re-recorded unwaited: dm_model_sync reports it
-    int next = -1;
-    for (int k = 0; k < dm_model::RANGE_SLOTS; ++k)
-        if (m->slot_free[k]) {
-            next = k;
-            break;
-        }
-    if (next < 0) {
-        // every slot is tied to a marker nobody waited for (more than 2 DM_MARKS + 1 recordings without a wait): marker i gets no slot and
-        // the launches go on writing the current one.  dm_model_wait_mark(i) then reports nothing; what was queued before marker i is reported
-        // later - by the next marker that finds a free slot, or by dm_model_sync - and exactly once: never silent, but not at marker i
-        m->mark_slot[i] = -1;
-        return DM_OK;
-    }
-    m->mark_slot[i] = m->range_cur;
-    m->slot_free[next] = false;
-    m->range_cur = next;
+    m->range.record(i);
     return DM_OK;
 }
 
@@ -951,12 +885,7 @@ int dm_model_wait_mark(dm_model* m, int i) {
     if (!m->marks[i]) return DM_OK;
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipEventSynchronize(m->marks[i]));
-    if (m->mark_slot[i] < 0) return DM_OK;          // reported already (or left to a later marker / dm_model_sync, see dm_model_mark)
-    const int sl = m->mark_slot[i];
-    m->mark_slot[i] = -1;
-    const bool bad = take_range_slot(m, sl);
-    m->slot_free[sl] = true;
-    return bad ? range_error(m) : DM_OK;
+    return m->range.take_mark(i) ? range_error(m) : DM_OK;
 }
 
 int dm_memcpy_d2h(int device, void* dst, const void* src, size_t bytes) {

@@ -1,7 +1,8 @@
 // host.h - what the host-side translation units of libdeepmod_hip.so share (deepmod_hip.hip, summary.hip, feed.hip, offline.hip; DESIGN.md
 // "Translation units").  Internal, not installed.  Declarations only: every object named here is defined exactly once, in deepmod_hip.hip
 // (map_read_core: in readmap.inc) - a variable defined in this header would silently become one copy per unit.  The two pieces of code it
-// holds are inline and own no object: DevBufs, the grow-only device blocks of a handle, and add_time.
+// holds are inline and own no object: DevBufs, the grow-only device blocks of a handle, and add_time.  Of dm_model it knows the name and three
+// accessors (its device, its stream, whether it is asynchronous); the struct is deepmod_hip.hip's own.
 // Without HIP (g++ on the host-only files: tests/asan/host_shim.cpp) the header is its first part alone: the C ABI and the error slot.
 #pragma once
 
@@ -94,68 +95,18 @@ DM_HIDDEN_SYM inline int add_time(hipEvent_t begin, hipEvent_t end, double& into
 }
 
 // ---------------------------------------------------------------------------------------------
-// handles that more than one file needs: dm_model crosses units (summary.hip follows its stream, offline.hip reads its device), dm_summary and
-// dm_cluster are shared by summary.hip and cluster_sites.hip.inc.  Every other handle is defined in the one file that uses it.
+// handles that more than one file needs: dm_summary and dm_cluster are shared by summary.hip and cluster_sites.hip.inc.  Every other handle is defined
+// in the one file that uses it - dm_model in deepmod_hip.hip: the other units follow its stream (summary.hip) and read its device (offline.hip)
+// through the accessors below, so a change of its fields recompiles the core unit alone.
 // ---------------------------------------------------------------------------------------------
-struct dm_model {
-    int device = 0;
-    int num_cu = 0;
-    hipStream_t stream = nullptr;
-    float* d_wpack = nullptr;
-    float* d_bpack = nullptr;
-    float* d_hpack = nullptr;
-    unsigned char* d_wpack16s = nullptr;  // experiment builds (DM_WITH_F16S): split-f16 weights in the tile-major layout of the 32x32x16 kernels
-    unsigned char* d_wpack16q = nullptr;  // the same weights in the 16x16x32 layout (lstm_f16q.hip.inc)
-    bool f16_q = true;                    // the split-f16 modes run lstm16q::bilstm_f16q_kernel (16x16x32 MFMAs): always, except in an experiment build with DM_OPT_F16X3_SHAPE = 32
-    unsigned char* d_wpack16i = nullptr;  // the same layout with int8 cross-term records (DM_PREC_F16I8)
-    float i8s[24] = {};                   // its fold scales [dir][layer][gate kind]
-    unsigned char* d_wpack16qi = nullptr; // DM_PREC_F16I8 in the 16x16x32 layout (lstm16q::bilstm_f16q_kernel<1>: int8 16x16x64 cross terms)
-    float i8s_q[24] = {};                 // its fold scales
-    float* d_wout = nullptr;              // head W[200][2] fp32 (DM_PREC_F16X3)
-    float* d_scratch = nullptr;
-    unsigned long long* d_dbg = nullptr;  // DM_TIMING builds only
-    float* d_plogit = nullptr;            // partial logits [2 directions][plogit_tiles * 128][2], grown on demand
-    int64_t plogit_tiles = 0;
-    float bout[2] = {0, 0};
-    int grid_cap = 0;
-    int last_grid = 0;                    // DM_INFO_LAST_GRID: workgroups of the last classifier launch (launch_bilstm)
-    std::vector<float> host_weights;      // canonical blob, kept for lazy packing of other precisions
-    // staging for host-pointer callers
-    static constexpr int64_t STAGE_WINDOWS = 65536;
-    float* d_x = nullptr;
-    float* d_x2 = nullptr;       // second staging buffer: H2D of batch i+1 overlaps the kernel of batch i
-    hipStream_t copy_stream = nullptr;
-    static constexpr int AHEAD_EVENTS = 8;      // dm_model_h2d_ahead: copy-done events, reused round robin (a wait captures the record it was queued behind)
-    hipEvent_t ahead_event[AHEAD_EVENTS] = {};
-    int ahead_next = 0;
-    float* d_prob = nullptr;
-    uint8_t* d_cls = nullptr;
-    int64_t stage_rows = 0;  // capacity of d_x in floats
-    // profiling
-    bool profile = false;
-    bool async = false;                   // DM_OPT_ASYNC: device-resident calls return after enqueue
-    int precision = DM_PREC_F16X3;        // default: fastest mode that meets the 1e-4 probability tolerance
-    float f16_max_abs = 0.0f;             // largest |packed weight| (x exponent scale)
-    bool f16_ok = true;                   // every packed weight is a finite f16 (checked at create; else the default is DM_PREC_F32)
-    bool i8_calibrated = false;           // DM_PREC_F16I8 was selected by dm_model_calibrate_i8 (for the MFMA shape of that moment)
-    int len_shift = 0;                    // DM_INFO_F16_LENGTH_SHIFT
-    // DM_ERANGE bookkeeping: host-mapped words the split-f16 kernels set on an input they cannot represent.  A launch writes
-    // the CURRENT slot; dm_model_mark(i) ties the current slot to marker i and moves on to a free one, so that
-    // dm_model_wait_mark(i) reports exactly the launches queued between the marker before it and marker i, and a later
-    // batch that is still in flight cannot leak into (or be cleared by) the check of an earlier one.
-    static constexpr int RANGE_SLOTS = 2 * DM_MARKS + 2;
-    int* range_flag = nullptr;            // [RANGE_SLOTS]
-    int* d_range_flag = nullptr;          // its device address
-    int range_cur = 0;                    // slot of the launches being queued now
-    int mark_slot[DM_MARKS];              // slot tied to marker i, -1: none
-    std::vector<int> range_orphans;       // slots of markers that were re-recorded before anybody waited for them: checked by dm_model_sync
-    bool slot_free[RANGE_SLOTS];
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-    hipEvent_t marks[DM_MARKS] = {};     // dm_model_mark / dm_model_wait_mark
-    size_t events_used = 0;
-    double prof_ms = 0.0;
-    int64_t prof_launches = 0, prof_windows = 0;
-};
+namespace dmhost {
+DM_HIDDEN_SYM int model_device(const dm_model* m);
+DM_HIDDEN_SYM hipStream_t model_stream(const dm_model* m);
+DM_HIDDEN_SYM bool model_async(const dm_model* m);      // DM_OPT_ASYNC
+}  // namespace dmhost
+using dmhost::model_device;
+using dmhost::model_async;
+using dmhost::model_stream;
 
 struct dm_summary {
     int device = 0;

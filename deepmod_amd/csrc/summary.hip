@@ -182,10 +182,10 @@ static int summary_add_impl(dm_summary* s, const int64_t* pos, const uint8_t* fl
     hipStream_t st = s->stream;
     if (s->follow) {
         if (pd && fd && cd) {
-            st = s->follow->stream;                                 // device-resident inputs: one in-order queue with the classifier
-            if (deferred && s->follow->async) *deferred = true;     // out-of-range check waits for dm_summary_sync / fetch
+            st = model_stream(s->follow);                           // device-resident inputs: one in-order queue with the classifier
+            if (deferred && model_async(s->follow)) *deferred = true;     // out-of-range check waits for dm_summary_sync / fetch
         }
-        else HIP_TRY(hipStreamSynchronize(s->follow->stream));      // staged inputs travel on the summary's own stream
+        else HIP_TRY(hipStreamSynchronize(model_stream(s->follow)));      // staged inputs travel on the summary's own stream
     }
     hipLaunchKernelGGL(summary_add_kernel, dim3(blocks), dim3(threads), 0, st, s->d_counts,
                        s->d_counts + s->length, s->d_counts + 2 * s->length, (long long)s->length, dpos, dfl, dcl,
@@ -196,7 +196,7 @@ static int summary_add_impl(dm_summary* s, const int64_t* pos, const uint8_t* fl
 
 static int summary_check_oob(dm_summary* s) {
     int oob = 0;
-    if (s->follow) HIP_TRY(hipStreamSynchronize(s->follow->stream));
+    if (s->follow) HIP_TRY(hipStreamSynchronize(model_stream(s->follow)));
     HIP_TRY(hipMemcpyAsync(&oob, s->d_oob, sizeof(int), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     if (oob) {
@@ -245,8 +245,8 @@ void* dm_summary_device_ptr(dm_summary* s) { return s ? s->d_counts : nullptr; }
 
 int dm_summary_follow(dm_summary* s, dm_model* m) {
     if (!s) return fail(DM_EINVAL, "null summary");
-    if (m && m->device != s->device) return fail(DM_EINVAL, "summary (device %d) cannot follow a model on device %d", s->device, m->device);
-    if (s->follow) HIP_TRY(hipStreamSynchronize(s->follow->stream));
+    if (m && model_device(m) != s->device) return fail(DM_EINVAL, "summary (device %d) cannot follow a model on device %d", s->device, model_device(m));
+    if (s->follow) HIP_TRY(hipStreamSynchronize(model_stream(s->follow)));
     HIP_TRY(hipStreamSynchronize(s->stream));
     s->follow = m;
     return DM_OK;
@@ -487,7 +487,7 @@ int dm_summary_reduce(dm_summary* s, dm_comm* c, int root) {
     if (root >= c->nranks) return fail(DM_EINVAL, "root %d outside the %d ranks", root, c->nranks);
     if (s->device != c->device) return fail(DM_EINVAL, "summary on device %d, communicator on device %d", s->device, c->device);
     HIP_TRY(hipSetDevice(s->device));
-    if (s->follow) HIP_TRY(hipStreamSynchronize(s->follow->stream));   // adds queued on the classifier's stream
+    if (s->follow) HIP_TRY(hipStreamSynchronize(model_stream(s->follow)));   // adds queued on the classifier's stream
     HIP_TRY(hipStreamSynchronize(s->stream));
     const size_t count = size_t(3) * s->length;
     ncclResult_t e = root >= 0 ? g_rccl.reduce(s->d_counts, s->d_counts, count, ncclInt32, ncclSum, root, c->comm, c->stream)
@@ -506,7 +506,7 @@ int dm_summary_grow(dm_summary* s, int64_t new_length) {
     if (new_length <= s->length) return DM_OK;
     if (new_length > (int64_t(1) << 33)) return fail(DM_EINVAL, "bad contig length %lld", (long long)new_length);
     HIP_TRY(hipSetDevice(s->device));
-    if (s->follow) HIP_TRY(hipStreamSynchronize(s->follow->stream));
+    if (s->follow) HIP_TRY(hipStreamSynchronize(model_stream(s->follow)));
     HIP_TRY(hipStreamSynchronize(s->stream));
     int* nd = nullptr;
     if (hipMalloc(&nd, sizeof(int) * (3 * new_length + dm_summary::SLACK)) != hipSuccess) {
@@ -537,7 +537,7 @@ int dm_summary_reduce_scatter(dm_summary* s, dm_comm* c, int64_t* first, int64_t
     if (c->nranks > dm_summary::SLACK) return fail(DM_EINVAL, "reduce-scatter over %d ranks (at most %lld)", c->nranks, (long long)dm_summary::SLACK);
     if (!g_rccl.reducescatter) return fail(DM_ERCCL, "librccl has no ncclReduceScatter");
     HIP_TRY(hipSetDevice(s->device));
-    if (s->follow) HIP_TRY(hipStreamSynchronize(s->follow->stream));   // adds queued on the classifier's stream
+    if (s->follow) HIP_TRY(hipStreamSynchronize(model_stream(s->follow)));   // adds queued on the classifier's stream
     HIP_TRY(hipStreamSynchronize(s->stream));
     const int64_t chunk = (s->length + c->nranks - 1) / c->nranks;
     s->slice_count = -1;                              // whatever the block held is gone from here on

@@ -370,7 +370,7 @@ int dm_xyload_fetch(dm_xyload* h, float* feats, float* head, int32_t* centre, ui
 int dm_xyload_classify(dm_xyload* h, dm_model* m, float* prob1, uint8_t* cls, uint8_t* label) {
     if (!h || !m) return fail(DM_EINVAL, "null handle");
     if (h->n_rows < 0 || h->n < 0) return fail(DM_ESTATE, "dm_xyload_classify: no selection");
-    if (m->device != h->xy->device) return fail(DM_EINVAL, "dm_xyload_classify: the model is on device %d, the table on device %d", m->device, h->xy->device);
+    if (model_device(m) != h->xy->device) return fail(DM_EINVAL, "dm_xyload_classify: the model is on device %d, the table on device %d", model_device(m), h->xy->device);
     if (h->n == 0) return DM_OK;
     if (!prob1 || !cls) return fail(DM_EINVAL, "dm_xyload_classify: null output");
     const int64_t n = h->n;
@@ -550,7 +550,7 @@ int64_t dm_xyset_bytes(dm_xyset* s) {
 int dm_xyset_classify(dm_xyset* s, dm_model* m, int64_t segment, float* prob1, uint8_t* cls, uint8_t* label) {
     if (!s || !m) return fail(DM_EINVAL, "null handle");
     if (segment < 0 || segment + 1 >= int64_t(s->row_off.size())) return fail(DM_EINVAL, "dm_xyset_classify: segment %lld of %lld", (long long)segment, (long long)s->row_off.size() - 1);
-    if (m->device != s->device) return fail(DM_EINVAL, "dm_xyset_classify: the model is on device %d, the set on device %d", m->device, s->device);
+    if (model_device(m) != s->device) return fail(DM_EINVAL, "dm_xyset_classify: the model is on device %d, the set on device %d", model_device(m), s->device);
     if (!prob1 || !cls) return fail(DM_EINVAL, "dm_xyset_classify: null output");
     const int64_t row0 = s->row_off[segment], R = s->row_off[segment + 1] - row0, win0 = s->win_off[segment], n = s->win_off[segment + 1] - win0;
     HIP_TRY(hipSetDevice(s->device));

@@ -667,3 +667,88 @@ def test_one_call_past_two_to_the_31_input_floats(gpu_device):
         m.close()
     for a in (big, d_prob, d_cls):
         a.free()
+
+
+# ---- where the arrays of a call live: every mix of host and device arrays gives the all-device call's bits ---------------------------------------------
+
+STAGED_N = 65537 + 128                 # two staged chunks of a host call, the second ragged (65,536 + 129)
+
+
+class _Mixes:
+    """The default model, one input per call form and the all-device result of each: computed once, shared, left unchanged."""
+
+    def __init__(self, device):
+        self.device = device
+        self.m = model.BiLSTMModel(synth.synthetic_weights(26, 4.0), device=device)
+        n = STAGED_N
+        self.x = np.tile(synth.synthetic_windows(1031, seed=47), (n // 1031 + 1, 1, 1))[:n]
+        self.rows = np.ascontiguousarray(np.tile(synth.synthetic_windows(1031, seed=48)[:, 10, :], ((n + 20) // 1031 + 1, 1))[:n + 20])
+        self.at_rows = np.ascontiguousarray(synth.synthetic_windows(1000, seed=49)[:, 10, :])
+        self.centres = np.sort(np.random.default_rng(9).choice(np.arange(10, 990), 300, replace=False)).astype(np.int32)
+        self.dev = {k: model.DeviceArray.from_host(getattr(self, k), device) for k in ("x", "rows", "at_rows", "centres")}
+        self.ref = {"windows": self.call("windows", True, "device", True), "read": self.call("read", True, "device", True),
+                    "read_at": self.call("read_at", True, "device", True, True)}
+        for p, c in self.ref.values():
+            p.setflags(write=False)
+            c.setflags(write=False)
+
+    def call(self, form, x_dev, prob_at, cls_dev, centres_dev=False):
+        """One call with the named arrays on the device, the others on the host -> (prob or None, cls) as host arrays."""
+        n = len(self.centres) if form == "read_at" else STAGED_N
+        d_prob = model.DeviceArray((n, 2), np.float32, self.device) if prob_at == "device" else None
+        d_cls = model.DeviceArray((n,), np.uint8, self.device) if cls_dev else None
+        try:
+            kw = dict(prob=d_prob, cls=d_cls, want_prob=prob_at is not None)
+            if form == "windows":
+                prob, cls = self.m.predict_windows(self.dev["x"] if x_dev else self.x, **kw)
+            elif form == "read":
+                prob, cls = self.m.predict_read(self.dev["rows"] if x_dev else self.rows, 10, n, **kw)
+            else:
+                prob, cls = self.m.predict_read_at(self.dev["at_rows"] if x_dev else self.at_rows, self.dev["centres"] if centres_dev else self.centres, **kw)
+            self.m.sync()
+            return (prob.to_host() if d_prob else prob), (cls.to_host() if d_cls else cls)
+        finally:
+            for d in (d_prob, d_cls):
+                if d:
+                    d.free()
+
+    def close(self):
+        for d in self.dev.values():
+            d.free()
+        self.m.close()
+
+
+@pytest.fixture(scope="module")
+def mixes(gpu_device):
+    s = _Mixes(gpu_device)
+    yield s
+    s.close()
+
+
+def _same_bits(got, want, want_prob):
+    prob, cls = got
+    assert np.array_equal(cls, want[1])
+    if want_prob:
+        assert np.array_equal(prob.view(np.uint32), want[0].view(np.uint32))
+    else:
+        assert prob is None
+
+
+@pytest.mark.parametrize("cls_at", ["host", "device"])
+@pytest.mark.parametrize("prob_at", ["host", "device", None], ids=["host", "device", "unwanted"])
+@pytest.mark.parametrize("x_at", ["host", "device"])
+@pytest.mark.parametrize("form", ["windows", "read"])
+def test_staged_call_gives_the_all_device_bits_wherever_its_arrays_live(mixes, form, x_at, prob_at, cls_at):
+    """dm_predict_windows and dm_predict_read (row matrix of n + 20 rows) at n = 65,537 + 128 windows - two staged chunks, the second ragged - with the input, the
+    probabilities (also: not wanted) and the classes each on the host or on the device: the all-device call of the same model, bit for bit."""
+    _same_bits(mixes.call(form, x_at == "device", prob_at, cls_at == "device"), mixes.ref[form], prob_at is not None)
+
+
+@pytest.mark.parametrize("cls_at", ["host", "device"])
+@pytest.mark.parametrize("prob_at", ["host", "device"])
+@pytest.mark.parametrize("centres_at", ["host", "device"])
+@pytest.mark.parametrize("rows_at", ["host", "device"])
+def test_centre_call_gives_the_all_device_bits_wherever_its_arrays_live(mixes, rows_at, centres_at, prob_at, cls_at):
+    """dm_predict_read_at at 300 centres (two full tiles and a ragged one) with the rows, the centres, the probabilities and the classes each on the host or on
+    the device: the all-device call of the same model, bit for bit."""
+    _same_bits(mixes.call("read_at", rows_at == "device", prob_at, cls_at == "device", centres_at == "device"), mixes.ref["read_at"], True)
